@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py - STA two-view image-pairs/sec on synthetic 512x384 RGB pairs (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,11 +15,16 @@ confidence, depth = pts[...,2] and the confidence map; slam.py:165-185).
 by re-executing itself under torch.distributed.run on 127.0.0.1.
 
 Prints ONE JSON line on rank 0 with the throughput (`value` = K steps / wall time between two
-barrier + synchronize brackets, max over ranks; `median_ms_per_step` = median of the K per-step stream-event
-durations of rank 0), the roofline of the dominant kernel (live HIP event timing of every launch of the in-place
-residual GEMM class inside the timed region - those per-launch event records are part of the timed region) and a CPU
-baseline (a torch-CPU re-expression of the forward and the C + OpenMP oracle, timed on the host cores on a bounded
-sample).
+barrier + synchronize brackets, max over ranks; `ms_per_step` = that wall time / K; `median_ms_per_step` = median of the
+K per-step stream-event durations of rank 0).  A plain run does only that: set up, warm up, time the K steps, write the
+outputs (--dump-outputs), print the line.  `--full` adds everything that takes runs of its own: the roofline of the
+dominant kernel (an untimed survey step, then live HIP event timing of every --timed-every-th launch of that kernel inside
+the timed region - those per-launch event records are part of the timed region), the SLAM-resolution probes and the CPU
+baseline (a torch-CPU re-expression of the forward and the C + OpenMP oracle, timed on the host cores on a bounded sample).
+
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 - main_* / supp_* {pts3d_pred, conf,
+relative_pose, relative_pose_conf}, float32 - as DIR/<name>.npy (at most 64 MB: beyond that only the leading pairs of
+the batch).  Weights and inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -378,6 +383,29 @@ def timed_region(runner, steps, warmup_done=True):
     return dt, step_ms, out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out, dirname, budget=DUMP_BUDGET_BYTES):
+    """The (main, supp) dicts of one forward_pair step -> dirname/{main,supp}_<key>.npy in float32.  Every array's leading
+    axis is the pair index; when the whole batch exceeds `budget` bytes only its first n pairs are written (the same n for
+    every array).  -> {file name: shape}."""
+    import numpy as np
+    import torch
+    arrs = {f"{side}_{k}": v for side, d in zip(("main", "supp"), out) for k, v in sorted(d.items())}
+    B = next(iter(arrs.values())).shape[0]
+    per_pair = sum(v[0].numel() * (8 if v.dtype == torch.float64 else 4) for v in arrs.values())
+    n = max(1, min(B, budget // max(per_pair, 1)))
+    os.makedirs(dirname, exist_ok=True)
+    shapes = {}
+    for name, v in arrs.items():
+        a = v[:n].detach()
+        a = np.ascontiguousarray((a if a.dtype == torch.float64 else a.float()).cpu().numpy())
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        shapes[name + ".npy"] = list(a.shape)
+    return shapes
+
+
 def rank_identity(dev):
     """What this rank actually drives: device name + PCI address (a launcher that maps two ranks onto one GPU shows up here)."""
     import socket
@@ -522,6 +550,11 @@ def main():
                     help="f16x3h = the default policy; f16x3m (opt-in, +2 %%): additionally mlp.fc2 in the f16mx arithmetic - holds every full-architecture "
                          "golden at <= 8.1e-5 but not two of the ten tiny stress sets (DESIGN.md section 2)")
     ap.add_argument("--pairs", type=int, default=PAIRS_PER_GPU, help="image pairs per GPU per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy, float32, <= 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sections that take runs of their own: the dominant kernel's roofline (survey step + event timing "
+                         "inside the timed region), the SLAM-resolution probes and the CPU baseline; the flags below tune them")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-224", action="store_true", help="time the oracle on one 224x224 pair (4.3x less work) instead of 512x384")
     ap.add_argument("--no-kernel-timing", action="store_true")
@@ -529,6 +562,9 @@ def main():
     ap.add_argument("--no-slam-probe", action="store_true")
     ap.add_argument("--slam-frames", type=int, default=120, help="frames of the slam_replay section (0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    kernel_timing = args.full and not args.no_kernel_timing
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, RCCL) and relay the JSON line
@@ -584,7 +620,7 @@ def main():
     if use_dist:
         dist.barrier()
     symtab = None
-    if not args.no_kernel_timing:
+    if kernel_timing:
         # untimed survey step: every GEMM / convolution launch carries an event pair (mode 2) -> per-symbol totals; the
         # symbol with the largest total time is the dominant kernel, and ONLY its launches are timed inside the timed region
         # (mode 3: a 1-in-TIMED_EVERY sample of them; an event pair costs ~9 us of dispatch)
@@ -607,9 +643,11 @@ def main():
             first_sums = runner.verify_gather()
         dt, dist_fields = distributed_fields(runner, dt, args.steps, first_sums)
     assert bool(torch.isfinite(out[0]["pts3d_pred"]).all()), "non-finite output"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     roof = None
-    if not args.no_kernel_timing:
+    if kernel_timing:
         # Every launch of the dominant kernel SYMBOL (largest total time in the survey step; the rocprofv3 row of the same name
         # is directly comparable) carried a HIP-event pair in the timed region, recorded by the library on its launch stream;
         # achieved = sum of algorithmic 2MNK over those launches / sum of their event durations.
@@ -664,11 +702,11 @@ def main():
                "roofline": roof}
         if use_dist:
             res.update(dist_fields)
-        if world == 1 and not args.no_slam_probe:
+        if args.full and world == 1 and not args.no_slam_probe:
             res["slam_224_b1"] = slam_probe(model, dev)
             if args.slam_frames > 0:
                 res["slam_replay"] = slam_replay(model, dev, frames=args.slam_frames)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline_subprocess(224, 224) if args.cpu_baseline_224 else cpu_baseline_subprocess(H, W_)
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(res) + "\n").encode())
