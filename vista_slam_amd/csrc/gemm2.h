@@ -321,6 +321,10 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     const int l31 = lane & 31, lhi = lane >> 5;
+    // 16x16x32 operand lanes (f16x3 / f16 main loop): m16 = row / column of the sub-block, g16 = 8-element K chunk; the A row of lane
+    // m16 is m16 with bits 2 and 3 swapped (see the rebuild behind the main loop)
+    const int m16 = lane & 15, g16 = lane >> 4;
+    const int a_perm = (m16 & 3) | ((m16 & 4) << 1) | ((m16 & 8) >> 1);
     unsigned long long clk0 = 0, rt0 = 0;
     if (p.clk_dbg) { clk0 = __builtin_readcyclecounter(); rt0 = __builtin_amdgcn_s_memrealtime(); }
     unsigned long long st0 = 0, st1 = 0, st2 = 0;
@@ -442,6 +446,15 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // f16x3 / f16 main loop: the four 16x16 sub-blocks (bi, bj) of every 32x32 accumulator tile (rebuilt into acc after the loop)
+    constexpr bool ACC16 = !MX && !TRN;
+    floatx4 acc4[ACC16 ? MT : 1][ACC16 ? NT : 1][2][2];
+#pragma unroll
+    for (int i = 0; i < (ACC16 ? MT : 1); ++i)
+#pragma unroll
+        for (int j = 0; j < (ACC16 ? NT : 1); ++j)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc4[i][j][b >> 1][b & 1] = floatx4{0.f, 0.f, 0.f, 0.f};
 
     // K tiles of this block's slice
     const int nkt_all = p.K / GEMM_BK;
@@ -465,10 +478,24 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
     }
 
     // STAGGER (ABL bit 3, experiment): the two waves that share a SIMD (w and w + NW/2) issue their DMA at
-    // different points of the K tile - the older half before K step 0, the younger half between the two
-    // K steps - so that one of them always has MFMAs to feed the matrix pipe while the other sits in the
+    // different points of the K tile - the older half before the first MFMA, the younger half half-way through
+    // the tile's sub-blocks - so that one of them always has MFMAs to feed the matrix pipe while the other sits in the
     // (slow, back-pressured) LDS-DMA issue.
     const bool late_dma = (ABL & 8) && !RING && wave >= NW / 2;
+    // relu(hi + lo) of an implicit-GEMM A fragment: the sign of hi decides.  Packed-half integer form, 5 VALU per 32-bit word for
+    // both planes (the vector compare scalarises to ~11 per word): s = sign bits at bit 0 / 16, m = 0xFFFF in every negative half
+    auto relu_frag = [](half8& hi, half8& lo) {
+        union { half8 h; unsigned u[4]; } ah, al;
+        ah.h = hi; al.h = lo;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const unsigned sgn = (ah.u[w] >> 15) & 0x00010001u;
+            const unsigned m = (sgn << 16) - sgn;        // 0xFFFF per set sign (mod 2^32)
+            ah.u[w] &= ~m;
+            if (SPLIT) al.u[w] &= ~m;
+        }
+        hi = ah.h; if (SPLIT) lo = al.h;
+    };
     // the arithmetic of ONE K tile held in LDS stage `cur` (kt: its index in this block's slice, for the STAGGER experiment)
     // relu_c: the input ReLU of resConfUnit*.conv1 (implicit-GEMM convolutions) as a COMPILE-time constant - the main loop below
     // exists once per value (round 6: as a wave-uniform runtime flag it was a branch per fragment inside the K tile, and hipcc
@@ -477,7 +504,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         constexpr bool RELU = AMODE == A_CONV3 && decltype(relu_c)::value;
         const char* sA = smem + cur * STAGE;
         const char* sB = sA + A_TILE;
-        if (MX) {
+        if constexpr (MX) {
             // precision f16mx (sta_common.h): per K tile and accumulator 2 f16 MFMAs (hi x hi, K steps 0 / 1) + ONE
             // block-scaled fp8 MFMA that carries both correction products.  Operand semantics of
             // v_mfma_scale_f32_32x32x64_f8f6f4 as decoded on hardware (tools/probes/mx_probe*.hip): byte q of lane
@@ -535,87 +562,108 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
                 for (int j = 0; j < NT; ++j)
                     acc[i][j] = TRN ? __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b8[j].v, a8[i].v, acc[i][j], 0 /* A: e4m3 weights */, 1 /* B: e5m2 */, 0, sc_b, 0, sc_a)
                                     : __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8[i].v, b8[j].v, acc[i][j], 1 /* A: e5m2 */, 0 /* B: e4m3 */, 0, sc_a, 0, sc_b);
-            return;
-        }
-        half8 a_hi[MT], a_lo[MT], b_hi[NT], b_lo[NT];
-        if (ABL & 2) {
+        } else if constexpr (TRN) {
+            // fused DPT tail (operands swapped, transposed 32x32 accumulators for head_epilogue_t): 32x32x16, two K steps
+            half8 a_hi[MT], a_lo[MT], b_hi[NT], b_lo[NT];
 #pragma unroll
-            for (int i = 0; i < MT; ++i) { a_hi[i] = (half8)(f16)(0.001f * (lane + i)); a_lo[i] = a_hi[i]; asm volatile("" : "+v"(a_hi[i]), "+v"(a_lo[i])); }
+            for (int ks = 0; ks < 2; ++ks) {
+                const int chunk = ks * 2 + lhi;
 #pragma unroll
-            for (int j = 0; j < NT; ++j) { b_hi[j] = (half8)(f16)(0.002f * (lane + j)); b_lo[j] = b_hi[j]; asm volatile("" : "+v"(b_hi[j]), "+v"(b_lo[j])); }
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int chunk = ks * 2 + lhi;
-#pragma unroll
-            for (int i = 0; i < MT && !(ABL & 2); ++i) {
-                const int ra = wm * WM + i * 32 + l31;
-                a_hi[i] = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, chunk));
-                if (SPLIT) a_lo[i] = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, 4 + chunk));
-                if (AMODE == A_CONV3) {
-                    if (RELU) {   // relu(hi + lo): the sign of hi decides.  Packed-half integer form, 5 VALU per
-                        // 32-bit word for both planes (the vector compare scalarises to ~11 per word):
-                        // s = sign bits at bit 0 / 16, m = 0xFFFF in every negative half, x &= ~m
-                        union { half8 h; unsigned u[4]; } ah, al;
-                        ah.h = a_hi[i]; al.h = a_lo[i];
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) {
-                            const unsigned sgn = (ah.u[w] >> 15) & 0x00010001u;
-                            const unsigned m = (sgn << 16) - sgn;        // 0xFFFF per set sign (mod 2^32)
-                            ah.u[w] &= ~m;
-                            if (SPLIT) al.u[w] &= ~m;
-                        }
-                        a_hi[i] = ah.h; if (SPLIT) a_lo[i] = al.h;
-                    }
+                for (int i = 0; i < MT; ++i) {
+                    const int ra = wm * WM + i * 32 + l31;
+                    a_hi[i] = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, chunk));
+                    if (SPLIT) a_lo[i] = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, 4 + chunk));
+                    if (RELU) relu_frag(a_hi[i], a_lo[i]);
                 }
-            }
 #pragma unroll
-            for (int j = 0; j < NT && !(ABL & 2); ++j) {
-                const int rb = wn * WN + j * 32 + l31;
-                b_hi[j] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, chunk));
-                if (SPLIT) b_lo[j] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, 4 + chunk));
-            }
-            if (ABL & 4) {      // keep the fragment loads alive, skip the matrix work
-#pragma unroll
-                for (int i = 0; i < MT; ++i) asm volatile("" ::"v"(a_hi[i]), "v"(a_lo[i]));
-#pragma unroll
-                for (int j = 0; j < NT; ++j) asm volatile("" ::"v"(b_hi[j]), "v"(b_lo[j]));
-                continue;
-            }
-            // product-major order: consecutive MFMAs hit different accumulators (MT*NT apart)
-            if (SPLIT && (ABL & 16)) {
-                // bench-only what-if (results are NOT a GEMM): the two correction products of both K steps replaced by
-                // ONE block-scaled fp8 MFMA (32x32x64, 2x rate) per accumulator per K tile - the instruction mix of an
-                // "f16 + MX-fp8 corrections" scheme, to price it before building it (operands: whatever bits are there)
-                if (ks == 1) {
-                    typedef int int8v __attribute__((ext_vector_type(8)));
+                for (int j = 0; j < NT; ++j) {
+                    const int rb = wn * WN + j * 32 + l31;
+                    b_hi[j] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, chunk));
+                    if (SPLIT) b_lo[j] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, 4 + chunk));
+                }
+                if (SPLIT) {
 #pragma unroll
                     for (int i = 0; i < MT; ++i)
 #pragma unroll
-                        for (int j = 0; j < NT; ++j) {
-                            union { struct { half8 x, y; } h; int8v v; } ua, ub;
-                            ua.h.x = a_lo[i]; ua.h.y = a_hi[i]; ub.h.x = b_hi[j]; ub.h.y = b_lo[j];
-                            acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ua.v, ub.v, acc[i][j], 0, 0, 0, 0x7f, 0, 0x7f);
-                        }
+                        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi[j], a_lo[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_lo[j], a_hi[i], acc[i][j], 0, 0, 0);
                 }
-            } else if (SPLIT) {
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = TRN ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi[j], a_lo[i], acc[i][j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo[i], b_hi[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = TRN ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b_lo[j], a_hi[i], acc[i][j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi[i], b_lo[j], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi[j], a_hi[i], acc[i][j], 0, 0, 0);
             }
+        } else {
+        // f16x3 / f16 main loop on 16x16x32 MFMAs (round 7): ONE MFMA per 16x16 sub-block and product covers the whole K tile.
+        // Sub-block (bi, bj) of the 32x32 accumulator tile (i, j) lives in acc4[i][j][bi][bj].  Lane (m16, g) reads logical chunk g
+        // (k = 8 g .. 8 g + 7) of the hi plane and chunk 4 + g of the lo plane - still one ds_read_b128 per plane and fragment, the
+        // same LDS bytes per K tile as the 32x32x16 loop.  B: tile column 16 bj + m16.  A: tile row 16 bi + (m16 with bits 2 and 3
+        // swapped), which makes the 32x32x16 C layout one permlane16 swap away after the loop (the rebuild behind main_loop).
+        // Registers: the B fragments of the whole K tile stay live (4 NT half8), the A fragments stream per (i, bi) - no fragment is
+        // read twice.  The products keep their order per accumulator: lo x hi, hi x lo, hi x hi.
+        half8 b_hi[NT][2], b_lo[NT][2];
+        if (ABL & 2) {
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+            for (int j = 0; j < NT; ++j)
 #pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = TRN ? __builtin_amdgcn_mfma_f32_32x32x16_f16(b_hi[j], a_hi[i], acc[i][j], 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi[i], b_hi[j], acc[i][j], 0, 0, 0);
-            if ((ABL & 8) && ks == 0 && late_dma && kt + 1 < nkt) issue_tile(kt0 + kt + 1, cur ^ 1);
+                for (int bj = 0; bj < 2; ++bj) {
+                    b_hi[j][bj] = (half8)(f16)(0.002f * (lane + 2 * j + bj)); b_lo[j][bj] = b_hi[j][bj];
+                    asm volatile("" : "+v"(b_hi[j][bj]), "+v"(b_lo[j][bj]));
+                }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) {
+                    const int rb = wn * WN + j * 32 + bj * 16 + m16;
+                    b_hi[j][bj] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, g16));
+                    if (SPLIT) b_lo[j][bj] = *reinterpret_cast<const half8*>(sB + lds2_off<SPLIT>(rb, 4 + g16));
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int bi = 0; bi < 2; ++bi) {
+                half8 a_hi, a_lo;
+                if (ABL & 2) {
+                    a_hi = (half8)(f16)(0.001f * (lane + 2 * i + bi)); a_lo = a_hi;
+                    asm volatile("" : "+v"(a_hi), "+v"(a_lo));
+                } else {
+                    const int ra = wm * WM + i * 32 + bi * 16 + a_perm;
+                    a_hi = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, g16));
+                    if (SPLIT) a_lo = *reinterpret_cast<const half8*>(sA + lds2_off<SPLIT>(ra, 4 + g16));
+                    if (RELU) relu_frag(a_hi, a_lo);
+                }
+                if (ABL & 4) {      // keep the fragment loads alive, skip the matrix work
+                    asm volatile("" ::"v"(a_hi), "v"(a_lo));
+                } else {
+                    if (SPLIT) {
+#pragma unroll
+                        for (int j = 0; j < NT; ++j)
+#pragma unroll
+                            for (int bj = 0; bj < 2; ++bj) acc4[i][j][bi][bj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, b_hi[j][bj], acc4[i][j][bi][bj], 0, 0, 0);
+#pragma unroll
+                        for (int j = 0; j < NT; ++j)
+#pragma unroll
+                            for (int bj = 0; bj < 2; ++bj) acc4[i][j][bi][bj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_lo[j][bj], acc4[i][j][bi][bj], 0, 0, 0);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NT; ++j)
+#pragma unroll
+                        for (int bj = 0; bj < 2; ++bj) acc4[i][j][bi][bj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_hi[j][bj], acc4[i][j][bi][bj], 0, 0, 0);
+                }
+                // STAGGER: the late half of the waves issues its DMA half-way through the K tile
+                if ((ABL & 8) && 2 * i + bi == MT - 1 && late_dma && kt + 1 < nkt) issue_tile(kt0 + kt + 1, cur ^ 1);
+            }
+        if (ABL & 4) {
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int bj = 0; bj < 2; ++bj) asm volatile("" ::"v"(b_hi[j][bj]), "v"(b_lo[j][bj]));
+        }
         }
     };
     auto main_loop = [&](auto relu_c) {
@@ -659,6 +707,25 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         else main_loop(std::integral_constant<bool, false>{});
     } else main_loop(std::integral_constant<bool, false>{});
 
+    // 16x16 sub-blocks -> the 32x32x16 C layout every epilogue reads (acc[i][j][r]: col = lane & 31, row = (r & 3) + 8 (r >> 2) +
+    // 4 (lane >> 5)).  Lane (c, g = lane >> 4) of sub-block (bi, bj) holds tile row 16 bi + 8 (g & 1) + 4 (g >> 1) + q (the A row
+    // permutation), column 16 bj + (c & 15).  Lane groups g, g ^ 1 trade halves with one v_permlane16_swap per (bi, q): the even
+    // group keeps its bj = 0 values and receives its partner's, the odd group keeps bj = 1 and receives its partner's - after the
+    // swap X = rows with (g & 1) = 0 and Y = rows with (g & 1) = 1 of the lane's own column, in every lane.
+    if constexpr (ACC16) {
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const auto xy = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc4[i][j][bi][0][q]), __float_as_uint(acc4[i][j][bi][1][q]), false, false);
+                        acc[i][j][8 * bi + q] = __uint_as_float(xy[0]);
+                        acc[i][j][8 * bi + 4 + q] = __uint_as_float(xy[1]);
+                    }
+    }
     if (p.stamps) {      // after the LAST MFMA has delivered (the stamp is scalar code: without the data dependence it is scheduled early)
         asm volatile("" ::"v"(acc[MT - 1][NT - 1][15]), "v"(acc[0][0][0]) : "memory");
         st2 = __builtin_amdgcn_s_memrealtime();

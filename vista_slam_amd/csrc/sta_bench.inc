@@ -145,8 +145,6 @@ extern "C" int sta_bench_gemm(sta_handle* h, int M, int N, int K, int iters, int
         if (tile == 3) return bench_launch2<256, 128, 4, 2, 0>(split, p, st);
         if (tile == 10) return split ? launch_gemm2<true, A_DENSE, EPI_F32, 256, 128, 4, 2, 3>(p, st)
                                      : launch_gemm2<false, A_DENSE, EPI_F32, 256, 128, 4, 2, 3>(p, st);   // 3-stage ring experiment
-        if (tile == 14) return bench_launch2<256, 256, 2, 4, 16>(split, p, st);  // instruction mix of the MX-fp8 correction scheme (not a GEMM)
-        if (tile == 15) return bench_launch2<192, 128, 2, 4, 16>(split, p, st);
         if (tile == 11) return bench_launch2<256, 256, 2, 4, 8>(split, p, st);   // staggered DMA issue
         if (tile == 12) return bench_launch2<192, 128, 2, 4, 8>(split, p, st);
         if (tile == 5) return bench_launch2<192, 256, 2, 4, 0>(split, p, st);
