@@ -29,6 +29,30 @@ STA_API int sta_set_gemm_variant(sta_handle* h, int variant);
  * (sta_launch.inc: pick_family). */
 STA_API int sta_debug_pick_family(int amode, int epi, long long M, int N, int K, int split, int cstride, int Ho, int Wo);
 
+/* The launch plan of a dense GEMM / convolution (pure host function, no handle, no GPU; sta_launch.inc: gemm_plan, what
+ * launch_gemm runs): tile family after the forced-family mapping and the f16mx remaps, its tile, the pose-token row tail the
+ * skinny tail blocks compute, and the K slices.  M_all: every row, tail rows included; precision: STA_PREC_*; mx: f16mx rows and
+ * weights (what use_mx() decides); tail_hint: the decoder's pose-token rows (0: none); forced_variant: as sta_set_gemm_variant
+ * (0..4, 8, 9).  out[8] = {family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks}; the main tiles cover rows
+ * [0, M_all - m_tail).  Fails when the plan would name a kernel that does not exist. */
+STA_API int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, int precision, int mx, int tail_hint, int forced_variant, int* out);
+
+/* The same record for the handle's LAST launch_gemm or paired QKV launch (family 7, bm x bn = 192 x 128, tiles_n = both halves'
+ * column tiles). */
+STA_API int sta_debug_last_gemm_plan(sta_handle* h, int* out);
+
+/* The paired QKV launch's decision (pure host function): out[2] = {1: one launch (gemm2_pair_kernel) / 0: two, m_tail of both
+ * halves}.  Both halves have M rows and the same K; N_a / N_b their widths, mx_a / mx_b their arithmetic. */
+STA_API int sta_debug_qkv_pair_plan(int precision, int M, int N_a, int N_b, int K, int mx_a, int mx_b, int tail_hint, int forced_variant, int* out);
+
+/* The decoder's attn.qkv + cross_attn.projk|projv pair through gemm_qkv_pair, pose-token tail hint S.  x_a, x_b [S*ntok + S, K]
+ * in the decoder's row order (patch rows sequence-major, then the S pose rows); w_a [3C,K] (q|k|v), w_b [2C,K] (k|v).  q_a, k_a,
+ * k_b out [S,C/64,ntok+1,64] with the pose token last; vt_a, vt_b out [S*C/64*64, roundup(ntok+1,64)] (transposed V, zero
+ * padding).  ntok % wp == 0 (the patch grid is ntok/wp x wp). */
+STA_API int sta_debug_qkv_pair(sta_handle* h, const float* x_a, const float* w_a, const float* bias_a, const float* x_b,
+                       const float* w_b, const float* bias_b, int S, int ntok, int K, int C, int wp,
+                       float* q_a, float* k_a, float* vt_a, float* k_b, float* vt_b, void* stream);
+
 /* nn.Linear (+GELU/ReLU, +residual): out[M,N] = act(A[M,K] W[N,K]^T + bias) (+resid).
  * act: 0 none, 1 erf-GELU, 2 ReLU.  via_f16 != 0 uses the fp16-plane epilogue (sta_blocks.py:73-79). */
 STA_API int sta_debug_gemm(sta_handle* h, const float* A, const float* W, const float* bias, int M, int N, int K,

@@ -69,7 +69,16 @@ def set_variant(m, variant):
 
 
 # ------------------------------------------------------------------------------------------ kernels
-def check_gemm(precision, M=300, N=200, K=96, act=0, via_f16=0, resid=False, seed=0, variant=0):
+def last_plan(lib, h):
+    """The plan (sta_launch.inc: gemm_plan) of the handle's last GEMM launch: family, tile, row tail, tiles, K slices."""
+    out = (C.c_int * 8)()
+    _lib.check(lib.sta_debug_last_gemm_plan(h, out))
+    return dict(zip(("family", "bm", "bn", "m_tail", "tiles_m", "tiles_n", "ksplit", "slab_ks"), out))
+
+
+def check_gemm(precision, M=300, N=200, K=96, act=0, via_f16=0, resid=False, seed=0, variant=0, tail_rows=0):
+    """tail_rows: also report the error of the last tail_rows rows alone (a wrong pose-token row among thousands of rows moves
+    the whole-matrix error by less than any bar) and the plan the GEMM ran under."""
     m, lib, h = kernel_handle(precision, variant)
     g = torch.Generator().manual_seed(seed)
     A = torch.randn(M, K, generator=g) * 1.3
@@ -89,7 +98,12 @@ def check_gemm(precision, M=300, N=200, K=96, act=0, via_f16=0, resid=False, see
     _lib.check(lib.sta_debug_gemm(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, act, via_f16,
                                   Rd.data_ptr() if resid else None, out.data_ptr(), st()))
     torch.cuda.synchronize()
-    return {"rel_l2": rel_l2(out.cpu().numpy(), ref.numpy()), "max_rel": max_rel(out.cpu().numpy(), ref.numpy())}
+    o, r = out.cpu().numpy(), ref.numpy()
+    res = {"rel_l2": rel_l2(o, r), "max_rel": max_rel(o, r)}
+    if tail_rows:
+        res.update(rel_l2_tail=rel_l2(o[M - tail_rows:], r[M - tail_rows:]), max_rel_tail=max_rel(o[M - tail_rows:], r[M - tail_rows:]),
+                   plan=last_plan(lib, h))
+    return res
 
 
 def check_qkv_rope(precision, S=2, hp=3, wp=4, pose_tok=1, K=128, Cdim=128, seed=1, variant=0):
@@ -135,17 +149,19 @@ def check_attention(precision, S=2, heads=2, nq=197, nk=197, kv_shift=0, sharp=1
     return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy()), "nan": float(np.isnan(o).sum())}
 
 
-def check_gemm_tail(precision, tiles_m=8, tail=16, N=2304, K=256, act=0, via_f16=0, resid=False, variant=0, seed=11):
-    """Dense GEMM whose last `tail` rows run on the skinny tail blocks (GemmParams::m_tail, the decoder's pose-token
-    rows): M = tiles_m x 192 (or 256) + tail at a size where the throughput families are selected."""
+def check_gemm_tail(precision, tiles_m=12, tail=16, N=2304, K=256, act=0, via_f16=0, resid=False, variant=0, seed=11, M=None):
+    """Dense GEMM whose last `tail` rows are the decoder's pose-token rows (tail hint; GemmParams::m_tail): M = tiles_m x 192
+    (or 256 under a forced 256-row family) + tail, unless M is given.  Returns the errors, those of the tail rows alone, and the
+    plan the GEMM ran under (whether the tail blocks took the rows is for the caller to assert)."""
     m, lib, h = kernel_handle(precision, variant)
     bm = 256 if variant == 2 else 192
-    M = tiles_m * bm + tail
+    M = tiles_m * bm + tail if M is None else M
     _lib.check(lib.sta_debug_set_tail_hint(h, tail))
     try:
-        r = check_gemm(precision, M=M, N=N, K=K, act=act, via_f16=via_f16, resid=resid, seed=seed, variant=variant)
+        r = check_gemm(precision, M=M, N=N, K=K, act=act, via_f16=via_f16, resid=resid, seed=seed, variant=variant, tail_rows=tail)
     finally:
         _lib.check(lib.sta_debug_set_tail_hint(h, 0))
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
     return r
 
 
@@ -175,8 +191,65 @@ def check_qkv_rope_decoder_rows(precision, S=2, hp=3, wp=4, K=128, Cdim=128, see
     order = list(range(1, ntok)) + [0]                          # device token order: patches, then the pose token
     v = vt.cpu().numpy().reshape(S, heads, 64, npad)[..., :ntok].transpose(0, 1, 3, 2)
     pad = vt.cpu().numpy().reshape(S, heads, 64, npad)[..., ntok:]
-    return {"q": max_rel(q.cpu().numpy(), qr[:, :, order]), "k": max_rel(k.cpu().numpy(), kr[:, :, order]), "v": max_rel(v, vr[:, :, order]),
-            "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0}
+    plan = last_plan(lib, h)
+    _lib.check(lib.sta_set_gemm_variant(h, 0))
+    qd_, kd_ = q.cpu().numpy(), k.cpu().numpy()
+    return {"q": max_rel(qd_, qr[:, :, order]), "k": max_rel(kd_, kr[:, :, order]), "v": max_rel(v, vr[:, :, order]),
+            "q_pose": max_rel(qd_[:, :, -1:], qr[:, :, :1]), "k_pose": max_rel(kd_[:, :, -1:], kr[:, :, :1]),
+            "v_pose": max_rel(v[:, :, -1:], vr[:, :, :1]),
+            "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0, "plan": plan}
+
+
+def check_qkv_pair(precision, S=4, hp=24, wp=32, Cdim=768, K=768, ints=False, seed=14):
+    """The decoder's paired launch (gemm_qkv_pair): a = attn.qkv (q | k | v) and b = cross_attn.projk|projv (k | v, nq = 0) on
+    two inputs in the decoder's row order [S*N patch rows | S pose rows], pose-token tail hint S.  Against an fp64 reference +
+    RoPE (pose token at position -1).  ints: small-integer operands, so that V (not rotated) must come out EXACT for both halves -
+    any column offset of the second GEMM in the one-grid launch shows up as a wrong integer."""
+    m, lib, h = kernel_handle(precision)
+    g = torch.Generator().manual_seed(seed)
+    N = hp * wp
+    nt = N + 1
+    heads = Cdim // 64
+    npad = (nt + 63) // 64 * 64
+
+    def operand(*shape, scale):
+        if ints:
+            return torch.randint(-2, 3, shape, generator=g).float()
+        return torch.randn(*shape, generator=g) * scale
+    xa, xb = operand(S, nt, K, scale=1.0), operand(S, nt, K, scale=1.0)        # reference order: pose token first
+    Wa, Wb = operand(3 * Cdim, K, scale=0.05), operand(2 * Cdim, K, scale=0.05)
+    ba, bb = operand(3 * Cdim, scale=0.1), operand(2 * Cdim, scale=0.1)
+
+    def dec(x):
+        return torch.cat([x[:, 1:].reshape(S * N, K), x[:, 0]], 0).contiguous()
+    q_a = torch.empty(S, heads, nt, 64, device=DEV)
+    k_a, k_b = torch.empty_like(q_a), torch.empty_like(q_a)
+    vt_a = torch.empty(S * heads * 64, npad, device=DEV)
+    vt_b = torch.empty_like(vt_a)
+    ins = [dev(t.numpy()) for t in (dec(xa), Wa, ba, dec(xb), Wb, bb)]
+    _lib.check(lib.sta_debug_set_tail_hint(h, 0))
+    _lib.check(lib.sta_debug_qkv_pair(h, *[t.data_ptr() for t in ins], S, N, K, Cdim, wp, q_a.data_ptr(), k_a.data_ptr(),
+                                      vt_a.data_ptr(), k_b.data_ptr(), vt_b.data_ptr(), st()))
+    torch.cuda.synchronize()
+    plan = last_plan(lib, h)
+    ya = (xa.reshape(S * nt, K).double() @ Wa.double().T + ba.double()).reshape(S, nt, 3, heads, 64).permute(2, 0, 3, 1, 4).numpy()
+    yb = (xb.reshape(S * nt, K).double() @ Wb.double().T + bb.double()).reshape(S, nt, 2, heads, 64).permute(2, 0, 3, 1, 4).numpy()
+    pos = grid_pos(S, hp, wp, pose_tok=True)
+    order = list(range(1, nt)) + [0]                             # device token order: patches, then the pose token
+    ref = {"q_a": rope2d_ref(ya[0], pos)[:, :, order], "k_a": rope2d_ref(ya[1], pos)[:, :, order], "v_a": ya[2][:, :, order],
+           "k_b": rope2d_ref(yb[0], pos)[:, :, order], "v_b": yb[1][:, :, order]}
+    got = {"q_a": q_a.cpu().numpy(), "k_a": k_a.cpu().numpy(), "k_b": k_b.cpu().numpy()}
+    res = {"plan": plan}
+    for name, vt in (("v_a", vt_a), ("v_b", vt_b)):
+        full = vt.cpu().numpy().reshape(S, heads, 64, npad)
+        got[name] = full[..., :nt].transpose(0, 1, 3, 2)
+        res[name + "_pad_abs"] = float(np.abs(full[..., nt:]).max()) if npad > nt else 0.0
+    for name in ref:
+        res[name] = max_rel(got[name], ref[name])
+        res[name + "_pose"] = max_rel(got[name][:, :, -1:], ref[name][:, :, -1:])
+    if ints:
+        res["v_exact_bad"] = int(sum((got[n].astype(np.float64) != ref[n]).sum() for n in ("v_a", "v_b")))
+    return res
 
 
 def check_attention_pose(precision, S=2, heads=2, n=196, kv_shift=0, sharp=1.0, seed=13):

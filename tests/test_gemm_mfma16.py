@@ -21,27 +21,37 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 A_DENSE, EPI_F32 = 0, 0
 
 
-def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0):
+def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0, tail=0, plan=None):
+    """tail: the last `tail` rows are pose-token rows (tail hint).  The output starts as NaN - an element no block writes fails -
+    or, with resid, as the residual itself (the in-place form x += A W^T: a row that two blocks add shows up as a wrong integer).
+    plan: the (family, m_tail) the launch must have run under.  Long K: operands in {-1, 0, 1} keep every sum exact."""
     import torch
     import gpu_checks as G
     from vista_slam_amd import _lib
     m, lib, h = G.kernel_handle(precision, variant)
     rng = np.random.default_rng(seed)
-    A = rng.integers(-3, 4, size=(M, K)).astype(np.float32)
-    Wt = rng.integers(-3, 4, size=(N, K)).astype(np.float32)
+    lim = 3 if K <= 256 else 1
+    A = rng.integers(-lim, lim + 1, size=(M, K)).astype(np.float32)
+    Wt = rng.integers(-lim, lim + 1, size=(N, K)).astype(np.float32)
     b = rng.integers(-8, 9, size=N).astype(np.float32)
     R = rng.integers(-8, 9, size=(M, N)).astype(np.float32) if resid else None
     ref = A.astype(np.float64) @ Wt.astype(np.float64).T + b.astype(np.float64)      # (integers: exact in float64)
     if resid:
         ref = ref + R.astype(np.float64)
     assert np.abs(ref).max() < 2 ** 11      # exact in fp32 and, for the plane epilogue, in the fp16 hi plane
-    out = torch.empty(M, N, device=G.DEV)
     Ad, Wd, bd = G.dev(A), G.dev(Wt), G.dev(b)
-    Rd = G.dev(R) if resid else None
-    _lib.check(lib.sta_debug_gemm(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, 0, via_f16,
-                                  Rd.data_ptr() if resid else None, out.data_ptr(), G.st()))
-    torch.cuda.synchronize()
-    _lib.check(lib.sta_set_gemm_variant(h, 0))
+    out = G.dev(R) if resid else torch.full((M, N), float("nan"), device=G.DEV)
+    _lib.check(lib.sta_debug_set_tail_hint(h, tail))
+    try:
+        _lib.check(lib.sta_debug_gemm(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, 0, via_f16,
+                                      out.data_ptr() if resid else None, out.data_ptr(), G.st()))
+        torch.cuda.synchronize()
+        got_plan = G.last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_debug_set_tail_hint(h, 0))
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    if plan is not None:
+        assert (got_plan["family"], got_plan["m_tail"]) == plan, got_plan
     got = out.cpu().numpy().astype(np.float64)
     bad = np.argwhere(got != ref)
     assert bad.size == 0, f"{len(bad)} wrong elements, first (row, col) {bad[:4].tolist()}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
@@ -63,6 +73,30 @@ def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0):
     dict(M=193, N=768, K=256, variant=0), dict(M=513, N=768, K=128, variant=0, resid=True), dict(M=700, N=768, K=96, variant=0),
 ])
 def test_gemm_integer_exact(prec, kw):
+    _int_gemm(prec, **kw)
+
+
+# Pose-token row tails (GemmParams::m_tail) on the skinny tail blocks, exact: forced families 2 (256x256), 3 (192x256), 4 (192x128)
+# and the automatic choice, fp32 and in-place-residual epilogues.  Under mlp_mx (precision f16x3m: mlp.fc2's f16mx arithmetic)
+# forced family 2 runs 192x256: 25 x 256 patch rows are no whole count of 192-row tiles, so the pose rows must stay in the main
+# tiles (before the row tail was checked against the remapped tile, the last main tile and the tail blocks both added them).
+TAIL_CASES = [dict(M=24 * 256 + 16, N=768, K=256, variant=2, tail=16, plan=(2, 16)),
+              dict(M=24 * 256 + 32, N=768, K=224, variant=2, tail=32, resid=True, plan=(2, 32)),
+              dict(M=36 * 192 + 1, N=768, K=224, variant=3, tail=1, plan=(3, 1)),
+              dict(M=36 * 192 + 20, N=768, K=160, variant=3, tail=20, resid=True, plan=(3, 20)),
+              dict(M=36 * 192 + 16, N=768, K=192, variant=4, tail=16, resid=True, plan=(5, 16)),
+              dict(M=36 * 192 + 16, N=768, K=3072, variant=0, tail=16, resid=True, plan=(5, 16)),
+              dict(M=12 * 192 + 2, N=2304, K=1024, variant=0, tail=2, plan=(5, 2))]
+MX_TAIL_CASES = [dict(M=36 * 192 + 16, N=768, K=1024, variant=3, tail=16, resid=True, plan=(3, 16)),
+                 dict(M=36 * 192 + 1, N=768, K=256, variant=4, tail=1, plan=(5, 1)),
+                 dict(M=12 * 192 + 32, N=2304, K=3072, variant=0, tail=32, resid=True, plan=(5, 32)),
+                 dict(M=48 * 192 + 16, N=768, K=256, variant=2, tail=16, resid=True, plan=(3, 16)),
+                 dict(M=25 * 256 + 16, N=768, K=256, variant=2, tail=16, resid=True, plan=(3, 0))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec,kw", [(p, kw) for p in ("f16x3", "f16") for kw in TAIL_CASES] + [("mlp_mx", kw) for kw in MX_TAIL_CASES])
+def test_gemm_tail_integer_exact(prec, kw):
     _int_gemm(prec, **kw)
 
 

@@ -56,29 +56,90 @@ def test_gemm_mlp_f16mx(G, kw):
     assert r["rel_l2"] < TOL["mlp_mx"], r
 
 
-@pytest.mark.parametrize("kw", [dict(resid=True), dict(variant=3, N=768, K=1024, tiles_m=22, resid=True), dict(tail=1), dict(tail=32, resid=True)])
+def _assert_tail(r, fam, tail, tol):
+    """The GEMM ran on tile family `fam` with the pose rows on the skinny tail blocks (m_tail == tail; tail=0: the case says the
+    rows sit in the main tiles), and both the whole matrix and the tail rows alone meet the bar."""
+    p = r["plan"]
+    assert (p["family"], p["m_tail"]) == (fam, tail), r
+    assert (p["tiles_m"] - 1) * p["bm"] < r["M"] - p["m_tail"] <= p["tiles_m"] * p["bm"], r
+    if p["m_tail"]:
+        assert (r["M"] - p["m_tail"]) % p["bm"] == 0, r
+    assert r["rel_l2"] < tol and r["rel_l2_tail"] < tol, r
+
+
+def _tail(G, prec, fam, tail=16, **kw):
+    r = G.check_gemm_tail(prec, tail=tail, **kw)
+    bm = 256 if kw.get("variant") == 2 else 192
+    r["M"] = kw["M"] if "M" in kw else kw.get("tiles_m", 12) * bm + tail
+    return r
+
+
+# mlp.fc2 under f16x3m: gemm2_tail<MX> on 192x128 and 192x256 (fragments straight from global memory).  Forced family 2 has no
+# f16mx fp32-epilogue kernel and runs 192x256: with 8 x 256 patch rows (no whole count of 192-row tiles) the pose rows must stay
+# in the main tiles, with 16 x 192 = 12 x 256 they go to the tail blocks.  Last: the product's own decision for the decoder's
+# mlp.fc2 at B = 10 @512x512 (20480 patch rows + 20 pose rows, K = 3072, in place): 256x256 by the cost model, 192x256 in f16mx.
+@pytest.mark.parametrize("kw", [dict(fam=5, resid=True), dict(fam=3, variant=3, N=768, K=1024, tiles_m=40, resid=True),
+                                dict(fam=5, tail=1), dict(fam=5, tail=32, resid=True), dict(fam=5, variant=4, N=768, tiles_m=40, tail=20),
+                                dict(fam=3, variant=2, tiles_m=12, resid=True), dict(fam=3, variant=2, tiles_m=8, resid=True, expect_tail=0),
+                                dict(fam=3, M=20480 + 20, tail=20, N=768, K=3072, resid=True, expect_tail=0)])
 def test_gemm_tail_rows_mlp_f16mx(G, kw):
     """The pose-token tail blocks of mlp.fc2 in the f16mx arithmetic (gemm2_tail<MX>: fragments straight from global memory)."""
-    r = G.check_gemm_tail("mlp_mx", **kw)
-    assert r["rel_l2"] < TOL["mlp_mx"], r
+    kw = dict(kw)
+    fam, expect = kw.pop("fam"), kw.pop("expect_tail", None)
+    r = _tail(G, "mlp_mx", fam, **kw)
+    _assert_tail(r, fam, kw.get("tail", 16) if expect is None else expect, TOL["mlp_mx"])
 
 
 @pytest.mark.parametrize("prec", ["f16x3", "f16"])
-@pytest.mark.parametrize("kw", [dict(), dict(resid=True), dict(act=1, via_f16=1), dict(variant=3, N=768, K=1024, tiles_m=22, resid=True),
-                                dict(variant=2, N=4096, K=128, tiles_m=6, act=1, via_f16=1), dict(tail=1), dict(tail=32, resid=True)])
+@pytest.mark.parametrize("kw", [dict(fam=5), dict(fam=5, resid=True), dict(fam=5, act=1, via_f16=1),
+                                dict(fam=3, variant=3, N=768, K=1024, tiles_m=40, resid=True),
+                                dict(fam=2, variant=2, N=4096, K=128, tiles_m=6, act=1, via_f16=1),
+                                dict(fam=2, variant=2, N=768, K=256, tiles_m=30, tail=32, resid=True),
+                                dict(fam=5, variant=4, N=768, K=256, tiles_m=40, tail=20, resid=True),
+                                dict(fam=5, tail=1), dict(fam=5, tail=32, resid=True)])
 def test_gemm_tail_rows(G, prec, kw):
-    """Skinny tail blocks (the decoder's pose-token rows) on every family / epilogue the decoder uses them with."""
-    r = G.check_gemm_tail(prec, **kw)
-    assert r["rel_l2"] < TOL[prec], r
+    """Skinny tail blocks (the decoder's pose-token rows) on every family / epilogue the decoder uses them with; every case is
+    above the small-grid predicate, so the tail blocks really run (the plan says so)."""
+    kw = dict(kw)
+    fam = kw.pop("fam")
+    r = _tail(G, prec, fam, **kw)
+    _assert_tail(r, fam, kw.get("tail", 16), TOL[prec])
 
 
+# plan: (family, m_tail) - small grids run 128x64 tiles with the pose rows in the main tiles; 24 x 32 tokens x 4 sequences at
+# C = 512 is past the small-grid predicate: 192x128 tiles, the 4 pose rows on tail blocks (V^T LDS-transpose path)
 @pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("kw", [dict(), dict(hp=14, wp=14, S=2), dict(hp=14, wp=14, S=2, variant=3), dict(hp=24, wp=32, S=4, K=64),
-                                dict(hp=24, wp=32, S=4, K=64, Cdim=512)])      # 192x128 tiles + tail blocks: V^T LDS-transpose path
+@pytest.mark.parametrize("kw", [dict(plan=(6, 0)), dict(hp=14, wp=14, S=2, plan=(6, 0)), dict(hp=14, wp=14, S=2, variant=3, plan=(6, 0)),
+                                dict(hp=24, wp=32, S=4, K=64, plan=(6, 0)), dict(hp=24, wp=32, S=4, K=64, Cdim=512, plan=(5, 4))])
 def test_qkv_rope_decoder_rows(G, prec, kw):
+    kw = dict(kw)
+    plan = kw.pop("plan")
     r = G.check_qkv_rope_decoder_rows(prec, **kw)
     assert r["q"] < TOL[prec] and r["k"] < TOL[prec] and r["v"] < TOL[prec], r
+    assert r["q_pose"] < TOL[prec] and r["k_pose"] < TOL[prec] and r["v_pose"] < TOL[prec], r
     assert r["vpad_abs"] == 0.0, r
+    assert (r["plan"]["family"], r["plan"]["m_tail"]) == plan, r
+
+
+# The decoder's paired launch (gemm_qkv_pair): attn.qkv + cross_attn.projk|projv.  24 x 32 tokens, S = 4: both halves past the
+# small-grid predicate, one launch (family 7), the 4 pose rows on tail blocks; S = 16 @14x14: 3136 patch rows are no whole
+# count of 192-row tiles - still one launch, the pose rows in the main tiles; S = 2 @24x32: below the predicate, two launches
+# (the last one: projk|projv on the small-grid family); precision f16: never paired (two 192x128 launches with tails).
+PAIR_CASES = [(dict(S=4), "f16x3", (7, 4)), (dict(S=4), "f16x3h", (7, 4)), (dict(S=16, hp=14, wp=14), "f16x3", (7, 0)),
+              (dict(S=16, hp=14, wp=14), "f16x3h", (7, 0)), (dict(S=2), "f16x3", (6, 0)), (dict(S=2), "f16x3h", (6, 0)),
+              (dict(S=4), "f16", (5, 4)), (dict(S=4, ints=True), "f16x3", (7, 4)), (dict(S=4, ints=True), "f16", (5, 4))]
+
+
+@pytest.mark.parametrize("kw,prec,plan", PAIR_CASES)
+def test_qkv_pair(G, kw, prec, plan):
+    r = G.check_qkv_pair(prec, **kw)
+    assert (r["plan"]["family"], r["plan"]["m_tail"]) == plan, r
+    tol = TOL["f16x3" if prec == "f16x3h" else prec]       # f16x3h: the transformer's GEMMs run f16x3
+    for name in ("q_a", "k_a", "v_a", "k_b", "v_b"):
+        assert r[name] < tol and r[name + "_pose"] < tol, (name, r)
+    assert r["v_a_pad_abs"] == 0.0 and r["v_b_pad_abs"] == 0.0, "V^T padding must stay zero"
+    if kw.get("ints"):
+        assert r["v_exact_bad"] == 0, r
 
 
 @pytest.mark.parametrize("prec", PRECS)

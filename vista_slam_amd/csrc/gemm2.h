@@ -210,6 +210,13 @@ __device__ __forceinline__ void head_epilogue_t(const GemmParams& p, const float
 // MX (round 6, mlp.fc2 in the f16mx arithmetic): the operands are f16mx rows - per K tile two fp16 MFMAs on the hi halves + ONE
 // block-scaled fp8 MFMA on the 32 pair bytes of the lane's half (bytes [64 + 32 lhi, 64 + 32 lhi + 32) of the row block: chunks
 // 4 + 2 lhi, 5 + 2 lhi - exactly what compute_tile's MX branch reads from LDS).
+// Which gemm2 instantiations carry the tail blocks: the dense 2-stage families of >= 192 rows (192x128, 192x256, 256x256, the
+// pair kernel) with the fp32 / in-place-residual epilogues, and GELU / QKV outside the f16mx arithmetic.  The host's launch
+// plan (sta_launch.inc: gemm_plan) keeps m_tail only where this holds.
+__host__ __device__ constexpr bool gemm2_has_tail(int amode, int epi, int bm, int nstg, bool mx) {
+    return amode == A_DENSE && nstg == 2 && bm >= 192 &&
+           (epi == EPI_F32 || epi == EPI_F32R || ((epi == EPI_GELU || epi == EPI_QKV) && !mx));
+}
 template <bool SPLIT, int EPI, int NW, bool MX = false>
 __device__ __forceinline__ void gemm2_tail(const GemmParams& p, const int tb, char* smem) {
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lhi = lane >> 5;
@@ -308,8 +315,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
 
     // skinny tail blocks come first in the grid (launch_gemm2 adds them): short, they overlap the first round of tiles
     int block_id = block_id_in;
-    constexpr bool HAS_TAIL = AMODE == A_DENSE && NSTG == 2 && ABL_ == 0 && BM >= 192 &&
-                              (EPI == EPI_F32 || EPI == EPI_F32R || ((EPI == EPI_GELU || EPI == EPI_QKV) && !MX));
+    constexpr bool HAS_TAIL = ABL_ == 0 && gemm2_has_tail(AMODE, EPI, BM, NSTG, MX);
     if constexpr (HAS_TAIL) {
         if (p.m_tail > 0) {
             const int ntail = (p.N + 31) >> 5;

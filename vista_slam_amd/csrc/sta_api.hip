@@ -105,6 +105,10 @@ struct StreamCtx {
     hipStream_t side = nullptr; float* side_skbuf = nullptr; hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
+// family: pick_family's ids (1 128x128 register-staged, 2 256x256, 3 192x256, 5 192x128, 6 128x64 small grid, 7 the paired
+// 192x128 launch, 8 halo-tiled 3x3 convolution); bm x bn = its tile; tiles_m x tiles_n main tiles cover rows [0, M - m_tail),
+// the m_tail rows after them run on the skinny tail blocks; ksplit K slices (slab_ks of them to the caller's slab).
+struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks; };
 struct sta_handle {
     sta_config cfg;
     int device = 0;
@@ -134,6 +138,7 @@ struct sta_handle {
     int opt[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // experiment switches (sta_debug_set_option; 0 = product behaviour)
     int tail_hint = 0;      // decode_impl: the last tail_hint rows of every dense GEMM are pose-token rows (GemmParams::m_tail)
     int gemm_variant = 0;   // tests / tools: 0 auto, 1..4 forced GEMM families, 8 = conv3h wherever legal, 9 = auto WITHOUT conv3h (A/B)
+    GemmPlan last_plan{};   // the plan of the last launch_gemm / paired launch (sta_debug_last_gemm_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
     // sta_decode_pos, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and rope_planes_kernel

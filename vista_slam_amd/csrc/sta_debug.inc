@@ -99,6 +99,57 @@ extern "C" int sta_debug_qkv_rope(sta_handle* h, const float* x, const float* W,
     return 0;
 }
 
+// The decoder's paired QKV launch (gemm_qkv_pair: attn.qkv + cross_attn.projk|projv) on inputs in the decoder's row order,
+// x_a / x_b = [S*ntok patch rows | S pose rows]: a = qkv (nq = nk = nv = C), b = projk|projv (nq = 0, nk = nv = C).  Outputs
+// hold ntok + 1 tokens per sequence, the pose token last: q_a, k_a, k_b fp32 [S, C/64, ntok + 1, 64]; vt_a, vt_b the
+// transposed buffers [S*C/64*64, roundup(ntok + 1, 64)] (padding zeroed before the launch).
+extern "C" int sta_debug_qkv_pair(sta_handle* h, const float* x_a, const float* w_a, const float* bias_a, const float* x_b,
+                                  const float* w_b, const float* bias_b, int S, int ntok, int K, int C, int wp,
+                                  float* q_a, float* k_a, float* vt_a, float* k_b, float* vt_b, void* stream) {
+    REQUIRE(h && x_a && w_a && bias_a && x_b && w_b && bias_b && q_a && k_a && vt_a && k_b && vt_b, "bad argument");
+    REQUIRE(S > 0 && ntok > 0 && wp > 0 && ntok % wp == 0 && C % 64 == 0 && K % GEMM_BK == 0, "bad shape");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int M = S * ntok + S, heads = C / 64, nt = ntok + 1, npad = rup(nt, 64);
+    CHK(ensure_rope(h, ntok / wp > wp ? ntok / wp : wp));
+    const int64_t hsz = (int64_t)S * heads * npad * 64;
+    CHK(ensure_ws(h, ((int64_t)2 * M * K + (int64_t)2 * 5 * C * K + 6 * hsz) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes a = ws.act(M, K, split), b = ws.act(M, K, split);
+    Lin La, Lb;
+    CHK(dbg_make_lin(h, ws, w_a, bias_a, 3 * C, K, 0, 3 * C, K, 1, 1, La, st));
+    CHK(dbg_make_lin(h, ws, w_b, bias_b, 2 * C, K, 0, 2 * C, K, 1, 1, Lb, st));
+    QKVOut oa, ob; oa.npad = ob.npad = npad;
+    oa.q = ws.planes(hsz, split); oa.k = ws.planes(hsz, split); oa.vt = ws.planes(hsz, split);
+    ob.q = ws.planes(hsz, split); ob.k = ws.planes(hsz, split); ob.vt = ws.planes(hsz, split);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    for (const Planes* v : {&oa.vt, &ob.vt}) { HIPCHK(hipMemsetAsync(v->hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(v->lo, 0, hsz * 2, st)); }
+    CHK(run_rows_to_planes(h, x_a, (int64_t)M * K, 1, M, K, a, st));
+    CHK(run_rows_to_planes(h, x_b, (int64_t)M * K, 1, M, K, b, st));
+    {
+        TailHint tail(h, S);
+        GemmParams pa, pb;
+        CHK(gp_qkv(h, pa, a, La, M, C, C, C, oa, ntok, heads, wp, 0, S * ntok));
+        CHK(gp_qkv(h, pb, b, Lb, M, 0, C, C, ob, ntok, heads, wp, 0, S * ntok));
+        CHK(gemm_qkv_pair(h, pa, pb, st));
+    }
+    CHK(dbg_planes_to_f32(h, oa.q, npad, S * heads, nt, 64, q_a, st));
+    CHK(dbg_planes_to_f32(h, oa.k, npad, S * heads, nt, 64, k_a, st));
+    CHK(dbg_planes_to_f32(h, ob.k, npad, S * heads, nt, 64, k_b, st));
+    CHK(dbg_planes_to_f32(h, oa.vt, 0, 1, S * heads * 64, npad, vt_a, st));
+    CHK(dbg_planes_to_f32(h, ob.vt, 0, 1, S * heads * 64, npad, vt_b, st));
+    return 0;
+}
+
+// The plan (gemm_plan) of the handle's last launch_gemm or paired QKV launch (family 7): out[8] = {family, bm, bn, m_tail,
+// tiles_m, tiles_n, ksplit, slab_ks}.
+extern "C" int sta_debug_last_gemm_plan(sta_handle* h, int* out) {
+    REQUIRE(h && out, "bad argument");
+    plan_out(h->last_plan, out);
+    return 0;
+}
+
 // q,k,v fp32 [S, heads, n*, 64] -> out fp32 [S, nq, heads*64]
 extern "C" int sta_debug_attention(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads,
                                    int nq, int nk, int kv_shift, float* out, void* stream) {

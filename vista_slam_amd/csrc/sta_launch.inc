@@ -59,9 +59,9 @@ static inline bool small_grid_m(int mode, int64_t M, int N) {
 // GEMM whose K slices would need a finisher kernel of their own (QKV, plane epilogues) is not split at all - the finisher is a
 // dispatch (5 - 7 us) for a K loop that two slices shorten by less -, one whose slices are summed by the LayerNorm kernel that
 // follows anyway (in-place residual GEMMs) takes two.  Measured against ceil(256 / tiles_r) everywhere: encode -2 %, 5-edge
-// scheduler -1.7 %, one pair @224 +3.5 %, one pair @512x384 +1 %.  h->opt[1] == 1: the old rule (A/B).
-static inline int sg_slices(const sta_handle* h, int tiles_r, bool own_finisher = false) {
-    if (h->opt[1] != 1) { const int f = 256 / tiles_r; if (f >= 2) return f; if (own_finisher) return 1; }
+// scheduler -1.7 %, one pair @224 +3.5 %, one pair @512x384 +1 %.  old_rule (h->opt[1] == 1): the old rule (A/B).
+static inline int sg_slices(bool old_rule, int tiles_r, bool own_finisher = false) {
+    if (!old_rule) { const int f = 256 / tiles_r; if (f >= 2) return f; if (own_finisher) return 1; }
     return (256 + tiles_r - 1) / tiles_r;
 }
 static inline bool small_grid(const sta_handle* h, int64_t M, int N) { return small_grid_m(h->small_grid_mode, M, N); }
@@ -140,12 +140,167 @@ extern "C" int sta_debug_pick_family(int amode, int epi, long long M, int N, int
 }
 #endif
 
+// ------------------------------------------------------------------------------------------ launch plan
+// Everything launch_gemm decides before it launches - tile family, tile size, the pose-token row tail, K slices - as ONE pure host
+// function of the shape and the handle's switches: launch_gemm runs exactly this plan, sta_debug_gemm_plan exposes it to the
+// host-only sweep (tests/test_gemm_plan.py) and sta_debug_last_gemm_plan reads back the plan of a handle's last launch.
+// The plan itself: struct GemmPlan (sta_api.hip, next to the handle that keeps the last one).
+struct PlanQuery {
+    int amode, epi; int M, N, K;                // M: every row, the tail rows included
+    bool split, mx;                             // split: f16x3 / f16x3h / f16x3m;  mx: f16mx rows and weights
+    int tail_hint, forced;                      // forced: sta_set_gemm_variant (0 / 9: automatic)
+    int sg_mode, head_gemm, old_slices;         // h->small_grid_mode, h->opt[0] == 1, h->opt[1] == 1
+    bool deterministic;
+    int inplace;                                // EPI_F32 added in place to its residual: 0 no, 1 with a caller slab, 2 without
+    int cstride, Ho, Wo;                        // convolutions only
+};
+static GemmPlan plan_tiles(int family, int M, int m_tail, int N, int Ho, int Wo) {
+    GemmPlan g{family, 0, 0, m_tail, 0, 0, 1, 0};
+    switch (family) {
+        case 1: g.bm = GEMM_BM; g.bn = GEMM_BN; break;
+        case 2: g.bm = 256; g.bn = 256; break;
+        case 3: g.bm = 192; g.bn = 256; break;
+        case 5: case 7: g.bm = 192; g.bn = 128; break;
+        case 6: g.bm = 128; g.bn = 64; break;
+        case 8: g.bm = 256; g.bn = N == 128 ? 128 : 256; break;      // 8 rows x 32 pixels of one image
+    }
+    if (g.bm == 0) return g;
+    if (family == 8) g.tiles_m = (int)((int64_t)M / ((int64_t)Ho * Wo) * ((Ho + 7) / 8) * ((Wo + 31) / 32));
+    else g.tiles_m = (M - m_tail + g.bm - 1) / g.bm;
+    g.tiles_n = (N + g.bn - 1) / g.bn;
+    return g;
+}
+// f16mx kernels exist for the DPT head's epilogues and (round 6, precision f16x3m) for the fp32 / in-place-residual epilogues of
+// dense GEMMs: mlp.fc2.  The latter only on the 192-row and small-grid families (no 256x256 instantiation: compile time).
+static bool mx_epi(int amode, int epi) {
+    return epi == EPI_F16 || epi == EPI_CONVT || epi == EPI_HEAD || (amode == A_DENSE && (epi == EPI_F32R || epi == EPI_F32));
+}
+// Is there a kernel for this family / epilogue / arithmetic?  Mirrors the launch branches of launch_gemm (each of which REQUIREs
+// it again instead of launching nothing).
+static bool plan_has_kernel(int amode, int epi, int family, bool mx, int N, int cstride) {
+    if (mx && !mx_epi(amode, epi)) return false;
+    if (family == 8) return amode == A_CONV3 && (epi == EPI_F16 || epi == EPI_HEAD) && cstride == 1 && (N == 128 || (N == 256 && epi == EPI_F16));
+    if (epi == EPI_HEAD) return family == 5 && N == 128;
+    switch (family) {
+        case 1: return !mx;
+        case 2: return epi != EPI_QKV && (!mx || epi == EPI_F16 || epi == EPI_CONVT);
+        case 3: return epi != EPI_QKV;
+        case 5: case 6: return true;
+        default: return false;
+    }
+}
+static int gemm_plan(const PlanQuery& q, GemmPlan& out) {
+    // Row tail hint (decode_impl: the 2B pose-token rows after the 2B x N patch rows).  Tile rules below look at the patch
+    // rows; the tail is kept only where the FINAL family tiles them exactly and has tail blocks (checked last).
+    const bool mx_f32 = q.epi == EPI_F32R || q.epi == EPI_F32;       // mlp.fc2 in the f16mx arithmetic (precision f16x3m)
+    int m_tail = 0;
+    if (q.amode == A_DENSE && q.tail_hint > 0 && q.tail_hint <= 32 && q.M > q.tail_hint && (!q.mx || mx_f32) && q.N % 128 == 0 && q.forced != 1) {
+        if (!small_grid_m(q.sg_mode, q.M - q.tail_hint, q.N)) m_tail = q.tail_hint;   // throughput scale only (the small-grid family splits K instead)
+    }
+    const int M = q.M - m_tail;
+    // Tile family (pick_family above: cost model calibrated on the measured table); a forced family never displaces the
+    // small-grid one, whose split-K plumbing the callers rely on
+    const FamilyQuery fq{q.amode, q.epi, M, q.N, q.K, q.split ? 1 : 0, q.cstride, q.Ho, q.Wo, q.sg_mode, q.head_gemm};
+    int variant = pick_family(fq);
+    if (q.forced == 9 && variant == 8) { FamilyQuery f2 = fq; f2.Wo = 0; variant = pick_family(f2); }     // A/B: no halo kernel
+    int ksplit = 1, slab_ks = 0;
+    // Small grids (SLAM scale: 224x224, batch 1..8 -> M = 196..3200 rows; the coarse DPT levels at any scale): 128x64 tiles,
+    // 3-stage DMA ring, and split-K so that ~256 workgroups stream the weights once instead of 16-64 workgroups looping over
+    // all of K.  The K slices go to fp32 SLABS that the next kernel sums (resid_ln_kernel / qkv_finish_kernel /
+    // splitk_finish_kernel: fixed order, bit-reproducible) - the product path.  Only an in-place residual GEMM whose caller
+    // passed no slab (forced tile families, N > 1024) still adds its slices with fp32 atomics, and not in deterministic mode.
+    if (variant == 6) {
+        const int tiles_r = ((M + 127) / 128) * (q.N / 64);
+        const int tiles = q.deterministic ? (1 << 30) : tiles_r;    // deterministic: no ATOMIC split-K (the slab forms below have a fixed order)
+        if (q.amode == A_DENSE && q.epi == EPI_F32 && q.inplace == 1) {
+            // the caller finishes the GEMM in the LayerNorm kernel that follows (gemm_resid_ln): slices store partial tiles
+            // to slabs instead of atomically adding to the residual stream (the device-scope fp32 atomics of 256 workgroups
+            // cost more than the 4-32 K tiles of a slice); fixed summation order -> also taken in deterministic mode
+            // (swept at M = 196 / 394 / 1970: a target of 128 / 192 / 256 / 384 / 512 workgroups -> encode 2.50 / 2.40 / 2.38 /
+            // 2.49 / 2.55 ms: one workgroup per CU; more slices cost more slab traffic than their shorter K loops save)
+            int ks = tiles_r < 256 ? sg_slices(q.old_slices, tiles_r) : 1;
+            const int max_ks = q.K / 128;                 // keep >= 4 K tiles per slice
+            if (ks > max_ks) ks = max_ks;
+            while (ks > 1 && (int64_t)ks * M * q.N > SKBUF_ELEMS) --ks;
+            if (ks > 1) { ksplit = ks; slab_ks = ks; }
+        } else if (q.amode == A_DENSE && q.epi == EPI_F32 && q.inplace == 2 && tiles < 256) {
+            int ks = (256 + tiles - 1) / tiles;
+            const int max_ks = q.K / 128;                 // keep >= 4 K tiles per slice
+            if (ks > max_ks) ks = max_ks;
+            if (ks > 1) ksplit = ks;
+        }
+        // QKV-epilogue GEMMs (attn.qkv, cross_attn.projq / projk|projv) on small grids: K slices to slabs, qkv_finish_kernel
+        // applies bias + RoPE and writes Q / K / V^T (un-split attn.qkv at M = 196: 96 workgroups x 32 K tiles = 25 us)
+        if (q.amode == A_DENSE && q.epi == EPI_QKV && tiles_r <= 192 && q.K >= 512) {
+            int ks = sg_slices(q.old_slices, tiles_r, true);
+            const int max_ks = q.K / 256;                 // keep >= 8 K tiles per slice
+            if (ks > max_ks) ks = max_ks;
+            while (ks > 1 && (int64_t)ks * M * q.N > SKBUF_ELEMS) --ks;
+            if (ks > 1) ksplit = ks;
+        }
+        // plane-epilogue GEMMs / convs on tiny grids (DPT levels at SLAM scale: 16-64 workgroups looping over K = 2304 ..
+        // 6912): split K into fp32 partial sums, a finishing kernel applies bias / activation / residuals.  Worth two
+        // extra tiny launches only when the K loop is long and the grid leaves most of the chip idle (swept with atomics: <= 96 /
+        // 160 / 256 tiles -> DPT 1.00 / 0.85 / 0.83 ms per view; with slabs, 5-edge scheduler: <= 192 / 256 tiles -> 6.04 / 5.89 ms).  An in-kernel fix-up (last slice finishes the tile behind a
+        // device-scope fence + ticket) was 1.7x SLOWER than this: the fence writes back / invalidates the XCD's L2.
+        if (q.epi == EPI_F16 && tiles_r <= 256 && q.K >= 1024 && q.N % 4 == 0 && (int64_t)M * q.N <= SKBUF_ELEMS) {
+            int ks = sg_slices(q.old_slices, tiles_r, true);
+            const int max_ks = q.K / 256;                 // keep >= 8 K tiles per slice
+            if (ks > max_ks) ks = max_ks;
+            while (ks > 1 && (int64_t)ks * M * q.N > SKBUF_ELEMS) --ks;      // one slab per K slice
+            if (ks > 1) ksplit = ks;
+        }
+    }
+    // forced families (tests / tools): 1 = 128x128 register-staged, 2 = 256x256, 3 = 192x256 (both wherever N % 256 == 0 and
+    // the epilogue is not the RoPE one), 4 = 192x128 everywhere
+    if ((q.forced == 2 || q.forced == 3) && variant != 6 && q.N % 128 == 0)
+        variant = (q.N % 256 == 0 && q.epi != EPI_QKV) ? q.forced : 5;
+    if (q.forced == 4 && variant != 6 && q.N % 128 == 0) variant = 5;
+    if (q.forced == 1) variant = 1;
+    // 8 forced (tests): the halo-tiled 3x3 convolution wherever it is legal (stride 1, Cout 128 / 256)
+    if (q.amode == A_CONV3 && (q.epi == EPI_F16 || q.epi == EPI_HEAD) && q.cstride == 1 && (q.N == 128 || q.N == 256) && q.forced == 8) variant = 8;
+    if (variant != 6) { ksplit = 1; slab_ks = 0; }
+    // f16mx arithmetic: no form of the register-staged kernel (use_mx() already requires N % 64 == 0), and the fp32 epilogues
+    // have no 256x256 one.  Remapped BEFORE the row tail is checked: the tail must fit the tile the launch really uses.
+    if (q.mx && variant == 1) variant = 5;
+    if (q.mx && mx_f32 && variant == 2) variant = q.N % 256 == 0 ? 3 : 5;
+    GemmPlan g = plan_tiles(variant, q.M, 0, q.N, q.Ho, q.Wo);
+    if (m_tail && g.bm && (q.M - m_tail) % g.bm == 0 && gemm2_has_tail(q.amode, q.epi, g.bm, variant == 6 ? 3 : 2, q.mx))
+        g = plan_tiles(variant, q.M, m_tail, q.N, q.Ho, q.Wo);
+    g.ksplit = ksplit; g.slab_ks = slab_ks;
+    REQUIRE(plan_has_kernel(q.amode, q.epi, variant, q.mx, q.N, q.cstride),
+            "internal: no kernel for tile family %d, epilogue %d, f16mx %d, N = %d", variant, q.epi, (int)q.mx, q.N);
+    out = g;
+    return 0;
+}
+static PlanQuery plan_query(const sta_handle* h, int amode, int epi, const GemmParams& p) {
+    PlanQuery q{amode, epi, p.M, p.N, p.K, h->prec != STA_PREC_F16, p.mx != 0, h->tail_hint, h->gemm_variant,
+                h->small_grid_mode, h->opt[0] == 1 ? 1 : 0, h->opt[1] == 1 ? 1 : 0, h->deterministic,
+                (epi == EPI_F32 && p.resid == p.C32) ? (p.slab ? 1 : 2) : 0, p.cstride, p.Ho, p.Wo};
+    return q;
+}
+#ifdef STA_TEST_HOOKS
+static void plan_out(const GemmPlan& g, int* out) {
+    const int v[8] = {g.family, g.bm, g.bn, g.m_tail, g.tiles_m, g.tiles_n, g.ksplit, g.slab_ks};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
+extern "C" int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, int precision, int mx, int tail_hint, int forced_variant, int* out) {
+    REQUIRE(out && M_all > 0 && N > 0 && K > 0 && (amode == A_DENSE || amode == A_CONV3), "bad argument");
+    REQUIRE(precision == STA_PREC_F16 || precision == STA_PREC_F16X3 || precision == STA_PREC_F16X3H || precision == STA_PREC_F16X3M, "bad precision");
+    PlanQuery q{amode, epi, M_all, N, K, precision != STA_PREC_F16, mx != 0, tail_hint, forced_variant, 0, 0, 0, false, 0, 0, 0, 0};
+    GemmPlan g;
+    CHK(gemm_plan(q, g));
+    plan_out(g, out);
+    return 0;
+}
+#endif
+
+static int no_mx_kernel(int family, int epi) { return set_err("internal: tile family %d has no f16mx form for epilogue %d", family, epi); }
 // slab_ks_out: K slices a slab GEMM wrote (0: it did not take the slab path) - the caller's finisher sums exactly those
 template <int AMODE, int EPI>
 static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, int* slab_ks_out = nullptr) {
     GemmParams p = p_in;
     p.range = h->range;
-    int slab_ks = 0;
     if (slab_ks_out) *slab_ks_out = 0;
     p.zero_page = h->zero_page;
     REQUIRE(p.K % GEMM_BK == 0, "GEMM K=%d must be a multiple of %d", p.K, GEMM_BK);
@@ -157,91 +312,17 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
     if (AMODE == A_CONV3) REQUIRE((int64_t)p.a_rp * 128 < ((int64_t)1 << 32), "convolution input of %lld pixels exceeds the 32-bit offset range of the tap loader", (long long)p.a_rp);
     if (h->dry) return 0;
     const bool split = h->prec != STA_PREC_F16;
-    // Row tail hint (decode_impl: the 2B pose-token rows after the 2B x N patch rows).  Tile rules below look at the
-    // patch rows; the tail is kept only where a gemm2 family tiles them exactly (checked after the family is chosen).
-    p.m_tail = 0;
-    constexpr bool MX_F32 = EPI == EPI_F32R || EPI == EPI_F32;       // mlp.fc2 in the f16mx arithmetic (precision f16x3m): these epilogues have MX tail blocks
-    if (AMODE == A_DENSE && h->tail_hint > 0 && h->tail_hint <= 32 && p.M > h->tail_hint && (!p.mx || MX_F32) && p.N % 128 == 0 && h->gemm_variant != 1) {
-        if (!small_grid(h, p.M - h->tail_hint, p.N)) p.m_tail = h->tail_hint;   // throughput scale only (the small-grid family splits K instead)
-    }
-    const int M_all = p.M;
-    p.M -= p.m_tail;
-    // Tile family (pick_family above: cost model calibrated on the measured table); a forced family never displaces the
-    // small-grid one, whose split-K plumbing the callers rely on
-    const FamilyQuery fq{AMODE, EPI, p.M, p.N, p.K, split ? 1 : 0, p.cstride, p.Ho, p.Wo, h->small_grid_mode, h->opt[0] == 1 ? 1 : 0};
-    int variant = pick_family(fq);
-    if (h->gemm_variant == 9 && variant == 8) { FamilyQuery f2 = fq; f2.Wo = 0; variant = pick_family(f2); }     // A/B: no halo kernel
-    // Small grids (SLAM scale: 224x224, batch 1..8 -> M = 196..3200 rows; the coarse DPT levels at any scale): 128x64 tiles,
-    // 3-stage DMA ring, and split-K so that ~256 workgroups stream the weights once instead of 16-64 workgroups looping over
-    // all of K.  The K slices go to fp32 SLABS that the next kernel sums (resid_ln_kernel / qkv_finish_kernel /
-    // splitk_finish_kernel: fixed order, bit-reproducible) - the product path.  Only an in-place residual GEMM whose caller
-    // passed no slab (forced tile families, N > 1024) still adds its slices with fp32 atomics, and not in deterministic mode.
-    if (variant == 6) {
-        const int tiles_r = ((p.M + 127) / 128) * (p.N / 64);
-        const int tiles = h->deterministic ? (1 << 30) : tiles_r;    // deterministic: no ATOMIC split-K (the slab forms below have a fixed order)
-        if (AMODE == A_DENSE && EPI == EPI_F32 && p.resid == p.C32 && p.slab) {
-            // the caller finishes the GEMM in the LayerNorm kernel that follows (gemm_resid_ln): slices store partial tiles
-            // to slabs instead of atomically adding to the residual stream (the device-scope fp32 atomics of 256 workgroups
-            // cost more than the 4-32 K tiles of a slice); fixed summation order -> also taken in deterministic mode
-            // (swept at M = 196 / 394 / 1970: a target of 128 / 192 / 256 / 384 / 512 workgroups -> encode 2.50 / 2.40 / 2.38 /
-            // 2.49 / 2.55 ms: one workgroup per CU; more slices cost more slab traffic than their shorter K loops save)
-            int ks = tiles_r < 256 ? sg_slices(h, tiles_r) : 1;
-            const int max_ks = p.K / 128;                 // keep >= 4 K tiles per slice
-            if (ks > max_ks) ks = max_ks;
-            while (ks > 1 && (int64_t)ks * p.M * p.N > SKBUF_ELEMS) --ks;
-            if (ks > 1) { p.ksplit = ks; slab_ks = ks; } else p.slab = nullptr;
-        } else if (AMODE == A_DENSE && EPI == EPI_F32 && p.resid == p.C32 && tiles < 256) {
-            int ks = (256 + tiles - 1) / tiles;
-            const int max_ks = p.K / 128;                 // keep >= 4 K tiles per slice
-            if (ks > max_ks) ks = max_ks;
-            if (ks > 1) p.ksplit = ks;
-        }
-        // QKV-epilogue GEMMs (attn.qkv, cross_attn.projq / projk|projv) on small grids: K slices to slabs, qkv_finish_kernel
-        // applies bias + RoPE and writes Q / K / V^T (un-split attn.qkv at M = 196: 96 workgroups x 32 K tiles = 25 us)
-        if (AMODE == A_DENSE && EPI == EPI_QKV && tiles_r <= 192 && p.K >= 512) {
-            int ks = sg_slices(h, tiles_r, true);
-            const int max_ks = p.K / 256;                 // keep >= 8 K tiles per slice
-            if (ks > max_ks) ks = max_ks;
-            while (ks > 1 && (int64_t)ks * p.M * p.N > SKBUF_ELEMS) --ks;
-            if (ks > 1) { p.ksplit = ks; p.skbuf = lane_skbuf(h); }
-        }
-        // plane-epilogue GEMMs / convs on tiny grids (DPT levels at SLAM scale: 16-64 workgroups looping over K = 2304 ..
-        // 6912): split K into fp32 partial sums, a finishing kernel applies bias / activation / residuals.  Worth two
-        // extra tiny launches only when the K loop is long and the grid leaves most of the chip idle (swept with atomics: <= 96 /
-        // 160 / 256 tiles -> DPT 1.00 / 0.85 / 0.83 ms per view; with slabs, 5-edge scheduler: <= 192 / 256 tiles -> 6.04 / 5.89 ms).  An in-kernel fix-up (last slice finishes the tile behind a
-        // device-scope fence + ticket) was 1.7x SLOWER than this: the fence writes back / invalidates the XCD's L2.
-        if (EPI == EPI_F16 && tiles_r <= 256 && p.K >= 1024 && p.N % 4 == 0 && (int64_t)p.M * p.N <= SKBUF_ELEMS) {
-            int ks = sg_slices(h, tiles_r, true);
-            const int max_ks = p.K / 256;                 // keep >= 8 K tiles per slice
-            if (ks > max_ks) ks = max_ks;
-            while (ks > 1 && (int64_t)ks * p.M * p.N > SKBUF_ELEMS) --ks;      // one slab per K slice
-            if (ks > 1) { p.ksplit = ks; p.skbuf = lane_skbuf(h); }
-        }
-    }
-    // forced families (tests / tools): 1 = 128x128 register-staged, 2 = 256x256, 3 = 192x256 (both wherever N % 256 == 0 and
-    // the epilogue is not the RoPE one), 4 = 192x128 everywhere
-    if ((h->gemm_variant == 2 || h->gemm_variant == 3) && variant != 6 && p.N % 128 == 0)
-        variant = (p.N % 256 == 0 && EPI != EPI_QKV) ? h->gemm_variant : 5;
-    if (h->gemm_variant == 4 && variant != 6 && p.N % 128 == 0) variant = 5;
-    if (h->gemm_variant == 1) variant = 1;
-    // 8 forced (tests): the halo-tiled 3x3 convolution wherever it is legal (stride 1, Cout 128 / 256)
-    if (AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD) && p.cstride == 1 && (p.N == 128 || p.N == 256) && h->gemm_variant == 8) variant = 8;
-    if (variant != 6) { p.ksplit = 1; slab_ks = 0; }
-    if (slab_ks == 0) p.slab = nullptr;
-    if (slab_ks_out) *slab_ks_out = slab_ks;
-    p.M = M_all;
-    {
-        const int bm_v = variant == 2 ? 256 : ((variant == 3 || variant == 5) ? 192 : 0);
-        constexpr bool tail_epi = EPI == EPI_F32 || EPI == EPI_F32R || EPI == EPI_GELU || EPI == EPI_QKV;   // gemm2_body: HAS_TAIL
-        if (p.m_tail && (bm_v == 0 || (p.M - p.m_tail) % bm_v != 0 || !tail_epi)) p.m_tail = 0;
-    }
-    // f16mx kernels exist for the DPT head's epilogues and (round 6, precision f16x3m) for the fp32 / in-place-residual epilogues of
-    // dense GEMMs: mlp.fc2.  The latter only on the 192-row and small-grid families (no 256x256 instantiation: compile time).
-    constexpr bool MX_EPI = EPI == EPI_F16 || EPI == EPI_CONVT || EPI == EPI_HEAD || (AMODE == A_DENSE && MX_F32);
-    constexpr bool MX_256 = MX_EPI && !MX_F32;
-    REQUIRE(MX_EPI || !p.mx, "internal: f16mx arithmetic in a GEMM without an f16mx kernel");
-    if (p.mx && variant == 1) variant = 5;     // no f16mx form of the register-staged kernel (use_mx() already requires N % 64 == 0)
-    if (p.mx && MX_F32 && variant == 2) variant = p.N % 256 == 0 ? 3 : 5;
+    GemmPlan g;
+    CHK(gemm_plan(plan_query(h, AMODE, EPI, p), g));
+    h->last_plan = g;
+    const int variant = g.family;
+    p.m_tail = g.m_tail;
+    p.ksplit = g.ksplit;
+    if (g.ksplit > 1 && (EPI == EPI_QKV || EPI == EPI_F16)) p.skbuf = lane_skbuf(h);
+    if (g.slab_ks == 0) p.slab = nullptr;
+    if (slab_ks_out) *slab_ks_out = g.slab_ks;
+    constexpr bool MX_EPI = EPI == EPI_F16 || EPI == EPI_CONVT || EPI == EPI_HEAD || (AMODE == A_DENSE && (EPI == EPI_F32R || EPI == EPI_F32));
+    constexpr bool MX_256 = MX_EPI && EPI != EPI_F32R && EPI != EPI_F32;
     // per-launch HIP-event timing (bench / tools): every launch (mode 2), or only the launches of ONE kernel symbol
     // (mode 3, sta_kernel_timing_filter: the event pairs break back-to-back dispatch, ~3.5 us each, so the timed region of
     // bench.py carries them on the dominant kernel only)
@@ -275,32 +356,35 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
                 if (p.mx) CHK((launch_conv3h<true, EPI, 256, 256, true>(p, st, h->device)));
                 else if (split) CHK((launch_conv3h<true, EPI, 256, 256, false>(p, st, h->device)));
                 else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 256, false>(p, st, h->device))));
-            }
+            } else REQUIRE(false, "internal: no halo-tiled convolution for epilogue %d at N = %d", EPI, p.N);
         }
     }
+    // gemm_plan admitted only instantiated kernels; every branch below that has none for this plan fails instead of returning 0
+    // with the output unwritten
     if (variant == 2 || variant == 3) REQUIRE(EPI != EPI_QKV, "internal: the RoPE epilogue exists on the 192x128 / 128x64 / 128x128 tiles only");
     if (variant == 8) {
+        REQUIRE(AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD), "internal: halo-tiled family for a GEMM without it");
     } else
     if constexpr (EPI == EPI_HEAD) {      // exists for the 192x128 family only (conv3_head checks the shape)
         REQUIRE(variant == 5 && p.N == 128, "internal: fused head epilogue on a tile family without it");
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); }
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
         else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device)));
         else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device))));
     } else
     if (variant == 2) {
       if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_256) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4, 2, true>(p, st, h->device))); }
+        if (p.mx) { if constexpr (MX_256) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
         else if (split) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device)));
         else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device))));
-      }
+      } else REQUIRE(false, "internal: no 256x256 RoPE epilogue");
     } else if (variant == 3) {
       if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4, 2, true>(p, st, h->device))); }
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
         else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device)));
         else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device))));
-      }
+      } else REQUIRE(false, "internal: no 192x256 RoPE epilogue");
     } else if (variant == 5) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); }
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
         else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device)));
         else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device))));
     } else if (variant == 6) {
@@ -315,7 +399,7 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
             if constexpr (MX_EPI) {
                 if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3, true>(p, st, h->device)));
                 else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3, true>(p, st, h->device)));
-            }
+            } else return no_mx_kernel(variant, EPI);
         } else if (split) {
             if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3>(p, st, h->device)));
             else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device)));
@@ -335,6 +419,7 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
             HIPCHK(hipGetLastError());
         }
     } else {
+        REQUIRE(variant == 1 && !p.mx, "internal: tile family %d (f16mx %d) has no launch", variant, p.mx);
         int tm = (p.M + GEMM_BM - 1) / GEMM_BM, tn = (p.N + GEMM_BN - 1) / GEMM_BN;
         dim3 grid((unsigned)(tm * tn));
         if (split) {
@@ -434,10 +519,33 @@ static int gemm_qkv(sta_handle* h, const Planes& A, const Lin& W, int M, int nq,
 }
 // Two QKV-epilogue GEMMs that do not depend on each other as ONE launch (gemm2_pair_kernel) when both run on the 192x128
 // family at throughput scale; otherwise two launches.  Decoder: attn.qkv on norm1(x) + cross_attn.projk|projv on norm_y.
-static bool qkv_pair_one_launch(const sta_handle* h, const GemmParams& pa, const GemmParams& pb) {
-    auto big = [h](const GemmParams& p) { return p.N % 128 == 0 && !small_grid(h, p.M, p.N); };
-    return h->prec != STA_PREC_F16 && !pa.mx && !pb.mx && big(pa) && big(pb) && pa.K == pb.K && pa.M == pb.M && auto_family(h);
+// The one decision (a pure host function like gemm_plan; sta_debug_qkv_pair_plan): true = one launch, with the pose-token rows
+// of both halves as tail blocks (*m_tail) where the patch rows are whole 192-row tiles.
+static bool qkv_pair_plan(bool split, bool auto_fam, int sg_mode, int tail_hint, int M_a, int N_a, int K_a, bool mx_a,
+                          int M_b, int N_b, int K_b, bool mx_b, int* m_tail) {
+    auto big = [sg_mode](int M, int N) { return N % 128 == 0 && !small_grid_m(sg_mode, M, N); };
+    *m_tail = 0;
+    if (!(split && !mx_a && !mx_b && big(M_a, N_a) && big(M_b, N_b) && K_a == K_b && M_a == M_b && auto_fam)) return false;
+    const int t = tail_hint;
+    if (t > 0 && t <= 32 && M_a > t && (M_a - t) % 192 == 0 && !small_grid_m(sg_mode, M_a - t, N_a) && !small_grid_m(sg_mode, M_b - t, N_b) &&
+        gemm2_has_tail(A_DENSE, EPI_QKV, 192, 2, false))
+        *m_tail = t;
+    return true;
 }
+static bool qkv_pair_one_launch(const sta_handle* h, const GemmParams& pa, const GemmParams& pb, int* m_tail = nullptr) {
+    int mt;
+    return qkv_pair_plan(h->prec != STA_PREC_F16, auto_family(h), h->small_grid_mode, h->tail_hint, pa.M, pa.N, pa.K, pa.mx != 0,
+                         pb.M, pb.N, pb.K, pb.mx != 0, m_tail ? m_tail : &mt);
+}
+#ifdef STA_TEST_HOOKS
+extern "C" int sta_debug_qkv_pair_plan(int precision, int M, int N_a, int N_b, int K, int mx_a, int mx_b, int tail_hint, int forced_variant, int* out) {
+    REQUIRE(out && M > 0 && N_a > 0 && N_b > 0 && K > 0, "bad argument");
+    REQUIRE(precision == STA_PREC_F16 || precision == STA_PREC_F16X3 || precision == STA_PREC_F16X3H || precision == STA_PREC_F16X3M, "bad precision");
+    out[0] = qkv_pair_plan(precision != STA_PREC_F16, forced_variant == 0 || forced_variant == 9, 0, tail_hint, M, N_a, K, mx_a != 0,
+                           M, N_b, K, mx_b != 0, &out[1]) ? 1 : 0;
+    return 0;
+}
+#endif
 // Side lanes of the current context (dpt_impl, decode_impl): inside one call the library forks an internal second stream for the
 // launches that are off the call's critical chain.  sta_set_side_lanes(h, mode) is the application's switch (include/sta_mi355.h):
 //   STA_LANES_OFF / STA_LANES_ON: what they say (results are bit-identical either way);
@@ -471,15 +579,15 @@ static int gemm_qkv_pair(sta_handle* h, const GemmParams& pa_in, const GemmParam
     GemmParams pa = pa_in, pb = pb_in;
     pa.range = pb.range = h->range;
     if (h->dry) return 0;
-    if (!qkv_pair_one_launch(h, pa, pb)) {
+    int m_tail = 0;
+    if (!qkv_pair_one_launch(h, pa, pb, &m_tail)) {
         CHK((launch_gemm<A_DENSE, EPI_QKV>(h, pa, st)));
         return launch_gemm<A_DENSE, EPI_QKV>(h, pb, st);
     }
     pa.zero_page = pb.zero_page = h->zero_page;
     pa.ksplit = pb.ksplit = 1;
-    // pose-token rows as skinny tail blocks (GemmParams::m_tail), same rule as launch_gemm
-    pa.m_tail = pb.m_tail = (h->tail_hint > 0 && h->tail_hint <= 32 && pa.M > h->tail_hint && (pa.M - h->tail_hint) % 192 == 0 &&
-                             !small_grid(h, pa.M - h->tail_hint, pa.N) && !small_grid(h, pb.M - h->tail_hint, pb.N)) ? h->tail_hint : 0;
+    pa.m_tail = pb.m_tail = m_tail;       // pose-token rows as skinny tail blocks (GemmParams::m_tail)
+    h->last_plan = GemmPlan{7, 192, 128, m_tail, (pa.M - m_tail + 191) / 192, pa.N / 128 + pb.N / 128, 1, 0};
     const int ta = ((pa.M - pa.m_tail + 191) / 192) * (pa.N / 128) + (pa.m_tail ? pa.N / 32 : 0);
     const int tb = ((pb.M - pb.m_tail + 191) / 192) * (pb.N / 128) + (pb.m_tail ? pb.N / 32 : 0);
     bool timed = h->ktime && (h->ktime_all || (h->kfilter[0] == EPI_QKV && h->kfilter[1] == A_DENSE && h->kfilter[2] == 7 && h->kfilter[3] == 0));
