@@ -77,6 +77,25 @@ STA_API int sta_debug_attention(sta_handle* h, const float* q, const float* k, c
 STA_API int sta_debug_attention_pose(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads,
                              int n, int kv_shift, float* out, void* stream);
 
+/* Both attention entries fill, before they pack their inputs, the output planes, both planes of the K padding and the Q rows
+ * past the last query with 0xFF (fp16 NaN patterns): an output element the kernel did not write, or a padded key or query it
+ * read, shows up as NaN.  The V^T padding is zero, as the kernel's contract requires.  sta_debug_conv3x3 / _convt / _up2 /
+ * _layernorm poison their output planes the same way. */
+
+/* The launch plan of the attention kernel (pure host function, no handle, no GPU; sta_launch.inc: attn_plan, what run_attn
+ * runs).  pose: decoder form (token nq == nk is the pose token); split: 1 for the f16x3 precisions; no_prefetch: option 5.
+ * out[11] = {pose mode (0 none, 1 side blocks, 2 spare row of the last query block), prefetch (4-stage schedule) flag, LDS
+ * stages, LDS bytes, grid, pose blocks, query blocks, ntiles, nfull, tail stage, pose-query scratch bytes}.  tail stage: -1 when
+ * nk % 64 == 0; under prefetch the tail tile's index (its LDS stage); in the double-buffered loop tile index & 1. */
+STA_API int sta_debug_attn_plan(int S, int heads, int nq, int nk, int pose, int split, int no_prefetch, int* out);
+
+/* The same record for the handle's LAST attention launch. */
+STA_API int sta_debug_last_attn_plan(sta_handle* h, int* out);
+
+/* out[b] = logical (sequence, head, query block) id of query-block workgroup b of a grid of nwg (attention.h: attn_block_map,
+ * the function the kernel calls). */
+STA_API int sta_debug_attn_block_map(int nwg, int* out);
+
 /* Switches of the tests / tools (0 everywhere = product behaviour; see tools/ab_option.py; settable as STA_OPT<idx> in the
  * environment at sta_create only in -DSTA_BENCH_EXPERIMENTS builds).  idx 4 = 1: sta_debug_gemm (plane epilogue) / conv3x3 /
  * convt / up2 run in the DPT head's f16mx arithmetic (f16mx rows in and out, f16mx weights) when the handle's precision is

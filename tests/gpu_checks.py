@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+import helpers as HP
 from helpers import load_golden, rel_l2, max_rel, rope2d_ref, grid_pos
 from vista_slam_amd import _lib
 from vista_slam_amd import weights as W
@@ -272,6 +273,95 @@ def check_attention_pose(precision, S=2, heads=2, n=196, kv_shift=0, sharp=1.0, 
     o = out.cpu().numpy()
     return {"rel_l2": rel_l2(o, ref.numpy()), "rel_l2_pose": rel_l2(o[S * n:], ref.numpy()[S * n:]),
             "max_rel": max_rel(o, ref.numpy()), "nan": float(np.isnan(o).sum())}
+
+
+# ---- tests/test_attention_exact.py: one launch of a case of tests/attention_cases.py, and the four kinds of check on it
+def last_attn_plan(lib, h):
+    """The plan (sta_launch.inc: attn_plan) of the handle's last attention launch."""
+    import attention_cases as AC
+    out = (C.c_int * len(AC.FIELDS))()
+    _lib.check(lib.sta_debug_last_attn_plan(h, out))
+    return dict(zip(AC.FIELDS, out))
+
+
+def attn_launch(precision, case, q, k, v):
+    """Run the case's launch on numpy q, k, v (token layout of helpers.py) -> (output per token [S, heads, nqt, 64] float32, the
+    schedule class the launch ran under).  The output buffer starts as NaN and the debug entry poisons the planes the kernel writes
+    to, so an element that no workgroup stored comes back as NaN."""
+    import attention_cases as AC
+    cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
+    m, lib, h = kernel_handle(precision)
+    qd, kd, vd = dev(q), dev(k), dev(v)
+    rows = S * nq + (S if form == "pose" else 0)
+    out = torch.full((rows, heads * 64), float("nan"), device=DEV)
+    _lib.check(lib.sta_debug_set_option(h, 5, opt5))
+    try:
+        if form == "pose":
+            _lib.check(lib.sta_debug_attention_pose(h, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), S, heads, nq, kv_shift, out.data_ptr(), st()))
+        else:
+            _lib.check(lib.sta_debug_attention(h, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), S, heads, nq, nk, kv_shift, out.data_ptr(), st()))
+        torch.cuda.synchronize()
+        plan = last_attn_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_debug_set_option(h, 5, 0))
+    return HP.attn_rows_to_tokens(out.cpu().numpy(), form, S, heads, nq), AC.schedule_class(plan, nq)
+
+
+def check_attention_selection(precision, case, pose_sel="self", seed=21):
+    """Every query selects one key with probability exactly 1 (helpers.attn_selection_inputs): the output must EQUAL V[pi(query)].
+    -> {"class", "margin", "nan", "wrong": number of wrong (sequence, head, query) rows, "first": text naming the first ones}."""
+    cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
+    q, k, v, pi, margin = HP.attn_selection_inputs(form, S, heads, nq, nk, pose_sel, seed)
+    assert margin > 160, (cid, margin)          # every other probability is exp2(-margin): exactly 0 in fp32
+    # q was built against its own sequence's keys: hand the kernel K / V rotated so that sequence (s + kv_shift) % S holds them
+    idx = [(s - kv_shift) % S for s in range(S)]
+    got, ran = attn_launch(precision, case, q, k[idx], v[idx])
+    want = np.take_along_axis(v, pi[..., None], 2)
+    bad = np.argwhere((got != want).any(-1))
+    first = []
+    for s, h, t in bad[:6]:
+        g = got[s, h, t]
+        who = "pose query" if form == "pose" and t == nq else f"query {t}"
+        first.append(f"(sequence {s}, head {h}, {who}): expected key {pi[s, h, t]} of (sequence {s}, head {h}), "
+                     f"got columns 0..2 = (sequence {g[0]:g}, head {g[1]:g}, key {g[2]:g}), {int((g != want[s, h, t]).sum())} of 64 columns differ")
+    return {"class": ran, "margin": margin, "nan": int(np.isnan(got).sum()), "wrong": len(bad), "first": "; ".join(first)}
+
+
+def check_attention_uniform(precision, case, seed=22):
+    """q = 0: the output is the column mean of V over exactly nk (+ 1) keys.  -> max |error|, max |V|, the fp16 half-ulp of the
+    largest mean (what the f16 form's single output rounding adds)."""
+    cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
+    q, k, v = HP.attn_uniform_inputs(form, S, heads, nq, nk, seed)
+    got, ran = attn_launch(precision, case, q, k, v)
+    idx = [(s + kv_shift) % S for s in range(S)]
+    ref = np.broadcast_to(v[idx].astype(np.float64).mean(2, keepdims=True), got.shape)
+    err = np.abs(got - ref)
+    w = np.unravel_index(np.nanargmax(err), err.shape) if not np.isnan(err).all() else (0, 0, 0, 0)
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "max_abs": float(np.nanmax(err)) if not np.isnan(err).all() else float("nan"),
+            "vmax": float(np.abs(v).max()), "half_ulp16": float(2.0 ** (np.floor(np.log2(np.abs(ref).max())) - 11)),
+            "worst": f"(sequence {w[0]}, head {w[1]}, query {w[2]}, column {w[3]}): got {got[w]} want {ref[w]}"}
+
+
+def _attn_rows(precision, case, q, k, v):
+    cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
+    got, ran = attn_launch(precision, case, q, k, v)
+    rows, glob = HP.attn_row_errors(got, HP.attn_ref64(q, k, v, kv_shift))
+    w = np.unravel_index(np.nanargmax(rows), rows.shape) if not np.isnan(rows).all() else (0, 0)
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "rel_l2": glob, "worst_row": float(np.nanmax(rows)) if not np.isnan(rows).all() else float("nan"),
+            "worst": f"(sequence {w[0]}, query {w[1]})"}
+
+
+def check_attention_ramp(precision, case, pattern, seed=101):
+    """Scores that rise / fall tile by tile or peak in the last tile / at the pose key (helpers.attn_ramp_inputs) against the fp64
+    softmax; per-row rel-L2."""
+    cid, form, S, heads, nq, nk = case[:6]
+    return _attn_rows(precision, case, *HP.attn_ramp_inputs(form, S, heads, nq, nk, pattern, seed))
+
+
+def check_attention_rows(precision, case, sharp, seed=100):
+    """Gaussian inputs, rel-L2 of every (sequence, query) row and of the whole output."""
+    cid, form, S, heads, nq, nk = case[:6]
+    return _attn_rows(precision, case, *HP.attn_gaussian_inputs(form, S, heads, nq, nk, sharp, seed))
 
 
 def check_conv3(precision, n=2, H=7, W_=5, Cin=32, Co=48, stride=1, relu_in=0, act=0, resid=False, seed=3, variant=0):

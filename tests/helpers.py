@@ -118,3 +118,164 @@ def compare_seq_edges(edges, g, meta, tol=1e-3):
                 note("scale_conf", np.array([r["scale_confs"][k]]), np.array([float(g[f"e{e}_scale_conf"][k])]))
     assert worst.get("confs_norm", 0.0) < tol and worst.get("depths_norm", 0.0) < tol, worst
     return worst
+
+
+# ---------------------------------------------------------------------------------------------------------
+# attention: inputs of tests/test_attention_exact.py, the fp64 reference and a numpy model of the kernel's documented arithmetic
+# (csrc/attention.h).  Token layout everywhere: q [S, heads, nqt, 64], k / v [S, heads, nkt, 64]; the decoder ("pose") form has
+# nqt = nkt = n + 1 with the pose token LAST.  Results are per token, [S, heads, nqt, 64] (attn_rows_to_tokens undoes the row order
+# of the debug entry points).
+ATT_SCALE_LOG2E = np.float32(0.125) * np.float32(1.44269504088896340736)
+
+
+def attn_rows_to_tokens(out, form, S, heads, nq):
+    """Output rows of sta_debug_attention ([S, nq, heads*64]) / sta_debug_attention_pose ([S*n + S, heads*64]: patch rows sequence-
+    major, then the S pose rows) -> [S, heads, nqt, 64]."""
+    out = np.asarray(out)
+    if form == "plain":
+        return out.reshape(S, nq, heads, 64).transpose(0, 2, 1, 3)
+    o = np.concatenate([out[:S * nq].reshape(S, nq, heads, 64), out[S * nq:].reshape(S, 1, heads, 64)], 1)
+    return o.transpose(0, 2, 1, 3)
+
+
+def attn_ref64(q, k, v, kv_shift):
+    """softmax(q k^T / 8) v in float64, K / V of sequence (s + kv_shift) % S."""
+    S = q.shape[0]
+    idx = [(s + kv_shift) % S for s in range(S)]
+    a = (q.astype(np.float64) @ k[idx].astype(np.float64).transpose(0, 1, 3, 2)) * 0.125
+    a -= a.max(-1, keepdims=True)
+    p = np.exp(a)
+    return (p / p.sum(-1, keepdims=True)) @ v[idx].astype(np.float64)
+
+
+def _split16(x):
+    hi = x.astype(np.float16)
+    lo = (x - hi.astype(np.float32)).astype(np.float16)
+    return hi.astype(np.float32), lo.astype(np.float32)
+
+
+def attn_model(q, k, v, kv_shift, precision):
+    """The documented arithmetic in numpy float32.  f16x3: operands and P as fp16 hi + lo, three products (hi hi + hi lo + lo hi),
+    fp32 accumulation, fp32 exp2 softmax, output as hi + lo.  f16: single fp16 roundings of operands, P and output, fp32 row sum of
+    the UNROUNDED p.  (Not modelled: the summation order of the MFMAs and the online rescaling, the hardware exp2 - the 4x margin
+    of the bounds derived from this model is for those.)"""
+    S = q.shape[0]
+    idx = [(s + kv_shift) % S for s in range(S)]
+    q, k, v = q.astype(np.float32), k[idx].astype(np.float32), v[idx].astype(np.float32)
+    split = precision != "f16"
+    qh, ql = _split16(q); kh, kl = _split16(k); vh, vl = _split16(v)
+    kt = kh.transpose(0, 1, 3, 2)
+    s = qh @ kt
+    if split:
+        s = s + (qh @ kl.transpose(0, 1, 3, 2) + ql @ kt)
+    m = (s.max(-1, keepdims=True) * ATT_SCALE_LOG2E).astype(np.float32)                  # the kernel: m = max * scale, p = exp2(fma(s, scale, -m))
+    t = (s.astype(np.float64) * np.float64(ATT_SCALE_LOG2E) - m.astype(np.float64)).astype(np.float32)
+    p = np.exp2(t).astype(np.float32)
+    l = p.sum(-1, keepdims=True, dtype=np.float32)
+    ph, pl = _split16(p)
+    o = ph @ vh
+    if split:
+        o = o + (ph @ vl + pl @ vh)
+    o = (o * (np.float32(1.0) / l)).astype(np.float32)
+    oh, ol = _split16(o)
+    return (oh + ol if split else oh).astype(np.float64)
+
+
+def attn_row_errors(got, ref):
+    """got, ref [S, heads, nqt, 64] -> (rel-L2 of every (sequence, query) row over heads x 64 columns [S, nqt], global rel-L2)."""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    num = ((got - ref) ** 2).sum((1, 3)); den = (ref ** 2).sum((1, 3))
+    return np.sqrt(num / np.maximum(den, 1e-300)), float(np.sqrt(num.sum() / max(den.sum(), 1e-300)))
+
+
+def attn_tokens(form, nq, nk):
+    return (nq, nk) if form == "plain" else (nq + 1, nk + 1)
+
+
+def attn_gaussian_inputs(form, S, heads, nq, nk, sharp, seed):
+    rng = np.random.default_rng(seed)
+    nqt, nkt = attn_tokens(form, nq, nk)
+    q = (rng.standard_normal((S, heads, nqt, 64)) * sharp).astype(np.float32)
+    k = rng.standard_normal((S, heads, nkt, 64)).astype(np.float32)
+    v = rng.standard_normal((S, heads, nkt, 64)).astype(np.float32)
+    return q, k, v
+
+
+def attn_ramp_inputs(form, S, heads, nq, nk, pattern, seed):
+    """Gaussian q, k, v whose score gets one more term r(key) (k[..., 0] = r, q[..., 0] = 8, so q0 k0 / 8 = r):
+    "rise": r = 8 x tile index - the running maximum moves in every key tile, every tile rescales the accumulator;
+    "fall": r = -8 x tile index - no score after the first tile reaches the running maximum (Gaussian part: |.| < 4 at these
+            sizes), so the wave-uniform alpha == 1 skip is taken on every later tile;
+    "peak": r = 12 on the keys of the LAST tile (the tail tile when nk % 64 != 0), in the pose form on the pose key instead."""
+    q, k, v = attn_gaussian_inputs(form, S, heads, nq, nk, 0.35, seed)       # Gaussian part of the score: std 0.35
+    tile = np.arange(k.shape[2]) // 64
+    if pattern == "rise":
+        r = 8.0 * tile
+    elif pattern == "fall":
+        r = -8.0 * tile
+    else:
+        assert pattern == "peak"
+        r = np.zeros(k.shape[2])
+        if form == "pose":
+            r[nk] = 12.0
+        else:
+            r[tile == tile[nk - 1]] = 12.0
+    if form == "pose" and pattern != "peak":
+        r[nk] = r[nk - 1]                # the pose key (folded into the initial state) sits with the last tile
+    k[..., 0] = r.astype(np.float32)
+    q[..., 0] = 8.0
+    return q, k, v
+
+
+def attn_uniform_inputs(form, S, heads, nq, nk, seed):
+    """q = 0: every score is 0, the output is the column mean of V over exactly nk (+ 1 with the pose token) keys.  V: integers
+    1024 +- 64, and 2048 at key 0, key nk - 1 and the pose key - fp16-exact, every partial sum below 2^24 (exact in fp32)."""
+    rng = np.random.default_rng(seed)
+    nqt, nkt = attn_tokens(form, nq, nk)
+    q = np.zeros((S, heads, nqt, 64), np.float32)
+    k = rng.standard_normal((S, heads, nkt, 64)).astype(np.float32)
+    v = (1024 + rng.integers(-64, 65, size=(S, heads, nkt, 64))).astype(np.float32)
+    v[:, :, 0] = 2048; v[:, :, nk - 1] = 2048; v[:, :, nkt - 1] = 2048
+    return q, k, v
+
+
+def attn_selection_inputs(form, S, heads, nq, nk, pose_sel, seed):
+    """Every query selects exactly one key.  Keys: random +-1 codes in 63 dimensions and a constant 1; query = 64 x [code of key
+    pi(query), -63]: raw score 64 (dot - 63) = 0 for the selected key, <= 64 (dot_max - 63) for every other one.  V: integers,
+    columns 0..2 = (sequence, head, key).  pi [S, heads, nqt]: a permutation when nq == nk, else a map that hits key 0, key nk - 1
+    and the first and last key of every 64-key tile as far as there are queries; pose form: the pose query selects itself
+    (pose_sel "self") or a patch key ("patch"), and up to three patch queries select the pose key.
+    -> q, k, v, pi, margin (the smallest distance, in log2 units of the softmax, of a non-selected key below the selected one)."""
+    rng = np.random.default_rng(seed)
+    nqt, nkt = attn_tokens(form, nq, nk)
+    code = (rng.integers(0, 2, size=(S, heads, nkt, 63)) * 2 - 1).astype(np.float32)
+    k = np.concatenate([code, np.ones((S, heads, nkt, 1), np.float32)], -1)
+    forced = [0, nk - 1] + [j for t in range((nk + 63) // 64) for j in (t * 64, min(t * 64 + 63, nk - 1))]
+    forced = list(dict.fromkeys(forced))
+    pi = np.zeros((S, heads, nqt), np.int64)
+    for s in range(S):
+        for h in range(heads):
+            if nq == nk:
+                p = rng.permutation(nk)
+            else:
+                p = rng.integers(0, nk, size=nq)
+                slots = rng.permutation(nq)[:len(forced)]
+                p[slots] = forced[:len(slots)]
+            if form == "pose":
+                free = [i for i in range(nq) if p[i] not in forced] or list(range(nq))
+                to_pose = rng.permutation(free)[:3]
+                p = np.concatenate([p, [nk if pose_sel == "self" else int(rng.integers(0, nk))]])
+                p[to_pose] = nk
+            pi[s, h] = p
+    q = np.empty((S, heads, nqt, 64), np.float32)
+    v = rng.integers(-1024, 1025, size=(S, heads, nkt, 64)).astype(np.float32)
+    for s in range(S):
+        for h in range(heads):
+            q[s, h, :, :63] = 64.0 * code[s, h, pi[s, h]]
+            v[s, h, :, 0] = s; v[s, h, :, 1] = h; v[s, h, :, 2] = np.arange(nkt)
+    q[..., 63] = -63.0 * 64.0
+    # the margin in float64: scores of the non-selected keys (each query's own key row masked out)
+    dots = code.astype(np.float64) @ code.astype(np.float64).transpose(0, 1, 3, 2)         # [S, heads, key, key]
+    dots[:, :, np.arange(nkt), np.arange(nkt)] = -np.inf
+    margin = -64.0 * (dots.max() - 63.0) * float(ATT_SCALE_LOG2E) if nkt > 1 else np.inf
+    return q, k, v, pi, margin

@@ -100,6 +100,9 @@ TEST_SIGNATURES = {
     "sta_debug_qkv_rope": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "sta_debug_attention": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_attention_pose": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
+    "sta_debug_attn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "sta_debug_last_attn_plan": (_i, [_vp, C.POINTER(_i)]),
+    "sta_debug_attn_block_map": (_i, [_i, C.POINTER(_i)]),
     "sta_debug_set_tail_hint": (_i, [_vp, _i]),
     "sta_debug_set_option": (_i, [_vp, _i, _i]),
     "sta_debug_pick_family": (_i, [_i, _i, C.c_longlong, _i, _i, _i, _i, _i, _i]),

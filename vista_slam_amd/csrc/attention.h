@@ -46,6 +46,15 @@ template <bool SPLIT>
 constexpr int attn_smem_bytes(int stages = 2) { return stages * (SPLIT ? 4 : 2) * ATT_TILE_BYTES; }
 #define ATT_PREFETCH_TILES 4
 
+// Query-block workgroup `bid` of `nwg` (pose blocks not counted) -> logical id = (sequence * heads + head) * query blocks + query
+// block.  Workgroup b runs on XCD b % 8 (observed dispatch); XCD x gets the contiguous logical range that starts after the ranges
+// of XCDs 0 .. x-1 (nwg / 8 ids each, one more for the first nwg % 8), so the query blocks of one (sequence, head) share that
+// XCD's L2 copy of K / V.  A bijection of [0, nwg) for every nwg (tests/test_attention_plan.py sweeps it on the host).
+__host__ __device__ inline int attn_block_map(int bid, int nwg) {
+    const int q = nwg / 8, r = nwg % 8, xcd = bid % 8;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
+}
+
 // The pose-token query of one (sequence, head) per workgroup: 1 x (nk + 1) scores, softmax and 1 x 64 output as fp32 dot products
 // (an MFMA tile would carry 31 dead queries through every key tile).  Phase 1: thread = key (K rows are 128 contiguous bytes),
 // phase 2: block-wide max / sum, probabilities parked in LDS, phase 3: lane = d (V^T rows are contiguous along the keys).
@@ -144,15 +153,10 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lhi = lane >> 5;
-    // 1-D grid, XCD-aware: block b runs on XCD b%8 (observed dispatch); give each XCD a contiguous range
-    // of logical ids so the query blocks of one (sequence, head) share that XCD's L2 copy of K/V.
+    // 1-D grid, XCD-aware (attn_block_map)
     const int nqb = (nqe + 127) / 128;
     const int nwg = nqb * p.heads * p.S;
-    int logical;
-    {
-        const int bid = blockIdx.x - npose_blocks, q = nwg / 8, r = nwg % 8, xcd = bid % 8;
-        logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + bid / 8;
-    }
+    const int logical = attn_block_map(blockIdx.x - npose_blocks, nwg);
     const int qb = logical % nqb;
     const int h = (logical / nqb) % p.heads, s = logical / (nqb * p.heads);
     const int skv = (s + p.kv_shift) % p.S;

@@ -109,6 +109,12 @@ struct StreamCtx {
 // 192x128 launch, 8 halo-tiled 3x3 convolution); bm x bn = its tile; tiles_m x tiles_n main tiles cover rows [0, M - m_tail),
 // the m_tail rows after them run on the skinny tail blocks; ksplit K slices (slab_ks of them to the caller's slab).
 struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks; };
+// What run_attn decides before it launches attn_kernel (attn_plan, sta_launch.inc).  pose: AttnParams::pose (0 none, 1 side
+// blocks, 2 spare row of the last query block); prefetch: the 4-stage request-everything schedule instead of the double-buffered
+// loop; grid = qblocks x heads x S + pose_blocks workgroups; ntiles key tiles of 64, nfull of them whole; tail_stage: where the
+// partly valid last tile runs (-1: none; prefetch: its tile index = its LDS stage; double-buffered: tile index & 1);
+// pose_scratch: LDS bytes the pose-query path needs at the smallest npad a caller can pass.
+struct AttnPlan { int pose, prefetch, stages, lds_bytes, grid, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; };
 struct sta_handle {
     sta_config cfg;
     int device = 0;
@@ -139,6 +145,7 @@ struct sta_handle {
     int tail_hint = 0;      // decode_impl: the last tail_hint rows of every dense GEMM are pose-token rows (GemmParams::m_tail)
     int gemm_variant = 0;   // tests / tools: 0 auto, 1..4 forced GEMM families, 8 = conv3h wherever legal, 9 = auto WITHOUT conv3h (A/B)
     GemmPlan last_plan{};   // the plan of the last launch_gemm / paired launch (sta_debug_last_gemm_plan)
+    AttnPlan last_attn{};   // the plan of the last run_attn (sta_debug_last_attn_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
     // sta_decode_pos, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and rope_planes_kernel

@@ -17,6 +17,23 @@ static int dbg_planes_to_f32(sta_handle* h, const Planes& p, int64_t ibstride_ro
     return 0;
 }
 
+// 0xFF (an fp16 NaN pattern) into what the kernel under test must overwrite: an element it never wrote reads back as NaN instead
+// of as whatever the shared workspace held - often the correct values of the previous, identically shaped test.
+static int dbg_poison(void* ptr, int64_t bytes, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(ptr, 0xFF, (size_t)bytes, st));
+    return 0;
+}
+// ... the blocked planes of Bump::act(rows, cols, split) (output planes that are not also an input)
+static int dbg_poison_act(const Planes& p, int64_t rows, int64_t cols, hipStream_t st) {
+    return dbg_poison(p.hi, rows * ((cols + 31) & ~int64_t(31)) * (p.lo ? 4 : 2), st);
+}
+// ... the row-major Q / K / V^T planes of Bump::planes(elems, split)
+static int dbg_poison_planes(const Planes& p, int64_t elems, hipStream_t st) {
+    CHK(dbg_poison(p.hi, elems * 2, st));
+    if (p.lo) CHK(dbg_poison(p.lo, elems * 2, st));
+    return 0;
+}
+
 static int dbg_make_lin(sta_handle* h, Bump& ws, const float* w, const float* bias, int N, int K, int mode,
                         int d0, int d1, int d2, int d3, Lin& L, hipStream_t st, bool mx = false, int cls = CLS_HEAD) {
     L.N = N; L.K = K; L.w = ws.act(N, K, true); L.bias = const_cast<float*>(bias);
@@ -164,9 +181,13 @@ extern "C" int sta_debug_attention(sta_handle* h, const float* q, const float* k
     QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
     Planes ao = ws.act((int64_t)S * nq, heads * 64, split);
     REQUIRE(!ws.overflow, "debug ws overflow");
+    // V^T padding stays ZERO: that is the kernel's documented contract (a masked key has p = 0, and 0 * NaN would be NaN; the
+    // QKV epilogue's buffers are memset the same way).  Everything else the kernel must not read or must overwrite is poisoned:
+    // both planes of the K padding (masked keys must never leak), the Q rows in [nq, npad), the output planes.
     HIPCHK(hipMemsetAsync(o.vt.hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(o.vt.lo, 0, hsz * 2, st));
-    // poison the K padding with NaN patterns: masked keys must never leak
-    HIPCHK(hipMemsetAsync(o.k.hi, 0xFF, hsz * 2, st));
+    CHK(dbg_poison_planes(o.k, hsz, st));
+    CHK(dbg_poison_planes(o.q, hsz, st));
+    CHK(dbg_poison_act(ao, (int64_t)S * nq, heads * 64, st));
     CHK(run_rows_to_planes(h, q, (int64_t)nq * 64, S * heads, nq, 64, o.q, st, npad));
     CHK(run_rows_to_planes(h, k, (int64_t)nk * 64, S * heads, nk, 64, o.k, st, npad));
     hipLaunchKernelGGL(pack_vt_kernel, dim3((unsigned)(((int64_t)S * heads * nk * 64 + 255) / 256)), dim3(256), 0, st,
@@ -193,8 +214,12 @@ extern "C" int sta_debug_attention_pose(sta_handle* h, const float* q, const flo
     QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
     Planes ao = ws.act(M, heads * 64, split);
     REQUIRE(!ws.overflow, "debug ws overflow");
+    // V^T padding stays ZERO (the kernel's contract: 0 * NaN, see sta_debug_attention); both planes of the K padding, the Q rows
+    // in [n + 1, npad) and the output planes are poisoned
     HIPCHK(hipMemsetAsync(o.vt.hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(o.vt.lo, 0, hsz * 2, st));
-    HIPCHK(hipMemsetAsync(o.k.hi, 0xFF, hsz * 2, st));       // NaN patterns in the K padding: masked keys must never leak
+    CHK(dbg_poison_planes(o.k, hsz, st));
+    CHK(dbg_poison_planes(o.q, hsz, st));
+    CHK(dbg_poison_act(ao, M, heads * 64, st));
     CHK(run_rows_to_planes(h, q, (int64_t)nt * 64, S * heads, nt, 64, o.q, st, npad));
     CHK(run_rows_to_planes(h, k, (int64_t)nt * 64, S * heads, nt, 64, o.k, st, npad));
     hipLaunchKernelGGL(pack_vt_kernel, dim3((unsigned)(((int64_t)S * heads * nt * 64 + 255) / 256)), dim3(256), 0, st,
@@ -241,6 +266,7 @@ extern "C" int sta_debug_conv3x3(sta_handle* h, const float* x, const float* w, 
     REQUIRE(!ws.overflow, "debug ws overflow");
     CHK(run_rows_to_planes(h, x, ein, 1, n * H * W, Cin, xi, st, 0, mx));
     if (resid) CHK(run_rows_to_planes(h, resid, eout, 1, n * Ho * Wo, Co, r, st, 0, mx));
+    CHK(dbg_poison_act(o, (int64_t)n * Ho * Wo, Co, st));
     CHK(conv3(h, xi, n, H, W, Cin, L, stride, relu_in != 0, act, o, resid ? &r : nullptr, nullptr, st));
     CHK(dbg_planes_to_f32(h, o, 0, 1, n * Ho * Wo, Co, out, st));
     return 0;
@@ -264,6 +290,7 @@ extern "C" int sta_debug_convt(sta_handle* h, const float* x, const float* w, co
     REQUIRE(!ws.overflow, "debug ws overflow");
     hipLaunchKernelGGL(expand_bias_kernel, dim3((C * k * k + 255) / 256), dim3(256), 0, st, bias, eb, C, k * k);
     CHK(run_rows_to_planes(h, x, ein, 1, n * H * W, C, xi, st, 0, mx));
+    CHK(dbg_poison_act(o, (int64_t)n * H * W * k * k, C, st));
     CHK(gemm_convt(h, xi, L, n, H, W, k, C, o, st));
     CHK(dbg_planes_to_f32(h, o, 0, 1, n * H * k * W * k, C, out, st));
     return 0;
@@ -281,6 +308,7 @@ extern "C" int sta_debug_up2(sta_handle* h, const float* x, int n, int H, int W,
     Planes xi = ws.act((int64_t)n * H * W, C, split), o = ws.act((int64_t)n * Hc * Wc, C, split);
     xi.mx = o.mx = dbg_mx(h);
     CHK(run_rows_to_planes(h, x, ein, 1, n * H * W, C, xi, st, 0, xi.mx));
+    CHK(dbg_poison_act(o, (int64_t)n * Hc * Wc, C, st));
     CHK(run_up2(h, xi, n, H, W, C, Hc, Wc, o, st));
     CHK(dbg_planes_to_f32(h, o, 0, 1, n * Hc * Wc, C, out, st));
     return 0;
@@ -297,6 +325,7 @@ extern "C" int sta_debug_layernorm(sta_handle* h, const float* x, const float* g
     Bump ws = cur_bump(h);
     Planes o = ws.act(M, C, split);
     LNp n; n.g = const_cast<float*>(g); n.b = const_cast<float*>(b);
+    CHK(dbg_poison_act(o, M, C, st));
     float keep = h->cfg.ln_eps; h->cfg.ln_eps = eps;
     int r = run_ln(h, x, M, C, n, o, nullptr, nullptr, out32, st);
     h->cfg.ln_eps = keep;

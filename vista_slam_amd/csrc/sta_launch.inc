@@ -705,34 +705,89 @@ static int rope_fix(sta_handle* h, const Planes& qk, int S, int heads, int npad,
     return 0;
 }
 
+static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+
+// ------------------------------------------------------------------------------------------ attention launch plan
+// Everything run_attn decides before it launches attn_kernel, as ONE pure host function of the shape and the switches (like
+// gemm_plan): run_attn runs exactly this plan and keeps it in the handle; sta_debug_attn_plan exposes it to the host-only sweep
+// (tests/test_attention_plan.py) and sta_debug_last_attn_plan reads back the plan a kernel test ran under.
+//   pose query: 2 = one more row of the last query block when that block has spare rows (nq = 196: rows 196..255 of the second
+//   block are dead anyway - free, and no latency-bound side path at SLAM scale: 12.8 vs 26.1 us for 10 x 12 heads); 1 = one side
+//   workgroup per (sequence, head) when the patch queries fill their blocks exactly (nq = 768)
+//   prefetch: small grids with <= 4 key tiles run on 4 LDS stages, every K / V^T tile requested up front (attention.h; one
+//   workgroup per CU then, which a grid of <= 256 workgroups has anyway); no_prefetch = debug option 5
+static int attn_plan(int S, int heads, int nq, int nk, bool pose, bool split, bool no_prefetch, AttnPlan& out) {
+    REQUIRE(S > 0 && heads > 0 && nq > 0 && nk > 0, "empty attention");
+    REQUIRE(!pose || nq == nk, "internal: pose-token attention needs nq == nk < npad");
+    AttnPlan a{};
+    a.pose = pose ? (nq % 128 != 0 ? 2 : 1) : 0;
+    a.pose_blocks = a.pose == 1 ? S * heads : 0;
+    a.qblocks = (nq + (a.pose == 2 ? 1 : 0) + 127) / 128;
+    const int64_t grid = (int64_t)a.qblocks * heads * S + a.pose_blocks;
+    REQUIRE(grid < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)grid);
+    a.grid = (int)grid;
+    a.ntiles = (nk + ATT_KV - 1) / ATT_KV; a.nfull = nk / ATT_KV;
+    a.prefetch = (nk <= ATT_PREFETCH_TILES * ATT_KV && a.grid <= 256 && !no_prefetch) ? 1 : 0;
+    a.stages = a.prefetch ? ATT_PREFETCH_TILES : 2;
+    a.lds_bytes = split ? attn_smem_bytes<true>(a.stages) : attn_smem_bytes<false>(a.stages);
+    a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
+    // the pose-query blocks park npad scores + 8 + 256 partials (fp32) in the smallest LDS allocation of the kernel
+    a.pose_scratch = pose ? (rup(nq + 1, 64) + 8 + 256) * 4 : 0;
+    REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+    out = a;
+    return 0;
+}
+#ifdef STA_TEST_HOOKS
+static void attn_plan_out(const AttnPlan& a, int* out) {
+    const int v[11] = {a.pose, a.prefetch, a.stages, a.lds_bytes, a.grid, a.pose_blocks, a.qblocks, a.ntiles, a.nfull, a.tail_stage, a.pose_scratch};
+    for (int i = 0; i < 11; ++i) out[i] = v[i];
+}
+// out[11] = {pose mode, prefetch, LDS stages, LDS bytes, grid, pose blocks, query blocks, ntiles, nfull, tail stage, pose scratch bytes}
+extern "C" int sta_debug_attn_plan(int S, int heads, int nq, int nk, int pose, int split, int no_prefetch, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnPlan a;
+    CHK(attn_plan(S, heads, nq, nk, pose != 0, split != 0, no_prefetch != 0, a));
+    attn_plan_out(a, out);
+    return 0;
+}
+extern "C" int sta_debug_last_attn_plan(sta_handle* h, int* out) {
+    REQUIRE(h && out, "bad argument");
+    attn_plan_out(h->last_attn, out);
+    return 0;
+}
+// out[b] = the logical id (attn_block_map, the function attn_kernel calls) of query-block workgroup b of nwg
+extern "C" int sta_debug_attn_block_map(int nwg, int* out) {
+    REQUIRE(out && nwg > 0, "bad argument");
+    for (int b = 0; b < nwg; ++b) out[b] = attn_block_map(b, nwg);
+    return 0;
+}
+#endif
+
 static int run_attn(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads,
                     int nq, int nk, int kv_shift, hipStream_t st, bool pose = false) {
     if (h->dry) return 0;
     REQUIRE(!pose || (nq == nk && nq + 1 <= qkv.npad), "internal: pose-token attention needs nq == nk < npad");
+    const bool split = h->prec != STA_PREC_F16;
+    AttnPlan a;
+    CHK(attn_plan(S, heads, nq, nk, pose, split, h->opt[5] == 1, a));
+    h->last_attn = a;
     AttnParams p; memset(&p, 0, sizeof p);
     p.range = h->range;
-    // the pose query: 2 = one more row of the last query block when that block has spare rows (nq = 196: rows 196..255 of the
-    // second block are dead anyway - free, and no latency-bound side path at SLAM scale: 12.8 vs 26.1 us for 10 x 12 heads);
-    // 1 = wave-per-(sequence, head) side blocks when the patch queries fill their blocks exactly (nq = 768)
-    p.pose = pose ? (nq % 128 != 0 ? 2 : 1) : 0;
+    p.pose = a.pose;
     p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
     p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
     p.S = S; p.heads = heads; p.nq = nq; p.nk = nk; p.npad = qkv.npad; p.kv_shift = kv_shift;
     p.scale_log2e = 0.125f * 1.44269504088896340736f;
-    const int npose = p.pose == 1 ? S * heads : 0;
     REQUIRE(!pose || (int64_t)(qkv.npad + 8 + 256) * 4 <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
     REQUIRE(!pose || qkv.npad % 64 == 0, "internal: pose-query path needs npad % 64 == 0");
-    dim3 grid((unsigned)(((nq + (p.pose == 2 ? 1 : 0) + 127) / 128) * heads * S + npose));
-    // small grids with <= 4 key tiles: 4 LDS stages, every K / V^T tile requested up front (attention.h; one workgroup per CU then,
-    // which a grid of <= 256 workgroups has anyway)
-    p.prefetch = (nk <= ATT_PREFETCH_TILES * ATT_KV && grid.x <= 256 && h->opt[5] != 1) ? 1 : 0;
-    const int stages = p.prefetch ? ATT_PREFETCH_TILES : 2;
-    if (h->prec != STA_PREC_F16) {
+    p.prefetch = a.prefetch;
+    const dim3 grid((unsigned)a.grid);
+    if (split) {
         static unsigned attr_done = 0;      // one bit per device
         if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
-        hipLaunchKernelGGL(attn_kernel<true>, grid, dim3(256), attn_smem_bytes<true>(stages), st, p);
+        hipLaunchKernelGGL(attn_kernel<true>, grid, dim3(256), a.lds_bytes, st, p);
     } else {
-        STA_F16ONLY(hipLaunchKernelGGL(attn_kernel<false>, grid, dim3(256), attn_smem_bytes<false>(stages), st, p));
+        STA_F16ONLY(hipLaunchKernelGGL(attn_kernel<false>, grid, dim3(256), a.lds_bytes, st, p));
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -784,5 +839,4 @@ static int ensure_rope(sta_handle* h, int P) {
     return 0;
 }
 
-static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
