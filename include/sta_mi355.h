@@ -208,6 +208,15 @@ STA_API int sta_encoder_norm(sta_handle* h, const float* feat_dev, int64_t rows,
 STA_API int sta_decode(sta_handle* h, const float* feat1, const float* feat2, int B, int hp, int wp,
                float* const* out1, float* const* out2, void* stream);
 
+/* _decode_stereo on two views of DIFFERENT resolution: feat1 [B, N1, enc_dim] on an hp1 x wp1 patch grid (N1 = hp1*wp1), feat2
+ * [B, N2, enc_dim] on hp2 x wp2 (the reference's module code takes them: cross attention accepts any memory length,
+ * sta_blocks.py:193-205).  out1[i] [B, N1+1, dec_dim], out2[i] [B, N2+1, dec_dim]; NULL skips a layer, the last index has dec_norm
+ * applied, as in sta_decode.  Patch-grid positions only.  Equal grids are accepted and take the same route (one more QKV launch
+ * per projection and no paired QKV launch: sta_decode stays the fast path for them).  sta_head_pts / sta_head_pose take per-call
+ * shapes and serve each side.  Not covered by sta_reserve: the first call of a shape pair allocates. */
+STA_API int sta_decode_mixed(sta_handle* h, const float* feat1, const float* feat2, int B, int hp1, int wp1, int hp2, int wp2,
+                     float* const* out1, float* const* out2, void* stream);
+
 /* _decode_stereo with CALLER positions (sta_model.py:177-244 hands pos1 / pos2 to every decoder block, whose attentions rotate
  * q / k by them: sta_blocks.py:134-137,196-199): pos1 / pos2 are device int64 [B, N, 2] (y, x) as _encode_image returns them,
  * but need not be the patch grid - a window of a larger grid, a permuted token order, repeated positions.  Values must lie in

@@ -89,6 +89,22 @@ STA_API int sta_debug_attention_pose(sta_handle* h, const float* q, const float*
  * nk % 64 == 0; under prefetch the tail tile's index (its LDS stage); in the double-buffered loop tile index & 1. */
 STA_API int sta_debug_attn_plan(int S, int heads, int nq, int nk, int pose, int split, int no_prefetch, int* out);
 
+/* Two-group form of the decoder's attention (attention.h: attn_mixed_kernel; the decoder on view pairs of different resolution):
+ * S1 sequences of nq_a queries over nk_a keys and S2 sequences of nq_b over nk_b, pose token LAST in every q / k / v
+ * ([S, heads, n + 1, 64]).  k / v of a sequence are the keys it reads; the entry stores them at buffer sequence
+ * (s + kv_shift) % (S1 + S2).  out [S1*nq_a + S1 + S2*nq_b + S2, heads*64]: per group the patch rows, then the pose rows.
+ * Poisons like sta_debug_attention_pose. */
+STA_API int sta_debug_attention_mixed(sta_handle* h, const float* q_a, const float* k_a, const float* v_a, const float* q_b,
+                                      const float* k_b, const float* v_b, int S1, int S2, int heads, int nq_a, int nk_a,
+                                      int nq_b, int nk_b, int kv_shift, float* out, void* stream);
+/* Its launch plan (pure host function; sta_launch.inc: attn_mixed_plan): out[20] = {LDS stages, LDS bytes, grid, query-block
+ * workgroups of group a, then per group {pose mode, prefetch, pose blocks, query blocks per (sequence, head), ntiles, nfull, tail
+ * stage, pose scratch bytes}}; the record of the handle's last two-group launch; and the kernel's workgroup map: out[3*b + 0..2] =
+ * (sequence, head, query block) of query-block workgroup b. */
+STA_API int sta_debug_attn_mixed_plan(int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, int split, int no_prefetch, int* out);
+STA_API int sta_debug_last_attn_mixed_plan(sta_handle* h, int* out);
+STA_API int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qblocks_a, int qblocks_b, int* out);
+
 /* The same record for the handle's LAST attention launch. */
 STA_API int sta_debug_last_attn_plan(sta_handle* h, int* out);
 
@@ -159,6 +175,9 @@ STA_API float sta_bench_gemm_last_ghz(void);
 /* The attention kernel alone on random operands (tools): ms per launch over `iters` back-to-back launches.  pose != 0: the
  * decoder form (nq == nk patch tokens + the pose token).  which: reserved for kernel variants under test, pass 0. */
 STA_API int sta_bench_attention(sta_handle* h, int S, int heads, int nq, int nk, int pose, int iters, int which, float* ms_out, void* stream);
+/* The two-group launch alone (attn_mixed_kernel, see sta_debug_attention_mixed for the arguments): ms per launch. */
+STA_API int sta_bench_attention_mixed(sta_handle* h, int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift,
+                                      int iters, float* ms_out, void* stream);
 
 #ifdef __cplusplus
 }

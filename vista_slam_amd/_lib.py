@@ -49,6 +49,7 @@ SIGNATURES = {
     "sta_finalize_weights": (_i, [_vp]),
     "sta_encode": (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     "sta_decode": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "sta_decode_mixed": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_decode_pos": (_i, [_vp, _fp, _fp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_head_pose": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp]),
     "sta_head_pts": (_i, [_vp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _i, _i, _i, _fp, _fp, _vp]),
@@ -95,11 +96,16 @@ TEST_SIGNATURES = {
     "sta_bench_gemm_stamps": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong), _i, _vp]),
     "sta_bench_gemm": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _vp]),
     "sta_bench_gemm_last_ghz": (C.c_float, []),
+    "sta_bench_attention_mixed": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _vp]),
     "sta_bench_attention": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _vp]),
     "sta_debug_gemm": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
     "sta_debug_qkv_rope": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "sta_debug_attention": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_attention_pose": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
+    "sta_debug_attention_mixed": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _vp]),
+    "sta_debug_attn_mixed_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "sta_debug_last_attn_mixed_plan": (_i, [_vp, C.POINTER(_i)]),
+    "sta_debug_attn_mixed_block_map": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_attn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_last_attn_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_attn_block_map": (_i, [_i, C.POINTER(_i)]),

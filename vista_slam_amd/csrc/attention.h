@@ -39,6 +39,19 @@ struct AttnParams {
                              // rides as query nq in the last query block's spare rows (pose == 2); its output row is S*nq + s
 };
 
+// Two-group launch (attn_mixed_kernel; the decoder on view pairs of different resolution): sequences [0, S1) are group a and use
+// AttnParams::nq / nk / pose / prefetch, sequences [S1, S) are group b and use the fields below.  Everything else is shared: one
+// npad for every buffer (>= the larger group's tokens + 1), kv_shift over all S sequences (0: both sides' self attention in one
+// launch; S1 == S / 2: the cross attention of both directions), one LDS size.  Pose key at token index nk, pose query at token
+// index nq of the group (they differ in cross attention).  Output rows: group a [S1*nq_a patch rows | S1 pose rows] from row 0,
+// group b the same from row orow0; `orows` rows in the output planes.
+struct AttnGroupB {
+    int S1;
+    int nq, nk, pose, prefetch;
+    int orow0, orows;
+};
+struct AttnMixedParams { AttnParams a; AttnGroupB b; };
+
 #define ATT_KV 64
 #define ATT_TILE_BYTES (64 * 128)   // 64 rows x 64 fp16
 
@@ -58,20 +71,20 @@ __host__ __device__ inline int attn_block_map(int bid, int nwg) {
 // The pose-token query of one (sequence, head) per workgroup: 1 x (nk + 1) scores, softmax and 1 x 64 output as fp32 dot products
 // (an MFMA tile would carry 31 dead queries through every key tile).  Phase 1: thread = key (K rows are 128 contiguous bytes),
 // phase 2: block-wide max / sum, probabilities parked in LDS, phase 3: lane = d (V^T rows are contiguous along the keys).
+// s / h: sequence and head; nq / nk: the pose query's and the pose key's token index; kpad: keys walked (a multiple of 64 that covers
+// nk + 1, at most npad); orow / orows: the output row and the rows of the output planes
 template <bool SPLIT>
-__device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem) {
+__device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem, int s, int h, int nq, int nk, int kpad, int64_t orow, int64_t orows) {
     // One workgroup per (sequence, head); its four waves split the keys (a single wave walking all 769 keys was a 58-us
     // dependent chain - longer than the whole kernel at B <= 4).  Phase 1: thread = key; phase 2: block-wide max / sum;
     // phase 3: lane = d, wave w sums over its quarter of the keys; wave partials meet in LDS.
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sh = blockIdx.x;
-    const int s = sh / p.heads, h = sh - s * p.heads;
     const int skv = (s + p.kv_shift) % p.S;
-    const size_t qoff = ((size_t)(s * p.heads + h) * p.npad + p.nq) * 64;
+    const size_t qoff = ((size_t)(s * p.heads + h) * p.npad + nq) * 64;
     const size_t koff = (size_t)(skv * p.heads + h) * p.npad * 64;
     const size_t voff = (size_t)(skv * p.heads + h) * 64 * p.npad;
     float* pl = reinterpret_cast<float*>(smem);               // [npad] scores, then probabilities
-    float* red = pl + p.npad;                                 // [4] wave maxima, [4] wave sums, [4][64] partial outputs
+    float* red = pl + kpad;                                   // [4] wave maxima, [4] wave sums, [4][64] partial outputs
     float q[64];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -80,9 +93,9 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem)
 #pragma unroll
         for (int e = 0; e < 8; ++e) q[c * 8 + e] = (float)a.e[e] + (SPLIT ? (float)b.e[e] : 0.f);
     }
-    const int nkeys = p.nk + 1;
+    const int nkeys = nk + 1;
     float mx = -INFINITY;
-    for (int j = tid; j < p.npad; j += 256) {
+    for (int j = tid; j < kpad; j += 256) {
         float t = -INFINITY;
         if (j < nkeys) {
             float acc = 0.f;
@@ -104,7 +117,7 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem)
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float sum = 0.f;
-    for (int j = tid; j < p.npad; j += 256) {
+    for (int j = tid; j < kpad; j += 256) {
         const float e = __builtin_amdgcn_exp2f(pl[j] - mx);       // exp2(-inf) = 0 for the padding
         pl[j] = e;
         sum += e;
@@ -112,10 +125,10 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem)
     sum = wave_sum(sum);
     if (lane == 0) red[4 + wave] = sum;
     __syncthreads();
-    // wave w: keys [w * npad / 4, (w + 1) * npad / 4) (npad % 64 == 0: whole 16-key groups), two 8-key chunks in flight
+    // wave w: keys [w * kpad / 4, (w + 1) * kpad / 4) (kpad % 64 == 0: whole 16-key groups), two 8-key chunks in flight
     const f16* vh = p.Vt_hi + voff + (size_t)lane * p.npad;
     const f16* vl = SPLIT ? p.Vt_lo + voff + (size_t)lane * p.npad : nullptr;
-    const int k0 = wave * (p.npad >> 2), k1 = k0 + (p.npad >> 2);
+    const int k0 = wave * (kpad >> 2), k1 = k0 + (kpad >> 2);
     float o = 0.f;
     for (int c0 = k0; c0 < k1; c0 += 16) {                         // V^T columns >= nkeys are zero (memset) and their p is 0
         H8 a[2], b[2];
@@ -135,30 +148,50 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem)
     if (wave != 0) return;
     o = (red[8 + lane] + red[8 + 64 + lane]) + (red[8 + 128 + lane] + red[8 + 192 + lane]);
     o /= (red[4] + red[5]) + (red[6] + red[7]);
-    const int64_t orow = (int64_t)p.S * p.nq + s, orows = (int64_t)p.S * p.nq + p.S;
     const size_t oo = blk_off<SPLIT>(orow, h * 64 + lane, orows);
     if (SPLIT) { f16 hh, ll; split_f16(o, hh, ll, p.range); p.O_hi[oo] = hh; p.O_hi[oo + 32] = ll; }
     else p.O_hi[oo] = to_f16_sat(o, p.range);
 }
 
-template <bool SPLIT>
-__global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// The kernel body.  MIXED = false: attn_kernel, one group (g is not read).  MIXED = true: attn_mixed_kernel, two groups; what
+// differs between them - nq, nk, the pose mode, the schedule, the query blocks per (sequence, head), the output rows - is uniform
+// over the workgroup (functions of blockIdx and the kernel arguments only: scalar registers).
+template <bool SPLIT, bool MIXED>
+__device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB& g, char* smem) {
     constexpr int NPL = SPLIT ? 2 : 1;
     constexpr int STAGE = 2 * NPL * ATT_TILE_BYTES;   // K planes then V^T planes
-    // pose blocks first in the grid (short: they end while the first round of query blocks is still running)
-    const int npose_blocks = p.pose == 1 ? p.S * p.heads : 0;
-    const int nqe = p.nq + (p.pose == 2 ? 1 : 0);       // pose == 2: the pose query rides in the last query block's spare rows
-    if ((int)blockIdx.x < npose_blocks) { attn_pose_query<SPLIT>(p, smem); return; }
+    // pose blocks first in the grid (short: they end while the first round of query blocks is still running); group a's, then b's
+    const int S1 = MIXED ? g.S1 : p.S;
+    const int npose_a = p.pose == 1 ? S1 * p.heads : 0;
+    const int npose_blocks = npose_a + (MIXED && g.pose == 1 ? (p.S - S1) * p.heads : 0);
+    if ((int)blockIdx.x < npose_blocks) {
+        int sh = blockIdx.x;
+        const bool inb = MIXED && sh >= npose_a;
+        if (inb) sh -= npose_a;
+        const int sl = sh / p.heads, h = sh - sl * p.heads;
+        const int nq = inb ? g.nq : p.nq, nk = inb ? g.nk : p.nk;
+        const int64_t orow = (inb ? g.orow0 : 0) + (int64_t)(inb ? p.S - S1 : S1) * nq + sl;
+        attn_pose_query<SPLIT>(p, smem, inb ? S1 + sl : sl, h, nq, nk, MIXED ? (nk + 64) & ~63 : p.npad, orow,
+                               MIXED ? (int64_t)g.orows : (int64_t)p.S * p.nq + p.S);
+        return;
+    }
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lhi = lane >> 5;
-    // 1-D grid, XCD-aware (attn_block_map)
-    const int nqb = (nqe + 127) / 128;
-    const int nwg = nqb * p.heads * p.S;
-    const int logical = attn_block_map(blockIdx.x - npose_blocks, nwg);
+    // 1-D grid, XCD-aware (attn_block_map); the logical ids of group a's query blocks come first, group b's follow
+    const int nqb_a = (p.nq + (p.pose == 2 ? 1 : 0) + 127) / 128, nwg_a = nqb_a * p.heads * S1;
+    const int nqb_b = MIXED ? (g.nq + (g.pose == 2 ? 1 : 0) + 127) / 128 : 0;
+    const int nwg = nwg_a + nqb_b * p.heads * (p.S - S1);
+    int logical = attn_block_map(blockIdx.x - npose_blocks, nwg);
+    const bool inb = MIXED && logical >= nwg_a;
+    if (inb) logical -= nwg_a;
+    const int nqb = inb ? nqb_b : nqb_a;
+    const int nq = inb ? g.nq : p.nq, nk = inb ? g.nk : p.nk, pose = inb ? g.pose : p.pose, prefetch = inb ? g.prefetch : p.prefetch;
+    const int nqe = nq + (pose == 2 ? 1 : 0);           // pose == 2: the pose query rides in the last query block's spare rows
     const int qb = logical % nqb;
-    const int h = (logical / nqb) % p.heads, s = logical / (nqb * p.heads);
+    const int h = (logical / nqb) % p.heads, sl = logical / (nqb * p.heads);     // sl: sequence within its group
+    const int s = inb ? S1 + sl : sl, Sg = inb ? p.S - S1 : S1;
+    const int64_t obase = inb ? g.orow0 : 0;
     const int skv = (s + p.kv_shift) % p.S;
     const int q0 = qb * 128 + wave * 32;
 
@@ -217,12 +250,12 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
     const bool wave_active = q0 < nqe;         // decoder: 769 = 6 x 128 + 1 queries -> the last block has one live wave
 
     // ---- the pose token as a key (index nk): initial online-softmax state m = s_p, l = 1, O = v_p in fp32
-    if (p.pose && wave_active) {
+    if (pose && wave_active) {
         float sp = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            H8 a, b; a.u = ldg16(p.K_hi + koff + (size_t)p.nk * 64 + kk * 16 + lhi * 8);
-            if (SPLIT) b.u = ldg16(p.K_lo + koff + (size_t)p.nk * 64 + kk * 16 + lhi * 8);
+            H8 a, b; a.u = ldg16(p.K_hi + koff + (size_t)nk * 64 + kk * 16 + lhi * 8);
+            if (SPLIT) b.u = ldg16(p.K_lo + koff + (size_t)nk * 64 + kk * 16 + lhi * 8);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const float kv = (float)a.e[e] + (SPLIT ? (float)b.e[e] : 0.f);
@@ -237,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
         for (int d = 0; d < 2; ++d)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const size_t o = voff + (size_t)(d * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * p.npad + p.nk;
+                const size_t o = voff + (size_t)(d * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * p.npad + nk;
                 oacc[d][r] = (float)p.Vt_hi[o] + (SPLIT ? (float)p.Vt_lo[o] : 0.f);
             }
     }
@@ -285,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = kv0 + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-                    if (key >= p.nk) sacc[t][r] = -INFINITY;
+                    if (key >= nk) sacc[t][r] = -INFINITY;
                 }
         }
         float mx = -INFINITY;
@@ -370,9 +403,9 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
         __syncthreads();
     };
 
-    const int ntiles = (p.nk + ATT_KV - 1) / ATT_KV, nfull = p.nk / ATT_KV;
+    const int ntiles = (nk + ATT_KV - 1) / ATT_KV, nfull = nk / ATT_KV;
     using F = integral_constant<bool, false>; using T = integral_constant<bool, true>;
-    if (p.prefetch) {
+    if (prefetch) {
         // Small grids (SLAM scale: 196 keys = 4 tiles, <= 256 workgroups): one tile's arithmetic (~0.7 us) is shorter than the
         // latency of the next tile's DMA (~2 us), so the double-buffered loop below waits ~1.3 us per tile on a chain of four.
         // With 4 LDS stages every tile is requested up front: one latency, then four tiles of arithmetic.  The DMAs complete in
@@ -413,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
     // as [query][column block][hi 64 B | lo 64 B] (= the row blocks of the output planes) in LDS and writes whole 128-B lines.
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
-    const int64_t orows = (int64_t)p.S * p.nq + (p.pose ? p.S : 0);
+    const int64_t orows = MIXED ? (int64_t)g.orows : (int64_t)p.S * p.nq + (p.pose ? p.S : 0);
     if constexpr (SPLIT) {
         // LDS image per wave: 64 rows of 128 B, row R = d * 32 + query = [hi 4 chunks | lo 4 chunks] of 16 B (8 d each), chunk c of
         // row R stored at position c ^ (R & 7).  Round 6: the first form ([query][d block] rows of 144 B, ds_write_b64 straight from
@@ -462,7 +495,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
                 const int qq = (lane >> 3) + 8 * it, ch = lane & 7;
                 const int q = q0 + qq;
                 if (q < nqe) {
-                    const int64_t orow = q < p.nq ? (int64_t)s * p.nq + q : (int64_t)p.S * p.nq + s;
+                    const int64_t orow = obase + (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl);
                     const size_t o = blk_off<true>(orow, h * 64 + d * 32, orows);
                     *reinterpret_cast<uint4*>(p.O_hi + o + ch * 8) = *reinterpret_cast<const uint4*>(wl + (d * 32 + qq) * 128 + ((ch ^ (qq & 7)) << 4));
                 }
@@ -471,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
         const int q = q0 + l31;
         if (q < nqe) {
             RangeAcc ra;
-            const int64_t orow = q < p.nq ? (int64_t)s * p.nq + q : (int64_t)p.S * p.nq + s;
+            const int64_t orow = obase + (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl);
 #pragma unroll
             for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -485,4 +518,17 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
                 }
         }
     }
+}
+
+template <bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body<SPLIT, false>(p, AttnGroupB{}, smem);
+}
+
+// Two groups of sequences with their own nq / nk in one launch (AttnGroupB)
+template <bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_mixed_kernel(const AttnMixedParams mp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body<SPLIT, true>(mp.a, mp.b, smem);
 }

@@ -115,6 +115,8 @@ struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks;
 // partly valid last tile runs (-1: none; prefetch: its tile index = its LDS stage; double-buffered: tile index & 1);
 // pose_scratch: LDS bytes the pose-query path needs at the smallest npad a caller can pass.
 struct AttnPlan { int pose, prefetch, stages, lds_bytes, grid, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; };
+// the two-group launch (attn_mixed_plan): stages / lds_bytes / grid of the launch, then what each group runs
+struct AttnMixedPlan { int stages, lds_bytes, grid, nwg_a; struct Group { int pose, prefetch, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; } g[2]; };
 struct sta_handle {
     sta_config cfg;
     int device = 0;
@@ -146,6 +148,7 @@ struct sta_handle {
     int gemm_variant = 0;   // tests / tools: 0 auto, 1..4 forced GEMM families, 8 = conv3h wherever legal, 9 = auto WITHOUT conv3h (A/B)
     GemmPlan last_plan{};   // the plan of the last launch_gemm / paired launch (sta_debug_last_gemm_plan)
     AttnPlan last_attn{};   // the plan of the last run_attn (sta_debug_last_attn_plan)
+    AttnMixedPlan last_attn_mixed{};   // ... of the last run_attn_mixed (sta_debug_last_attn_mixed_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
     // sta_decode_pos, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and rope_planes_kernel
@@ -684,6 +687,25 @@ extern "C" int sta_decode(sta_handle* h, const float* feat1, const float* feat2,
     return plan_and_run(h, st, [&](Bump& ws) {
         float* x = (float*)ws.take(xbytes);
         return decode_impl(h, ws, feat1, feat2, B, hp, wp, x, out1, out2, true, st);
+    });
+}
+
+// _decode_stereo on two views of DIFFERENT resolution (decode_mixed_impl): side 1 an hp1 x wp1 patch grid, side 2 hp2 x wp2.
+extern "C" int sta_decode_mixed(sta_handle* h, const float* feat1, const float* feat2, int B, int hp1, int wp1, int hp2, int wp2,
+                                float* const* out1, float* const* out2, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    CHK(check_ready(h, B, hp1 * 16, wp1 * 16));
+    CHK(check_ready(h, B, hp2 * 16, wp2 * 16));
+    REQUIRE(feat1 && feat2, "null device pointer");
+    const int64_t rows = (int64_t)B * ((int64_t)hp1 * wp1 + 1) + (int64_t)B * ((int64_t)hp2 * wp2 + 1);
+    REQUIRE(rows < ((int64_t)1 << 31), "too many decoder rows (%lld)", (long long)rows);
+    hipStream_t st = (hipStream_t)stream;
+    CHK(ensure_rope(h, std::max(std::max(hp1, wp1), std::max(hp2, wp2))));
+    const int64_t xbytes = rows * h->cfg.dec_embed_dim * 4;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        float* x = (float*)ws.take(xbytes);
+        return decode_mixed_impl(h, ws, feat1, feat2, B, hp1, wp1, hp2, wp2, x, out1, out2, st);
     });
 }
 

@@ -287,4 +287,38 @@ extern "C" int sta_bench_attention(sta_handle* h, int S, int heads, int nq, int 
     hipEventDestroy(e0); hipEventDestroy(e1);
     return 0;
 }
+// The two-group attention launch alone (run_attn_mixed) on random operands: ms per launch over `iters` back-to-back launches.
+extern "C" int sta_bench_attention_mixed(sta_handle* h, int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift,
+                                         int iters, float* ms_out, void* stream) {
+    REQUIRE(h && ms_out && iters > 0 && S1 > 0 && S2 >= 0 && heads > 0 && nq_a > 0 && nk_a > 0 && (S2 == 0 || (nq_b > 0 && nk_b > 0)), "bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int S = S1 + S2;
+    const int nmax = std::max(std::max(nq_a, nk_a), S2 ? std::max(nq_b, nk_b) : 0), npad = rup(nmax + 1, 64);
+    const int64_t hsz = (int64_t)S * heads * npad * 64, M = (int64_t)S1 * (nq_a + 1) + (int64_t)S2 * (nq_b + 1);
+    CHK(ensure_ws(h, (3 * hsz + M * heads * 64) * 4 + (1 << 16), st));
+    h->dry = false;
+    Bump ws = cur_bump(h);
+    QKVOut o; o.npad = npad; o.q = ws.planes(hsz, true); o.k = ws.planes(hsz, true); o.vt = ws.planes(hsz, true);
+    Planes ao = ws.act(M, heads * 64, true);
+    REQUIRE(!ws.overflow, "internal: bench workspace overflow");
+    if (!split) { o.q.lo = o.k.lo = o.vt.lo = nullptr; ao.lo = nullptr; }
+    hipLaunchKernelGGL(fill_rand_f16_kernel, dim3(2048), dim3(256), 0, st, o.q.hi, hsz * 2, 5u, 1.0f);
+    hipLaunchKernelGGL(fill_rand_f16_kernel, dim3(2048), dim3(256), 0, st, o.k.hi, hsz * 2, 7u, 1.0f);
+    hipLaunchKernelGGL(fill_rand_f16_kernel, dim3(2048), dim3(256), 0, st, o.vt.hi, hsz * 2, 9u, 1.0f);
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    int rc = 0;
+    for (int i = 0; i < 2 && rc == 0; ++i) rc = run_attn_mixed(h, o, ao, heads * 64, S1, S2, heads, nq_a, nk_a, nq_b, nk_b, kv_shift, st);
+    HIPCHK(hipEventRecord(e0, st));
+    for (int i = 0; i < iters && rc == 0; ++i) rc = run_attn_mixed(h, o, ao, heads * 64, S1, S2, heads, nq_a, nk_a, nq_b, nk_b, kv_shift, st);
+    HIPCHK(hipEventRecord(e1, st));
+    if (rc != 0) return rc;
+    HIPCHK(hipEventSynchronize(e1));
+    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    *ms_out = ms / iters;
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return 0;
+}
 #endif   // STA_TEST_HOOKS

@@ -230,6 +230,52 @@ extern "C" int sta_debug_attention_pose(sta_handle* h, const float* q, const flo
     return 0;
 }
 
+// The two-group form (attn_mixed_kernel / run_attn_mixed).  Group a: S1 sequences, q_a fp32 [S1, heads, nq_a + 1, 64], k_a / v_a
+// [S1, heads, nk_a + 1, 64], pose token LAST; group b the same with S2, nq_b, nk_b (S2 == 0: q_b, k_b, v_b may be NULL).  k / v of
+// a sequence are the keys IT READS: the entry stores those of sequence s at buffer sequence (s + kv_shift) % (S1 + S2), where the
+// kernel looks for them.  out fp32 [S1*nq_a + S1 + S2*nq_b + S2, heads*64]: per group the patch rows sequence-major, then its pose
+// rows.  Poisoning as in sta_debug_attention_pose: V^T padding zero; K padding, dead Q rows and the output planes 0xFF.
+extern "C" int sta_debug_attention_mixed(sta_handle* h, const float* q_a, const float* k_a, const float* v_a, const float* q_b,
+                                         const float* k_b, const float* v_b, int S1, int S2, int heads, int nq_a, int nk_a,
+                                         int nq_b, int nk_b, int kv_shift, float* out, void* stream) {
+    REQUIRE(h && q_a && k_a && v_a && out && S1 > 0 && S2 >= 0 && heads > 0 && nq_a > 0 && nk_a > 0, "bad argument");
+    REQUIRE(S2 == 0 || (q_b && k_b && v_b && nq_b > 0 && nk_b > 0), "bad argument (second group)");
+    REQUIRE(kv_shift >= 0 && kv_shift < S1 + S2, "bad kv_shift");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int S = S1 + S2;
+    const int nmax = std::max(std::max(nq_a, nk_a), S2 ? std::max(nq_b, nk_b) : 0), npad = rup(nmax + 1, 64);
+    const int64_t seq = (int64_t)heads * npad * 64, hsz = S * seq;
+    const int64_t M = (int64_t)S1 * (nq_a + 1) + (int64_t)S2 * (nq_b + 1);
+    CHK(ensure_ws(h, (3 * hsz + M * heads * 64) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
+    Planes ao = ws.act(M, heads * 64, split);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    HIPCHK(hipMemsetAsync(o.vt.hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(o.vt.lo, 0, hsz * 2, st));
+    CHK(dbg_poison_planes(o.k, hsz, st));
+    CHK(dbg_poison_planes(o.q, hsz, st));
+    CHK(dbg_poison_act(ao, M, heads * 64, st));
+    auto at = [&](const Planes& p, int64_t s) { Planes r = p; r.hi = p.hi + s * seq; if (p.lo) r.lo = p.lo + s * seq; return r; };
+    for (int s = 0; s < S; ++s) {
+        const bool inb = s >= S1;
+        const int sl = inb ? s - S1 : s, nqt = (inb ? nq_b : nq_a) + 1, nkt = (inb ? nk_b : nk_a) + 1, skv = (s + kv_shift) % S;
+        const float* q = (inb ? q_b : q_a) + (int64_t)sl * heads * nqt * 64;
+        const float* k = (inb ? k_b : k_a) + (int64_t)sl * heads * nkt * 64;
+        const float* v = (inb ? v_b : v_a) + (int64_t)sl * heads * nkt * 64;
+        CHK(run_rows_to_planes(h, q, (int64_t)nqt * 64, heads, nqt, 64, at(o.q, s), st, npad));
+        CHK(run_rows_to_planes(h, k, (int64_t)nkt * 64, heads, nkt, 64, at(o.k, skv), st, npad));
+        const Planes vt = at(o.vt, skv);
+        hipLaunchKernelGGL(pack_vt_kernel, dim3((unsigned)(((int64_t)heads * nkt * 64 + 255) / 256)), dim3(256), 0, st,
+                           v, heads, nkt, npad, vt.hi, vt.lo, h->range);
+        HIPCHK(hipGetLastError());
+    }
+    CHK(run_attn_mixed(h, o, ao, heads * 64, S1, S2, heads, nq_a, nk_a, nq_b, nk_b, kv_shift, st));
+    CHK(dbg_planes_to_f32(h, ao, 0, 1, (int)M, heads * 64, out, st));
+    return 0;
+}
+
 // A/B switches of the product's round-4 choices (tools/ab_option.py, ab_slam.py, ab_replay.py; 0 everywhere = product behaviour):
 //   1 = 1: small-grid K slices by the old rule ceil(256 / tiles)          2 = 1: small-grid GEMMs always on 4 waves (> 1: the lone-grid limit)
 //   4 = 1: debug GEMM entry points in the f16mx arithmetic                5 = 1: attention without the 4-stage prefetch schedule

@@ -170,6 +170,100 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ decoder, two token counts
+// The decoder on a view pair of DIFFERENT resolution: side 1 has N1 = hp1 x wp1 patch tokens, side 2 N2 = hp2 x wp2 (the reference's
+// module code takes them: cross attention accepts any memory length, sta_blocks.py:193-205; sta_model.py:177-244 is shape-agnostic).
+// Row order of x (fp32, [B*(N1+1) + B*(N2+1), D]) and of every plane buffer derived from it: each side is decode_impl's layout with
+// S = B, and the two sides are adjacent:
+//     [B*N1 patch rows of side 1 | B pose rows of side 1 | B*N2 patch rows of side 2 | B pose rows of side 2]
+// LayerNorm, proj, cproj, fc1, fc2 and the residual epilogues are row-wise: ONE launch over all rows, the calls of decode_impl
+// without the TailHint (the pose rows are not the last rows of the launch: gemm_plan drops the row tail, as for any caller without
+// a hint).  What knows the sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SIDE on that side's contiguous row
+// range (own ntok, wp, pose_base = B*Nx; Q / K / V^T planes advanced by B sequences of the shared npad) - the hot GEMMs' EPI_QKV is
+// untouched -, attention is the two-group launch (run_attn_mixed): kv_shift = 0 for the self attention of both sides, kv_shift = B
+// with (nq, nk) = (N1, N2) | (N2, N1) for the cross attention of both directions.  One lane (no side stream), patch-grid
+// positions only, outside sta_reserve's coverage.  Equal grids are served too (the same route: tests compare it with decode_impl).
+// want1[i] [B, N1+1, D] / want2[i] [B, N2+1, D] in the reference's token order (pose token first), or NULL.
+static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, int B, int hp1, int wp1, int hp2, int wp2,
+                             float* x, float* const* want1, float* const* want2, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim, Hh = c.dec_num_heads;
+    const int Nn[2] = {hp1 * wp1, hp2 * wp2}, wps[2] = {wp1, wp2};
+    const int Mp[2] = {B * Nn[0], B * Nn[1]};                        // patch rows of a side = its pose_base
+    const int R[2] = {Mp[0] + B, Mp[1] + B}, row0[2] = {0, R[0]};    // rows of a side, its first row
+    const int M = R[0] + R[1], S = 2 * B, npad = rup((Nn[0] > Nn[1] ? Nn[0] : Nn[1]) + 1, 64);
+    Planes fp = ws.act((int64_t)Mp[0] + Mp[1], E, split);
+    Planes a1 = ws.act(M, D, split);
+    Planes ay = ws.act(M, D, split);
+    Planes ao = ws.act(M, D, split);
+    Planes f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
+    f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
+    QKVOut qkv; qkv.npad = npad;
+    const int64_t ssz = (int64_t)B * Hh * npad * 64, hsz = 2 * ssz;   // B sequences = one side; all S sequences
+    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split);
+    QKVOut cqkv; cqkv.npad = npad;
+    cqkv.q = ws.planes(hsz, split); cqkv.k = ws.planes(hsz, split);
+    qkv.vt = ws.planes(hsz, split); cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
+    { const Planes* z[2] = {&qkv.vt, &cqkv.vt}; CHK(zero_planes(z, 2, hsz, split, st)); }
+    auto side_planes = [&](const Planes& p, int side) { Planes q = p; q.hi = p.hi + side * ssz; if (p.lo) q.lo = p.lo + side * ssz; return q; };
+    auto side_qkv = [&](const QKVOut& o, int side) { QKVOut q; q.npad = o.npad; q.q = side_planes(o.q, side); q.k = side_planes(o.k, side); q.vt = side_planes(o.vt, side); return q; };
+
+    for (int side = 0; side < 2; ++side) {
+        const Planes fps = slice_rows(fp, side ? Mp[0] : 0);
+        float* xs = x + (size_t)row0[side] * D;
+        CHK(run_rows_to_planes(h, side ? feat2 : feat1, (int64_t)Nn[side] * E, B, Nn[side], E, fps, st));
+        CHK(gemm_f32(h, fps, h->dec_embed, Mp[side], xs, D, nullptr, st));
+        hipLaunchKernelGGL(fill_pose_token_kernel, dim3((B * D + 255) / 256), dim3(256), 0, st, xs + (size_t)Mp[side] * D, B, 1, D, h->pose_tok);
+        HIPCHK(hipGetLastError());
+    }
+    auto emit = [&](int idx, const float* src) -> int {
+        for (int side = 0; side < 2; ++side) {
+            float* dst = side == 0 ? (want1 ? want1[idx] : nullptr) : (want2 ? want2[idx] : nullptr);
+            if (!dst) continue;
+            const int64_t total4 = (int64_t)B * (Nn[side] + 1) * D / 4;
+            int blocks = (int)((total4 + 255) / 256); if (blocks > 8192) blocks = 8192;
+            hipLaunchKernelGGL(emit_tokens_kernel, dim3(blocks), dim3(256), 0, st, src + (size_t)row0[side] * D, 0, B, Nn[side], D, (int64_t)Mp[side], dst);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    };
+    // one QKV-epilogue GEMM per side: rows [row0, row0 + R) of A -> the side's B sequences of the Q / K / V^T buffers
+    auto qkv_sides = [&](const Planes& A, const Lin& W, int nq, int nk, int nv, const QKVOut& o) -> int {
+        for (int side = 0; side < 2; ++side)
+            CHK(gemm_qkv(h, slice_rows(A, row0[side]), W, R[side], nq, nk, nv, side_qkv(o, side), Nn[side], Hh, wps[side], 0, st, Mp[side]));
+        return 0;
+    };
+    CHK(emit(0, x));
+    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, a1, &h->dec[0].ny, &ay, nullptr, st));
+    for (int i = 0; i < c.dec_depth; ++i) {
+        const DecBlk& b = h->dec[i];
+        CHK(qkv_sides(a1, b.qkv, D, D, D, qkv));
+        CHK(qkv_sides(ay, b.ckv, 0, D, D, cqkv));         // K / V of a side's OWN tokens: the other side's queries read them (kv_shift = B)
+        CHK(run_attn_mixed(h, qkv, ao, D, B, B, Hh, Nn[0], Nn[0], Nn[1], Nn[1], 0, st));
+        CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
+        CHK(qkv_sides(a1, b.cq, D, 0, 0, cqkv));
+        CHK(run_attn_mixed(h, cqkv, ao, D, B, B, Hh, Nn[0], Nn[1], Nn[1], Nn[0], B, st));
+        CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
+        CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));
+        if (i + 1 < c.dec_depth) {
+            const DecBlk& nb = h->dec[i + 1];
+            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, &nb.n1, &a1, &nb.ny, &ay, st));
+            CHK(emit(i + 1, x));
+        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
+            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
+            if ((want1 && want1[i + 1]) || (want2 && want2[i + 1])) {
+                Planes none;
+                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, x, st));          // x is dead after the last layer: in place
+                CHK(emit(i + 1, x));
+            }
+        }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ pose head
 // pose2 / conf2 (optional): the last B - split samples write there (the two sides of a pair: one set of four launches)
 static int pose_impl(sta_handle* h, Bump& ws, const float* tok, int B, int64_t stride, float* pose, float* conf, hipStream_t st,

@@ -793,6 +793,122 @@ static int run_attn(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ two-group attention (decode_mixed_impl)
+// The plan of attn_mixed_kernel, pure like attn_plan: group a = S1 sequences of nq_a queries over nk_a keys, group b = S2 sequences of
+// nq_b over nk_b, both in the decoder's pose-token form (pose key at token index nk, pose query at token index nq of the group).
+// Per group exactly attn_plan's rules on the group's own numbers - pose mode from its nq, tiles and tail from its nk, pose-query
+// scratch from its nk -; the prefetch decision uses the grid of the WHOLE launch (it is about how many workgroups share a CU), and
+// the launch carries the LDS of the hungrier group: 4 stages as soon as one group prefetches (a double-buffered group then simply
+// leaves stages 2 and 3 alone; the grid is <= 256 workgroups in that case, one per CU either way).  S2 == 0, or two groups of equal
+// (nq, nk) with nq == nk, reduce to attn_plan(S1 + S2, ..., pose) field by field (tests/test_attention_mixed_plan.py).
+static int attn_mixed_plan(int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, bool split, bool no_prefetch, AttnMixedPlan& out) {
+    REQUIRE(S1 > 0 && S2 >= 0 && heads > 0 && nq_a > 0 && nk_a > 0, "empty attention");
+    REQUIRE(S2 == 0 || (nq_b > 0 && nk_b > 0), "empty attention (second group)");
+    AttnMixedPlan m{};
+    const int Sg[2] = {S1, S2}, nq[2] = {nq_a, nq_b}, nk[2] = {nk_a, nk_b};
+    int64_t grid = 0;
+    for (int i = 0; i < 2; ++i) {
+        AttnMixedPlan::Group& a = m.g[i];
+        if (Sg[i] == 0) continue;
+        a.pose = nq[i] % 128 != 0 ? 2 : 1;
+        a.pose_blocks = a.pose == 1 ? Sg[i] * heads : 0;
+        a.qblocks = (nq[i] + (a.pose == 2 ? 1 : 0) + 127) / 128;
+        grid += (int64_t)a.qblocks * heads * Sg[i] + a.pose_blocks;
+        a.ntiles = (nk[i] + ATT_KV - 1) / ATT_KV; a.nfull = nk[i] / ATT_KV;
+        a.pose_scratch = (rup(nk[i] + 1, 64) + 8 + 256) * 4;
+        REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+    }
+    REQUIRE(grid < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)grid);
+    m.grid = (int)grid;
+    m.nwg_a = m.g[0].qblocks * heads * S1;
+    m.stages = 2;
+    for (int i = 0; i < 2; ++i) {
+        AttnMixedPlan::Group& a = m.g[i];
+        if (Sg[i] == 0) continue;
+        a.prefetch = (nk[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
+        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
+        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
+    }
+    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
+    out = m;
+    return 0;
+}
+#ifdef STA_TEST_HOOKS
+static void attn_mixed_plan_out(const AttnMixedPlan& m, int* out) {
+    out[0] = m.stages; out[1] = m.lds_bytes; out[2] = m.grid; out[3] = m.nwg_a;
+    for (int i = 0; i < 2; ++i) {
+        const AttnMixedPlan::Group& a = m.g[i];
+        const int v[8] = {a.pose, a.prefetch, a.pose_blocks, a.qblocks, a.ntiles, a.nfull, a.tail_stage, a.pose_scratch};
+        for (int j = 0; j < 8; ++j) out[4 + 8 * i + j] = v[j];
+    }
+}
+// out[20] = {LDS stages, LDS bytes, grid, query-block workgroups of group a, then per group {pose mode, prefetch, pose blocks, query
+// blocks, ntiles, nfull, tail stage, pose scratch bytes}}
+extern "C" int sta_debug_attn_mixed_plan(int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, int split, int no_prefetch, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnMixedPlan m;
+    CHK(attn_mixed_plan(S1, S2, heads, nq_a, nk_a, nq_b, nk_b, split != 0, no_prefetch != 0, m));
+    attn_mixed_plan_out(m, out);
+    return 0;
+}
+extern "C" int sta_debug_last_attn_mixed_plan(sta_handle* h, int* out) {
+    REQUIRE(h && out, "bad argument");
+    attn_mixed_plan_out(h->last_attn_mixed, out);
+    return 0;
+}
+// The workgroup -> (sequence, head, query block) map of attn_mixed_kernel's query-block workgroups, computed by the arithmetic the
+// kernel uses (attn_block_map over both groups' blocks, group a's logical ids first): out[3 * b + {0, 1, 2}] for workgroup b of
+// nwg = heads * (S1 * qblocks_a + S2 * qblocks_b).
+extern "C" int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qblocks_a, int qblocks_b, int* out) {
+    REQUIRE(out && S1 > 0 && S2 >= 0 && heads > 0 && qblocks_a > 0 && (S2 == 0 || qblocks_b > 0), "bad argument");
+    const int nwg_a = qblocks_a * heads * S1, nwg = nwg_a + qblocks_b * heads * S2;
+    for (int b = 0; b < nwg; ++b) {
+        int logical = attn_block_map(b, nwg);
+        const bool inb = logical >= nwg_a;
+        if (inb) logical -= nwg_a;
+        const int nqb = inb ? qblocks_b : qblocks_a;
+        out[3 * b] = logical / (nqb * heads) + (inb ? S1 : 0); out[3 * b + 1] = (logical / nqb) % heads; out[3 * b + 2] = logical % nqb;
+    }
+    return 0;
+}
+#endif
+
+// out: [S1*nq_a patch rows | S1 pose rows | S2*nq_b patch rows | S2 pose rows] (decode_mixed_impl's row order), out.rp rows in all
+static int run_attn_mixed(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S1, int S2, int heads,
+                          int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift, hipStream_t st) {
+    if (h->dry) return 0;
+    const bool split = h->prec != STA_PREC_F16;
+    AttnMixedPlan m;
+    CHK(attn_mixed_plan(S1, S2, heads, nq_a, nk_a, nq_b, nk_b, split, h->opt[5] == 1, m));
+    h->last_attn_mixed = m;
+    const int nmax = std::max(std::max(nq_a, nk_a), S2 ? std::max(nq_b, nk_b) : 0);
+    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: two-group attention needs max(nq, nk) < npad, npad %% 64 == 0");
+    REQUIRE(kv_shift >= 0 && kv_shift < S1 + S2, "internal: kv_shift out of range");
+    const int64_t orows = (int64_t)S1 * (nq_a + 1) + (int64_t)S2 * (nq_b + 1);
+    REQUIRE(out.rp == orows && orows < ((int64_t)1 << 31), "internal: two-group attention output of %lld rows in planes of %lld", (long long)orows, (long long)out.rp);
+    AttnMixedParams mp; memset(&mp, 0, sizeof mp);
+    AttnParams& p = mp.a;
+    p.range = h->range;
+    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
+    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
+    p.S = S1 + S2; p.heads = heads; p.nq = nq_a; p.nk = nk_a; p.npad = qkv.npad; p.kv_shift = kv_shift;
+    p.scale_log2e = 0.125f * 1.44269504088896340736f;
+    p.pose = m.g[0].pose; p.prefetch = m.g[0].prefetch;
+    mp.b.S1 = S1;
+    mp.b.nq = S2 ? nq_b : nq_a; mp.b.nk = S2 ? nk_b : nk_a; mp.b.pose = S2 ? m.g[1].pose : m.g[0].pose; mp.b.prefetch = m.g[1].prefetch;
+    mp.b.orow0 = S1 * (nq_a + 1); mp.b.orows = (int)orows;
+    const dim3 grid((unsigned)m.grid);
+    if (split) {
+        static unsigned attr_done = 0;      // one bit per device
+        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_mixed_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
+        hipLaunchKernelGGL(attn_mixed_kernel<true>, grid, dim3(256), m.lds_bytes, st, mp);
+    } else {
+        STA_F16ONLY(hipLaunchKernelGGL(attn_mixed_kernel<false>, grid, dim3(256), m.lds_bytes, st, mp));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 static int run_rows_to_planes(sta_handle* h, const float* x, int64_t bstride, int nb, int rows, int C, const Planes& o, hipStream_t st, int64_t obstride = 0, bool mx = false) {
     if (h->dry) return 0;
     int64_t total4 = (int64_t)nb * rows * C / 4;

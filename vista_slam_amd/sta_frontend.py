@@ -284,6 +284,60 @@ class STAFrontend:
                                                B, N, pos_max, p1, p2, self._stream()))
         return out1, out2
 
+    def decode_stereo_mixed(self, feat1: torch.Tensor, feat2: torch.Tensor, pos1: torch.Tensor, pos2: torch.Tensor,
+                            layers: Sequence[int] | None = None):
+        """`_decode_stereo` for two views with DIFFERENT token counts (a landscape and a portrait frame, two cameras, a loop
+        candidate kept at a lower resolution): feat1 [B, N1, E], feat2 [B, N2, E] -> two lists of dec_depth+1 tensors
+        [B, N1+1, D] / [B, N2+1, D] like the reference's module code returns for such a pair (cross attention takes any memory
+        length, sta_blocks.py:193-205).  Positions must be each side's own patch grid (what `_encode_image` returns).  Equal
+        counts are accepted and take the same route (sta_decode_mixed), so the two routes can be compared."""
+        feat1 = self._f32(feat1).contiguous()
+        feat2 = self._f32(feat2).contiguous()
+        B, N1, E = feat1.shape
+        N2 = feat2.shape[1]
+        assert feat2.shape[0] == B and feat2.shape[2] == E and E == self.cfg.enc_embed_dim, \
+            f"both views need the same batch and feature width (got {tuple(feat1.shape)} and {tuple(feat2.shape)})"
+        assert pos1.shape[0] == B and pos2.shape[0] == B, "one positions row per batch entry"
+        g1, g2 = self._grid_from_pos(pos1, N1), self._grid_from_pos(pos2, N2)
+        if g1[2] is not None or g2[2] is not None:
+            raise NotImplementedError("decode_stereo_mixed serves patch-grid positions only: foreign positions (a window of a larger "
+                                      "grid, a permuted order) are served for equal token counts by _decode_stereo")
+        L = self.cfg.dec_depth + 1
+        want = range(L) if layers is None else layers
+        D = self.cfg.dec_embed_dim
+        out1: List[torch.Tensor | None] = [None] * L
+        out2: List[torch.Tensor | None] = [None] * L
+        p1 = (C.c_void_p * L)()
+        p2 = (C.c_void_p * L)()
+        for i in want:
+            out1[i] = torch.empty(B, N1 + 1, D, device=self.device, dtype=torch.float32)
+            out2[i] = torch.empty(B, N2 + 1, D, device=self.device, dtype=torch.float32)
+            p1[i] = out1[i].data_ptr()
+            p2[i] = out2[i].data_ptr()
+        _lib.check(self.lib.sta_decode_mixed(self._h, feat1.data_ptr(), feat2.data_ptr(), B, g1[0], g1[1], g2[0], g2[1],
+                                             p1, p2, self._stream()))
+        return out1, out2
+
+    def forward_pair_mixed(self, img_a: torch.Tensor, img_b: torch.Tensor):
+        """`forward_pair` for two images of different shape [B,3,Ha,Wa] / [B,3,Hb,Wb]: each is encoded at its own shape, the pair
+        is decoded by `decode_stereo_mixed`, and both heads run per side at that side's shape.  Returns (main, support) dicts with
+        pts3d_pred, conf, relative_pose, relative_pose_conf; a portrait side's per-pixel outputs are transposed views, like
+        everywhere else."""
+        img_a, img_b = self._f32(img_a).contiguous(), self._f32(img_b).contiguous()
+        assert img_a.shape[0] == img_b.shape[0], "both views need the same batch"
+        hooks = self.cfg.hooks
+        layers = sorted({hk - 1 for hk in hooks[1:]})
+        feats = [self._encode_image(im, None, normalize=False) for im in (img_a, img_b)]
+        d1, d2 = self.decode_stereo_mixed(feats[0][0], feats[1][0], feats[0][1], feats[1][1], layers=layers)
+        res = []
+        for im, (feat, _pos), dec in zip((img_a, img_b), feats, (d1, d2)):
+            B, _c, H, W_ = im.shape
+            toks = [feat] + [None if t is None else t[:, 1:, :] for t in dec]
+            pts = self.head_pts(toks, [[H, W_]] * B)
+            pose = self.head_pose_s(dec[-1][:, 0, :])
+            res.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"], "relative_pose_conf": pose["conf"]})
+        return res[0], res[1]
+
     def head_pose_s(self, pose_token: torch.Tensor):
         tok = self._f32(pose_token)
         B, D = tok.shape
