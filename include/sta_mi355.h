@@ -141,7 +141,8 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
- * its plan holds the positions table on top of sta_decode's). */
+ * its plan holds the positions table on top of sta_decode's), sta_view_consistency (pair matrices per view count and window) and
+ * sta_symmetric_geo_mask (error plane per edge count). */
 STA_API int sta_reserve(sta_handle* h, int B, int H, int W, int max_edges, void* const* streams, int n_streams);
 STA_API int sta_alloc_stats(const sta_handle* h, int64_t out[2]);
 
@@ -302,6 +303,31 @@ STA_API int sta_world_pointcloud(sta_handle* h, const float* depths, const float
                          const float* confs, const float* imgs, int N, int H, int W, float conf_thres,
                          float* pts_out, float* col_out, uint8_t* ply_records_out, int64_t* count_host, void* stream);
 STA_API int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream);
+
+/* geometric consistency of the depth maps the path produced (vista_slam/utils/slam_utils.py; the CODE is the
+ * definition where it disagrees with its docstring).  All pointers are device memory; H, W need not be multiples of 16 and
+ * H > W is accepted (the kernels have no orientation).  The workspace (pair matrices; error plane, histograms, counters) is
+ * taken from the stream's scratch context, which grows - behind one device synchronisation - on the first call of a larger
+ * size and never afterwards; apart from that neither call synchronises, allocates or copies to the host.
+ * sta_view_consistency <- view_consistency_check(depth, intrinsics, poses, threshold) (slam_utils.py:346-419): every pixel of
+ * view i is unprojected (K_i^-1 [x,y,1] d_i), moved to view j (T_j^-1 T_i, poses camera-to-world), projected with K_j
+ * (uv = uvw[:2] / uvw[2], the unclamped third coordinate) and compared with depth[j] sampled bilinearly there
+ * (grid_sample, align_corners=True, zero padding): agree = |sampled - max(z_j, 1e-6)| < threshold.  count_out [n,H,W] int32 =
+ * the number of agreeing views j in [max(0, i-window), min(n, i+window+1)) \ {i}; window = 4 is the reference (its loop, not
+ * the +-2 of its docstring).  A point behind view j whose uv falls outside the frame samples 0 and agrees when
+ * threshold > 1e-6, as in the reference.  depths [n,H,W], K [n,3,3], poses [n,4,4].
+ * sta_symmetric_geo_mask <- compute_symmetric_geo_valid_mask(depths, intri, relative_pose) (slam_utils.py:269-343) for P edges
+ * at once, in the layout sta_regress_views writes: depths [P,2,H,W], K [P,3,3] (shared by the pair), rel_pose [P,4,4].
+ * Direction 0 warps view 0 by rel_pose into view 1, direction 1 warps view 1 by rel_pose^-1 into view 0; the target pixel is
+ * round-half-even(uv), uv = (K p)[:2] / ((K p)[2] + 1e-8); err = |depth_target - z|; thres = 2 * median(err over the pixels that
+ * land inside the frame) - torch.median: the LOWER middle element, NaN if any such err is NaN -, 1e10 when none does.
+ * mask_out [P,2,H,W] bytes 0/1 = inside && err < thres; thres_out [P,2] (may be NULL) = the thresholds.  The median is an
+ * exact device-side selection (four 8-bit radix passes over the fp32 bit patterns).  For portrait frames of
+ * sta_regress_views pass the transposed views [P,2,W,H] (the K it returns was computed on those). */
+STA_API int sta_view_consistency(sta_handle* h, const float* depths, const float* K, const float* poses, int n, int H, int W,
+                         float threshold, int window, int32_t* count_out, void* stream);
+STA_API int sta_symmetric_geo_mask(sta_handle* h, const float* depths, const float* K, const float* rel_pose, int P, int H, int W,
+                           uint8_t* mask_out, float* thres_out, void* stream);
 
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one

@@ -10,6 +10,7 @@
 #include "conv3h.h"
 #include "attention.h"
 #include "elementwise.h"
+#include "geo.h"
 
 #include <algorithm>
 #include <cmath>

@@ -1,7 +1,8 @@
 // Entry points of the rows either side of the STA forward (SURVEY.md section 8 rows f1-f4), declared in
 // include/sta_mi355.h: f3 input step (sta_preprocess_frame), f4 output step (sta_world_pointcloud, sta_mat_to_se3),
-// f1 post-STA reductions (sta_estimate_intrinsics, sta_estimate_scale), f2 keyframe scheduler (sta_regress_views).
-// Included by sta_api.hip (one translation unit); kernels live in elementwise.h.
+// f1 post-STA reductions (sta_estimate_intrinsics, sta_estimate_scale), f2 keyframe scheduler (sta_regress_views),
+// f5 geometric consistency (sta_view_consistency, sta_symmetric_geo_mask).
+// Included by sta_api.hip (one translation unit); kernels live in elementwise.h and geo.h.
 
 // ---------------------------------------------------------------------------------------------------------
 // f3: input step.  Host side = the integer geometry of _crop_resize_if_necessary_image_only
@@ -160,6 +161,64 @@ extern "C" int sta_world_pointcloud(sta_handle* h, const float* depths, const fl
     });
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// f5: geometric consistency of depth maps (slam_utils.py:269-419; kernels in geo.h).  Neither call synchronises or copies to
+// the host; the workspace comes from the stream's scratch context like f4's.
+extern "C" int sta_view_consistency(sta_handle* h, const float* depths, const float* K, const float* poses, int n, int H, int W,
+                                    float threshold, int window, int32_t* count_out, void* stream) {
+    REQUIRE(h && depths && K && poses && count_out, "null argument");
+    REQUIRE(n >= 1 && H > 0 && W > 0, "bad size");
+    REQUIRE(window >= 0, "window must be >= 0 (got %d)", window);
+    REQUIRE((int64_t)H * W < (int64_t)1 << 30 && n <= 65535, "depth maps too large");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int w = window < n - 1 ? window : n - 1;             // views further than n - 1 apart do not exist: same votes, bounded table
+    const int64_t npair = (int64_t)n * (2 * w + 1);
+    REQUIRE(npair < (int64_t)1 << 30, "too many view pairs");
+    return plan_and_run(h, st, [&](Bump& ws) -> int {
+        GeoPair* pairs = (GeoPair*)ws.take(npair * (int64_t)sizeof(GeoPair));
+        if (h->dry) return 0;
+        REQUIRE(!ws.overflow, "internal: workspace overflow");
+        hipLaunchKernelGGL(vote_pairs_kernel, dim3((unsigned)((npair + 63) / 64)), dim3(64), 0, st, K, poses, n, w, pairs);
+        hipLaunchKernelGGL(view_consistency_kernel, dim3((H * W + 255) / 256, n), dim3(256), 0, st, depths, pairs, n, H, W, w,
+                           threshold, count_out);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
+extern "C" int sta_symmetric_geo_mask(sta_handle* h, const float* depths, const float* K, const float* rel_pose, int P, int H, int W,
+                                      uint8_t* mask_out, float* thres_out, void* stream) {
+    REQUIRE(h && depths && K && rel_pose && mask_out, "null argument");
+    REQUIRE(P >= 1 && H > 0 && W > 0, "bad size");
+    REQUIRE((int64_t)H * W < (int64_t)1 << 30 && P <= 32767, "depth maps too large");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = H * W, slots = 2 * P, gx = (hw + 255) / 256;
+    return plan_and_run(h, st, [&](Bump& ws) -> int {
+        GeoPair* pairs = (GeoPair*)ws.take((int64_t)slots * sizeof(GeoPair));
+        unsigned* err = (unsigned*)ws.take((int64_t)slots * hw * 4);
+        const int64_t zero_bytes = (int64_t)slots * (GEO_STATE + 4 * 256) * 4;      // state + the four histograms, cleared together
+        int* state = (int*)ws.take(zero_bytes);
+        unsigned* hist = (unsigned*)(state + slots * GEO_STATE);
+        if (h->dry) return 0;
+        REQUIRE(!ws.overflow, "internal: workspace overflow");
+        HIPCHK(hipMemsetAsync(state, 0, (size_t)zero_bytes, st));
+        hipLaunchKernelGGL(sym_pairs_kernel, dim3((slots + 63) / 64), dim3(64), 0, st, K, rel_pose, P, pairs);
+        hipLaunchKernelGGL(geo_warp_kernel, dim3(gx, 2, P), dim3(256), 0, st, depths, pairs, H, W, err, state, hist);
+        hipLaunchKernelGGL(geo_pick_kernel, dim3(slots), dim3(64), 0, st, hist, 0, state, thres_out);
+        for (int pass = 1; pass < 4; ++pass) {
+            unsigned* hp = hist + (int64_t)pass * slots * 256;
+            hipLaunchKernelGGL(geo_hist_kernel, dim3(gx, slots), dim3(256), 0, st, err, hw, state, pass, hp);
+            hipLaunchKernelGGL(geo_pick_kernel, dim3(slots), dim3(64), 0, st, hp, pass, state, thres_out);
+        }
+        hipLaunchKernelGGL(geo_mask_kernel, dim3(gx, slots), dim3(256), 0, st, err, hw, state, mask_out);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
+// f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
     DEV_SCOPE(h->device);

@@ -39,14 +39,22 @@ def mat_to_se3(frontend: STAFrontend, pose: torch.Tensor) -> torch.Tensor:
 
 
 def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres: float,
-                     want_records: bool = False):
-    """slam.py:396-408 -> (points [M,3] fp32, colors [M,3] fp32 [, records [M] PLY_RECORD numpy array])."""
+                     want_records: bool = False, counts=None, min_views: int = 0):
+    """slam.py:396-408 -> (points [M,3] fp32, colors [M,3] fp32 [, records [M] PLY_RECORD numpy array]).
+
+    counts [N,H,W] (geo.view_consistency_check) with min_views > 0: a pixel is kept iff conf > conf_thres AND counts >= min_views
+    (the confidence of the other pixels is lowered to -inf on a copy before the same library call).  The defaults leave the
+    output unchanged."""
     depths = _dev(frontend, depths)
     N, H, W = depths.shape
     scales = _dev(frontend, scales).reshape(N)
     K = _dev(frontend, intrinsics, (N, 3, 3))
     poses = _dev(frontend, poses, (N, 4, 4))
     confs = _dev(frontend, confs, (N, H, W))
+    if counts is not None and min_views > 0:
+        counts = torch.as_tensor(counts).to(frontend.device)
+        assert tuple(counts.shape) == (N, H, W), f"expected counts of shape {(N, H, W)}, got {tuple(counts.shape)}"
+        confs = torch.where(counts >= min_views, confs, torch.full_like(confs, float("-inf")))
     imgs = _dev(frontend, imgs, (N, 3, H, W)) if imgs is not None else None
     cap = N * H * W
     pts = torch.empty(cap, 3, device=frontend.device, dtype=torch.float32)
@@ -93,9 +101,12 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
                   conf_thres: float, view_graph: Optional[Dict[int, List[int]]] = None, loop_min_dist=None,
                   view_names: Optional[Sequence[str]] = None, save_view_graph=True, traj_name_postfix=None,
                   save_poses=True, save_images=True, save_scales=True, save_depths=True, save_intrinsics=True,
-                  save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None):
+                  save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None,
+                  counts=None, min_views: int = 0):
     """Same switches and files as OnlineSLAM.save_data_all (slam.py:338-421).  poses [N,4,4] (rotation + translation
-    of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1]."""
+    of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1].
+    counts / min_views: pointcloud.ply keeps only pixels that at least min_views neighbouring views agree with
+    (world_pointcloud); every other file is unaffected."""
     os.makedirs(output_folder, exist_ok=True)
 
     def host(t):
@@ -118,7 +129,8 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
     if save_intrinsics:
         np.save(f"{output_folder}/intrinsics.npy", host(intrinsics))
     if save_ply:
-        _, _, records = world_pointcloud(frontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres, want_records=True)
+        _, _, records = world_pointcloud(frontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres, want_records=True,
+                                         counts=counts, min_views=min_views)
         write_ply(f"{output_folder}/pointcloud.ply", records)
     if gt_poses is not None:
         np.save(f"{output_folder}/gt_poses.npy", np.array(gt_poses).astype(np.float32))
