@@ -37,6 +37,14 @@ STA_API int sta_debug_pick_family(int amode, int epi, long long M, int N, int K,
  * [0, M_all - m_tail).  Fails when the plan would name a kernel that does not exist. */
 STA_API int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, int precision, int mx, int tail_hint, int forced_variant, int* out);
 
+/* The launch plan of a 3x3 convolution (pure host function: gemm_plan with the implicit-GEMM loader and the image geometry, so
+ * that the halo-tiled family 8 is a candidate).  epi: 1 plane epilogue, 6 fused DPT tail; M = images x Ho x Wo output pixels,
+ * N = Cout, K = 9 Cin; cstride 1 | 2; head_gemm: experiment switch 0 (the fused tail as an implicit GEMM from 2^21 pixels on).
+ * out[8] as sta_debug_gemm_plan; family 8: bm = 256 = 8 rows x 32 pixels of one image, tiles_m = images x ceil(Ho / 8) x
+ * ceil(Wo / 32). */
+STA_API int sta_debug_conv_plan(int epi, int M, int N, int K, int precision, int mx, int forced_variant, int cstride, int Ho, int Wo,
+                        int head_gemm, int* out);
+
 /* The same record for the handle's LAST launch_gemm or paired QKV launch (family 7, bm x bn = 192 x 128, tiles_n = both halves'
  * column tiles). */
 STA_API int sta_debug_last_gemm_plan(sta_handle* h, int* out);
@@ -79,8 +87,8 @@ STA_API int sta_debug_attention_pose(sta_handle* h, const float* q, const float*
 
 /* Both attention entries fill, before they pack their inputs, the output planes, both planes of the K padding and the Q rows
  * past the last query with 0xFF (fp16 NaN patterns): an output element the kernel did not write, or a padded key or query it
- * read, shows up as NaN.  The V^T padding is zero, as the kernel's contract requires.  sta_debug_conv3x3 / _convt / _up2 /
- * _layernorm poison their output planes the same way. */
+ * read, shows up as NaN.  The V^T padding is zero, as the kernel's contract requires.  sta_debug_conv3x3 / _conv3x3_r2 / _convt /
+ * _up2 / _layernorm poison their output planes the same way, sta_debug_conv3_head its four fp32 outputs. */
 
 /* The launch plan of the attention kernel (pure host function, no handle, no GPU; sta_launch.inc: attn_plan, what run_attn
  * runs).  pose: decoder form (token nq == nk is the pose token); split: 1 for the f16x3 precisions; no_prefetch: option 5.
@@ -128,6 +136,19 @@ STA_API int sta_debug_set_tail_hint(sta_handle* h, int rows);
  * optional ReLU on the input, activation on the output, residual add (dpt_block.py:94-142). */
 STA_API int sta_debug_conv3x3(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
                       int stride, int relu_in, int act, const float* resid, float* out, void* stream);
+
+/* The same with the second residual of the refinenet fusion (out = act(conv) + resid + resid2; resid2 only with resid). */
+STA_API int sta_debug_conv3x3_r2(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
+                         int stride, int relu_in, int act, const float* resid, const float* resid2, float* out, void* stream);
+
+/* The fused DPT tail as ONE kernel (dpt_block.py:316-324 + postprocess.py:10-62): head.2 (3x3, 128 -> 128) + ReLU + head.4 (1x1,
+ * 128 -> 4) + point-map / confidence activations on x NHWC [n,H,W,128].  w2 [128,128,3,3], b2 [128], w4 [4,128], b4 [4]; head.4's
+ * rows are scaled by powers of two exactly as sta_finalize_weights does.  Images [0, nA) -> ptsA [nA,H,W,3], confA [nA,H,W]; the
+ * rest -> ptsB, confB (an empty side may be NULL); all four are filled with 0xFF first.  Runs the halo form under forced family 8
+ * and, above the small-grid predicate (>= 36673 pixels), what the cost model picks under 0 / the implicit-GEMM form under 9; FAILS
+ * where the product would take the unfused path. */
+STA_API int sta_debug_conv3_head(sta_handle* h, const float* x, const float* w2, const float* b2, const float* w4, const float* b4,
+                         int n, int H, int W, int nA, float* ptsA, float* confA, float* ptsB, float* confB, void* stream);
 
 /* nn.ConvTranspose2d kernel=stride=k on NHWC data, weights [C,C,k,k] (dpt_block.py:369-390). */
 STA_API int sta_debug_convt(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int C, int k,

@@ -100,10 +100,9 @@ def check_gemm(precision, M=300, N=200, K=96, act=0, via_f16=0, resid=False, see
                                   Rd.data_ptr() if resid else None, out.data_ptr(), st()))
     torch.cuda.synchronize()
     o, r = out.cpu().numpy(), ref.numpy()
-    res = {"rel_l2": rel_l2(o, r), "max_rel": max_rel(o, r)}
+    res = {"rel_l2": rel_l2(o, r), "max_rel": max_rel(o, r), "plan": last_plan(lib, h), "nan": int(np.isnan(o).sum())}
     if tail_rows:
-        res.update(rel_l2_tail=rel_l2(o[M - tail_rows:], r[M - tail_rows:]), max_rel_tail=max_rel(o[M - tail_rows:], r[M - tail_rows:]),
-                   plan=last_plan(lib, h))
+        res.update(rel_l2_tail=rel_l2(o[M - tail_rows:], r[M - tail_rows:]), max_rel_tail=max_rel(o[M - tail_rows:], r[M - tail_rows:]))
     return res
 
 
@@ -386,7 +385,7 @@ def check_conv3(precision, n=2, H=7, W_=5, Cin=32, Co=48, stride=1, relu_in=0, a
                                      relu_in, act, Rd.data_ptr() if resid else None, out.data_ptr(), st()))
     torch.cuda.synchronize()
     o = out.cpu().permute(0, 3, 1, 2).numpy()
-    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy())}
+    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy()), "plan": last_plan(lib, h), "nan": int(np.isnan(o).sum())}
 
 
 def check_convt(precision, n=2, H=3, W_=5, Cdim=96, k=4, seed=4, variant=0):
@@ -401,22 +400,33 @@ def check_convt(precision, n=2, H=3, W_=5, Cdim=96, k=4, seed=4, variant=0):
     _lib.check(lib.sta_debug_convt(h, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), n, H, W_, Cdim, k, out.data_ptr(), st()))
     torch.cuda.synchronize()
     o = out.cpu().permute(0, 3, 1, 2).numpy()
-    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy())}
+    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy()), "plan": last_plan(lib, h), "nan": int(np.isnan(o).sum())}
 
 
-def check_up2(precision, n=2, H=7, W_=5, Cdim=16, crop=None, seed=5):
+def check_up2(precision, n=2, H=7, W_=5, Cdim=16, crop=None, seed=5, one_row=0, ints=False):
+    """one_row: experiment switch 7 (one output row per workgroup where the product would run four).  ints: integer inputs.  Also
+    the error of every border class (helpers.conv_pixel_classes, and the rows of the last, partly filled group of four)."""
     m, lib, h = kernel_handle(precision)
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, Cdim, H, W_, generator=g)
+    x = torch.randint(-1024, 1025, (n, Cdim, H, W_), generator=g).float() if ints else torch.randn(n, Cdim, H, W_, generator=g)
     ref = torch.nn.functional.interpolate(x.double(), scale_factor=2, mode="bilinear", align_corners=True)
     Hc, Wc = crop if crop else (2 * H, 2 * W_)
     ref = ref[:, :, :Hc, :Wc]
     out = torch.empty(n, Hc, Wc, Cdim, device=DEV)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
-    _lib.check(lib.sta_debug_up2(h, xd.data_ptr(), n, H, W_, Cdim, Hc, Wc, out.data_ptr(), st()))
-    torch.cuda.synchronize()
+    _lib.check(lib.sta_debug_set_option(h, 7, one_row))
+    try:
+        _lib.check(lib.sta_debug_up2(h, xd.data_ptr(), n, H, W_, Cdim, Hc, Wc, out.data_ptr(), st()))
+        torch.cuda.synchronize()
+    finally:
+        _lib.check(lib.sta_debug_set_option(h, 7, 0))
     o = out.cpu().permute(0, 3, 1, 2).numpy()
-    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy())}
+    masks = HP.conv_pixel_classes(n, Hc, Wc, None, 1)
+    if Hc % 4:
+        masks["last_group_of_four_rows"] = np.broadcast_to((np.arange(Hc) >= 4 * ((Hc - 1) // 4))[None, :, None], (n, Hc, Wc))
+    errs = HP.class_errors(out.cpu().numpy(), ref.permute(0, 2, 3, 1).numpy(), masks, channel_blocks=False)
+    return {"rel_l2": rel_l2(o, ref.numpy()), "max_rel": max_rel(o, ref.numpy()), "nan": int(np.isnan(o).sum()),
+            "worst": HP.worst_class(errs), "exact_bad": int((o.astype(np.float64) != ref.numpy()).sum())}
 
 
 def check_layernorm(precision, M=37, Cdim=768, seed=6):
@@ -556,3 +566,169 @@ def run_golden_case(name, precision, taps=True, variant=0, frontend=None):
     global last_range
     last_range = m.range_report(reset=True)
     return res
+
+
+# ---- tests/test_conv_exact.py: one launch of a case of tests/conv_cases.py, and the kinds of check on it.  Inputs and float64
+# references are cached for the LAST case of each kind only: the parametrisation runs the three arithmetics of one case back to back.
+_conv_cache = {}
+
+
+def _cached(key, make):
+    kind = key[0]
+    if kind not in _conv_cache or _conv_cache[kind][0] != key:
+        _conv_cache[kind] = (key, make())
+    return _conv_cache[kind][1]
+
+
+def conv_launch(precision, case, x, w, b, res):
+    """Run the case's launch (sta_debug_conv3x3_r2) on numpy NHWC inputs -> (output [n, Ho, Wo, Co] float32, the class the launch ran
+    under).  The output buffer starts as NaN and the entry poisons the output planes: an element no workgroup stored is a NaN."""
+    import conv_cases as CC
+    cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
+    assert len(res) == nres
+    m, lib, h = kernel_handle(precision, variant)
+    Ho, Wo = CC.out_size(H, W_, stride)
+    out = torch.full((n, Ho, Wo, Co), float("nan"), device=DEV)
+    xd, wd, bd = dev(x), dev(w), dev(b)
+    rd = [dev(r) for r in res]
+    m.range_report(reset=True)
+    try:
+        _lib.check(lib.sta_debug_conv3x3_r2(h, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), n, H, W_, Cin, Co, stride, relu_in, act,
+                                            rd[0].data_ptr() if nres > 0 else None, rd[1].data_ptr() if nres > 1 else None,
+                                            out.data_ptr(), st()))
+        torch.cuda.synchronize()
+        plan = last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    rng = tuple(m.range_report(reset=True))
+    assert rng == (0, 0), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}"
+    return out.cpu().numpy(), CC.conv_class(plan, Cin, stride, CC.EPI_NAME[(relu_in, act, nres)])
+
+
+def check_conv_selection(precision, case):
+    """One-hot weights on inputs that carry their own address (helpers.conv_selection_inputs): the output must EQUAL the shifted
+    input planes.  Residual planes, where the case has them, are zero.  -> {"class", "nan", "wrong", "first"}."""
+    cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
+
+    def make():
+        x, w, tap, ci = HP.conv_selection_inputs(n, H, W_, Cin, Co, relu_in)
+        return x, w, tap, ci, HP.conv_selection_expected(x, tap, ci, stride, relu_in)
+    x, w, tap, ci, want = _cached(("sel", cid), make)
+    if act == 2:
+        want = np.maximum(want, 0)
+    res = [np.zeros(want.shape, np.float32)] * nres
+    got, ran = conv_launch(precision, case, x, w, np.zeros(Co, np.float32), res)
+    wrong, first = HP.conv_selection_report(got, want, tap, ci, stride)
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "wrong": wrong, "first": first}
+
+
+def check_conv_integers(precision, case, seed=31):
+    """Small-integer inputs, weights, bias and residuals (helpers.conv_integer_inputs): every exact output is an integer of
+    magnitude <= 2048 (asserted here in int64), so every arithmetic must return the integer itself."""
+    cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
+
+    def make():
+        x, w, b, res = HP.conv_integer_inputs(n, H, W_, Cin, Co, stride, nres, seed)
+        ref = HP.conv_ref64(x, w, b, stride, relu_in, act, res)
+        want = np.rint(ref).astype(np.int64)
+        assert np.array_equal(want.astype(np.float64), ref) and np.abs(want).max() <= 2048, (cid, np.abs(ref).max())
+        return x, w, b, res, want
+    x, w, b, res, want = _cached(("int", cid), make)
+    got, ran = conv_launch(precision, case, x, w, b, res)
+    bad = np.argwhere(~(got.astype(np.float64) == want))
+    first = "; ".join(f"output (image {i}, y {y}, x {xo}), channel {co}: want {want[i, y, xo, co]}, got {got[i, y, xo, co]:g}" for i, y, xo, co in bad[:6])
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "wrong": len(bad), "first": first, "max_abs": int(np.abs(want).max())}
+
+
+def check_conv_classes(precision, case, seed=32):
+    """Gaussian inputs against the float64 conv2d: rel-L2 of the whole tensor and of every class of helpers.conv_pixel_classes and
+    every 32-channel block.  -> {"class", "nan", "rel_l2", "errs": {class: error}, "worst": (class, error)}."""
+    import conv_cases as CC
+    cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
+
+    def make():
+        x, w, b, res = HP.conv_gaussian_inputs(n, H, W_, Cin, Co, stride, nres, seed)
+        return x, w, b, res, HP.conv_ref64(x, w, b, stride, relu_in, act, res)
+    x, w, b, res, ref = _cached(("gauss", cid), make)
+    got, ran = conv_launch(precision, case, x, w, b, res)
+    Ho, Wo = CC.out_size(H, W_, stride)
+    bm = {2: 256, 3: 192, 5: 192, 6: 128, 8: 256}[ran[0]]
+    errs = HP.class_errors(got, ref, HP.conv_pixel_classes(n, Ho, Wo, ran[0], bm))
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "rel_l2": rel_l2(got, ref), "errs": errs, "worst": HP.worst_class(errs)}
+
+
+def tail_launch(precision, hcase, nA, x, w2, b2, w4, b4):
+    """sta_debug_conv3_head on numpy inputs -> (pts [n, H, W, 3], conf [n, H, W], class).  The two output pairs are separate
+    allocations of exactly nA and n - nA images, NaN before the launch."""
+    import conv_cases as CC
+    cid, n, H, W_, variant, w4scale, cls = hcase
+    m, lib, h = kernel_handle(precision, variant)
+    pa, ca = torch.full((nA, H, W_, 3), float("nan"), device=DEV), torch.full((nA, H, W_), float("nan"), device=DEV)
+    pb, cb = torch.full((n - nA, H, W_, 3), float("nan"), device=DEV), torch.full((n - nA, H, W_), float("nan"), device=DEV)
+    ins = [dev(t) for t in (x, w2, b2, w4, b4)]
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    m.range_report(reset=True)
+    try:
+        _lib.check(lib.sta_debug_conv3_head(h, *[t.data_ptr() for t in ins], n, H, W_, nA, ptr(pa), ptr(ca), ptr(pb), ptr(cb), st()))
+        torch.cuda.synchronize()
+        plan = last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    rng = tuple(m.range_report(reset=True))
+    assert rng == (0, 0), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}"
+    return torch.cat([pa, pb]).cpu().numpy(), torch.cat([ca, cb]).cpu().numpy(), CC.conv_class(plan, 128, 1, "head")
+
+
+def check_tail_classes(precision, hcase, nA):
+    """The fused tail on Gaussian inputs against float64 (helpers.tail_ref64), per pixel class, for pts and conf."""
+    cid, n, H, W_, variant, w4scale, cls = hcase
+
+    def make():
+        ins = HP.tail_gaussian_inputs(n, H, W_, w4scale)
+        return ins, HP.tail_ref64(*ins)
+    ins, (rp, rc) = _cached(("tail", cid), make)
+    pts, conf, ran = tail_launch(precision, hcase, nA, *ins)
+    masks = HP.conv_pixel_classes(n, H, W_, ran[0], 256 if ran[0] == 8 else 192)
+    ep = HP.class_errors(pts, rp, masks, channel_blocks=False)
+    ec = HP.class_errors(conf[..., None], rc[..., None], masks, channel_blocks=False)
+    return {"class": ran, "nan": int(np.isnan(pts).sum() + np.isnan(conf).sum()), "pts": rel_l2(pts, rp), "conf": rel_l2(conf, rc),
+            "worst_pts": HP.worst_class(ep), "worst_conf": HP.worst_class(ec)}
+
+
+def tail_exact_inputs(hcase, seed=42):
+    """One-hot head.2 on inputs in {0, 1}, head.4 with four weights of +-1 per row (two of each sign, one per 32-channel block of the
+    tile's four waves), integer bias: the four pre-activation sums are integers in [-3, 3].  -> inputs, pre [n, H, W, 4] int64."""
+    cid, n, H, W_, variant, w4scale, cls = hcase
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 2, size=(n, H, W_, 128)).astype(np.float32)
+    tap, ci = HP.conv_selection_map(128, 128)
+    w2 = np.zeros((128, 128, 3, 3), np.float32)
+    w2[np.arange(128), ci, tap // 3, tap % 3] = 1.0
+    y = HP.conv_selection_expected(x, tap, ci, 1, 0)                      # relu(y) = y: the inputs are not negative
+    w4 = np.zeros((4, 128), np.float32)
+    for o in range(4):
+        for blk in range(4):
+            w4[o, 32 * blk + (7 * o + 11 * blk + 3) % 32] = 1.0 if blk < 2 else -1.0
+    b4 = np.array([1, -1, 0, 1], np.float32)
+    pre = np.rint(y.astype(np.float64) @ w4.T.astype(np.float64) + b4).astype(np.int64)
+    assert np.abs(pre).max() <= 3
+    return (x, w2, np.zeros(128, np.float32), w4, b4), pre
+
+
+def check_tail_exact(precision, hcase, nA):
+    """The fused tail on inputs whose four pre-activation sums are known integers: pts / conf against the float64 activations of
+    those integers, in ulps of the fp32 result.  -> worst ulp errors and the pixels that hold them."""
+    cid, n, H, W_, variant, w4scale, cls = hcase
+    ins, pre = _cached(("tail_exact", cid), lambda: tail_exact_inputs(hcase))
+    rp, rc = HP.tail_activations64(pre)
+    pts, conf, ran = tail_launch(precision, hcase, nA, *ins)
+
+    def ulps(got, ref):
+        ulp = np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
+        e = np.abs(got.astype(np.float64) - ref) / ulp
+        e[np.isnan(got)] = np.inf
+        w = np.unravel_index(np.argmax(e), e.shape)
+        return float(e[w]), f"(image {w[0]}, y {w[1]}, x {w[2]}): pre-activations {pre[w[0], w[1], w[2]].tolist()}, got {got[w]!r}, want {ref[w]!r}"
+    up, wp = ulps(pts, rp)
+    uc, wc = ulps(conf, rc)
+    return {"class": ran, "nan": int(np.isnan(pts).sum() + np.isnan(conf).sum()), "pts_ulp": up, "pts_worst": wp, "conf_ulp": uc, "conf_worst": wc}

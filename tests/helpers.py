@@ -279,3 +279,244 @@ def attn_selection_inputs(form, S, heads, nq, nk, pose_sel, seed):
     dots[:, :, np.arange(nkt), np.arange(nkt)] = -np.inf
     margin = -64.0 * (dots.max() - 63.0) * float(ATT_SCALE_LOG2E) if nkt > 1 else np.inf
     return q, k, v, pi, margin
+
+
+# ---------------------------------------------------------------------------------------------------------
+# 3x3 convolutions of the DPT head: inputs of tests/test_conv_exact.py, the float64 reference, a model of the documented arithmetic
+# and the pixel classes the errors are taken over.  Layout everywhere: x NHWC [n, H, W, Cin], w [Co, Cin, 3, 3] (reference layout),
+# residuals and results NHWC [n, Ho, Wo, Co].
+def _conv2d(x, w, stride, dtype, device="cpu"):
+    """3x3, pad 1, as nine shifted matrix products in `dtype` (the same code for the float64 reference and the float32 model)."""
+    import torch
+    xt = torch.from_numpy(np.ascontiguousarray(x)).to(device=device, dtype=dtype)
+    wt = torch.from_numpy(np.ascontiguousarray(w)).to(device=device, dtype=dtype)
+    n, H, W, Cin = xt.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    xp = torch.nn.functional.pad(xt, (0, 0, 1, 1, 1, 1))
+    y = torch.zeros((n * Ho * Wo, wt.shape[0]), dtype=dtype, device=device)
+    for ky in range(3):
+        for kx in range(3):
+            a = xp[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride].reshape(n * Ho * Wo, Cin)
+            y += a @ wt[:, :, ky, kx].T
+    return y.reshape(n, Ho, Wo, -1).cpu().numpy()
+
+
+def _ref_device():
+    import torch
+    return "cuda:0" if torch.cuda.is_available() else "cpu"
+
+
+def conv_ref64(x, w, b, stride=1, relu_in=0, act=0, res=()):
+    """act(conv3x3(relu?(x)) + b) + residuals in float64."""
+    import torch
+    x = np.asarray(x, np.float64)
+    y = _conv2d(np.maximum(x, 0.0) if relu_in else x, np.asarray(w, np.float64), stride, torch.float64, _ref_device()) + np.asarray(b, np.float64)
+    if act == 2:
+        y = np.maximum(y, 0.0)
+    for r in res:
+        y = y + np.asarray(r, np.float64)
+    return y
+
+
+def conv_model(x, w, b, stride, relu_in, act, res, precision, round_out=True):
+    """The documented arithmetic in float32.  f16x3: input, weights and residuals as fp16 hi + lo, three products (hi hi + hi lo +
+    lo hi), fp32 accumulation, output as hi + lo; the input ReLU looks at the sign of hi.  f16: single fp16 roundings of input,
+    weights, residuals and output.  round_out=False: the fp32 accumulator + bias (+ activation), what the fused tail keeps on chip.
+    (Not modelled: the summation order of the MFMAs and of the K slices - the 4x margin of the bounds is for those.)"""
+    import torch
+    split = precision != "f16"
+    xh, xl = _split16(np.asarray(x, np.float32))
+    if relu_in:
+        neg = xh < 0
+        xh = np.where(neg, np.float32(0), xh); xl = np.where(neg, np.float32(0), xl)
+    wh, wl = _split16(np.asarray(w, np.float32))
+    acc = _conv2d(xh, wh, stride, torch.float32)
+    if split:
+        acc = acc + (_conv2d(xh, wl, stride, torch.float32) + _conv2d(xl, wh, stride, torch.float32))
+    y = (acc + np.asarray(b, np.float32)).astype(np.float32)
+    if act == 2:
+        y = np.maximum(y, np.float32(0))
+    if not round_out:
+        return y
+    for r in res:
+        rh, rl = _split16(np.asarray(r, np.float32))
+        y = (y + (rh + rl if split else rh)).astype(np.float32)
+    oh, ol = _split16(y)
+    return (oh + ol if split else oh).astype(np.float64)
+
+
+def tail_activations64(pre):
+    """pre [..., 4] float64 (x, y, z, c) -> pts [..., 3], conf [...]: pts = xyz expm1(d) / d, conf = 1 + exp(c) (postprocess.py:10-62)."""
+    pre = np.asarray(pre, np.float64)
+    xyz = pre[..., :3]
+    d = np.sqrt((xyz ** 2).sum(-1, keepdims=True))
+    return xyz * (np.expm1(d) / np.maximum(d, 1e-8)), 1.0 + np.exp(pre[..., 3])
+
+
+def tail_ref64(x, w2, b2, w4, b4):
+    """The fused DPT tail in float64: head.2 (3x3) + ReLU, head.4 (1x1 128 -> 4), activations."""
+    y = conv_ref64(x, w2, b2, 1, 0, 2)
+    return tail_activations64(y @ np.asarray(w4, np.float64).T + np.asarray(b4, np.float64))
+
+
+def tail_model(x, w2, b2, w4, b4, precision):
+    """head.2 in the arithmetic of conv_model with the accumulators kept in fp32; relu(acc + b2) and head.4's rows (scaled by a power of
+    two into [0.5, 1), which is exact) enter the 128 -> 4 contraction as fp16 hi + lo with three products; fp32 activations."""
+    y = conv_model(x, w2, b2, 1, 0, 2, (), precision, round_out=False)
+    yh, yl = _split16(y)
+    w4 = np.asarray(w4, np.float32)
+    sc = np.ldexp(np.float32(1), -np.frexp(np.abs(w4).max(1, keepdims=True))[1]).astype(np.float32)      # as head4_row_scales (sta_api.hip)
+    vh, vl = _split16(w4 * sc)
+    pre = (yh @ vh.T + (yh @ vl.T + yl @ vh.T)).astype(np.float32) / sc.T + np.asarray(b4, np.float32)
+    pre = pre.astype(np.float32)
+    xyz = pre[..., :3]
+    d = np.sqrt((xyz * xyz).sum(-1, keepdims=True, dtype=np.float32))
+    s = (np.expm1(d) / np.maximum(d, np.float32(1e-8))).astype(np.float32)
+    return (xyz * s).astype(np.float64), (np.float32(1) + np.exp(pre[..., 3])).astype(np.float64)
+
+
+def tail_gaussian_inputs(n, H, W, w4scale, seed=41):
+    """x [n, H, W, 128], head.2 (w2, b2), head.4 (w4, b4) with head.4 at `w4scale` times its ordinary size."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, H, W, 128)).astype(np.float32)
+    w2 = (rng.standard_normal((128, 128, 3, 3)) * 0.03).astype(np.float32)
+    b2 = (rng.standard_normal(128) * 0.5).astype(np.float32)
+    w4 = (rng.standard_normal((4, 128)) * 0.05 * w4scale).astype(np.float32)
+    b4 = (rng.standard_normal(4) * 0.3 * w4scale).astype(np.float32)
+    return x, w2, b2, w4, b4
+
+
+def conv_pixel_classes(n, Ho, Wo, family, bm):
+    """{name: bool mask [n, Ho, Wo]} - the small sets of pixels where these kernels go wrong: the four corners, each border, the
+    interior, the ragged last tile column / row (family 8: 8 x 32-pixel tiles of one image; None: no tiles; else the last bm-row
+    tile of the FLATTENED pixels), the first and last row of every image after the first (tiles that span two images)."""
+    yy, xx = np.meshgrid(np.arange(Ho), np.arange(Wo), indexing="ij")
+    top, bot, lef, rig = yy == 0, yy == Ho - 1, xx == 0, xx == Wo - 1
+    one = {"corner_tl": top & lef, "corner_tr": top & rig, "corner_bl": bot & lef, "corner_br": bot & rig,
+           "border_top": top & ~lef & ~rig, "border_bottom": bot & ~lef & ~rig, "border_left": lef & ~top & ~bot,
+           "border_right": rig & ~top & ~bot, "interior": ~(top | bot | lef | rig)}
+    m = {k: np.broadcast_to(v, (n, Ho, Wo)) for k, v in one.items()}
+    if family == 8:
+        if Wo % 32:
+            m["ragged_tile_column"] = np.broadcast_to(xx >= 32 * ((Wo - 1) // 32), (n, Ho, Wo))
+        if Ho % 8:
+            m["ragged_tile_row"] = np.broadcast_to(yy >= 8 * ((Ho - 1) // 8), (n, Ho, Wo))
+    elif family is not None and (n * Ho * Wo) % bm:
+        flat = np.arange(n * Ho * Wo).reshape(n, Ho, Wo)
+        m["ragged_last_tile"] = flat >= bm * ((n * Ho * Wo - 1) // bm)
+    for i in range(1, n):
+        for name, row in (("first_row", top), ("last_row", bot)):
+            k = np.zeros((n, Ho, Wo), bool)
+            k[i] = row
+            m[f"image{i}_{name}"] = k
+    return {k: v for k, v in m.items() if v.any()}
+
+
+def class_errors(got, ref, masks, channel_blocks=True):
+    """got, ref [n, Ho, Wo, C] -> {class: rel-L2 over the class}: the pixel classes of `masks`, and every 32-channel block over all
+    pixels.  A NaN in a class makes its error NaN."""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    e2, r2 = (got - ref) ** 2, ref ** 2
+    pe, pr = e2.sum(-1), r2.sum(-1)
+    out = {k: float(np.sqrt(pe[m].sum() / max(pr[m].sum(), 1e-300))) for k, m in masks.items()}
+    if channel_blocks:
+        C = got.shape[-1]
+        for c0 in range(0, C, 32):
+            out[f"channels_{c0}_{min(c0 + 32, C) - 1}"] = float(np.sqrt(e2[..., c0:c0 + 32].sum() / max(r2[..., c0:c0 + 32].sum(), 1e-300)))
+    return out
+
+
+def worst_class(errs):
+    """-> (name, error) of the worst class; a NaN class wins."""
+    return max(errs.items(), key=lambda kv: np.inf if np.isnan(kv[1]) else kv[1])
+
+
+def conv_gaussian_inputs(n, H, W, Cin, Co, stride, nres, seed):
+    rng = np.random.default_rng(seed)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    x = rng.standard_normal((n, H, W, Cin)).astype(np.float32)
+    w = (rng.standard_normal((Co, Cin, 3, 3)) * 0.1).astype(np.float32)
+    b = rng.standard_normal(Co).astype(np.float32)
+    res = [rng.standard_normal((n, Ho, Wo, Co)).astype(np.float32) for _ in range(nres)]
+    return x, w, b, res
+
+
+CONV_SEL_OFFSET = 40.0       # relu_in cases: subtracted from every second group of four planes, so that the input ReLU clamps
+
+
+def conv_selection_map(Cin, Co):
+    """Output channel co -> (tap, input channel): tap co % 9 of 32-channel block (co // 9) % (Cin / 32), so that with Co >= 9 Cin / 32
+    EVERY (tap, input block) pair - every K tile of the loop, e.g. tap 8 of block b next to tap 0 of block b + 1 - is selected by
+    some output channel (asserted), on planes of all four kinds."""
+    co = np.arange(Co)
+    nb = Cin // 32
+    tap, blk = co % 9, (co // 9) % nb
+    ci = 32 * blk + (7 * co + 3) % 32
+    assert Co >= 9 * nb and len(set(zip(tap.tolist(), blk.tolist()))) == 9 * nb, "every (tap, input block) pair must be selected"
+    assert set((ci % 4).tolist()) == {0, 1, 2, 3}
+    return tap, ci
+
+
+def conv_selection_inputs(n, H, W, Cin, Co, relu_in):
+    """Inputs that carry their own address: plane 4j holds y, 4j + 1 holds x, 4j + 2 the image index, 4j + 3 the group j (all <= 2047:
+    one fp16 holds them).  Weights one-hot by conv_selection_map.  -> x, w, tap [Co], ci [Co]."""
+    assert max(H, W, n, Cin // 4) <= 2047
+    x = np.empty((n, H, W, Cin), np.float32)
+    x[..., 0::4] = np.arange(H, dtype=np.float32)[None, :, None, None]
+    x[..., 1::4] = np.arange(W, dtype=np.float32)[None, None, :, None]
+    x[..., 2::4] = np.arange(n, dtype=np.float32)[:, None, None, None]
+    x[..., 3::4] = np.arange(Cin // 4, dtype=np.float32)
+    if relu_in:
+        g = (np.arange(Cin) // 4) % 2 == 1
+        x[..., g] -= np.float32(CONV_SEL_OFFSET)
+    tap, ci = conv_selection_map(Cin, Co)
+    w = np.zeros((Co, Cin, 3, 3), np.float32)
+    w[np.arange(Co), ci, tap // 3, tap % 3] = 1.0
+    return x, w, tap, ci
+
+
+def conv_selection_expected(x, tap, ci, stride, relu_in):
+    """The shifted input planes, 0 outside the image (relu_in: of relu(x))."""
+    n, H, W, _ = x.shape
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    xp = np.zeros((n, H + 2, W + 2, x.shape[3]), np.float32)
+    xp[:, 1:-1, 1:-1] = np.maximum(x, 0) if relu_in else x
+    out = np.empty((n, Ho, Wo, len(tap)), np.float32)
+    for t in range(9):
+        ky, kx = divmod(t, 3)
+        sel = np.nonzero(tap == t)[0]
+        out[..., sel] = xp[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride][..., ci[sel]]
+    return out
+
+
+def conv_selection_report(got, want, tap, ci, stride, limit=6):
+    """Text naming the first wrong elements: output pixel, channel, the source pixel expected and the value found."""
+    bad = np.argwhere(~(got == want))
+    names = ("y", "x", "image", "group")
+    lines = []
+    for i, y, xo, co in bad[:limit]:
+        ky, kx = divmod(int(tap[co]), 3)
+        kind = names[int(ci[co]) % 4]
+        lines.append(f"output (image {i}, y {y}, x {xo}), channel {co}: expected input pixel (image {i}, y {y * stride + ky - 1}, "
+                     f"x {xo * stride + kx - 1}) channel {ci[co]} (tap {tap[co]}, a plane of {kind}) = {want[i, y, xo, co]:g}, found {got[i, y, xo, co]:g}"
+                     f" (the pixel actually read has {kind} = {got[i, y, xo, co]:g}, + {CONV_SEL_OFFSET:g} on an offset plane)")
+    return len(bad), "; ".join(lines)
+
+
+def conv_integer_inputs(n, H, W, Cin, Co, stride, nres, seed):
+    """Small integers whose exact convolution is an integer of magnitude <= 2048 BY CONSTRUCTION: x in [-3, 3], every output channel
+    has min(9 Cin, 512) weights of +-1 (the rest 0), bias in [-32, 32], residuals in [-100, 100]: |sum| <= 3 x 512 + 32 + 2 x 100 =
+    1768.  fp16 holds every operand and every result, fp32 every partial sum."""
+    rng = np.random.default_rng(seed)
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    K = 9 * Cin
+    x = rng.integers(-3, 4, size=(n, H, W, Cin)).astype(np.float32)
+    w = rng.integers(0, 2, size=(Co, K)).astype(np.float32) * 2 - 1
+    if K > 512:
+        keep = np.argsort(rng.random((Co, K)), axis=1)[:, :512]
+        mask = np.zeros((Co, K), bool)
+        np.put_along_axis(mask, keep, True, 1)
+        w = w * mask
+    b = rng.integers(-32, 33, size=Co).astype(np.float32)
+    res = [rng.integers(-100, 101, size=(n, Ho, Wo, Co)).astype(np.float32) for _ in range(nres)]
+    return x, w.reshape(Co, Cin, 3, 3).astype(np.float32), b, res

@@ -18,17 +18,46 @@ def G():
     return gpu_checks
 
 
+def small_grid(M, N):
+    """The small-grid predicate (sta_launch.inc: small_grid_m), restated."""
+    return M <= 640 or ((M + 191) // 192) * ((N + 127) // 128) < 192
+
+
+def small_shape_family(M, N, variant=0):
+    """The tile family a shape BELOW the small-grid predicate runs (sta_launch.inc: gemm_plan): the small-grid family 6 whatever
+    family 2 / 3 / 4 is forced - a forced family never displaces it -, the register-staged 128x128 kernel (1) where N is no
+    multiple of 64, the halo-tiled convolution (8) only where that is forced."""
+    assert small_grid(M, N), (M, N)
+    return 8 if variant == 8 else (6 if N % 64 == 0 else 1)
+
+
 @pytest.mark.parametrize("prec", HEAD_PRECS)
 @pytest.mark.parametrize("kw", [dict(), dict(resid=True), dict(M=520, N=384, K=1024), dict(act=1, via_f16=1),
                                 dict(act=2, via_f16=1), dict(M=1, N=96, K=32), dict(M=129, N=129, K=64),
-                                # 256-row direct-to-LDS family (forced on small shapes): 256x256 and 256x128 tiles, M tails
+                                # forced 256-row and 192-row families on SMALL shapes: below the small-grid predicate a forced family never
+                                # displaces family 6, so these run 128x64 tiles (asserted below) - M tails and every epilogue of that
+                                # family.  The forced families themselves run in test_gemm_tail_rows (dense) and test_conv_exact.py
                                 dict(M=700, N=512, K=256, variant=2), dict(M=300, N=384, K=96, variant=2, resid=True),
                                 dict(M=513, N=256, K=1024, variant=2, act=1, via_f16=1), dict(M=5, N=128, K=32, variant=2, act=2, via_f16=1),
-                                # 192-row tiles (fractional DMA slot assignment)
                                 dict(M=700, N=512, K=256, variant=3), dict(M=385, N=384, K=96, variant=3, resid=True),
-                                dict(M=193, N=128, K=64, variant=3, act=1, via_f16=1)])
+                                dict(M=193, N=128, K=64, variant=3, act=1, via_f16=1),
+                                # ... and ABOVE the predicate (6200 rows x 768 columns: 33 x 6 = 198 tiles of 192x128), where the forced
+                                # families do run (fam: asserted): the plane epilogue + ReLU of the head's 1x1 convolutions, in the
+                                # f16mx arithmetic too, on 256x256 / 192x256 / 192x128, the automatic choice, and the fp32 + residual one (GELU on these
+                                # families: test_gemm_tail_rows)
+                                dict(M=6200, N=768, K=256, variant=2, act=2, via_f16=1, fam=2), dict(M=6200, N=768, K=256, variant=3, act=2, via_f16=1, fam=3),
+                                dict(M=6200, N=768, K=256, variant=4, act=2, via_f16=1, fam=5), dict(M=6200, N=768, K=256, via_f16=1, fam=5),
+                                dict(M=6200, N=768, K=256, variant=3, resid=True, fam=3)])
 def test_gemm(G, prec, kw):
+    kw = dict(kw)
+    fam = kw.pop("fam", None)
     r = G.check_gemm(prec, **kw)
+    if fam is None:
+        fam = small_shape_family(kw.get("M", 300), kw.get("N", 200), kw.get("variant", 0))
+    else:
+        assert not small_grid(kw["M"], kw["N"]), kw
+    assert r["plan"]["family"] == fam, r
+    assert r["nan"] == 0, r
     assert r["rel_l2"] < TOL[prec], r
 
 
@@ -162,9 +191,16 @@ def test_attention(G, prec, kw):
     assert r["rel_l2"] < TOL[prec], r
 
 
+def _conv_pixels(kw):
+    s = kw.get("stride", 1)
+    return kw.get("n", 2) * ((kw.get("H", 7) - 1) // s + 1) * ((kw.get("W_", 5) - 1) // s + 1)
+
+
 @pytest.mark.parametrize("prec", HEAD_PRECS)
 @pytest.mark.parametrize("kw", [dict(), dict(stride=2), dict(stride=2, H=6, W_=8),
                                 dict(relu_in=1, act=2, resid=True, Cin=96, Co=256, H=9, W_=12), dict(H=1, W_=1),
+                                # forced families 2 / 3 at <= 874 pixels: below the small-grid predicate, so these run family 6 (asserted
+                                # below).  The implicit-GEMM loader on families 2 / 3 / 5 runs in test_conv_exact.py (tests/conv_cases.py)
                                 dict(relu_in=1, act=2, resid=True, Cin=96, Co=256, H=19, W_=23, variant=2),
                                 dict(Cin=64, Co=128, H=17, W_=9, variant=2), dict(stride=2, Cin=32, Co=256, H=15, W_=14, variant=2),
                                 dict(relu_in=1, act=2, resid=True, Cin=96, Co=256, H=19, W_=23, variant=3), dict(Cin=64, Co=128, H=17, W_=9, variant=3),
@@ -173,6 +209,9 @@ def test_attention(G, prec, kw):
                                 dict(stride=2, Cin=768, Co=256, H=14, W_=14, n=1)])
 def test_conv3x3(G, prec, kw):
     r = G.check_conv3(prec, **kw)
+    assert r["plan"]["family"] == small_shape_family(_conv_pixels(kw), kw.get("Co", 48), kw.get("variant", 0)), r
+    assert r["plan"]["ksplit"] > 1 or kw.get("Cin", 32) < 128, r          # the three long-K cases do split K
+    assert r["nan"] == 0, r
     assert r["rel_l2"] < TOL[prec], r
 
 
@@ -184,21 +223,58 @@ def test_conv3x3_halo_tiles(G, prec, kw):
     """conv3h.h (forced with tile family 8): pixel tiles of 8 x 32 outputs, halo in LDS, image borders / ragged tiles /
     several channel blocks (double-buffered halo) / ReLU on fragments / residual planes."""
     r = G.check_conv3(prec, variant=8, **kw)
+    assert (r["plan"]["family"], r["plan"]["bn"]) == (8, kw["Co"]), r
+    assert r["nan"] == 0, r
     assert r["rel_l2"] < TOL[prec], r
 
 
 @pytest.mark.parametrize("prec", HEAD_PRECS)
-@pytest.mark.parametrize("kw", [dict(), dict(Cdim=192, k=2), dict(Cdim=192, k=2, variant=2), dict(Cdim=96, k=4, variant=2, H=9, W_=11)])
+# (the first two variant=2 cases: 30 .. 198 input pixels, below the small-grid predicate - family 6 like the others, asserted below.
+#  Above it - 2 x 55 x 56 = 6160 pixels x N = 4 x 192: 33 x 6 = 198 tiles of 192x128, the tiles span image rows and both images -
+#  the scatter epilogue runs on the automatic choice and on the forced 256x256 / 192x256 / 192x128 tiles; k = 4 at Cdim = 96 as in
+#  act_postprocess[0])
+@pytest.mark.parametrize("kw", [dict(), dict(Cdim=192, k=2), dict(Cdim=192, k=2, variant=2), dict(Cdim=96, k=4, variant=2, H=9, W_=11),
+                                dict(H=55, W_=56, Cdim=192, k=2, fam=5), dict(H=55, W_=56, Cdim=192, k=2, variant=2, fam=2),
+                                dict(H=55, W_=56, Cdim=192, k=2, variant=3, fam=3), dict(H=55, W_=56, Cdim=192, k=2, variant=4, fam=5),
+                                dict(H=37, W_=41, Cdim=96, k=4, variant=2, fam=2), dict(H=37, W_=41, Cdim=96, k=4, variant=3, fam=3)])
 def test_convt(G, prec, kw):
+    kw = dict(kw)
+    fam = kw.pop("fam", None)
     r = G.check_convt(prec, **kw)
+    M, N = kw.get("n", 2) * kw.get("H", 3) * kw.get("W_", 5), kw.get("k", 4) ** 2 * kw.get("Cdim", 96)
+    if fam is None:
+        fam = small_shape_family(M, N, kw.get("variant", 0))
+    else:
+        assert not small_grid(M, N) and M % 192 and M % 256 and (kw["H"] * kw["W_"]) % 192, kw
+    assert r["plan"]["family"] == fam, r
+    assert r["nan"] == 0, r
     assert r["rel_l2"] < TOL[prec], r
 
 
+# the product's shapes: 256 channels between the refinenets, the cropped output of refinenet4 (odd sizes: 7 x 9 -> 13 x 17 of
+# 14 x 18), 128 channels in front of head.2; 16 images of 64 (65) rows = 512 (528) groups of four output rows: where run_up2
+# (sta_launch.inc) gives the split precisions four rows per workgroup (the last group of 129 rows partly filled) and precision f16
+# one, and every precision one under experiment switch 7
 @pytest.mark.parametrize("prec", HEAD_PRECS)
-@pytest.mark.parametrize("kw", [dict(), dict(H=2, W_=3, crop=(3, 5)), dict(H=1, W_=1)])
+@pytest.mark.parametrize("kw", [dict(), dict(H=2, W_=3, crop=(3, 5)), dict(H=1, W_=1),
+                                dict(Cdim=256, H=12, W_=16), dict(Cdim=256, H=7, W_=9, crop=(13, 17)), dict(Cdim=128, H=24, W_=20),
+                                dict(Cdim=128, n=16, H=64, W_=10), dict(Cdim=256, n=16, H=65, W_=5, crop=(129, 9)),
+                                dict(Cdim=128, n=16, H=64, W_=10, one_row=1)])
 def test_up2(G, prec, kw):
     r = G.check_up2(prec, **kw)
+    assert r["nan"] == 0, r
     assert r["rel_l2"] < TOL[prec], r
+    # every border class under the whole-tensor bar: a rounding error that is iid over the elements has the same expected rel-L2 on
+    # a class as on the whole
+    assert r["worst"][1] < TOL[prec], r
+
+
+@pytest.mark.parametrize("prec", HEAD_PRECS)
+def test_up2_of_one_pixel_is_exact(G, prec):
+    """x2 with align_corners has the weights j (H - 1) / (2 H - 1): odd denominators, so integer inputs give no dyadic results in
+    general - except for a 1 x 1 image, whose four outputs ARE the input (integers an fp16 holds)."""
+    r = G.check_up2(prec, n=3, H=1, W_=1, Cdim=64, ints=True)
+    assert r["nan"] == 0 and r["exact_bad"] == 0, r
 
 
 @pytest.mark.parametrize("prec", PRECS)

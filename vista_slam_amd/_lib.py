@@ -119,6 +119,9 @@ TEST_SIGNATURES = {
     "sta_debug_qkv_pair_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_qkv_pair": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _vp]),
     "sta_debug_conv3x3": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _vp]),
+    "sta_debug_conv3x3_r2": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
+    "sta_debug_conv3_head": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _fp, _fp, _vp]),
+    "sta_debug_conv_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_convt": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_up2": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_layernorm": (_i, [_vp, _fp, _fp, _fp, _i, _i, _f, _fp, _fp, _vp]),

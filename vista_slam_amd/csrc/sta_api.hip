@@ -586,26 +586,31 @@ extern "C" int sta_load_tensor(sta_handle* h, const char* name, const void* host
     return 0;
 }
 
+// head.4 (1x1 conv 128 -> 4) enters the fused DPT tail as fp16 hi / lo planes (head_epilogue_t, gemm2.h).  Its values can be far
+// below fp16's normal range (a checkpoint whose DPT feature maps are large has correspondingly small head.4 weights: the outlier
+// goldens scale them by 1/300 -> 1e-5, subnormal in fp16, 1e-3 relative error) - so they are split AFTER an exact power-of-two
+// scaling into [0.5, 1) and the result is scaled back.  w4: host copy [4][128]; scale[o]: the power of two of output row o.
+static void head4_row_scales(const float* w4, float* scale) {
+    for (int o = 0; o < 4; ++o) {
+        float mx = 0.f;
+        for (int c = 0; c < 128; ++c) mx = fmaxf(mx, fabsf(w4[o * 128 + c]));
+        int e = 0;
+        if (mx > 0.f && std::isfinite(mx)) (void)frexpf(mx, &e);        // mx = f * 2^e, f in [0.5, 1)
+        if (e > 100) e = 100; if (e < -100) e = -100;
+        scale[o] = ldexpf(1.0f, -e);
+    }
+}
+
 extern "C" int sta_finalize_weights(sta_handle* h) {
     REQUIRE(h, "null handle");
     for (auto& kv : h->slots)
         REQUIRE(kv.second.loaded, "missing key in state_dict: %s", kv.first.c_str());
     DEV_SCOPE(h->device);
     HIPCHK(hipDeviceSynchronize());
-    {   // head.4 (1x1 conv 128 -> 4) enters the fused DPT tail as fp16 hi / lo planes (head_epilogue_t, gemm2.h).  Its values can be far
-        // below fp16's normal range (a checkpoint whose DPT feature maps are large has correspondingly small head.4 weights: the outlier
-        // goldens scale them by 1/300 -> 1e-5, subnormal in fp16, 1e-3 relative error) - so they are split AFTER an exact power-of-two
-        // scaling into [0.5, 1) and the result is scaled back
+    {
         std::vector<float> w4(4 * 128);
         HIPCHK(hipMemcpy(w4.data(), h->head4.w, w4.size() * 4, hipMemcpyDeviceToHost));
-        for (int o = 0; o < 4; ++o) {
-            float mx = 0.f;
-            for (int c = 0; c < 128; ++c) mx = fmaxf(mx, fabsf(w4[o * 128 + c]));
-            int e = 0;
-            if (mx > 0.f && std::isfinite(mx)) (void)frexpf(mx, &e);        // mx = f * 2^e, f in [0.5, 1)
-            if (e > 100) e = 100; if (e < -100) e = -100;
-            h->head4_scale[o] = ldexpf(1.0f, -e);
-        }
+        head4_row_scales(w4.data(), h->head4_scale);
     }
     h->finalized = true;
     return 0;

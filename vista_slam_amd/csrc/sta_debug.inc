@@ -294,28 +294,79 @@ extern "C" int sta_debug_set_tail_hint(sta_handle* h, int rows) {
     return 0;
 }
 
-// x NHWC fp32 [n,H,W,Cin], w [Co,Cin,3,3] fp32 (reference layout), out NHWC fp32 [n,Ho,Wo,Co]
-extern "C" int sta_debug_conv3x3(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
-                                 int stride, int relu_in, int act, const float* resid, float* out, void* stream) {
+// x NHWC fp32 [n,H,W,Cin], w [Co,Cin,3,3] fp32 (reference layout), out NHWC fp32 [n,Ho,Wo,Co]; resid / resid2 (may be NULL; resid2
+// only with resid): the residual planes of the epilogue, as the refinenet fusion passes them (conv3(..., &r[k], &path))
+static int dbg_conv3(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
+                     int stride, int relu_in, int act, const float* resid, const float* resid2, float* out, void* stream) {
     REQUIRE(h && x && w && out, "bad argument");
+    REQUIRE(n > 0 && H > 0 && W > 0 && Cin > 0 && Co > 0 && (stride == 1 || stride == 2) && (resid || !resid2), "bad argument");
     DEV_SCOPE(h->device);
     hipStream_t st = (hipStream_t)stream;
     const bool split = h->prec != STA_PREC_F16;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     int64_t ein = (int64_t)n * H * W * Cin, eout = (int64_t)n * Ho * Wo * Co;
-    CHK(ensure_ws(h, (ein + (int64_t)2 * Co * Cin * 9 + 2 * eout) * 4 + (1 << 16), st));      // (two packed copies of the weight in the f16mx arithmetic)
+    CHK(ensure_ws(h, (ein + (int64_t)2 * Co * Cin * 9 + 3 * eout) * 4 + (1 << 16), st));      // (two packed copies of the weight in the f16mx arithmetic)
     Bump ws = cur_bump(h);
     Planes xi = ws.act((int64_t)n * H * W, Cin, split), o = ws.act((int64_t)n * Ho * Wo, Co, split), r = ws.act((int64_t)n * Ho * Wo, Co, split);
+    Planes r2 = ws.act((int64_t)n * Ho * Wo, Co, split);
     const bool mx = dbg_mx(h) && Co % 64 == 0;
-    xi.mx = o.mx = r.mx = mx;
+    xi.mx = o.mx = r.mx = r2.mx = mx;
     Lin L; CHK(dbg_make_lin(h, ws, w, bias, Co, Cin * 9, 1, Co, Cin, 3, 3, L, st, mx));
     REQUIRE(!ws.overflow, "debug ws overflow");
     CHK(run_rows_to_planes(h, x, ein, 1, n * H * W, Cin, xi, st, 0, mx));
     if (resid) CHK(run_rows_to_planes(h, resid, eout, 1, n * Ho * Wo, Co, r, st, 0, mx));
+    if (resid2) CHK(run_rows_to_planes(h, resid2, eout, 1, n * Ho * Wo, Co, r2, st, 0, mx));
     CHK(dbg_poison_act(o, (int64_t)n * Ho * Wo, Co, st));
-    CHK(conv3(h, xi, n, H, W, Cin, L, stride, relu_in != 0, act, o, resid ? &r : nullptr, nullptr, st));
+    CHK(conv3(h, xi, n, H, W, Cin, L, stride, relu_in != 0, act, o, resid ? &r : nullptr, resid2 ? &r2 : nullptr, st));
     CHK(dbg_planes_to_f32(h, o, 0, 1, n * Ho * Wo, Co, out, st));
     return 0;
+}
+extern "C" int sta_debug_conv3x3(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
+                                 int stride, int relu_in, int act, const float* resid, float* out, void* stream) {
+    return dbg_conv3(h, x, w, bias, n, H, W, Cin, Co, stride, relu_in, act, resid, nullptr, out, stream);
+}
+extern "C" int sta_debug_conv3x3_r2(sta_handle* h, const float* x, const float* w, const float* bias, int n, int H, int W, int Cin, int Co,
+                                    int stride, int relu_in, int act, const float* resid, const float* resid2, float* out, void* stream) {
+    return dbg_conv3(h, x, w, bias, n, H, W, Cin, Co, stride, relu_in, act, resid, resid2, out, stream);
+}
+
+// The fused DPT tail (conv3_head: head.2 3x3 128 -> 128 + ReLU + head.4 1x1 128 -> 4 + point-map / confidence activations) on
+// x NHWC fp32 [n,H,W,128]; w2 [128,128,3,3], b2 [128], w4 [4,128], b4 [4] fp32.  The first nA images go to (ptsA [nA,H,W,3],
+// confA [nA,H,W]), the rest to (ptsB, confB).  head.4's rows are scaled as sta_finalize_weights scales them (head4_row_scales).
+// Fails when conv3_head_ok is false (small grids, forced implicit-GEMM families): the unfused path is never taken here.
+extern "C" int sta_debug_conv3_head(sta_handle* h, const float* x, const float* w2, const float* b2, const float* w4, const float* b4,
+                                    int n, int H, int W, int nA, float* ptsA, float* confA, float* ptsB, float* confB, void* stream) {
+    REQUIRE(h && x && w2 && b2 && w4 && b4 && n > 0 && H > 0 && W > 0 && nA >= 0 && nA <= n, "bad argument");
+    REQUIRE((nA == 0 || (ptsA && confA)) && (nA == n || (ptsB && confB)), "bad argument (outputs)");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int64_t npix = (int64_t)n * H * W, ein = npix * 128;
+    REQUIRE(npix < ((int64_t)1 << 31) / 128, "too many pixels");
+    CHK(ensure_ws(h, (ein + (int64_t)2 * 128 * 128 * 9) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes xi = ws.act(npix, 128, split);
+    const bool mx = dbg_mx(h);
+    xi.mx = mx;
+    Lin L; CHK(dbg_make_lin(h, ws, w2, b2, 128, 128 * 9, 1, 128, 128, 3, 3, L, st, mx));
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    REQUIRE(conv3_head_ok(h, L, npix), "the fused tail does not run at %lld pixels under tile family %d (conv3_head_ok)", (long long)npix, h->gemm_variant);
+    F32Lin L4; L4.w = const_cast<float*>(w4); L4.b = const_cast<float*>(b4);
+    std::vector<float> w4h(4 * 128);
+    HIPCHK(hipMemcpyAsync(w4h.data(), w4, w4h.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    // the row scales of THIS head.4 for the duration of the call: the handle's own (its loaded weights') come back on every path out
+    struct ScaleGuard {
+        float* dst; float keep[4];
+        explicit ScaleGuard(float* d) : dst(d) { for (int o = 0; o < 4; ++o) keep[o] = d[o]; }
+        ~ScaleGuard() { for (int o = 0; o < 4; ++o) dst[o] = keep[o]; }
+    } restore_scales(h->head4_scale);
+    head4_row_scales(w4h.data(), h->head4_scale);
+    CHK(run_rows_to_planes(h, x, ein, 1, (int)npix, 128, xi, st, 0, mx));
+    const int64_t pa = (int64_t)nA * H * W, pb = npix - pa;
+    if (pa) { CHK(dbg_poison(ptsA, pa * 12, st)); CHK(dbg_poison(confA, pa * 4, st)); }
+    if (pb) { CHK(dbg_poison(ptsB, pb * 12, st)); CHK(dbg_poison(confB, pb * 4, st)); }
+    return conv3_head(h, xi, n, H, W, 128, L, L4, ptsA, confA, nA, ptsB, confB, st);
 }
 
 // x NHWC fp32 [n,H,W,C], w [C,C,k,k] (ConvTranspose2d layout), out NHWC fp32 [n,kH,kW,C]

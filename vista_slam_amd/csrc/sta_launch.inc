@@ -293,6 +293,19 @@ extern "C" int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, 
     plan_out(g, out);
     return 0;
 }
+// The same for a 3x3 convolution (A_CONV3; epi 1 plane epilogue, 6 fused head): M = images x Ho x Wo output pixels, K = 9 Cin; with the
+// image geometry the halo-tiled family 8 is a candidate.  head_gemm: experiment switch 0.
+extern "C" int sta_debug_conv_plan(int epi, int M, int N, int K, int precision, int mx, int forced_variant, int cstride, int Ho, int Wo,
+                                   int head_gemm, int* out) {
+    REQUIRE(out && M > 0 && N > 0 && K > 0 && (epi == EPI_F16 || epi == EPI_HEAD) && (cstride == 1 || cstride == 2) && Ho > 0 && Wo > 0 &&
+            M % (Ho * Wo) == 0, "bad argument");
+    REQUIRE(precision == STA_PREC_F16 || precision == STA_PREC_F16X3 || precision == STA_PREC_F16X3H || precision == STA_PREC_F16X3M, "bad precision");
+    PlanQuery q{A_CONV3, epi, M, N, K, precision != STA_PREC_F16, mx != 0, 0, forced_variant, 0, head_gemm != 0 ? 1 : 0, 0, false, 0, cstride, Ho, Wo};
+    GemmPlan g;
+    CHK(gemm_plan(q, g));
+    plan_out(g, out);
+    return 0;
+}
 #endif
 
 static int no_mx_kernel(int family, int epi) { return set_err("internal: tile family %d has no f16mx form for epilogue %d", family, epi); }
@@ -923,10 +936,12 @@ static int run_up2(sta_handle* h, const Planes& in, int n, int Hi, int Wi, int C
     if (h->dry) return 0;
     REQUIRE(in.mx == out.mx && C % 8 == 0, "internal: bilinear format mismatch");
     // four output rows per workgroup from 64 rows on (shared taps: half the tap loads, a third of the L2 fetches); one row per
-    // workgroup below that, where the grid would no longer fill the chip
-    const bool quad = Hc >= 64 && (int64_t)n * ((Hc + 3) / 4) >= 512 && h->opt[7] != 1;
+    // workgroup below that, where the grid would no longer fill the chip - and in precision f16, which has the one-row form only
+    // (its grid must be n * Hc workgroups: sized for four rows it left three quarters of the output unwritten)
+    const bool split = h->prec != STA_PREC_F16;
+    const bool quad = split && Hc >= 64 && (int64_t)n * ((Hc + 3) / 4) >= 512 && h->opt[7] != 1;
     const int blocks = quad ? n * ((Hc + 3) / 4) : n * Hc;
-    if (h->prec != STA_PREC_F16) {
+    if (split) {
         if (quad) hipLaunchKernelGGL((bilinear_up2_kernel<true, 4>), dim3(blocks), dim3(256), 0, st, in.hi, in.lo, n, Hi, Wi, C, Hc, Wc, out.hi, out.lo, in.mx ? 1 : 0, h->range);
         else hipLaunchKernelGGL((bilinear_up2_kernel<true, 1>), dim3(blocks), dim3(256), 0, st, in.hi, in.lo, n, Hi, Wi, C, Hc, Wc, out.hi, out.lo, in.mx ? 1 : 0, h->range);
     } else {
