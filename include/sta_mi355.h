@@ -141,8 +141,9 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
- * its plan holds the positions table on top of sta_decode's), sta_view_consistency (pair matrices per view count and window) and
- * sta_symmetric_geo_mask (error plane per edge count). */
+ * its plan holds the positions table on top of sta_decode's), sta_view_consistency (pair matrices per view count and window),
+ * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
+ * sta_ray_depth (one K^-1 per view). */
 STA_API int sta_reserve(sta_handle* h, int B, int H, int W, int max_edges, void* const* streams, int n_streams);
 STA_API int sta_alloc_stats(const sta_handle* h, int64_t out[2]);
 
@@ -328,6 +329,35 @@ STA_API int sta_view_consistency(sta_handle* h, const float* depths, const float
                          float threshold, int window, int32_t* count_out, void* stream);
 STA_API int sta_symmetric_geo_mask(sta_handle* h, const float* depths, const float* K, const float* rel_pose, int P, int H, int W,
                            uint8_t* mask_out, float* thres_out, void* stream);
+
+/* the rest of slam_utils.py - the general two-view check with a quantile threshold, local point clouds and ray
+ * depths.  Same rules as f5: device pointers, any H and W (H > W included), workspace from the stream's scratch context (one
+ * synchronisation when it first grows), otherwise no allocation, synchronisation or copy to the host; an argument error returns
+ * a status and a message and launches nothing.
+ * sta_geo_valid_mask <- compute_geo_valid_mask_batched(depth1, depth2, K1, K2, T1, T2, error_thres_rel) (slam_utils.py:193-266):
+ * depth1, depth2 [B,H,W], K1, K2 [B,3,3] (only fx, fy, cx, cy are read, as in the reference), T1, T2 [B,4,4] camera-to-world.
+ * Pixel (x, y) of view 1 is unprojected ((x - cx1) z / fx1, (y - cy1) z / fy1, z = depth1), moved by T2^-1 T1 (top three rows of
+ * each, like the reference's [..., :3]) and projected: u2 = fx2 x2 / z2 + cx2, v2 likewise - the unclamped z2, no epsilon, so a
+ * point behind camera 2 projects too.  The target pixel is (int(v2), int(u2)): TRUNCATION toward zero, so u2 in (-1, 0) reads
+ * column 0; a coordinate that is not finite or beyond the int32 range is invalid.  err = |z2 - depth2[b, v, u]|;
+ * thres = torch.quantile(err of the valid pixels of ALL B images, q), linear interpolation, bit for bit in fp32:
+ * rank = q (n - 1), a and b = the floor(rank)-th and ceil(rank)-th smallest, w = rank - floor(rank),
+ * thres = w < 0.5 ? fma(w, b - a, a) : fma(-(b - a), 1 - w, b); NaN if any valid err is NaN.  The two order statistics are an
+ * exact device-side selection (four 8-bit radix passes, both ranks at once); the launch count does not depend on B.
+ * mask_out [B,H,W] bytes 0/1 = valid && err < thres (strict).  thres_out (1 float, may be NULL) = thres; count_out (1 int32, may
+ * be NULL) = n, the number of valid pixels.  No valid pixel (torch raises there): count 0, thres NaN, mask all 0.
+ * Refused: q outside [0, 1], B*H*W above 16 000 000 (torch.quantile's own limit).
+ * sta_local_pointclouds <- compute_local_pointclouds(depths, intrinsics) (slam_utils.py:82-121): out [N,H,W,3] =
+ * K^-1 [x, y, 1] * depths[n, y, x]; K is one [3,3] (k_batched = 0) or [N,3,3] (k_batched = 1), inverted once per view in double.
+ * sta_ray_depth <- depth_from_pointcloud_dot_batched(pointclouds, intrinsics) (slam_utils.py:124-165): out [B,H,W] = the dot
+ * product of pts[b, y, x, :] with the unit ray K^-1 [x, y, 1] / |K^-1 [x, y, 1]|; K as above. */
+STA_API int sta_geo_valid_mask(sta_handle* h, const float* depth1, const float* depth2, const float* K1, const float* K2,
+                       const float* T1, const float* T2, int B, int H, int W, float q, uint8_t* mask_out, float* thres_out,
+                       int32_t* count_out, void* stream);
+STA_API int sta_local_pointclouds(sta_handle* h, const float* depths, const float* K, int k_batched, int N, int H, int W,
+                          float* out, void* stream);
+STA_API int sta_ray_depth(sta_handle* h, const float* pts, const float* K, int k_batched, int B, int H, int W, float* out,
+                  void* stream);
 
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one

@@ -67,6 +67,9 @@ SIGNATURES = {
     "sta_mat_to_se3": (_i, [_vp, _fp, _i, _fp, _vp]),
     "sta_view_consistency": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _fp, _vp]),
     "sta_symmetric_geo_mask": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp]),
+    "sta_geo_valid_mask": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _fp, _fp, _fp, _vp]),
+    "sta_local_pointclouds": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
+    "sta_ray_depth": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
     "sta_regress_views": (_i, [_vp, _fp, C.POINTER(_vp), _i, C.c_char_p, _f, _i, _i, _fp, C.POINTER(C.c_float),
                                C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),

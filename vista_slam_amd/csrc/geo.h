@@ -5,6 +5,9 @@
 // Both warp a pixel of a source view into a target view: cam_t = M [K_s^-1 [x,y,1] d, 1], uvw = K_t cam_t.  A set-up kernel
 // (one thread per warp) inverts and composes the matrices once, in double, so the per-pixel kernels only multiply:
 //   cam_t = A [x,y,1] * d + t     with A = M[:3,:3] K_s^-1, t = M[:3,3], M = X^-1 Y (top three rows; see geo_compose).
+// f6 (slam_utils.py:82-266), at the end of this file, reuses the set-up and generalises the selection:
+//   compute_geo_valid_mask_batched(depth1, depth2, K1, K2, T1, T2, q) -> masks, err < torch.quantile(err of the whole batch, q)
+//   compute_local_pointclouds / depth_from_pointcloud_dot_batched     -> element-wise behind one K^-1 per view
 #pragma once
 
 struct GeoPair { float A[9]; float t[3]; float K[9]; float pad[3]; };      // 96 bytes per warp
@@ -250,4 +253,182 @@ __global__ __launch_bounds__(256) void geo_mask_kernel(const unsigned* err, int 
     const float thres = __int_as_float(state[slot * GEO_STATE + GEO_THRES]);
     const unsigned bits = err[(int64_t)slot * hw + pix];
     mask[(int64_t)slot * hw + pix] = bits != GEO_INVALID && __uint_as_float(bits) < thres ? 1 : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// f6: compute_geo_valid_mask_batched (slam_utils.py:193-266), compute_local_pointclouds (:82-121) and
+// depth_from_pointcloud_dot_batched (:124-165).
+//   mask[b] = valid && |z2 - depth2[b, int(v2), int(u2)]| < quantile(valid errors of the WHOLE batch, q)
+// The warp is geo_compose's with Y = T1[b], X = T2[b] and the two intrinsics rebuilt from the four entries the reference reads
+// (fx, fy, cx, cy; :217-223, :243-249).  The error plane [B, HW] has f5's format and is selected from as ONE array: the state
+// and the histograms below exist once per call, whatever B is.
+//   state [GQ_STATE] int32; hist0 [256] (top byte, shared by both ranks); hist [3 passes, 2 ranks, 256].
+enum { GQ_COUNT = 0, GQ_NAN = 1, GQ_PREFIX = 2 /* +rank */, GQ_K = 4 /* +rank */, GQ_THRES = 6, GQ_STATE = 8 };
+constexpr int GQ_PER = 8;                                  // keys per thread of geo_q_hist_kernel
+
+__device__ inline void geo_four_entries(const float* K, float* o) {
+    o[0] = K[0]; o[1] = 0.f; o[2] = K[2]; o[3] = 0.f; o[4] = K[4]; o[5] = K[5]; o[6] = 0.f; o[7] = 0.f; o[8] = 1.f;
+}
+__global__ void geo_q_pairs_kernel(const float* K1, const float* K2, const float* T1, const float* T2, int B, GeoPair* pairs) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float ks[9], kt[9];
+    geo_four_entries(K1 + b * 9, ks); geo_four_entries(K2 + b * 9, kt);
+    geo_compose(ks, kt, T1 + b * 16, T2 + b * 16, pairs + b);
+}
+
+// grid (B * gx), gx = ceil(HW / 256): image b = blockIdx.x / gx is uniform per workgroup.  u2 = fx2 x2 / z2 + cx2 divides by the
+// unclamped z2 (no epsilon; a point behind camera 2 projects like any other), the target pixel is the coordinate TRUNCATED toward
+// zero, so (-1, 0) lands on column 0.  The float comparisons fail for NaN / inf / beyond-int32 values: never an index.
+__global__ __launch_bounds__(256) void geo_q_warp_kernel(const float* depth1, const float* depth2, const GeoPair* pairs, int H, int W,
+                                                         int gx, unsigned* err, int* state, unsigned* hist0) {
+    __shared__ unsigned lds[256];
+    __shared__ int wc[8];
+    const int b = blockIdx.x / gx, hw = H * W, pix = (blockIdx.x - b * gx) * 256 + threadIdx.x;
+    bool valid = false;
+    unsigned bits = GEO_INVALID;
+    if (pix < hw) {
+        const GeoPair& g = pairs[b];
+        const int y = pix / W, x = pix - y * W;
+        const float fx = (float)x, fy = (float)y, d = depth1[(int64_t)b * hw + pix];
+        const float rx = fmaf(g.A[0], fx, fmaf(g.A[1], fy, g.A[2])), ry = fmaf(g.A[3], fx, fmaf(g.A[4], fy, g.A[5])),
+                    rz = fmaf(g.A[6], fx, fmaf(g.A[7], fy, g.A[8]));
+        const float cx = fmaf(rx, d, g.t[0]), cy = fmaf(ry, d, g.t[1]), cz = fmaf(rz, d, g.t[2]);
+        const float u = g.K[0] * cx / cz + g.K[2], v = g.K[4] * cy / cz + g.K[5];
+        valid = u > -1.f && u < (float)W && v > -1.f && v < (float)H;
+        const int idx = valid ? (int)v * W + (int)u : 0;
+        const float e = cz - depth2[(int64_t)b * hw + idx];
+        if (valid) bits = __float_as_uint(e) & 0x7fffffffu;
+        err[(int64_t)b * hw + pix] = bits;
+    }
+    const bool isnan_ = valid && bits > 0x7f800000u;
+    const unsigned long long bv = __ballot(valid), bn = __ballot(isnan_);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { wc[wave] = __popcll(bv); wc[4 + wave] = __popcll(bn); }
+    geo_hist_block(lds, valid, bits >> 24, hist0);                           // (its barriers also publish wc)
+    if (threadIdx.x == 0) {
+        const int cv = wc[0] + wc[1] + wc[2] + wc[3], cn = wc[4] + wc[5] + wc[6] + wc[7];
+        if (cv) atomicAdd(&state[GQ_COUNT], cv);
+        if (cn) atomicAdd(&state[GQ_NAN], cn);
+    }
+}
+
+// radix pass `pass` (1..3) for both ranks at once: hist [2, 256], rank r counts the keys under its own prefix.  A workgroup takes
+// 256 * GQ_PER consecutive keys, so the number of global adds per pass stays small next to the number of keys.
+__global__ __launch_bounds__(256) void geo_q_hist_kernel(const unsigned* err, int total, const int* state, int pass, unsigned* hist) {
+    __shared__ unsigned lds[512];
+    const unsigned p0 = (unsigned)state[GQ_PREFIX], p1 = (unsigned)state[GQ_PREFIX + 1];
+    const int hb = 32 - 8 * pass;
+    lds[threadIdx.x] = 0; lds[256 + threadIdx.x] = 0;
+    __syncthreads();
+    const int base = blockIdx.x * (256 * GQ_PER) + threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < GQ_PER; ++q) {
+        const int i = base + q * 256;
+        const unsigned bits = i < total ? err[i] : GEO_INVALID;
+        if (bits == GEO_INVALID) continue;
+        const unsigned digit = (bits >> (hb - 8)) & 255u;
+        if (((bits ^ p0) >> hb) == 0) atomicAdd(&lds[digit], 1u);
+        if (((bits ^ p1) >> hb) == 0) atomicAdd(&lds[256 + digit], 1u);
+    }
+    __syncthreads();
+    const unsigned c0 = lds[threadIdx.x], c1 = lds[256 + threadIdx.x];
+    if (c0) atomicAdd(&hist[threadIdx.x], c0);
+    if (c1) atomicAdd(&hist[256 + threadIdx.x], c1);
+}
+
+// One workgroup of two waves, wave r = rank r.  Pass 0 fixes the ranks the way torch.quantile (linear interpolation) does, in
+// fp32: rank = q * (n - 1), lo = floor, hi = ceil; both waves read hist0.  After pass 3 the two prefixes ARE the bit patterns of
+// the lo-th and the hi-th smallest error a and b, and thres = lerp(a, b, w = rank - lo) as ATen evaluates it: one fused
+// multiply-add per branch, w < 0.5 ? fma(w, b - a, a) : fma(-(b - a), 1 - w, b).  NaN when a valid error is NaN (quantile
+// propagates it) or when no pixel is valid (torch raises; the caller reads count_out).
+__global__ __launch_bounds__(128) void geo_q_pick_kernel(const unsigned* hist, int pass, float q, int* st, float* thres_out, int* count_out) {
+    __shared__ unsigned ab[2];
+    const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int count = st[GQ_COUNT];
+    if (count == 0) {                                      // (uniform: the whole workgroup leaves)
+        if (pass == 3 && threadIdx.x == 0) {
+            st[GQ_THRES] = (int)0x7fc00000u;
+            if (thres_out) *thres_out = __uint_as_float(0x7fc00000u);
+            if (count_out) *count_out = 0;
+        }
+        return;
+    }
+    const float rank = __fmul_rn(q, (float)(count - 1));
+    int k;
+    unsigned prefix = 0u;
+    if (pass == 0) {
+        k = (int)(r == 0 ? floorf(rank) : ceilf(rank));
+        k = k < 0 ? 0 : (k > count - 1 ? count - 1 : k);
+    } else { k = st[GQ_K + r]; prefix = (unsigned)st[GQ_PREFIX + r]; }
+    const unsigned* h = hist + (pass == 0 ? 0 : r * 256) + lane * 4;
+    const int b0 = (int)h[0], b1 = (int)h[1], b2 = (int)h[2], b3 = (int)h[3];
+    const int sum = b0 + b1 + b2 + b3;
+    int incl = sum;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    const int excl = incl - sum;
+    if (k >= excl && k < incl) {                           // exactly one lane per wave: the pass's keys number more than k
+        int rr = k - excl, bn = 0;
+        if (rr >= b0) { rr -= b0; bn = 1; if (rr >= b1) { rr -= b1; bn = 2; if (rr >= b2) { rr -= b2; bn = 3; } } }
+        const unsigned np = prefix | ((unsigned)(lane * 4 + bn) << (24 - 8 * pass));
+        st[GQ_PREFIX + r] = (int)np; st[GQ_K + r] = rr;    // (wave r reads and writes only its own two words)
+        ab[r] = np;
+    }
+    if (pass != 3) return;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float a = __uint_as_float(ab[0]), b = __uint_as_float(ab[1]);
+        const float w = rank - floorf(rank), diff = b - a;
+        float th = w < 0.5f ? fmaf(w, diff, a) : fmaf(-diff, 1.0f - w, b);
+        if (st[GQ_NAN] > 0) th = __uint_as_float(0x7fc00000u);
+        st[GQ_THRES] = __float_as_int(th);
+        if (thres_out) *thres_out = th;
+        if (count_out) *count_out = count;
+    }
+}
+
+// mask = valid && err < thres over the whole error plane, one byte per pixel (a NaN threshold leaves it all 0)
+__global__ __launch_bounds__(256) void geo_q_mask_kernel(const unsigned* err, int total, const int* state, uint8_t* mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const float thres = __int_as_float(state[GQ_THRES]);
+    const unsigned bits = err[i];
+    mask[i] = bits != GEO_INVALID && __uint_as_float(bits) < thres ? 1 : 0;
+}
+
+// K^-1 of every view (n = 1 for shared intrinsics), once, in double
+__global__ void geo_kinv_kernel(const float* K, int n, float* kinv) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    double k[9], ki[9];
+    for (int q = 0; q < 9; ++q) k[q] = (double)K[v * 9 + q];
+    geo_inv3(k, ki);
+    for (int q = 0; q < 9; ++q) kinv[v * 9 + q] = (float)ki[q];
+}
+
+// compute_local_pointclouds: out[n, y, x, :] = K^-1 [x, y, 1] * depth.  grid (N * gx), gx = ceil(3 HW / 256): one thread per
+// OUTPUT float, so the stores are contiguous (the three threads of a pixel share its depth load).
+__global__ __launch_bounds__(256) void geo_local_points_kernel(const float* depths, const float* kinv, int k_batched, int H, int W,
+                                                               int gx, float* out) {
+    const int n = blockIdx.x / gx, hw = H * W, e = (blockIdx.x - n * gx) * 256 + threadIdx.x;
+    if (e >= 3 * hw) return;
+    const int pix = e / 3, c = e - pix * 3, y = pix / W, x = pix - y * W;
+    const float* ki = kinv + (k_batched ? n * 9 : 0) + c * 3;
+    const float ray = fmaf(ki[0], (float)x, fmaf(ki[1], (float)y, ki[2]));
+    out[(int64_t)n * 3 * hw + e] = ray * depths[(int64_t)n * hw + pix];
+}
+
+// depth_from_pointcloud_dot_batched: the dot product of each point with its unit ray K^-1 [x, y, 1] / |.|
+__global__ __launch_bounds__(256) void geo_ray_depth_kernel(const float* pts, const float* kinv, int k_batched, int H, int W, int gx,
+                                                            float* out) {
+    const int n = blockIdx.x / gx, hw = H * W, pix = (blockIdx.x - n * gx) * 256 + threadIdx.x;
+    if (pix >= hw) return;
+    const int y = pix / W, x = pix - y * W;
+    const float* ki = kinv + (k_batched ? n * 9 : 0);
+    const float fx = (float)x, fy = (float)y;
+    const float rx = fmaf(ki[0], fx, fmaf(ki[1], fy, ki[2])), ry = fmaf(ki[3], fx, fmaf(ki[4], fy, ki[5])),
+                rz = fmaf(ki[6], fx, fmaf(ki[7], fy, ki[8]));
+    const float nrm = sqrtf(rx * rx + ry * ry + rz * rz);
+    const float* p = pts + ((int64_t)n * hw + pix) * 3;
+    out[(int64_t)n * hw + pix] = p[0] * (rx / nrm) + p[1] * (ry / nrm) + p[2] * (rz / nrm);
 }

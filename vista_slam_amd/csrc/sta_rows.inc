@@ -218,6 +218,84 @@ extern "C" int sta_symmetric_geo_mask(sta_handle* h, const float* depths, const 
     });
 }
 
+// f6: the general two-view check, local point clouds and ray depths (slam_utils.py:193-266, 82-165; kernels in geo.h).  Like f5:
+// no synchronisation, no copy to the host, workspace from the stream's scratch context.  The mask is ten launches behind one
+// memset whatever B is: the quantile is ONE selection over the whole batch.
+extern "C" int sta_geo_valid_mask(sta_handle* h, const float* depth1, const float* depth2, const float* K1, const float* K2,
+                                  const float* T1, const float* T2, int B, int H, int W, float q, uint8_t* mask_out,
+                                  float* thres_out, int32_t* count_out, void* stream) {
+    REQUIRE(h && depth1 && depth2 && K1 && K2 && T1 && T2 && mask_out, "null argument");
+    REQUIRE(B >= 1 && H > 0 && W > 0, "bad size");
+    REQUIRE(q >= 0.f && q <= 1.f, "q must lie in [0, 1] (got %g)", (double)q);          // (a NaN q fails too)
+    REQUIRE((int64_t)B * H * W <= 16000000, "B*H*W = %lld is above torch.quantile's limit of 16 000 000 elements", (long long)B * H * W);
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int hw = H * W, total = B * hw, gx = (hw + 255) / 256;
+    return plan_and_run(h, st, [&](Bump& ws) -> int {
+        GeoPair* pairs = (GeoPair*)ws.take((int64_t)B * sizeof(GeoPair));
+        unsigned* err = (unsigned*)ws.take((int64_t)total * 4);
+        const int64_t zero_bytes = (GQ_STATE + 256 + 3 * 2 * 256) * 4;              // state + hist0 + three two-rank passes, cleared together
+        int* state = (int*)ws.take(zero_bytes);
+        unsigned* hist0 = (unsigned*)(state + GQ_STATE);
+        if (h->dry) return 0;
+        REQUIRE(!ws.overflow, "internal: workspace overflow");
+        HIPCHK(hipMemsetAsync(state, 0, (size_t)zero_bytes, st));
+        hipLaunchKernelGGL(geo_q_pairs_kernel, dim3((B + 63) / 64), dim3(64), 0, st, K1, K2, T1, T2, B, pairs);
+        hipLaunchKernelGGL(geo_q_warp_kernel, dim3(B * gx), dim3(256), 0, st, depth1, depth2, pairs, H, W, gx, err, state, hist0);
+        hipLaunchKernelGGL(geo_q_pick_kernel, dim3(1), dim3(128), 0, st, hist0, 0, q, state, thres_out, count_out);
+        const int gh = (total + 256 * GQ_PER - 1) / (256 * GQ_PER);
+        for (int pass = 1; pass < 4; ++pass) {
+            unsigned* hp = hist0 + 256 + (pass - 1) * 512;
+            hipLaunchKernelGGL(geo_q_hist_kernel, dim3(gh), dim3(256), 0, st, err, total, state, pass, hp);
+            hipLaunchKernelGGL(geo_q_pick_kernel, dim3(1), dim3(128), 0, st, hp, pass, q, state, thres_out, count_out);
+        }
+        hipLaunchKernelGGL(geo_q_mask_kernel, dim3((total + 255) / 256), dim3(256), 0, st, err, total, state, mask_out);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
+// out = element-wise kernel behind one K^-1 per view (n_k = N or 1 matrices)
+template <class Launch>
+static int geo_with_kinv(sta_handle* h, const float* K, int k_batched, int N, hipStream_t st, Launch launch) {
+    const int nk = k_batched ? N : 1;
+    return plan_and_run(h, st, [&](Bump& ws) -> int {
+        float* kinv = (float*)ws.take((int64_t)nk * 9 * 4);
+        if (h->dry) return 0;
+        REQUIRE(!ws.overflow, "internal: workspace overflow");
+        hipLaunchKernelGGL(geo_kinv_kernel, dim3((nk + 63) / 64), dim3(64), 0, st, K, nk, kinv);
+        launch(kinv);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+extern "C" int sta_local_pointclouds(sta_handle* h, const float* depths, const float* K, int k_batched, int N, int H, int W,
+                                     float* out, void* stream) {
+    REQUIRE(h && depths && K && out, "null argument");
+    REQUIRE(N >= 1 && H > 0 && W > 0, "bad size");
+    REQUIRE(k_batched == 0 || k_batched == 1, "k_batched must be 0 or 1 (got %d)", k_batched);
+    const int64_t hw = (int64_t)H * W, gx = (3 * hw + 255) / 256;
+    REQUIRE(hw < (int64_t)1 << 29 && N * gx < (int64_t)1 << 31, "depth maps too large");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    return geo_with_kinv(h, K, k_batched, N, st, [&](const float* kinv) {
+        hipLaunchKernelGGL(geo_local_points_kernel, dim3((unsigned)(N * gx)), dim3(256), 0, st, depths, kinv, k_batched, H, W, (int)gx, out);
+    });
+}
+extern "C" int sta_ray_depth(sta_handle* h, const float* pts, const float* K, int k_batched, int B, int H, int W, float* out,
+                             void* stream) {
+    REQUIRE(h && pts && K && out, "null argument");
+    REQUIRE(B >= 1 && H > 0 && W > 0, "bad size");
+    REQUIRE(k_batched == 0 || k_batched == 1, "k_batched must be 0 or 1 (got %d)", k_batched);
+    const int64_t hw = (int64_t)H * W, gx = (hw + 255) / 256;
+    REQUIRE(hw < (int64_t)1 << 29 && B * gx < (int64_t)1 << 31, "point maps too large");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    return geo_with_kinv(h, K, k_batched, B, st, [&](const float* kinv) {
+        hipLaunchKernelGGL(geo_ray_depth_kernel, dim3((unsigned)(B * gx)), dim3(256), 0, st, pts, kinv, k_batched, H, W, (int)gx, out);
+    });
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
