@@ -11,7 +11,8 @@
  *   sta_encode        <- _encode_image(image, true_shape, normalize=False)
  *                        (sta_model.py:163-174, called from slam.py:144)
  *   sta_decode        <- _decode_stereo(feat1, feat2, pos1, pos2)   (positions = the patch grid; sta_decode_pos: any positions)
- *                        (sta_model.py:177-244, called from slam.py:162)
+ *                        (sta_model.py:177-244, called from slam.py:162; N1 != N2 tokens: sta_decode_mixed on two patch
+ *                        grids, sta_decode_tokens on token subsets with any positions)
  *   sta_head_pose     <- head_pose_s(tok[:,0,:])        (heads/pose_head.py:109-120, slam.py:165)
  *   sta_head_pts      <- head_pts(list14, true_shape)   (heads/dpt_head.py:34-66 +
  *                        heads/postprocess.py:10-62 + utils/misc.py:36-78, slam.py:179-180)
@@ -141,7 +142,8 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
- * its plan holds the positions table on top of sta_decode's), sta_view_consistency (pair matrices per view count and window),
+ * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts),
+ * sta_view_consistency (pair matrices per view count and window),
  * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
  * sta_ray_depth (one K^-1 per view). */
 STA_API int sta_reserve(sta_handle* h, int B, int H, int W, int max_edges, void* const* streams, int n_streams);
@@ -228,6 +230,19 @@ STA_API int sta_decode_mixed(sta_handle* h, const float* feat1, const float* fea
  * grid's own positions the two agree to the rounding of one more fp16-plane split (~1e-7), not bit for bit. */
 STA_API int sta_decode_pos(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
                    int B, int N, int pos_max, float* const* out1, float* const* out2, void* stream);
+
+/* _decode_stereo on TOKEN SUBSETS: caller positions AND unequal token counts, the last input of the reference's _decode_stereo
+ * (sta_model.py:177-244; every attention rotates q / k by the positions it is handed, sta_blocks.py:134-137,196-199) - a rectangular
+ * window of one view against the whole other view, a pruned token set.  feat1 [B, N1, enc_dim], feat2 [B, N2, enc_dim]; pos1
+ * [B, N1, 2], pos2 [B, N2, 2] device int64 (y, x), every batch entry its own.  Values must lie in [-1, pos_max] (out-of-range values
+ * are clamped, as in sta_decode_pos; the RoPE table grows to pos_max on first use).  out1[i] [B, N1+1, dec_dim], out2[i]
+ * [B, N2+1, dec_dim]; NULL skips a layer, the last index has dec_norm applied.  N1, N2 >= 1 need not be products of a grid; N1 == N2
+ * is served by the same route.  Implementation: sta_decode_mixed's row layout and two-group attention with the identity table in the
+ * QKV epilogues, then two launches per layer of one kernel that rotates the Q / K buffers of both sides from the positions table.
+ * Like sta_decode_mixed the call runs on one lane and is NOT covered by sta_reserve: the first call of a shape pair allocates.
+ * Returns -1 with a message for null pointers, N < 1, pos_max outside [0, 2^20) or 2^31 or more decoder rows. */
+STA_API int sta_decode_tokens(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
+                      int B, int N1, int N2, int pos_max, float* const* out1, float* const* out2, void* stream);
 
 /* tok: B rows of dec_dim floats, consecutive rows `tok_stride` floats apart.
  * pose [B,16] row-major 4x4, conf [B]. */

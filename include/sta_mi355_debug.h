@@ -113,6 +113,15 @@ STA_API int sta_debug_attn_mixed_plan(int S1, int S2, int heads, int nq_a, int n
 STA_API int sta_debug_last_attn_mixed_plan(sta_handle* h, int* out);
 STA_API int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qblocks_a, int qblocks_b, int* out);
 
+/* The rotation step of sta_decode_tokens alone: 2-D RoPE from a positions table on nbuf (1..3) head-major buffers for two groups
+ * of sequences with different token counts.  bufs[b]: fp32 [S1 + S2][heads][npad][64], npad = roundup(max(ntok_a, ntok_b) + 1, 64);
+ * every row is split to fp16 planes inside, rotated IN PLACE and returned as hi + lo.  Sequences [0, S1) hold ntok_a tokens,
+ * sequences [S1, S1 + S2) ntok_b; token index ntok of a sequence is its pose token (position -1), rows (ntok, npad) are not
+ * touched.  pos_i32: device int32 [S1*ntok_a*2 | S2*ntok_b*2] of (y, x), clamped to [-1, pos_max].  which = 0: rope_tokens_kernel
+ * (one launch); which = 1: rope_planes_kernel launched per buffer and per side. */
+STA_API int sta_debug_rope_tokens(sta_handle* h, float* const* bufs, int nbuf, int S1, int S2, int heads, int ntok_a, int ntok_b,
+                                  const int* pos_i32, int pos_max, int which, void* stream);
+
 /* The same record for the handle's LAST attention launch. */
 STA_API int sta_debug_last_attn_plan(sta_handle* h, int* out);
 
@@ -125,7 +134,8 @@ STA_API int sta_debug_attn_block_map(int nwg, int* out);
  * convt / up2 run in the DPT head's f16mx arithmetic (f16mx rows in and out, f16mx weights) when the handle's precision is
  * f16x3h - the kernels that precision uses inside the head.  A/B switches of round-4 choices: 1 = 1 small-grid K slices by the
  * old rule; 2 = 1 small-grid GEMMs always on 4 waves; 5 = 1 attention without the 4-stage prefetch schedule; 6 = 1 no side
- * lanes (2: always); 7 = 1 bilinear one output row per workgroup.  Indices 0 and 3 are free. */
+ * lanes (2: always); 7 = 1 bilinear one output row per workgroup; 3 = 1 sta_decode_tokens rotates Q / K by per-buffer
+ * rope_planes_kernel launches (one per buffer and side: eight per decoder layer) instead of the two rope_tokens_kernel launches. */
 STA_API int sta_debug_set_option(sta_handle* h, int idx, int value);
 
 /* Row-tail hint for the dense GEMMs (what the decoder sets to its 2B pose-token rows): the last `rows` (<= 32) rows of the

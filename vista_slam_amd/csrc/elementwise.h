@@ -327,6 +327,71 @@ __global__ __launch_bounds__(256) void rope_planes_kernel(f16* hi, f16* lo, int 
     ra.flush(rng);
 }
 
+// sta_decode_tokens: the positions table of two sides with DIFFERENT token counts: pos1 [n1 = B*N1*2] and pos2 [n2 = B*N2*2] -> one
+// int32 table [n1 | n2] (side 2 starts at n1), clamped to [-1, pos_max] like rope_pos_table_kernel's; the tail of the grid fills the
+// identity cos / sin table of the call's QKV epilogues.  T = int64_t (the entry) or int (sta_debug_rope_tokens: clamps the test's table)
+template <typename T>
+__global__ __launch_bounds__(256) void rope_tokens_table_kernel(const T* pos1, const T* pos2, int64_t n1, int64_t n2, int pos_max, int* out,
+                                                                float2* ident, int64_t n_ident) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n1 + n2) {
+        int64_t v = i < n1 ? (int64_t)pos1[i] : (int64_t)pos2[i - n1];
+        v = v < -1 ? -1 : (v > pos_max ? pos_max : v);
+        out[i] = (int)v;
+    } else if (i - n1 - n2 < n_ident) ident[i - n1 - n2] = make_float2(1.f, 0.f);
+}
+
+// sta_decode_tokens: rope_planes_kernel's rotation for TWO GROUPS of sequences with different token counts and up to three Q / K
+// buffers [S1 + S2][heads][npad][64] in ONE launch (blockIdx.y = buffer).  Sequences [0, S1) hold ntok_a tokens and read the table
+// slice pos[0, S1*ntok_a*2); sequences [S1, S1 + S2) hold ntok_b tokens and read the slice behind it.  Token index ntok of a sequence
+// is its pose token (position -1); rows (ntok, npad) of a sequence are never touched.  One thread = eight consecutive frequencies
+// f0 .. f0 + 7 of one (sequence, head, token, y | x half): the pairs (d, d + 16) are two 16-byte accesses per plane at o and o + 16,
+// and the eight (cos, sin) entries four 16-byte loads of one table row - the planes move in the widest access instead of 2-byte ones.
+struct RopeTokParams {
+    f16* hi[3]; f16* lo[3];
+    int S1, S2, heads, npad, ntok_a, ntok_b;
+    const int* pos; const float* tab; unsigned long long* rng;
+};
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void rope_tokens_kernel(RopeTokParams p) {
+    const int b = blockIdx.y;
+    f16* hi = b == 0 ? p.hi[0] : (b == 1 ? p.hi[1] : p.hi[2]);
+    f16* lo = b == 0 ? p.lo[0] : (b == 1 ? p.lo[1] : p.lo[2]);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rows_a = (int64_t)p.S1 * p.heads * (p.ntok_a + 1), rows_b = (int64_t)p.S2 * p.heads * (p.ntok_b + 1);
+    if (i >= (rows_a + rows_b) * 4) return;
+    const int j = (int)(i & 3), xp = j >> 1, f0 = (j & 1) * 8;
+    int64_t r = i >> 2;
+    const bool gb = r >= rows_a;                       // second group
+    if (gb) r -= rows_a;
+    const int ntok = gb ? p.ntok_b : p.ntok_a;
+    const int t = (int)(r % (ntok + 1)); r /= ntok + 1;
+    const int hd = (int)(r % p.heads), sl = (int)(r / p.heads);          // sl: the sequence inside its group
+    const int* pos = p.pos + (gb ? (int64_t)p.S1 * p.ntok_a * 2 : 0);
+    const int ps = t < ntok ? pos[((int64_t)sl * ntok + t) * 2 + xp] : -1;
+    const float4* tab = reinterpret_cast<const float4*>(p.tab + ((size_t)(ps + 1) * 16 + f0) * 2);
+    const int s = sl + (gb ? p.S1 : 0);
+    const int64_t o = (((int64_t)s * p.heads + hd) * p.npad + t) * 64 + xp * 32 + f0;
+    union { float4 v[4]; float2 e[8]; } cs;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cs.v[q] = tab[q];
+    H8 h0, h1, l0, l1;
+    h0.u = ldg16(hi + o); h1.u = ldg16(hi + o + 16);
+    if (SPLIT) { l0.u = ldg16(lo + o); l1.u = ldg16(lo + o + 16); }
+    RangeAcc ra;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float v0 = (float)h0.e[e], v1 = (float)h1.e[e];
+        if (SPLIT) { v0 += (float)l0.e[e]; v1 += (float)l1.e[e]; }
+        const float r0 = v0 * cs.e[e].x - v1 * cs.e[e].y, r1 = v1 * cs.e[e].x + v0 * cs.e[e].y;
+        if (SPLIT) { split_f16(r0, h0.e[e], l0.e[e], ra); split_f16(r1, h1.e[e], l1.e[e], ra); }
+        else { h0.e[e] = to_f16_sat(r0, ra); h1.e[e] = to_f16_sat(r1, ra); }
+    }
+    *reinterpret_cast<uint4*>(hi + o) = h0.u; *reinterpret_cast<uint4*>(hi + o + 16) = h1.u;
+    if (SPLIT) { *reinterpret_cast<uint4*>(lo + o) = l0.u; *reinterpret_cast<uint4*>(lo + o + 16) = l1.u; }
+    ra.flush(p.rng);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Bilinear x2 upsample, align_corners=True (dpt_block.py:215-216,320), NHWC fp16 planes.
 // Output may be cropped to (Hc,Wc) <= (2Hi,2Wi) (dpt_head.py:58); interpolation ratios always use

@@ -152,8 +152,8 @@ struct sta_handle {
     AttnMixedPlan last_attn_mixed{};   // ... of the last run_attn_mixed (sta_debug_last_attn_mixed_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
-    // sta_decode_pos, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and rope_planes_kernel
-    // rotates Q / K by the caller's positions afterwards (decode_impl)
+    // sta_decode_pos / sta_decode_tokens, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and
+    // rope_planes_kernel / rope_tokens_kernel rotates Q / K by the caller's positions afterwards (decode_impl / decode_mixed_impl)
     bool rope_foreign = false; const int* rope_pos = nullptr; const float* rope_ident = nullptr;
     // timing
     bool timing = false; hipEvent_t ev[5]; bool ev_ok = false;
@@ -745,6 +745,40 @@ extern "C" int sta_decode_pos(sta_handle* h, const float* feat1, const float* fe
             h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return decode_impl(h, ws, feat1, feat2, B, 1, N, x, out1, out2, true, st);
+    });
+}
+
+// _decode_stereo on TOKEN SUBSETS: caller positions AND unequal token counts (a window of one view against the whole other view, a
+// pruned token set).  decode_mixed_impl's row layout and two-group attention with each side as the grid 1 x Nx; the positions of
+// both sides become one int32 table [B*N1*2 | B*N2*2] in the workspace, the QKV epilogues rotate by the identity table (rope_foreign,
+// as in sta_decode_pos) and rope_tokens_kernel rotates the Q / K buffers of both groups in place: two launches per decoder layer.
+extern "C" int sta_decode_tokens(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
+                                 int B, int N1, int N2, int pos_max, float* const* out1, float* const* out2, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    CHK(check_ready(h, B, 16, 16));
+    REQUIRE(feat1 && feat2 && pos1 && pos2, "null device pointer");
+    REQUIRE(N1 >= 1 && N2 >= 1 && pos_max >= 0 && pos_max < (1 << 20), "bad argument (N1 %d, N2 %d, pos_max %d)", N1, N2, pos_max);
+    const int64_t rows = (int64_t)B * ((int64_t)N1 + 1) + (int64_t)B * ((int64_t)N2 + 1);
+    REQUIRE(rows < ((int64_t)1 << 31), "too many decoder rows (%lld)", (long long)rows);
+    hipStream_t st = (hipStream_t)stream;
+    CHK(ensure_rope(h, pos_max + 1));
+    const int64_t xbytes = rows * h->cfg.dec_embed_dim * 4;
+    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
+    h->rope_foreign = true;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        float* x = (float*)ws.take(xbytes);
+        const int64_t n1 = (int64_t)B * N1 * 2, n2 = (int64_t)B * N2 * 2;
+        int* rp = (int*)ws.take((n1 + n2) * 4);
+        const int64_t n_ident = (int64_t)(std::max(N1, N2) + 2) * 16;      // each side is the grid 1 x Nx: table rows 0 .. max(N1, N2) + 1
+        float2* ident = (float2*)ws.take(n_ident * 8);
+        if (!h->dry) {
+            hipLaunchKernelGGL(rope_tokens_table_kernel<int64_t>, dim3((unsigned)((n1 + n2 + n_ident + 255) / 256)), dim3(256), 0, st,
+                               pos1, pos2, n1, n2, pos_max, rp, ident, n_ident);
+            HIPCHK(hipGetLastError());
+            h->rope_pos = rp; h->rope_ident = (const float*)ident;
+        }
+        return decode_mixed_impl(h, ws, feat1, feat2, B, 1, N1, 1, N2, x, out1, out2, st);
     });
 }
 

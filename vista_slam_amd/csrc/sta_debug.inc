@@ -276,10 +276,42 @@ extern "C" int sta_debug_attention_mixed(sta_handle* h, const float* q_a, const 
     return 0;
 }
 
+// The rotation step of sta_decode_tokens alone.  bufs: nbuf (<= 3) fp32 device buffers [S1 + S2][heads][npad][64], npad =
+// roundup(max(ntok_a, ntok_b) + 1, 64): EVERY row is split to planes (the rows past a sequence's pose token too), rotated in place and
+// returned as hi + lo, so a row the kernel must not touch comes back as it went in.  pos_i32: device int32 [S1*ntok_a*2 | S2*ntok_b*2]
+// (y, x), clamped to [-1, pos_max] into a copy first.  which = 0: rope_tokens_kernel, one launch; 1: rope_planes_kernel per buffer and side.
+extern "C" int sta_debug_rope_tokens(sta_handle* h, float* const* bufs, int nbuf, int S1, int S2, int heads, int ntok_a, int ntok_b,
+                                     const int* pos_i32, int pos_max, int which, void* stream) {
+    REQUIRE(h && bufs && pos_i32 && nbuf >= 1 && nbuf <= 3 && S1 > 0 && S2 > 0 && heads > 0 && ntok_a > 0 && ntok_b > 0, "bad argument");
+    REQUIRE(pos_max >= 0 && pos_max < (1 << 20) && (which == 0 || which == 1), "bad argument (pos_max %d, which %d)", pos_max, which);
+    for (int b = 0; b < nbuf; ++b) REQUIRE(bufs[b], "null buffer %d", b);
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int S = S1 + S2, npad = rup(std::max(ntok_a, ntok_b) + 1, 64);
+    const int64_t hsz = (int64_t)S * heads * npad * 64;
+    const int64_t n1 = (int64_t)S1 * ntok_a * 2, n2 = (int64_t)S2 * ntok_b * 2;
+    CHK(ensure_rope(h, pos_max + 1));
+    CHK(ensure_ws(h, nbuf * hsz * 4 + (n1 + n2) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes pl[3]; const Planes* pp[3];
+    for (int b = 0; b < nbuf; ++b) { pl[b] = ws.planes(hsz, split); pp[b] = &pl[b]; }
+    int* pos = (int*)ws.take((n1 + n2) * 4);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    hipLaunchKernelGGL(rope_tokens_table_kernel<int>, dim3((unsigned)((n1 + n2 + 255) / 256)), dim3(256), 0, st,
+                       pos_i32, pos_i32 + n1, n1, n2, pos_max, pos, (float2*)nullptr, (int64_t)0);
+    HIPCHK(hipGetLastError());
+    for (int b = 0; b < nbuf; ++b) CHK(run_rows_to_planes(h, bufs[b], (int64_t)npad * 64, S * heads, npad, 64, pl[b], st, npad));
+    CHK(rope_tokens_launch(h, pp, nbuf, S1, S2, heads, npad, ntok_a, ntok_b, pos, which == 1, st));
+    for (int b = 0; b < nbuf; ++b) CHK(dbg_planes_to_f32(h, pl[b], npad, S * heads, npad, 64, bufs[b], st));
+    return 0;
+}
+
 // A/B switches of the product's round-4 choices (tools/ab_option.py, ab_slam.py, ab_replay.py; 0 everywhere = product behaviour):
 //   1 = 1: small-grid K slices by the old rule ceil(256 / tiles)          2 = 1: small-grid GEMMs always on 4 waves (> 1: the lone-grid limit)
 //   4 = 1: debug GEMM entry points in the f16mx arithmetic                5 = 1: attention without the 4-stage prefetch schedule
 //   6 = 1: no side lanes, 2: side lanes even under a multi-stream caller  7 = 1: bilinear one output row per workgroup
+//   3 = 1: sta_decode_tokens rotates by per-buffer rope_planes_kernel launches (eight per layer) instead of rope_tokens_kernel (two)
 extern "C" int sta_debug_set_option(sta_handle* h, int idx, int value) {
     REQUIRE(h && idx >= 0 && idx < 8, "bad argument");
     h->opt[idx] = value;

@@ -181,8 +181,11 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
 // a hint).  What knows the sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SIDE on that side's contiguous row
 // range (own ntok, wp, pose_base = B*Nx; Q / K / V^T planes advanced by B sequences of the shared npad) - the hot GEMMs' EPI_QKV is
 // untouched -, attention is the two-group launch (run_attn_mixed): kv_shift = 0 for the self attention of both sides, kv_shift = B
-// with (nq, nk) = (N1, N2) | (N2, N1) for the cross attention of both directions.  One lane (no side stream), patch-grid
-// positions only, outside sta_reserve's coverage.  Equal grids are served too (the same route: tests compare it with decode_impl).
+// with (nq, nk) = (N1, N2) | (N2, N1) for the cross attention of both directions.  One lane (no side stream), outside
+// sta_reserve's coverage.  Equal grids are served too (the same route: tests compare it with decode_impl).  Positions: each side's
+// patch grid (sta_decode_mixed), or the caller's (sta_decode_tokens: each side enters as the grid 1 x Nx, the QKV epilogues rotate by
+// the identity table - h->rope_foreign - and rope_tokens rotates the Q / K buffers of both groups from the positions table, two
+// launches per layer).
 // want1[i] [B, N1+1, D] / want2[i] [B, N2+1, D] in the reference's token order (pose token first), or NULL.
 static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, int B, int hp1, int wp1, int hp2, int wp2,
                              float* x, float* const* want1, float* const* want2, hipStream_t st) {
@@ -242,9 +245,14 @@ static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const 
         const DecBlk& b = h->dec[i];
         CHK(qkv_sides(a1, b.qkv, D, D, D, qkv));
         CHK(qkv_sides(ay, b.ckv, 0, D, D, cqkv));         // K / V of a side's OWN tokens: the other side's queries read them (kv_shift = B)
+        {   // sta_decode_tokens: the epilogues above rotated by the identity; both groups' q / k by their own positions now (one launch)
+            const Planes* rot[3] = {&qkv.q, &qkv.k, &cqkv.k};
+            CHK(rope_tokens(h, rot, 3, B, B, Hh, npad, Nn[0], Nn[1], st));
+        }
         CHK(run_attn_mixed(h, qkv, ao, D, B, B, Hh, Nn[0], Nn[0], Nn[1], Nn[1], 0, st));
         CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
         CHK(qkv_sides(a1, b.cq, D, 0, 0, cqkv));
+        { const Planes* rot[1] = {&cqkv.q}; CHK(rope_tokens(h, rot, 1, B, B, Hh, npad, Nn[0], Nn[1], st)); }
         CHK(run_attn_mixed(h, cqkv, ao, D, B, B, Hh, Nn[0], Nn[1], Nn[1], Nn[0], B, st));
         CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
         CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));

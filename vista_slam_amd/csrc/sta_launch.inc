@@ -717,6 +717,43 @@ static int rope_fix(sta_handle* h, const Planes& qk, int S, int heads, int npad,
     HIPCHK(hipGetLastError());
     return 0;
 }
+// sta_decode_tokens: rotate nbuf (<= 3) Q / K buffers [S1 + S2][heads][npad][64] in place, sequences [0, S1) with ntok_a tokens and
+// the table slice pos[0, S1*ntok_a*2), sequences [S1, S1 + S2) with ntok_b tokens and the slice behind it: ONE launch of
+// rope_tokens_kernel.  per_buffer (experiment switch 3 / sta_debug_rope_tokens which = 1): the same rotation as 2 * nbuf launches of
+// rope_planes_kernel, one per buffer and side - what the entry would cost on the existing kernel (A/B only).
+static int rope_tokens_launch(sta_handle* h, const Planes* const* bufs, int nbuf, int S1, int S2, int heads, int npad, int ntok_a, int ntok_b,
+                              const int* pos, bool per_buffer, hipStream_t st) {
+    REQUIRE(nbuf >= 1 && nbuf <= 3 && pos && h->rope_tab, "internal: rope_tokens_launch arguments");
+    const bool split = bufs[0]->lo != nullptr;
+    if (per_buffer) {
+        for (int b = 0; b < nbuf; ++b)
+            for (int side = 0; side < 2; ++side) {
+                const int S = side ? S2 : S1, ntok = side ? ntok_b : ntok_a;
+                const int64_t off = side ? (int64_t)S1 * heads * npad * 64 : 0;
+                const int* ps = pos + (side ? (int64_t)S1 * ntok_a * 2 : 0);
+                const dim3 grid((unsigned)(((int64_t)S * heads * (ntok + 1) * 32 + 255) / 256));
+                if (split) hipLaunchKernelGGL(rope_planes_kernel<true>, grid, dim3(256), 0, st, bufs[b]->hi + off, bufs[b]->lo + off, S, heads, npad, ntok, ps, h->rope_tab, h->range);
+                else hipLaunchKernelGGL(rope_planes_kernel<false>, grid, dim3(256), 0, st, bufs[b]->hi + off, (f16*)nullptr, S, heads, npad, ntok, ps, h->rope_tab, h->range);
+            }
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    RopeTokParams p;
+    for (int b = 0; b < 3; ++b) { p.hi[b] = bufs[b < nbuf ? b : 0]->hi; p.lo[b] = bufs[b < nbuf ? b : 0]->lo; }
+    p.S1 = S1; p.S2 = S2; p.heads = heads; p.npad = npad; p.ntok_a = ntok_a; p.ntok_b = ntok_b;
+    p.pos = pos; p.tab = h->rope_tab; p.rng = h->range;
+    const int64_t total = ((int64_t)S1 * (ntok_a + 1) + (int64_t)S2 * (ntok_b + 1)) * heads * 4;
+    const dim3 grid((unsigned)((total + 255) / 256), nbuf);
+    if (split) hipLaunchKernelGGL(rope_tokens_kernel<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(rope_tokens_kernel<false>, grid, dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// ... inside a decoder call: nothing unless the call carries caller positions (sta_decode_tokens)
+static int rope_tokens(sta_handle* h, const Planes* const* bufs, int nbuf, int S1, int S2, int heads, int npad, int ntok_a, int ntok_b, hipStream_t st) {
+    if (h->dry || !h->rope_foreign) return 0;
+    return rope_tokens_launch(h, bufs, nbuf, S1, S2, heads, npad, ntok_a, ntok_b, h->rope_pos, h->opt[3] == 1, st);
+}
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 

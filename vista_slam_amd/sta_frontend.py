@@ -301,7 +301,8 @@ class STAFrontend:
         g1, g2 = self._grid_from_pos(pos1, N1), self._grid_from_pos(pos2, N2)
         if g1[2] is not None or g2[2] is not None:
             raise NotImplementedError("decode_stereo_mixed serves patch-grid positions only: foreign positions (a window of a larger "
-                                      "grid, a permuted order) are served for equal token counts by _decode_stereo")
+                                      "grid, a permuted order) are served for equal token counts by _decode_stereo and for any "
+                                      "token counts by decode_stereo_tokens")
         L = self.cfg.dec_depth + 1
         want = range(L) if layers is None else layers
         D = self.cfg.dec_embed_dim
@@ -334,6 +335,105 @@ class STAFrontend:
             B, _c, H, W_ = im.shape
             toks = [feat] + [None if t is None else t[:, 1:, :] for t in dec]
             pts = self.head_pts(toks, [[H, W_]] * B)
+            pose = self.head_pose_s(dec[-1][:, 0, :])
+            res.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"], "relative_pose_conf": pose["conf"]})
+        return res[0], res[1]
+
+    def decode_stereo_tokens(self, feat1: torch.Tensor, feat2: torch.Tensor, pos1: torch.Tensor, pos2: torch.Tensor,
+                             layers: Sequence[int] | None = None):
+        """`_decode_stereo` on TOKEN SUBSETS: feat1 [B, N1, E] with positions pos1 [B, N1, 2], feat2 [B, N2, E] with pos2
+        [B, N2, 2] - any token counts (down to 1, equal or not) with any integer (y, x) positions >= -1, each batch entry its own:
+        a rectangular window of one view against the whole other view, a pruned token set (see `window_tokens`, `select_tokens`).
+        Returns two lists of dec_depth+1 tensors [B, N1+1, D] / [B, N2+1, D] like the reference's module code returns for such
+        inputs (every attention rotates q / k by the positions it is handed, sta_blocks.py:134-137,196-199).  Always takes the
+        sta_decode_tokens route, also for inputs the other entries serve, so the routes can be compared."""
+        feat1 = self._f32(feat1).contiguous()
+        feat2 = self._f32(feat2).contiguous()
+        assert feat1.dim() == 3 and feat2.dim() == 3, "features are [B, N, E]"
+        B, N1, E = feat1.shape
+        N2 = feat2.shape[1]
+        assert feat2.shape[0] == B and feat2.shape[2] == E and E == self.cfg.enc_embed_dim, \
+            f"both views need the same batch and feature width (got {tuple(feat1.shape)} and {tuple(feat2.shape)})"
+        assert N1 >= 1 and N2 >= 1, "every side needs at least one token"
+        assert pos1.shape[0] == B and pos2.shape[0] == B, "one positions row per batch entry"
+        g1, g2 = self._grid_from_pos(pos1, N1), self._grid_from_pos(pos2, N2)
+        pos_max = max(g[2] if g[2] is not None else max(g[0], g[1]) - 1 for g in (g1, g2))
+        q1 = pos1.to(self.device, torch.int64).contiguous()
+        q2 = pos2.to(self.device, torch.int64).contiguous()
+        L = self.cfg.dec_depth + 1
+        want = range(L) if layers is None else layers
+        D = self.cfg.dec_embed_dim
+        out1: List[torch.Tensor | None] = [None] * L
+        out2: List[torch.Tensor | None] = [None] * L
+        p1 = (C.c_void_p * L)()
+        p2 = (C.c_void_p * L)()
+        for i in want:
+            out1[i] = torch.empty(B, N1 + 1, D, device=self.device, dtype=torch.float32)
+            out2[i] = torch.empty(B, N2 + 1, D, device=self.device, dtype=torch.float32)
+            p1[i] = out1[i].data_ptr()
+            p2[i] = out2[i].data_ptr()
+        _lib.check(self.lib.sta_decode_tokens(self._h, feat1.data_ptr(), feat2.data_ptr(), q1.data_ptr(), q2.data_ptr(),
+                                              B, N1, N2, pos_max, p1, p2, self._stream()))
+        return out1, out2
+
+    @staticmethod
+    def select_tokens(feat: torch.Tensor, pos: torch.Tensor, index):
+        """Gather a token subset: feat [B, N, E], pos [B, N, 2], index [K] (the same tokens of every batch entry) or [B, K] ->
+        (feat [B, K, E], pos [B, K, 2]) in the order of `index` - the inputs of `decode_stereo_tokens`."""
+        index = torch.as_tensor(index, dtype=torch.int64, device=feat.device)
+        B, N, E = feat.shape
+        assert tuple(pos.shape) == (B, N, 2), f"positions must be [{B}, {N}, 2] (got {tuple(pos.shape)})"
+        if index.dim() == 1:
+            index = index[None].expand(B, -1)
+        assert index.dim() == 2 and index.shape[0] == B and index.shape[1] >= 1, f"index must be [K] or [{B}, K] (got {tuple(index.shape)})"
+        assert int(index.min()) >= 0 and int(index.max()) < N, "token index out of range"
+        f = torch.gather(feat, 1, index[:, :, None].expand(-1, -1, E))
+        p = torch.gather(pos.to(feat.device), 1, index[:, :, None].expand(-1, -1, 2))
+        return f.contiguous(), p.contiguous()
+
+    @staticmethod
+    def window_tokens(feat: torch.Tensor, pos: torch.Tensor, grid, window):
+        """The tokens of a rectangular window of an encoded frame, row-major: feat [B, hp*wp, E], pos [B, hp*wp, 2] on the patch
+        grid `grid` = (hp, wp); `window` = (y0, x0, h, w) in patches, one tuple for all batch entries or one per entry (all of one
+        size h x w).  -> (feat [B, h*w, E], pos [B, h*w, 2])."""
+        hp, wp = int(grid[0]), int(grid[1])
+        B = feat.shape[0]
+        assert feat.shape[1] == hp * wp, f"{feat.shape[1]} tokens are not a {hp} x {wp} grid"
+        wins = [tuple(int(v) for v in window)] * B if not isinstance(window[0], (tuple, list)) else [tuple(int(v) for v in w) for w in window]
+        assert len(wins) == B and len({w[2:] for w in wins}) == 1, "one window per batch entry, all of one size"
+        rows = []
+        for y0, x0, h, w in wins:
+            assert h >= 1 and w >= 1 and 0 <= y0 and y0 + h <= hp and 0 <= x0 and x0 + w <= wp, f"window {(y0, x0, h, w)} leaves the {hp} x {wp} grid"
+            rows.append(((torch.arange(y0, y0 + h)[:, None] * wp) + torch.arange(x0, x0 + w)[None, :]).reshape(-1))
+        return STAFrontend.select_tokens(feat, pos, torch.stack(rows))
+
+    def forward_pair_window(self, img_a: torch.Tensor, img_b: torch.Tensor, window_a=None, window_b=None):
+        """`forward_pair` with one or both views restricted to a rectangular window of patches (a region of interest, the
+        overlapping part of a loop candidate): both frames [B,3,Ha,Wa] / [B,3,Hb,Wb] are encoded WHOLE, `window_a` / `window_b`
+        = (y0, x0, h, w) in patches (or one per batch entry; None = the whole frame) select the tokens that enter the decoder
+        (`decode_stereo_tokens`, with their true grid positions), and both heads run per side at that side's token shape
+        (16 h, 16 w).  Returns (main, support) dicts like `forward_pair_mixed`.  A window's outputs are what the reference computes
+        for those tokens: the decoder attends to the selected tokens only and the DPT head sees the window as an image of its own,
+        so they are NOT a crop of the full-frame outputs."""
+        img_a, img_b = self._f32(img_a).contiguous(), self._f32(img_b).contiguous()
+        assert img_a.shape[0] == img_b.shape[0], "both views need the same batch"
+        hooks = self.cfg.hooks
+        layers = sorted({hk - 1 for hk in hooks[1:]})
+        sides = []
+        for im, win in ((img_a, window_a), (img_b, window_b)):
+            B, _c, H, W_ = im.shape
+            feat, pos = self._encode_image(im, None, normalize=False)
+            shape = (H, W_)
+            if win is not None:
+                feat, pos = self.window_tokens(feat, pos, (H // 16, W_ // 16), win)
+                w0 = win if not isinstance(win[0], (tuple, list)) else win[0]
+                shape = (16 * int(w0[2]), 16 * int(w0[3]))
+            sides.append((feat, pos, shape))
+        d1, d2 = self.decode_stereo_tokens(sides[0][0], sides[1][0], sides[0][1], sides[1][1], layers=layers)
+        res = []
+        for (feat, _pos, (H, W_)), dec in zip(sides, (d1, d2)):
+            toks = [feat] + [None if t is None else t[:, 1:, :] for t in dec]
+            pts = self.head_pts(toks, [[H, W_]] * feat.shape[0])
             pose = self.head_pose_s(dec[-1][:, 0, :])
             res.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"], "relative_pose_conf": pose["conf"]})
         return res[0], res[1]
