@@ -8,7 +8,7 @@
  *   sta_create / sta_load_tensor / sta_finalize_weights
  *        <- STA() + load_state_dict(ckpt['model'], strict=True) + .to(device).eval()
  *           (vista_slam/slam.py:95-106).  Tensor names == reference state_dict keys.
- *   sta_encode        <- _encode_image(image, true_shape, normalize=False)
+ *   sta_encode        <- _encode_image(image, true_shape, normalize=False)   (sta_encode_tokens: on a token subset)
  *                        (sta_model.py:163-174, called from slam.py:144)
  *   sta_decode        <- _decode_stereo(feat1, feat2, pos1, pos2)   (positions = the patch grid; sta_decode_pos: any positions)
  *                        (sta_model.py:177-244, called from slam.py:162; N1 != N2 tokens: sta_decode_mixed on two patch
@@ -142,7 +142,7 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
- * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts),
+ * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_encode_tokens[_u8hwc] (a plan per token count),
  * sta_view_consistency (pair matrices per view count and window),
  * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
  * sta_ray_depth (one K^-1 per view). */
@@ -199,6 +199,21 @@ STA_API int sta_finalize_weights(sta_handle* h);
 /* img_dev [B,3,H,W] -> feat_dev [B, N, enc_dim], N = (H/16)*(W/16); no final norm. */
 STA_API int sta_encode(sta_handle* h, const float* img_dev, int B, int H, int W,
                float* feat_dev, void* stream);
+
+/* _encode_image(normalize=False) on a TOKEN SUBSET: the encoder counterpart of sta_decode_tokens.  Only the N selected patches of
+ * every image are read, embedded and run through the encoder blocks, attending to each other only - what the reference's module code
+ * computes for them (patch_embed, gather, then every Block with the gathered positions: sta_model.py:163-174; Block / XFormer_Attention
+ * take any token count and rotate q / k by the positions they are handed, sta_blocks.py:129-148,166-169).  It is NOT a slice of
+ * sta_encode's output: the tokens left out are not attended to.  img_dev [B,3,H,W] fp32; pos device int64 [B, N, 2] of (y, x) in
+ * [0, H/16) x [0, W/16), every batch entry its own, any order, repeats allowed: a position names both the patch that is gathered and
+ * the RoPE position of the token.  Values outside the grid are clamped into it (y and x separately; the shim refuses them before the
+ * call).  feat_dev [B, N, enc_dim], no final norm, exactly as sta_encode.  Implementation: a gather driven by the positions table,
+ * sta_encode's GEMM chain on B*N rows with the identity table in the QKV epilogues, and one launch per layer that rotates the Q and K
+ * buffers from the table.  Like sta_decode_mixed / sta_decode_tokens the call runs on one lane and is NOT covered by sta_reserve: the
+ * first call of a shape allocates.  Stage and kernel timing see it as they see sta_encode.  Returns -1 with a message for null
+ * pointers, N < 1, H / W not multiples of 16, or 2^31 or more rows. */
+STA_API int sta_encode_tokens(sta_handle* h, const float* img_dev, const int64_t* pos, int B, int H, int W, int N,
+                      float* feat_dev, void* stream);
 
 /* enc_norm (the encoder's final LayerNorm) on `rows` token rows of enc_dim floats: what
  * _encode_image(normalize=True) adds after the blocks (sta_model.py:172-173).  The forward / SLAM paths call
@@ -271,6 +286,10 @@ STA_API int sta_forward_pair(sta_handle* h, const float* img_a, const float* img
  * (vista_slam/utils/image.py:13; datasets/slam_images_only.py:19,30) is fused into the patch gather;
  * results are bit-identical to sta_encode / sta_forward_pair on the normalised fp32 NCHW tensor. */
 STA_API int sta_encode_u8hwc(sta_handle* h, const uint8_t* img_dev, int B, int H, int W, float* feat_dev, void* stream);
+/* sta_encode_tokens on camera-format input [B,H,W,3] uint8 (16-byte aligned) with the fused ImgNorm of sta_encode_u8hwc: bit-identical
+ * to sta_encode_tokens on the normalised fp32 NCHW tensor. */
+STA_API int sta_encode_tokens_u8hwc(sta_handle* h, const uint8_t* img_dev, const int64_t* pos, int B, int H, int W, int N,
+                            float* feat_dev, void* stream);
 STA_API int sta_forward_pair_u8hwc(sta_handle* h, const uint8_t* img_a, const uint8_t* img_b, int B, int H, int W,
                            float* const pts[2], float* const conf[2],
                            float* const pose[2], float* const pose_conf[2], void* stream);

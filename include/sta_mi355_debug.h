@@ -122,6 +122,15 @@ STA_API int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qblock
 STA_API int sta_debug_rope_tokens(sta_handle* h, float* const* bufs, int nbuf, int S1, int S2, int heads, int ntok_a, int ntok_b,
                                   const int* pos_i32, int pos_max, int which, void* stream);
 
+/* The rotation step of sta_encode_tokens alone: the encoder's Q / K layout has NO pose row.  bufs[b] (nbuf 1..2): fp32
+ * [S*heads + 1][npad][64], npad = roundup(ntok, 64) - the S*heads blocks of the buffer and ONE guard block behind them; every row
+ * (the guard's too) is split to fp16 planes inside, the buffer is rotated IN PLACE and everything is returned as hi + lo.  pos_i32:
+ * device int32 [S*ntok*2] of (y, x) in [0, pos_max].  pose = 0: the launch of sta_encode_tokens (exactly ntok rows per (sequence,
+ * head)); pose = 1: the decoder's pose-row form of the same kernel on the same buffers (ntok + 1 rows: with ntok a multiple of 64 it
+ * writes row 0 of the next head and of the guard). */
+STA_API int sta_debug_rope_enc_tokens(sta_handle* h, float* const* bufs, int nbuf, int S, int heads, int ntok, const int* pos_i32,
+                                      int pos_max, int pose, void* stream);
+
 /* The same record for the handle's LAST attention launch. */
 STA_API int sta_debug_last_attn_plan(sta_handle* h, int* out);
 

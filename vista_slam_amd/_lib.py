@@ -57,6 +57,8 @@ SIGNATURES = {
     "sta_forward_pair": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                               C.POINTER(_vp), _vp]),
     "sta_encode_u8hwc": (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
+    "sta_encode_tokens": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _fp, _vp]),
+    "sta_encode_tokens_u8hwc": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _fp, _vp]),
     "sta_encoder_norm": (_i, [_vp, _fp, C.c_int64, _fp, _vp]),
     "sta_forward_pair_u8hwc": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                     C.POINTER(_vp), _vp]),
@@ -113,6 +115,7 @@ TEST_SIGNATURES = {
     "sta_debug_last_attn_mixed_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_attn_mixed_block_map": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_rope_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "sta_debug_rope_enc_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sta_debug_attn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_last_attn_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_attn_block_map": (_i, [_i, C.POINTER(_i)]),

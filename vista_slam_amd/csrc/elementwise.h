@@ -268,6 +268,84 @@ __global__ void patch_gather_u8hwc_kernel(const uint8_t* img, int n, int H, int 
     }
 }
 
+// sta_encode_tokens: the positions table of one side: pos [n = B*N*2] int64 (y, x) -> int32, y clamped to [0, hp - 1] and x to
+// [0, wp - 1] (the gather and the rotation read the SAME clamped value: a position names the patch and the RoPE position); the tail of
+// the grid fills the identity cos / sin table of the call's QKV epilogues, as rope_tokens_table_kernel does.
+__global__ __launch_bounds__(256) void enc_tokens_table_kernel(const int64_t* pos, int64_t n, int hp, int wp, int* out, float2* ident, int64_t n_ident) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const int64_t hi = (i & 1) ? wp - 1 : hp - 1;
+        int64_t v = pos[i];
+        v = v < 0 ? 0 : (v > hi ? hi : v);
+        out[i] = (int)v;
+    } else if (i - n < n_ident) ident[i - n] = make_float2(1.f, 0.f);
+}
+
+// sta_encode_tokens: patch_gather_kernel for a token SUBSET.  Token tok = b * N + t of the output is the patch at pos[tok] = (py, px)
+// of image b (int32 table [B][N][2], already inside the grid: enc_tokens_table_kernel); only the selected patches are read.  Same
+// thread decomposition, accesses and arithmetic as patch_gather_kernel: equal pixel values give equal planes.
+template <bool SPLIT>
+__global__ void patch_gather_tokens_kernel(const float* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng) {
+    const int64_t total = (int64_t)n * N * 48;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += step) {
+        int ck = (int)(i % 48); int64_t tok = i / 48;
+        int c = ck / 16, ky = ck % 16;
+        const int2 yx = *reinterpret_cast<const int2*>(pos + tok * 2);
+        const int py = yx.x, px = yx.y; const int b = (int)(tok / N);
+        const float* src = img + (((int64_t)b * 3 + c) * H + py * 16 + ky) * W + px * 16;
+        H8 h0, h1, l0, l1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float4 v = *reinterpret_cast<const float4*>(src + q * 4);
+            float y[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                f16 hh, ll;
+                if (SPLIT) split_f16(y[e], hh, ll, rng); else { hh = to_f16_sat(y[e], rng); ll = (f16)0; }
+                int k = q * 4 + e;
+                if (k < 8) { h0.e[k] = hh; l0.e[k] = ll; } else { h1.e[k - 8] = hh; l1.e[k - 8] = ll; }
+            }
+        }
+        const size_t o = blk_off<SPLIT>(tok, ck * 16, orows);
+        *reinterpret_cast<uint4*>(o_hi + o) = h0.u; *reinterpret_cast<uint4*>(o_hi + o + 8) = h1.u;
+        if (SPLIT) { *reinterpret_cast<uint4*>(o_hi + o + 32) = l0.u; *reinterpret_cast<uint4*>(o_hi + o + 40) = l1.u; }
+    }
+}
+
+// ... and patch_gather_u8hwc_kernel for a token subset: one thread = one (token, ky) row of 48 contiguous bytes, the ImgNorm fused
+// with the same operation order, so the result is bit-identical to patch_gather_tokens_kernel on the normalised fp32 NCHW image.
+template <bool SPLIT>
+__global__ void patch_gather_tokens_u8hwc_kernel(const uint8_t* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng) {
+    const int64_t total = (int64_t)n * N * 16;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (; i < total; i += step) {
+        const int ky = (int)(i % 16); const int64_t tok = i / 16;
+        const int2 yx = *reinterpret_cast<const int2*>(pos + tok * 2);
+        const int py = yx.x, px = yx.y; const int b = (int)(tok / N);
+        const uint8_t* src = img + (((int64_t)b * H + py * 16 + ky) * W + px * 16) * 3;   // 48 B, 16-B aligned (W % 16 == 0)
+        union { uint4 v[3]; uint8_t e[48]; } raw;
+        raw.v[0] = ldg16(src); raw.v[1] = ldg16(src + 16); raw.v[2] = ldg16(src + 32);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            H8 h0, h1, l0, l1;
+#pragma unroll
+            for (int kx = 0; kx < 16; ++kx) {
+                const float a = (float)raw.e[kx * 3 + c] / 255.0f;
+                const float v = (a - 0.5f) / 0.5f;
+                f16 hh, ll;
+                if (SPLIT) split_f16(v, hh, ll, rng); else { hh = to_f16_sat(v, rng); ll = (f16)0; }
+                if (kx < 8) { h0.e[kx] = hh; l0.e[kx] = ll; } else { h1.e[kx - 8] = hh; l1.e[kx - 8] = ll; }
+            }
+            const size_t o = blk_off<SPLIT>(tok, (c * 16 + ky) * 16, orows);
+            *reinterpret_cast<uint4*>(o_hi + o) = h0.u; *reinterpret_cast<uint4*>(o_hi + o + 8) = h1.u;
+            if (SPLIT) { *reinterpret_cast<uint4*>(o_hi + o + 32) = l0.u; *reinterpret_cast<uint4*>(o_hi + o + 40) = l1.u; }
+        }
+    }
+}
+
 // x[s, 0, :] = token  (pose token prepend, sta_model.py:206-213)
 __global__ void fill_pose_token_kernel(float* x, int S, int ntok, int D, const float* tok) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -352,23 +430,28 @@ struct RopeTokParams {
     int S1, S2, heads, npad, ntok_a, ntok_b;
     const int* pos; const float* tab; unsigned long long* rng;
 };
-template <bool SPLIT>
+// POSE = false (sta_encode_tokens): the encoder's buffers have NO pose row - [S][heads][npad][64] with npad = roundup(ntok, 64), so
+// with ntok a multiple of 64 row ntok of a (sequence, head) is row 0 of the next head, and for the last head of the last sequence it
+// lies past the end of the buffer: exactly ntok rows per (sequence, head) are rotated, every one from the table.  POSE = true is the
+// decoder's form (the same instructions as before the flag existed).
+template <bool SPLIT, bool POSE = true>
 __global__ __launch_bounds__(256) void rope_tokens_kernel(RopeTokParams p) {
+    constexpr int PR = POSE ? 1 : 0;                   // rows per (sequence, head): ntok + PR
     const int b = blockIdx.y;
     f16* hi = b == 0 ? p.hi[0] : (b == 1 ? p.hi[1] : p.hi[2]);
     f16* lo = b == 0 ? p.lo[0] : (b == 1 ? p.lo[1] : p.lo[2]);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t rows_a = (int64_t)p.S1 * p.heads * (p.ntok_a + 1), rows_b = (int64_t)p.S2 * p.heads * (p.ntok_b + 1);
+    const int64_t rows_a = (int64_t)p.S1 * p.heads * (p.ntok_a + PR), rows_b = (int64_t)p.S2 * p.heads * (p.ntok_b + PR);
     if (i >= (rows_a + rows_b) * 4) return;
     const int j = (int)(i & 3), xp = j >> 1, f0 = (j & 1) * 8;
     int64_t r = i >> 2;
     const bool gb = r >= rows_a;                       // second group
     if (gb) r -= rows_a;
     const int ntok = gb ? p.ntok_b : p.ntok_a;
-    const int t = (int)(r % (ntok + 1)); r /= ntok + 1;
+    const int t = (int)(r % (ntok + PR)); r /= ntok + PR;
     const int hd = (int)(r % p.heads), sl = (int)(r / p.heads);          // sl: the sequence inside its group
     const int* pos = p.pos + (gb ? (int64_t)p.S1 * p.ntok_a * 2 : 0);
-    const int ps = t < ntok ? pos[((int64_t)sl * ntok + t) * 2 + xp] : -1;
+    const int ps = (!POSE || t < ntok) ? pos[((int64_t)sl * ntok + t) * 2 + xp] : -1;
     const float4* tab = reinterpret_cast<const float4*>(p.tab + ((size_t)(ps + 1) * 16 + f0) * 2);
     const int s = sl + (gb ? p.S1 : 0);
     const int64_t o = (((int64_t)s * p.heads + hd) * p.npad + t) * 64 + xp * 32 + f0;

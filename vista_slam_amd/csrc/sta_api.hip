@@ -672,6 +672,41 @@ extern "C" int sta_encode_u8hwc(sta_handle* h, const uint8_t* img_dev, int B, in
     return plan_and_run(h, st, [&](Bump& ws) { return encode_impl(h, ws, imgs, true, 1, B, H, W, feat_dev, st); });
 }
 
+// _encode_image(normalize=False) on a TOKEN SUBSET (encode_tokens_impl): pos [B, N, 2] device int64 (y, x) names the patch that is
+// gathered AND the RoPE position of the token.  The positions become an int32 table in the workspace, clamped into the grid.
+static int encode_tokens_any(sta_handle* h, const void* img_dev, bool u8hwc, const int64_t* pos, int B, int H, int W, int N, float* feat_dev, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    CHK(check_ready(h, B, H, W));
+    REQUIRE(img_dev && pos && feat_dev, "null device pointer");
+    REQUIRE(N >= 1, "bad argument (N %d): a token subset has at least one token", N);
+    REQUIRE((int64_t)B * N < ((int64_t)1 << 31), "too many encoder rows (%lld)", (long long)((int64_t)B * N));
+    REQUIRE(!u8hwc || ((uintptr_t)img_dev & 15) == 0, "u8 HWC image must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int hp = H / 16, wp = W / 16;
+    CHK(ensure_rope(h, hp > wp ? hp : wp));
+    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
+    h->rope_foreign = true;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        const int64_t n = (int64_t)B * N * 2;
+        int* rp = (int*)ws.take(n * 4);
+        const int64_t n_ident = (int64_t)(N + 2) * 16;            // the grid form of the call is 1 x N: table rows 0 .. N + 1
+        float2* ident = (float2*)ws.take(n_ident * 8);
+        if (!h->dry) {
+            hipLaunchKernelGGL(enc_tokens_table_kernel, dim3((unsigned)((n + n_ident + 255) / 256)), dim3(256), 0, st, pos, n, hp, wp, rp, ident, n_ident);
+            HIPCHK(hipGetLastError());
+            h->rope_pos = rp; h->rope_ident = (const float*)ident;
+        }
+        return encode_tokens_impl(h, ws, img_dev, u8hwc, B, H, W, N, feat_dev, st);
+    });
+}
+extern "C" int sta_encode_tokens(sta_handle* h, const float* img_dev, const int64_t* pos, int B, int H, int W, int N, float* feat_dev, void* stream) {
+    return encode_tokens_any(h, img_dev, false, pos, B, H, W, N, feat_dev, stream);
+}
+extern "C" int sta_encode_tokens_u8hwc(sta_handle* h, const uint8_t* img_dev, const int64_t* pos, int B, int H, int W, int N, float* feat_dev, void* stream) {
+    return encode_tokens_any(h, img_dev, true, pos, B, H, W, N, feat_dev, stream);
+}
+
 extern "C" int sta_encoder_norm(sta_handle* h, const float* feat_dev, int64_t rows, float* out_dev, void* stream) {
     REQUIRE(h && h->finalized, "handle not ready");
     REQUIRE(feat_dev && out_dev && rows > 0 && rows < (int64_t)1 << 31, "bad argument");

@@ -307,6 +307,50 @@ extern "C" int sta_debug_rope_tokens(sta_handle* h, float* const* bufs, int nbuf
     return 0;
 }
 
+// The rotation step of sta_encode_tokens alone.  bufs: nbuf (<= 2) fp32 device buffers [S*heads + 1][npad][64], npad = roundup(ntok, 64)
+// with NO pose row: the encoder's Q / K layout plus ONE guard block of npad x 64 behind the last head of the last sequence.  Every row,
+// the guard's too, is split to planes, rotated in place and returned as hi + lo, so a row the kernel must not touch comes back as it
+// went in.  pos_i32: device int32 [S*ntok*2] (y, x) in [0, pos_max].  pose = 0: rope_tokens_kernel<., false>, the launch of
+// encode_tokens_impl; pose = 1: the decoder's pose-row form on the same buffers (ntok + 1 rows per (sequence, head): with ntok a
+// multiple of 64 it writes row 0 of the next head and the guard - what the flag exists to prevent).
+extern "C" int sta_debug_rope_enc_tokens(sta_handle* h, float* const* bufs, int nbuf, int S, int heads, int ntok, const int* pos_i32,
+                                         int pos_max, int pose, void* stream) {
+    REQUIRE(h && bufs && pos_i32 && nbuf >= 1 && nbuf <= 2 && S > 0 && heads > 0 && ntok > 0, "bad argument");
+    REQUIRE(pos_max >= 0 && pos_max < (1 << 20) && (pose == 0 || pose == 1), "bad argument (pos_max %d, pose %d)", pos_max, pose);
+    for (int b = 0; b < nbuf; ++b) REQUIRE(bufs[b], "null buffer %d", b);
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int npad = rup(ntok, 64);
+    const int64_t hsz = ((int64_t)S * heads + 1) * npad * 64;          // with the guard block
+    const int64_t n = (int64_t)S * ntok * 2;
+    CHK(ensure_rope(h, pos_max + 1));
+    CHK(ensure_ws(h, nbuf * hsz * 4 + n * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes pl[2]; const Planes* pp[2];
+    for (int b = 0; b < nbuf; ++b) { pl[b] = ws.planes(hsz, split); pp[b] = &pl[b]; }
+    int* pos = (int*)ws.take(n * 4);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    hipLaunchKernelGGL(rope_tokens_table_kernel<int>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                       pos_i32, pos_i32, n, (int64_t)0, pos_max, pos, (float2*)nullptr, (int64_t)0);
+    HIPCHK(hipGetLastError());
+    for (int b = 0; b < nbuf; ++b) CHK(run_rows_to_planes(h, bufs[b], (int64_t)npad * 64, S * heads + 1, npad, 64, pl[b], st, npad));
+    if (pose) {       // the decoder's form needs ntok + 1 <= npad of ITS layout; here the extra row is the next block's row 0 (inside the guarded allocation)
+        RopeTokParams p;
+        for (int b = 0; b < 3; ++b) { p.hi[b] = pl[b < nbuf ? b : 0].hi; p.lo[b] = pl[b < nbuf ? b : 0].lo; }
+        p.S1 = S; p.S2 = 0; p.heads = heads; p.npad = npad; p.ntok_a = ntok; p.ntok_b = 0;
+        p.pos = pos; p.tab = h->rope_tab; p.rng = h->range;
+        const dim3 grid((unsigned)(((int64_t)S * (ntok + 1) * heads * 4 + 255) / 256), nbuf);
+        if (split) hipLaunchKernelGGL(rope_tokens_kernel<true>, grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(rope_tokens_kernel<false>, grid, dim3(256), 0, st, p);
+        HIPCHK(hipGetLastError());
+    } else {
+        CHK(rope_tokens_launch(h, pp, nbuf, S, 0, heads, npad, ntok, 0, pos, false, st, false));
+    }
+    for (int b = 0; b < nbuf; ++b) CHK(dbg_planes_to_f32(h, pl[b], npad, S * heads + 1, npad, 64, bufs[b], st));
+    return 0;
+}
+
 // A/B switches of the product's round-4 choices (tools/ab_option.py, ab_slam.py, ab_replay.py; 0 everywhere = product behaviour):
 //   1 = 1: small-grid K slices by the old rule ceil(256 / tiles)          2 = 1: small-grid GEMMs always on 4 waves (> 1: the lone-grid limit)
 //   4 = 1: debug GEMM entry points in the f16mx arithmetic                5 = 1: attention without the 4-stage prefetch schedule

@@ -46,6 +46,53 @@ static int encode_impl(sta_handle* h, Bump& ws, const void* const* imgs, bool u8
     return 0;
 }
 
+// The encoder on a TOKEN SUBSET (sta_encode_tokens): N tokens per image, token t of image b = the patch at pos[b][t] = (y, x), which is
+// also its RoPE position - the reference's module code on the gathered patch embeddings (patch_embed, then every Block with the
+// gathered positions: sta_model.py:163-174, sta_blocks.py:129-148,166-169).  encode_impl with M = B*N rows: the gather reads the
+// selected patches only, every QKV epilogue sees the grid 1 x N and rotates by the identity table (h->rope_foreign), one
+// rope_tokens_kernel<., false> launch per layer rotates Q and K from the positions table, attention runs with nq = nk = N.
+// h->rope_pos: the int32 table [B][N][2] inside the grid (enc_tokens_table_kernel).
+static int encode_tokens_impl(sta_handle* h, Bump& ws, const void* img, bool u8hwc, int B, int H, int W, int N, float* feat, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, Hh = c.enc_num_heads;
+    const int M = B * N, npad = rup(N, 64);
+    Planes patches = ws.act(M, 768, split);
+    Planes lnp = ws.act(M, E, split);
+    Planes ao = ws.act(M, E, split);
+    Planes f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
+    f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);
+    QKVOut qkv; qkv.npad = npad;
+    int64_t hsz = (int64_t)B * Hh * npad * 64;
+    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split); qkv.vt = ws.planes(hsz, split);
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
+    { const Planes* z[1] = {&qkv.vt}; CHK(zero_planes(z, 1, hsz, split, st)); }
+    {
+        const int per = u8hwc ? 16 : 48;
+        const int blocks = (int)(((int64_t)M * per + 255) / 256);
+        if (u8hwc) {
+            if (split) hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<true>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
+            else hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<false>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
+        } else if (split) hipLaunchKernelGGL(patch_gather_tokens_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
+        else hipLaunchKernelGGL(patch_gather_tokens_kernel<false>, dim3(blocks), dim3(256), 0, st, (const float*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
+        HIPCHK(hipGetLastError());
+    }
+    CHK(gemm_f32(h, patches, h->patch, M, feat, E, nullptr, st));
+    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, lnp, nullptr, nullptr, nullptr, st));
+    for (int i = 0; i < c.enc_depth; ++i) {
+        const EncBlk& b = h->enc[i];
+        CHK(gemm_qkv(h, lnp, b.qkv, M, E, E, E, qkv, N, Hh, N, 0, st));          // the grid 1 x N, identity table
+        CHK(rope_enc_tokens(h, qkv.q, qkv.k, B, Hh, npad, N, st));
+        CHK(run_attn(h, qkv, ao, E, B, Hh, N, N, 0, st));
+        CHK(gemm_resid_ln(h, ao, b.proj, M, feat, E, &b.n2, &lnp, nullptr, nullptr, st));
+        CHK(gemm_f16(h, lnp, b.fc1, M, f1, ACT_GELU, st, f1.mx));
+        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &lnp, nullptr, nullptr, st));
+        else CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ decoder
 // Row order of the decoder's residual stream x (fp32, [2B*N + 2B, D]) and of every plane buffer derived from it:
 //     rows [0, 2B*N)        patch tokens, sequence-major (sequence s = side * B + b, token t: row s*N + t)

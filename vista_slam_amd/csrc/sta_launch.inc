@@ -721,9 +721,12 @@ static int rope_fix(sta_handle* h, const Planes& qk, int S, int heads, int npad,
 // the table slice pos[0, S1*ntok_a*2), sequences [S1, S1 + S2) with ntok_b tokens and the slice behind it: ONE launch of
 // rope_tokens_kernel.  per_buffer (experiment switch 3 / sta_debug_rope_tokens which = 1): the same rotation as 2 * nbuf launches of
 // rope_planes_kernel, one per buffer and side - what the entry would cost on the existing kernel (A/B only).
+// pose = false (sta_encode_tokens, rope_enc_tokens): buffers without a pose row - ntok rows per (sequence, head), see rope_tokens_kernel.
 static int rope_tokens_launch(sta_handle* h, const Planes* const* bufs, int nbuf, int S1, int S2, int heads, int npad, int ntok_a, int ntok_b,
-                              const int* pos, bool per_buffer, hipStream_t st) {
+                              const int* pos, bool per_buffer, hipStream_t st, bool pose = true) {
     REQUIRE(nbuf >= 1 && nbuf <= 3 && pos && h->rope_tab, "internal: rope_tokens_launch arguments");
+    REQUIRE(pose || !per_buffer, "internal: the per-buffer rotation has the pose-row form only");
+    REQUIRE(std::max(S1 > 0 ? ntok_a : 0, S2 > 0 ? ntok_b : 0) + (pose ? 1 : 0) <= npad, "internal: rope_tokens_launch rows exceed npad");
     const bool split = bufs[0]->lo != nullptr;
     if (per_buffer) {
         for (int b = 0; b < nbuf; ++b)
@@ -742,9 +745,13 @@ static int rope_tokens_launch(sta_handle* h, const Planes* const* bufs, int nbuf
     for (int b = 0; b < 3; ++b) { p.hi[b] = bufs[b < nbuf ? b : 0]->hi; p.lo[b] = bufs[b < nbuf ? b : 0]->lo; }
     p.S1 = S1; p.S2 = S2; p.heads = heads; p.npad = npad; p.ntok_a = ntok_a; p.ntok_b = ntok_b;
     p.pos = pos; p.tab = h->rope_tab; p.rng = h->range;
-    const int64_t total = ((int64_t)S1 * (ntok_a + 1) + (int64_t)S2 * (ntok_b + 1)) * heads * 4;
+    const int pr = pose ? 1 : 0;
+    const int64_t total = ((int64_t)S1 * (ntok_a + pr) + (int64_t)S2 * (ntok_b + pr)) * heads * 4;
     const dim3 grid((unsigned)((total + 255) / 256), nbuf);
-    if (split) hipLaunchKernelGGL(rope_tokens_kernel<true>, grid, dim3(256), 0, st, p);
+    if (!pose) {
+        if (split) hipLaunchKernelGGL((rope_tokens_kernel<true, false>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((rope_tokens_kernel<false, false>), grid, dim3(256), 0, st, p);
+    } else if (split) hipLaunchKernelGGL(rope_tokens_kernel<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(rope_tokens_kernel<false>, grid, dim3(256), 0, st, p);
     HIPCHK(hipGetLastError());
     return 0;
@@ -753,6 +760,15 @@ static int rope_tokens_launch(sta_handle* h, const Planes* const* bufs, int nbuf
 static int rope_tokens(sta_handle* h, const Planes* const* bufs, int nbuf, int S1, int S2, int heads, int npad, int ntok_a, int ntok_b, hipStream_t st) {
     if (h->dry || !h->rope_foreign) return 0;
     return rope_tokens_launch(h, bufs, nbuf, S1, S2, heads, npad, ntok_a, ntok_b, h->rope_pos, h->opt[3] == 1, st);
+}
+
+// sta_encode_tokens: the encoder's Q and K buffers [S][heads][npad][64] (npad = roundup(ntok, 64), no pose row) by the call's
+// positions table: one launch per layer (blockIdx.y = buffer)
+static int rope_enc_tokens(sta_handle* h, const Planes& q, const Planes& k, int S, int heads, int npad, int ntok, hipStream_t st) {
+    if (h->dry) return 0;
+    REQUIRE(h->rope_foreign && h->rope_pos, "internal: rope_enc_tokens outside sta_encode_tokens");
+    const Planes* rot[2] = {&q, &k};
+    return rope_tokens_launch(h, rot, 2, S, 0, heads, npad, ntok, 0, h->rope_pos, false, st, false);
 }
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }

@@ -399,22 +399,34 @@ class STAFrontend:
         hp, wp = int(grid[0]), int(grid[1])
         B = feat.shape[0]
         assert feat.shape[1] == hp * wp, f"{feat.shape[1]} tokens are not a {hp} x {wp} grid"
+        return STAFrontend.select_tokens(feat, pos, STAFrontend.window_index((hp, wp), window, B))
+
+    @staticmethod
+    def window_index(grid, window, B: int) -> torch.Tensor:
+        """Row-major token indices [B, h*w] (int64, CPU) of a rectangular window of the patch grid `grid` = (hp, wp); `window` as in
+        `window_tokens` - the `index` argument of `encode_tokens`."""
+        hp, wp = int(grid[0]), int(grid[1])
         wins = [tuple(int(v) for v in window)] * B if not isinstance(window[0], (tuple, list)) else [tuple(int(v) for v in w) for w in window]
         assert len(wins) == B and len({w[2:] for w in wins}) == 1, "one window per batch entry, all of one size"
         rows = []
         for y0, x0, h, w in wins:
             assert h >= 1 and w >= 1 and 0 <= y0 and y0 + h <= hp and 0 <= x0 and x0 + w <= wp, f"window {(y0, x0, h, w)} leaves the {hp} x {wp} grid"
             rows.append(((torch.arange(y0, y0 + h)[:, None] * wp) + torch.arange(x0, x0 + w)[None, :]).reshape(-1))
-        return STAFrontend.select_tokens(feat, pos, torch.stack(rows))
+        return torch.stack(rows)
 
-    def forward_pair_window(self, img_a: torch.Tensor, img_b: torch.Tensor, window_a=None, window_b=None):
+    def forward_pair_window(self, img_a: torch.Tensor, img_b: torch.Tensor, window_a=None, window_b=None, encode: str = "frame"):
         """`forward_pair` with one or both views restricted to a rectangular window of patches (a region of interest, the
         overlapping part of a loop candidate): both frames [B,3,Ha,Wa] / [B,3,Hb,Wb] are encoded WHOLE, `window_a` / `window_b`
         = (y0, x0, h, w) in patches (or one per batch entry; None = the whole frame) select the tokens that enter the decoder
         (`decode_stereo_tokens`, with their true grid positions), and both heads run per side at that side's token shape
         (16 h, 16 w).  Returns (main, support) dicts like `forward_pair_mixed`.  A window's outputs are what the reference computes
         for those tokens: the decoder attends to the selected tokens only and the DPT head sees the window as an image of its own,
-        so they are NOT a crop of the full-frame outputs."""
+        so they are NOT a crop of the full-frame outputs.
+        `encode`: "frame" (default) as above - a window's tokens are a slice of the whole frame's encoding, they have attended to the
+        rest of the frame; "window": a windowed side is encoded from its window's patches alone (`encode_tokens`, the reference's
+        encoder on those tokens with their frame positions) and pays for those tokens only."""
+        if encode not in ("frame", "window"):
+            raise ValueError(f'encode must be "frame" or "window" (got {encode!r})')
         img_a, img_b = self._f32(img_a).contiguous(), self._f32(img_b).contiguous()
         assert img_a.shape[0] == img_b.shape[0], "both views need the same batch"
         hooks = self.cfg.hooks
@@ -422,10 +434,14 @@ class STAFrontend:
         sides = []
         for im, win in ((img_a, window_a), (img_b, window_b)):
             B, _c, H, W_ = im.shape
-            feat, pos = self._encode_image(im, None, normalize=False)
             shape = (H, W_)
+            if win is not None and encode == "window":
+                feat, pos = self.encode_tokens(im, index=self.window_index((H // 16, W_ // 16), win, B))
+            else:
+                feat, pos = self._encode_image(im, None, normalize=False)
             if win is not None:
-                feat, pos = self.window_tokens(feat, pos, (H // 16, W_ // 16), win)
+                if encode == "frame":
+                    feat, pos = self.window_tokens(feat, pos, (H // 16, W_ // 16), win)
                 w0 = win if not isinstance(win[0], (tuple, list)) else win[0]
                 shape = (16 * int(w0[2]), 16 * int(w0[3]))
             sides.append((feat, pos, shape))
@@ -530,6 +546,92 @@ class STAFrontend:
         feat = torch.empty(B, hp * wp, self.cfg.enc_embed_dim, device=self.device, dtype=torch.float32)
         _lib.check(self.lib.sta_encode_u8hwc(self._h, img.data_ptr(), B, H, W_, feat.data_ptr(), self._stream()))
         return feat, self._positions(B, hp, wp)
+
+    # ------------------------------------------------------------------ the encoder on token subsets
+    def _subset_positions(self, B: int, hp: int, wp: int, pos, index) -> torch.Tensor:
+        """The one of `pos` [B, N, 2] / `index` [B, N] that was given -> device int64 [B, N, 2] (y, x) positions, checked on the host."""
+        if (pos is None) == (index is None):
+            raise ValueError("give exactly one of pos ([B, N, 2] (y, x) patch positions) and index ([B, N] into the row-major patch grid)")
+        if index is not None:
+            index = torch.as_tensor(index)
+            assert index.dtype == torch.int64, f"index must be int64 (got {index.dtype})"
+            assert index.dim() == 2 and index.shape[0] == B and index.shape[1] >= 1, f"index must be [{B}, N >= 1] (got {tuple(index.shape)})"
+            lo, hi = int(index.min()), int(index.max())
+            if lo < 0 or hi >= hp * wp:
+                raise ValueError(f"token index outside the {hp} x {wp} patch grid (range [{lo}, {hi}])")
+            index = index.to(self.device)
+            return torch.stack([torch.div(index, wp, rounding_mode="floor"), index % wp], -1).contiguous()
+        pos = torch.as_tensor(pos)
+        assert pos.dtype == torch.int64, f"positions must be int64 (y, x) patch coordinates (got {pos.dtype})"
+        assert pos.dim() == 3 and pos.shape[0] == B and pos.shape[1] >= 1 and pos.shape[2] == 2, f"positions must be [{B}, N >= 1, 2] (got {tuple(pos.shape)})"
+        lo = pos.reshape(-1, 2).min(dim=0).values.tolist()
+        hi = pos.reshape(-1, 2).max(dim=0).values.tolist()
+        if lo[0] < 0 or lo[1] < 0 or hi[0] >= hp or hi[1] >= wp:
+            raise ValueError(f"positions outside the {hp} x {wp} patch grid (y in [{lo[0]}, {hi[0]}], x in [{lo[1]}, {hi[1]}])")
+        return pos.to(self.device).contiguous()
+
+    def encode_tokens(self, image: torch.Tensor, pos=None, index=None):
+        """`_encode_image(normalize=False)` on a TOKEN SUBSET: image [B,3,H,W]; exactly one of `pos` ([B, N, 2] int64 (y, x) patch
+        positions, CPU or device) and `index` ([B, N] int64 into the row-major patch grid) selects the N tokens of every batch entry -
+        each entry its own, any order, repeats allowed.  A position names the patch that is gathered AND the RoPE position of the
+        token.  -> (feat [B, N, E], pos [B, N, 2] on the device): what the reference's encoder computes for those tokens alone
+        (patch_embed, gather, every Block with the gathered positions) - NOT a slice of the frame's encoding; only B*N rows are
+        computed.  The positions keep the frame's coordinates and go on to `decode_stereo_tokens` as they are."""
+        image = self._f32(image).contiguous()
+        assert image.dim() == 4 and image.shape[1] == 3, f"image must be [B, 3, H, W] (got {tuple(image.shape)})"
+        B, _c, H, W_ = image.shape
+        self._check_hw(H, W_, self.patch_size)
+        q = self._subset_positions(B, H // 16, W_ // 16, pos, index)
+        N = q.shape[1]
+        feat = torch.empty(B, N, self.cfg.enc_embed_dim, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.sta_encode_tokens(self._h, image.data_ptr(), q.data_ptr(), B, H, W_, N, feat.data_ptr(), self._stream()))
+        return feat, q
+
+    def encode_tokens_u8hwc(self, image_u8: torch.Tensor, pos=None, index=None):
+        """`encode_tokens` on uint8 HWC camera frames [B,H,W,3] with the fused ImgNorm of `encode_u8hwc`: bit-identical to
+        `encode_tokens` on the normalised NCHW tensor."""
+        assert image_u8.dtype == torch.uint8 and image_u8.dim() == 4 and image_u8.shape[-1] == 3
+        img = image_u8.to(self.device).contiguous()
+        B, H, W_, _ = img.shape
+        self._check_hw(H, W_, self.patch_size)
+        q = self._subset_positions(B, H // 16, W_ // 16, pos, index)
+        N = q.shape[1]
+        feat = torch.empty(B, N, self.cfg.enc_embed_dim, device=self.device, dtype=torch.float32)
+        _lib.check(self.lib.sta_encode_tokens_u8hwc(self._h, img.data_ptr(), q.data_ptr(), B, H, W_, N, feat.data_ptr(), self._stream()))
+        return feat, q
+
+    @staticmethod
+    def _rectangle_of(pos: torch.Tensor):
+        """(h, w) when every batch entry of pos [B, N, 2] is a row-major h x w rectangle of patches (anywhere, all of one size), else None."""
+        p = pos.cpu()
+        B, N, _ = p.shape
+        h, w = int(p[0, -1, 0] - p[0, 0, 0]) + 1, int(p[0, -1, 1] - p[0, 0, 1]) + 1
+        if h < 1 or w < 1 or h * w != N:
+            return None
+        rect = torch.cartesian_prod(torch.arange(h), torch.arange(w)).view(1, N, 2)
+        return (h, w) if bool(torch.equal(p - p[:, :1, :], rect.expand(B, -1, -1))) else None
+
+    def forward_pair_tokens(self, img_a: torch.Tensor, img_b: torch.Tensor, pos_a: torch.Tensor, pos_b: torch.Tensor):
+        """`forward_pair` on token subsets of both views, encoder included: `encode_tokens` on each frame with its positions
+        ([B, Na, 2] / [B, Nb, 2]), `decode_stereo_tokens` on the two subsets, the pose head on both sides.  Returns (main, support)
+        dicts like `forward_pair_window`.  The DPT head runs at a side's token shape (16 h, 16 w) only where that side is a row-major
+        h x w rectangle of patches in every batch entry; any other side has None for pts3d_pred / conf."""
+        img_a, img_b = self._f32(img_a).contiguous(), self._f32(img_b).contiguous()
+        assert img_a.shape[0] == img_b.shape[0], "both views need the same batch"
+        hooks = self.cfg.hooks
+        layers = sorted({hk - 1 for hk in hooks[1:]})
+        sides = [self.encode_tokens(im, pos=p) for im, p in ((img_a, pos_a), (img_b, pos_b))]
+        d1, d2 = self.decode_stereo_tokens(sides[0][0], sides[1][0], sides[0][1], sides[1][1], layers=layers)
+        res = []
+        for (feat, pos), dec in zip(sides, (d1, d2)):
+            rect = self._rectangle_of(pos)
+            pts = {"pts3d": None, "conf": None}
+            if rect is not None:
+                toks = [feat] + [None if t is None else t[:, 1:, :] for t in dec]
+                pts = self.head_pts(toks, [[16 * rect[0], 16 * rect[1]]] * feat.shape[0])
+            pose = self.head_pose_s(dec[-1][:, 0, :])
+            res.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"], "relative_pose_conf": pose["conf"]})
+        return res[0], res[1]
 
     def forward_pair_u8hwc(self, img_a: torch.Tensor, img_b: torch.Tensor):
         """`forward_pair` on uint8 HWC frames [B,H,W,3]."""
