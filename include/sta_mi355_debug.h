@@ -34,7 +34,9 @@ STA_API int sta_debug_pick_family(int amode, int epi, long long M, int N, int K,
  * skinny tail blocks compute, and the K slices.  M_all: every row, tail rows included; precision: STA_PREC_*; mx: f16mx rows and
  * weights (what use_mx() decides); tail_hint: the decoder's pose-token rows (0: none); forced_variant: as sta_set_gemm_variant
  * (0..4, 8, 9).  out[8] = {family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks}; the main tiles cover rows
- * [0, M_all - m_tail).  Fails when the plan would name a kernel that does not exist. */
+ * [0, M_all - m_tail).  Fails when the plan would name a kernel that does not exist.  epi 5 below the small-grid predicate (where the
+ * product never launches that epilogue): the plan of gemm_resid_ln's launch there - the fp32 epilogue in place with the handle's
+ * slab, slab_ks > 1 when its K slices are left to resid_ln_kernel (N % 64 == 0, N <= 1024, forced_variant 0 or 9). */
 STA_API int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, int precision, int mx, int tail_hint, int forced_variant, int* out);
 
 /* The launch plan of a 3x3 convolution (pure host function: gemm_plan with the implicit-GEMM loader and the image geometry, so
@@ -179,6 +181,17 @@ STA_API int sta_debug_up2(sta_handle* h, const float* x, int n, int H, int W, in
 /* nn.LayerNorm(eps) rows; out32 = direct fp32 output, out_planes = value carried by the fp16 planes. */
 STA_API int sta_debug_layernorm(sta_handle* h, const float* x, const float* g, const float* b, int M, int C, float eps,
                         float* out32, float* out_planes, void* stream);
+
+/* The residual stream step of a transformer layer as the forward pass issues it (sta_launch.inc: gemm_resid_ln; sta_blocks.py:
+ * x = x + proj(...) followed by the next norm): x[M,N] += A[M,K] W[N,K]^T + bias IN PLACE, then up to two LayerNorm(eps) affine
+ * sets of the new x into fp16 planes.  g1 == NULL: only the add; g2 == NULL: one set (g2 only with g1).  Below the small-grid
+ * predicate the K slices go to the handle's own slab buffer and resid_ln_kernel sums them before it normalises; above it the
+ * in-place GEMM is followed by ln_kernel.  Which ran: sta_debug_last_gemm_plan (slab_ks > 1).  out1 / out2 (may be NULL): the
+ * values carried by the two plane sets, fp32 [M,N]; both sets are filled with 0xFF before the call, so a set that must not be
+ * written reads back as NaN.  N % 4 == 0, N <= 1024, K % 32 == 0. */
+STA_API int sta_debug_gemm_resid_ln(sta_handle* h, const float* A, const float* W, const float* bias, float* x, int M, int N, int K,
+                            const float* g1, const float* b1, const float* g2, const float* b2, float eps,
+                            float* out1, float* out2, void* stream);
 
 /* head.4 (1x1 128->4) + postprocess (postprocess.py:10-62) on [npix,128] features. */
 STA_API int sta_debug_head_final(sta_handle* h, const float* x, const float* w, const float* bias, int64_t npix,

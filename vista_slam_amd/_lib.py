@@ -133,6 +133,7 @@ TEST_SIGNATURES = {
     "sta_debug_convt": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_up2": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_debug_layernorm": (_i, [_vp, _fp, _fp, _fp, _i, _i, _f, _fp, _fp, _vp]),
+    "sta_debug_gemm_resid_ln": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp]),
     "sta_debug_head_final": (_i, [_vp, _fp, _fp, _fp, _i64, _fp, _fp, _vp]),
     "sta_debug_svd_orthogonalize": (_i, [_vp, _fp, _fp, _i, _vp]),
 }

@@ -68,33 +68,45 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
     const float* xr = p.x + (size_t)row * p.ldx;
     float4 v[4];
     LnAffine af[4];
-    float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int idx = (i * 64 + lane) * 4;
         if (idx < p.C) {
             v[i] = *reinterpret_cast<const float4*>(xr + idx);
             af[i] = ln_load_affine(p, idx);
+        }
+    }
+    // Everything is taken relative to a PIVOT, the row's first element (lane 0 always holds column 0): the mean is piv + m and is never
+    // rounded to one float.  x - mean with a mean rounded to fp32 is off by up to half an ulp of the MEAN on every element - rows
+    // 1e4 +- 1 came out 1e-4 .. 7e-4 off (not fp32 class), and a constant row whose sum C * x is not exact came out up to 3e-4
+    // away from the bias (tests/test_row_gpu.py).  x - piv is exact or rounds at the size of the SPREAD.
+    const float piv = __shfl(v[0].x, 0);
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        int idx = (i * 64 + lane) * 4;
+        if (idx < p.C) {
+            v[i].x -= piv; v[i].y -= piv; v[i].z -= piv; v[i].w -= piv;
             sum += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
     }
-    const float mean = wave_sum(sum) / (float)p.C;
+    const float m = wave_sum(sum) / (float)p.C;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int idx = (i * 64 + lane) * 4;
         if (idx < p.C) {
-            float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+            float a = v[i].x - m, b = v[i].y - m, c = v[i].z - m, d = v[i].w - m;
             sq += (a * a + b * b) + (c * c + d * d);
         }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(sq) / (float)p.C + p.eps);
-    if (lane == 0 && !(fabsf(mean) <= 3.0e38f && rstd <= 3.0e38f && rstd > 0.f)) atomicAdd(p.range, 1ull);   // non-finite row, or a variance that overflowed fp32 (rstd == 0: the row would silently become pure bias)
+    if (lane == 0 && !(fabsf(piv + m) <= 3.0e38f && rstd <= 3.0e38f && rstd > 0.f)) atomicAdd(p.range, 1ull);   // non-finite row, or a variance that overflowed fp32 (rstd == 0: the row would silently become pure bias)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         int idx = (i * 64 + lane) * 4;
         if (idx < p.C) {
-            float n[4] = {(v[i].x - mean) * rstd, (v[i].y - mean) * rstd, (v[i].z - mean) * rstd, (v[i].w - mean) * rstd};
+            float n[4] = {(v[i].x - m) * rstd, (v[i].y - m) * rstd, (v[i].z - m) * rstd, (v[i].w - m) * rstd};
             ln_store4<SPLIT>(p, row, idx, n, af[i]);
         }
     }
@@ -121,19 +133,24 @@ __global__ __launch_bounds__(256) void resid_ln_kernel(const LnParams p) {
     }
     if (!p.g1) return;
     __shared__ float red[2][4];
+    __shared__ float pivot;
+    if (threadIdx.x == 0) pivot = v.x;       // the row's first element (thread 0 always holds column 0): see ln_kernel
+    __syncthreads();
+    const float piv = pivot;
+    if (on) { v.x -= piv; v.y -= piv; v.z -= piv; v.w -= piv; }
     float sum = wave_sum((v.x + v.y) + (v.z + v.w));
     if (lane == 0) red[0][wave] = sum;
     __syncthreads();
-    const float mean = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)p.C;
+    const float m = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)p.C;
     float sq = 0.f;
-    if (on) { float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean; sq = (a * a + b * b) + (c * c + d * d); }
+    if (on) { float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m; sq = (a * a + b * b) + (c * c + d * d); }
     sq = wave_sum(sq);
     if (lane == 0) red[1][wave] = sq;
     __syncthreads();
     const float rstd = 1.0f / sqrtf(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)p.C + p.eps);
-    if (threadIdx.x == 0 && !(fabsf(mean) <= 3.0e38f && rstd <= 3.0e38f && rstd > 0.f)) atomicAdd(p.range, 1ull);   // non-finite row, or a variance that overflowed fp32 (rstd == 0: the row would silently become pure bias)
+    if (threadIdx.x == 0 && !(fabsf(piv + m) <= 3.0e38f && rstd <= 3.0e38f && rstd > 0.f)) atomicAdd(p.range, 1ull);   // non-finite row, or a variance that overflowed fp32 (rstd == 0: the row would silently become pure bias)
     if (on) {
-        float n[4] = {(v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd};
+        float n[4] = {(v.x - m) * rstd, (v.y - m) * rstd, (v.z - m) * rstd, (v.w - m) * rstd};
         ln_store4<SPLIT>(p, row, idx, n, af);
     }
 }
@@ -693,11 +710,23 @@ __device__ inline void nearest_rotation(const double M[3][3], double R[3][3]) {
     for (int k = 0; k < 3; ++k) { w0[k] = W[k][idx[0]]; w1[k] = W[k][idx[1]]; }
     for (int i = 0; i < 3; ++i) { l0[i] = 0; l1[i] = 0; for (int k = 0; k < 3; ++k) { l0[i] += M[i][k] * w0[k]; l1[i] += M[i][k] * w1[k]; } }
     double n0 = sqrt(l0[0] * l0[0] + l0[1] * l0[1] + l0[2] * l0[2]);
-    for (int i = 0; i < 3; ++i) l0[i] /= n0;
+    if (n0 > 0) { for (int i = 0; i < 3; ++i) l0[i] /= n0; }
+    else { l0[0] = 1; l0[1] = 0; l0[2] = 0; }                 // M == 0: every rotation is equally near; any unit vector starts the frame
+    const double nb1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
     double dp = l0[0] * l1[0] + l0[1] * l1[1] + l0[2] * l1[2];
     for (int i = 0; i < 3; ++i) l1[i] -= dp * l0[i];
     double n1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
-    for (int i = 0; i < 3; ++i) l1[i] /= n1;
+    if (n1 > 1e-8 * nb1) { for (int i = 0; i < 3; ++i) l1[i] /= n1; }
+    else {
+        // rank <= 1: M w1 is zero or parallel to l0, what the projection left is rounding noise (n1 == 0 gave a NaN pose).  The
+        // second left vector is then free - torch.svd's is arbitrary there too -: the unit vector orthogonal to l0 nearest to the
+        // axis l0 is furthest from (its norm before scaling is >= sqrt(2/3))
+        int k = 0;
+        for (int i = 1; i < 3; ++i) if (fabs(l0[i]) < fabs(l0[k])) k = i;
+        for (int i = 0; i < 3; ++i) l1[i] = (i == k ? 1.0 : 0.0) - l0[k] * l0[i];
+        n1 = sqrt(l1[0] * l1[0] + l1[1] * l1[1] + l1[2] * l1[2]);
+        for (int i = 0; i < 3; ++i) l1[i] /= n1;
+    }
     double l2[3] = {l0[1] * l1[2] - l0[2] * l1[1], l0[2] * l1[0] - l0[0] * l1[2], l0[0] * l1[1] - l0[1] * l1[0]};
     double w2[3] = {w0[1] * w1[2] - w0[2] * w1[1], w0[2] * w1[0] - w0[0] * w1[2], w0[0] * w1[1] - w0[1] * w1[0]};
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[i][j] = l0[i] * w0[j] + l1[i] * w1[j] + l2[i] * w2[j];

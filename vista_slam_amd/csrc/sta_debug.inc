@@ -507,6 +507,38 @@ extern "C" int sta_debug_layernorm(sta_handle* h, const float* x, const float* g
     return 0;
 }
 
+// The residual stream step of every transformer layer, exactly as the forward pass issues it (gemm_resid_ln): x[M,N] += A[M,K] W[N,K]^T
+// + bias IN PLACE, then the LayerNorm(s) of the new x into fp16 planes.  g1 == NULL: only the add (no planes are written); g2 == NULL:
+// one affine set.  Below the small-grid predicate the K slices go through the handle's own slab buffer and resid_ln_kernel sums them;
+// which path ran is read from sta_debug_last_gemm_plan (slab_ks > 1), not from here.  out1 / out2 (may be NULL): the values the two
+// plane sets carry, fp32 [M,N]; both plane sets are filled with 0xFF first, so a set the call must not write reads back as NaN.
+extern "C" int sta_debug_gemm_resid_ln(sta_handle* h, const float* A, const float* W, const float* bias, float* x, int M, int N, int K,
+                                       const float* g1, const float* b1, const float* g2, const float* b2, float eps,
+                                       float* out1, float* out2, void* stream) {
+    REQUIRE(h && A && W && bias && x && M > 0 && N > 0 && K > 0, "bad argument");
+    REQUIRE(N % 4 == 0 && N <= 1024 && K % GEMM_BK == 0, "bad shape (N %% 4 == 0, N <= 1024, K %% %d == 0)", GEMM_BK);
+    REQUIRE((g1 != nullptr) == (b1 != nullptr) && (g2 != nullptr) == (b2 != nullptr) && (g1 || !g2), "bad affine sets (g2 only with g1)");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    CHK(ensure_ws(h, ((int64_t)M * K + (int64_t)N * K + (int64_t)2 * M * rup(N, 32)) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes a = ws.act(M, K, split), o1 = ws.act(M, N, split), o2 = ws.act(M, N, split);
+    Lin L; CHK(dbg_make_lin(h, ws, W, bias, N, K, 0, N, K, 1, 1, L, st));
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    CHK(run_rows_to_planes(h, A, (int64_t)M * K, 1, M, K, a, st));
+    CHK(dbg_poison_act(o1, M, N, st));
+    CHK(dbg_poison_act(o2, M, N, st));
+    LNp la, lb; la.g = const_cast<float*>(g1); la.b = const_cast<float*>(b1); lb.g = const_cast<float*>(g2); lb.b = const_cast<float*>(b2);
+    float keep = h->cfg.ln_eps; h->cfg.ln_eps = eps;
+    int r = gemm_resid_ln(h, a, L, M, x, N, g1 ? &la : nullptr, g1 ? &o1 : nullptr, g2 ? &lb : nullptr, g2 ? &o2 : nullptr, st);
+    h->cfg.ln_eps = keep;
+    CHK(r);
+    if (out1) CHK(dbg_planes_to_f32(h, o1, 0, 1, M, N, out1, st));
+    if (out2) CHK(dbg_planes_to_f32(h, o2, 0, 1, M, N, out2, st));
+    return 0;
+}
+
 // final 1x1 conv (128->4) + postprocess on an NHWC fp32 feature map [npix,128]
 extern "C" int sta_debug_head_final(sta_handle* h, const float* x, const float* w, const float* bias, int64_t npix,
                                     float* pts, float* conf, void* stream) {

@@ -288,6 +288,12 @@ extern "C" int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, 
     REQUIRE(out && M_all > 0 && N > 0 && K > 0 && (amode == A_DENSE || amode == A_CONV3), "bad argument");
     REQUIRE(precision == STA_PREC_F16 || precision == STA_PREC_F16X3 || precision == STA_PREC_F16X3H || precision == STA_PREC_F16X3M, "bad precision");
     PlanQuery q{amode, epi, M_all, N, K, precision != STA_PREC_F16, mx != 0, tail_hint, forced_variant, 0, 0, 0, false, 0, 0, 0, 0};
+    // epi 5 (in-place residual) BELOW the small-grid predicate: the product never launches EPI_F32R there - the residual GEMMs of the
+    // forward go through gemm_resid_ln, which launches the fp32 epilogue in place with the context's slab (its condition, restated;
+    // tests/test_row_gpu.py holds the restatement to the last-plan record of real launches): slab_ks of THAT plan is reported
+    if (amode == A_DENSE && epi == EPI_F32R && small_grid_m(0, M_all, N) && N % 64 == 0 && N <= 1024 && (forced_variant == 0 || forced_variant == 9)) {
+        q.epi = EPI_F32; q.inplace = 1;
+    }
     GemmPlan g;
     CHK(gemm_plan(q, g));
     plan_out(g, out);
