@@ -12,7 +12,7 @@
  *                        (sta_model.py:163-174, called from slam.py:144)
  *   sta_decode        <- _decode_stereo(feat1, feat2, pos1, pos2)   (positions = the patch grid; sta_decode_pos: any positions)
  *                        (sta_model.py:177-244, called from slam.py:162; N1 != N2 tokens: sta_decode_mixed on two patch
- *                        grids, sta_decode_tokens on token subsets with any positions)
+ *                        grids, sta_decode_tokens on token subsets with any positions, sta_decode_varlen with one token count per batch entry)
  *   sta_head_pose     <- head_pose_s(tok[:,0,:])        (heads/pose_head.py:109-120, slam.py:165)
  *   sta_head_pts      <- head_pts(list14, true_shape)   (heads/dpt_head.py:34-66 +
  *                        heads/postprocess.py:10-62 + utils/misc.py:36-78, slam.py:179-180)
@@ -142,7 +142,7 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
- * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_encode_tokens[_u8hwc] (a plan per token count),
+ * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_decode_varlen (a plan per set of counts), sta_encode_tokens[_u8hwc] (a plan per token count),
  * sta_view_consistency (pair matrices per view count and window),
  * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
  * sta_ray_depth (one K^-1 per view). */
@@ -258,6 +258,25 @@ STA_API int sta_decode_pos(sta_handle* h, const float* feat1, const float* feat2
  * Returns -1 with a message for null pointers, N < 1, pos_max outside [0, 2^20) or 2^31 or more decoder rows. */
 STA_API int sta_decode_tokens(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
                       int B, int N1, int N2, int pos_max, float* const* out1, float* const* out2, void* stream);
+
+/* _decode_stereo on a batch whose ENTRIES have their own token counts: sta_decode_tokens with one (N1, N2) per entry - the pruned
+ * token set of every frame, the overlap window of every loop candidate, the edges of one keyframe in one call.  Batch entries of the
+ * reference's _decode_stereo never interact (sta_model.py:177-244, sta_blocks.py:129-148,188-208), so entry b is what the reference
+ * returns for that entry alone at B = 1; nothing is padded and no token attends to another entry's.
+ * n1 / n2: HOST arrays [B], entry b has n1[b] >= 1 tokens on side 1 and n2[b] >= 1 on side 2 (they size the launches and travel in
+ * the kernel arguments: the call copies nothing to the device for them and does not synchronise it).  feat1 [sum(n1), enc_dim] and
+ * pos1 [sum(n1), 2] (device int64 (y, x)) are packed entry-major; side 2 the same with n2.  Positions must lie in [-1, pos_max]
+ * (out-of-range values are clamped, as in sta_decode_tokens; the RoPE table grows to pos_max on first use).  out1[i] is packed
+ * [sum(n1) + B, dec_dim]: entry b occupies n1[b] + 1 consecutive rows, pose token first (the reference's order), starting at row
+ * sum(n1[0 .. b)) + b; out2[i] the same with n2; NULL skips a layer, the last index has dec_norm applied.  1 <= B <= 16.
+ * Implementation: rows are packed, so every row-wise step (LayerNorm, proj, cproj, the MLP, the residual epilogues) is one launch over
+ * all rows; the QKV GEMMs run once per (side, entry) with the epilogue of sta_decode_tokens; one kernel per layer and buffer set rotates
+ * Q / K from the packed positions table; attention is ONE launch for all 2B sequences, each with its own counts and schedule
+ * (attn_varlen_kernel).  Like sta_decode_mixed / sta_decode_tokens the call runs on one lane and is NOT covered by sta_reserve: the first
+ * call of a set of counts may allocate.  Returns -1 with a message for null pointers, a count below 1, B outside [1, 16], pos_max
+ * outside [0, 2^20) or 2^31 or more decoder rows. */
+STA_API int sta_decode_varlen(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
+                      const int* n1, const int* n2, int B, int pos_max, float* const* out1, float* const* out2, void* stream);
 
 /* tok: B rows of dec_dim floats, consecutive rows `tok_stride` floats apart.
  * pose [B,16] row-major 4x4, conf [B]. */

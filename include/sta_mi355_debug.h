@@ -115,6 +115,30 @@ STA_API int sta_debug_attn_mixed_plan(int S1, int S2, int heads, int nq_a, int n
 STA_API int sta_debug_last_attn_mixed_plan(sta_handle* h, int* out);
 STA_API int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qblocks_a, int qblocks_b, int* out);
 
+/* Per-sequence form of the decoder's attention (attention.h: attn_varlen_kernel; sta_decode_varlen): S <= 32 sequences, sequence s
+ * with nq[s] queries over nk[s] keys (HOST arrays).  q: sequence after sequence [heads, nq[s] + 1, 64]; k / v: [heads, nk[s] + 1, 64],
+ * pose token LAST.  k / v of a sequence are the keys it reads; the entry stores them at buffer sequence (s + kv_shift) % S.  out
+ * [sum(nq[s] + 1) + 64, heads*64]: per sequence its patch rows, then its pose row; the last 64 rows return a guard block that lies
+ * directly behind the output planes, every byte 0x3C on entry.  Poisons like sta_debug_attention_pose. */
+STA_API int sta_debug_attn_varlen(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads,
+                                  const int* nq, const int* nk, int kv_shift, float* out, void* stream);
+/* Its launch plan (pure host function; sta_launch.inc: attn_varlen_plan): out[7 + 11*S] = {S, LDS stages, LDS bytes, grid,
+ * query-block workgroups, pose blocks, output rows, then per sequence {pose mode, prefetch, pose blocks, query blocks per head,
+ * ntiles, nfull, tail stage, pose scratch bytes, first logical query-block id, first pose block, first output row}}; the record of
+ * the handle's last per-sequence launch; and the kernel's workgroup map: out[3*b + 0..2] = (sequence, head, query block) of
+ * query-block workgroup b. */
+STA_API int sta_debug_attn_varlen_plan(int S, int heads, const int* nq, const int* nk, int split, int no_prefetch, int* out);
+STA_API int sta_debug_last_attn_varlen_plan(sta_handle* h, int* out);
+STA_API int sta_debug_attn_varlen_block_map(int S, int heads, const int* nq, const int* nk, int* out);
+
+/* The rotation step of sta_decode_varlen alone (rope_varlen_kernel): n HOST array [S] of token counts.  bufs[b] (nbuf 1..3): fp32
+ * [S*heads + 1][npad][64], npad = roundup(max(n) + 1, 64) - the decoder's Q / K layout and ONE guard block behind it; every row (the
+ * guard's too) is split to fp16 planes inside, the buffer is rotated IN PLACE and everything is returned as hi + lo.  Token index n[s]
+ * of sequence s is its pose token (position -1), rows (n[s], npad) are not touched.  pos_i32: device int32 [sum(n)*2] of (y, x),
+ * packed, clamped to [-1, pos_max]. */
+STA_API int sta_debug_rope_varlen(sta_handle* h, float* const* bufs, int nbuf, int S, int heads, const int* n, const int* pos_i32,
+                                  int pos_max, void* stream);
+
 /* The rotation step of sta_decode_tokens alone: 2-D RoPE from a positions table on nbuf (1..3) head-major buffers for two groups
  * of sequences with different token counts.  bufs[b]: fp32 [S1 + S2][heads][npad][64], npad = roundup(max(ntok_a, ntok_b) + 1, 64);
  * every row is split to fp16 planes inside, rotated IN PLACE and returned as hi + lo.  Sequences [0, S1) hold ntok_a tokens,

@@ -52,6 +52,7 @@ SIGNATURES = {
     "sta_decode_mixed": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_decode_pos": (_i, [_vp, _fp, _fp, _vp, _vp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_decode_tokens": (_i, [_vp, _fp, _fp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    "sta_decode_varlen": (_i, [_vp, _fp, _fp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_head_pose": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp]),
     "sta_head_pts": (_i, [_vp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _i, _i, _i, _fp, _fp, _vp]),
     "sta_forward_pair": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
@@ -114,6 +115,11 @@ TEST_SIGNATURES = {
     "sta_debug_attn_mixed_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_last_attn_mixed_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_attn_mixed_block_map": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i)]),
+    "sta_debug_attn_varlen": (_i, [_vp, _fp, _fp, _fp, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _fp, _vp]),
+    "sta_debug_attn_varlen_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_i)]),
+    "sta_debug_last_attn_varlen_plan": (_i, [_vp, C.POINTER(_i)]),
+    "sta_debug_attn_varlen_block_map": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "sta_debug_rope_varlen": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, C.POINTER(_i), _vp, _i, _vp]),
     "sta_debug_rope_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sta_debug_rope_enc_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sta_debug_attn_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),

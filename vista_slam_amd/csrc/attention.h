@@ -52,6 +52,17 @@ struct AttnGroupB {
 };
 struct AttnMixedParams { AttnParams a; AttnGroupB b; };
 
+// One group PER SEQUENCE (attn_varlen_kernel; sta_decode_varlen: every batch entry has its own token counts).  The launch carries a
+// table with one entry per sequence, S <= ATT_MAX_SEQ, in the kernel arguments (uniform reads; nothing is copied to the device
+// ahead of the launch).  AttnParams::nq / nk / pose / prefetch are not read.  Entry s: nq queries over the nk keys of sequence
+// (s + kv_shift) % S, pose key at token index nk of the KEY sequence, pose query at token index nq of s; blk0 = its first logical
+// query-block id (its ids: blk0 + head * query blocks + query block), pose_blk0 = its first pose block (pose == 1 only: one per
+// head; an entry without pose blocks carries the next entry's start), orow0 = its first output row: patch query q -> row
+// orow0 + q, pose query -> row orow0 + nq (decode_varlen_impl's row order).  One npad for every buffer, one LDS size.
+#define ATT_MAX_SEQ 32
+struct AttnSeq { int nq, nk, pose, prefetch, blk0, pose_blk0, orow0, rsv; };
+struct AttnVarlenParams { AttnParams a; int nwg, npose_blocks, orows, rsv; AttnSeq seq[ATT_MAX_SEQ]; };
+
 #define ATT_KV 64
 #define ATT_TILE_BYTES (64 * 128)   // 64 rows x 64 fp16
 
@@ -155,16 +166,28 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem,
 
 // The kernel body.  MIXED = false: attn_kernel, one group (g is not read).  MIXED = true: attn_mixed_kernel, two groups; what
 // differs between them - nq, nk, the pose mode, the schedule, the query blocks per (sequence, head), the output rows - is uniform
-// over the workgroup (functions of blockIdx and the kernel arguments only: scalar registers).
-template <bool SPLIT, bool MIXED>
-__device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB& g, char* smem) {
+// over the workgroup (functions of blockIdx and the kernel arguments only: scalar registers).  VARLEN = true (MIXED = false):
+// attn_varlen_kernel, one group per sequence; the workgroup finds its sequence by a scan of the table `v` (at most ATT_MAX_SEQ
+// entries, scalar values) and takes all of the above from that entry (p's and g's per-group fields are not read).
+template <bool SPLIT, bool MIXED, bool VARLEN = false>
+__device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB& g, char* smem, const AttnVarlenParams* v = nullptr) {
     constexpr int NPL = SPLIT ? 2 : 1;
     constexpr int STAGE = 2 * NPL * ATT_TILE_BYTES;   // K planes then V^T planes
+    if constexpr (VARLEN) {
+        // pose blocks first in the grid, in sequence order: the last entry that starts at or before this block owns it
+        if ((int)blockIdx.x < v->npose_blocks) {
+            int s = 0;
+            for (int i = 1; i < p.S; ++i) if (v->seq[i].pose_blk0 <= (int)blockIdx.x) s = i;
+            const AttnSeq e = v->seq[s];
+            attn_pose_query<SPLIT>(p, smem, s, (int)blockIdx.x - e.pose_blk0, e.nq, e.nk, (e.nk + 64) & ~63, (int64_t)e.orow0 + e.nq, (int64_t)v->orows);
+            return;
+        }
+    }
     // pose blocks first in the grid (short: they end while the first round of query blocks is still running); group a's, then b's
     const int S1 = MIXED ? g.S1 : p.S;
     const int npose_a = p.pose == 1 ? S1 * p.heads : 0;
-    const int npose_blocks = npose_a + (MIXED && g.pose == 1 ? (p.S - S1) * p.heads : 0);
-    if ((int)blockIdx.x < npose_blocks) {
+    const int npose_blocks = VARLEN ? v->npose_blocks : npose_a + (MIXED && g.pose == 1 ? (p.S - S1) * p.heads : 0);
+    if (!VARLEN && (int)blockIdx.x < npose_blocks) {
         int sh = blockIdx.x;
         const bool inb = MIXED && sh >= npose_a;
         if (inb) sh -= npose_a;
@@ -181,17 +204,23 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
     // 1-D grid, XCD-aware (attn_block_map); the logical ids of group a's query blocks come first, group b's follow
     const int nqb_a = (p.nq + (p.pose == 2 ? 1 : 0) + 127) / 128, nwg_a = nqb_a * p.heads * S1;
     const int nqb_b = MIXED ? (g.nq + (g.pose == 2 ? 1 : 0) + 127) / 128 : 0;
-    const int nwg = nwg_a + nqb_b * p.heads * (p.S - S1);
+    const int nwg = VARLEN ? v->nwg : nwg_a + nqb_b * p.heads * (p.S - S1);
     int logical = attn_block_map(blockIdx.x - npose_blocks, nwg);
     const bool inb = MIXED && logical >= nwg_a;
     if (inb) logical -= nwg_a;
-    const int nqb = inb ? nqb_b : nqb_a;
-    const int nq = inb ? g.nq : p.nq, nk = inb ? g.nk : p.nk, pose = inb ? g.pose : p.pose, prefetch = inb ? g.prefetch : p.prefetch;
+    int vs = 0;                                         // VARLEN: the sequence whose logical ids hold this one
+    if constexpr (VARLEN) {
+        for (int i = 1; i < p.S; ++i) if (v->seq[i].blk0 <= logical) vs = i;
+        logical -= v->seq[vs].blk0;
+    }
+    const int nqb = VARLEN ? (v->seq[vs].nq + (v->seq[vs].pose == 2 ? 1 : 0) + 127) / 128 : (inb ? nqb_b : nqb_a);
+    const int nq = VARLEN ? v->seq[vs].nq : (inb ? g.nq : p.nq), nk = VARLEN ? v->seq[vs].nk : (inb ? g.nk : p.nk);
+    const int pose = VARLEN ? v->seq[vs].pose : (inb ? g.pose : p.pose), prefetch = VARLEN ? v->seq[vs].prefetch : (inb ? g.prefetch : p.prefetch);
     const int nqe = nq + (pose == 2 ? 1 : 0);           // pose == 2: the pose query rides in the last query block's spare rows
     const int qb = logical % nqb;
-    const int h = (logical / nqb) % p.heads, sl = logical / (nqb * p.heads);     // sl: sequence within its group
-    const int s = inb ? S1 + sl : sl, Sg = inb ? p.S - S1 : S1;
-    const int64_t obase = inb ? g.orow0 : 0;
+    const int h = (logical / nqb) % p.heads, sl = logical / (nqb * p.heads);     // sl: sequence within its group (VARLEN: 0)
+    const int s = VARLEN ? vs : (inb ? S1 + sl : sl), Sg = inb ? p.S - S1 : S1;
+    const int64_t obase = VARLEN ? v->seq[vs].orow0 : (inb ? g.orow0 : 0);
     const int skv = (s + p.kv_shift) % p.S;
     const int q0 = qb * 128 + wave * 32;
 
@@ -446,7 +475,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
     // as [query][column block][hi 64 B | lo 64 B] (= the row blocks of the output planes) in LDS and writes whole 128-B lines.
     const float l_tot = l_run + __shfl_xor(l_run, 32);
     const float inv = 1.0f / l_tot;
-    const int64_t orows = MIXED ? (int64_t)g.orows : (int64_t)p.S * p.nq + (p.pose ? p.S : 0);
+    const int64_t orows = VARLEN ? (int64_t)v->orows : (MIXED ? (int64_t)g.orows : (int64_t)p.S * p.nq + (p.pose ? p.S : 0));
     if constexpr (SPLIT) {
         // LDS image per wave: 64 rows of 128 B, row R = d * 32 + query = [hi 4 chunks | lo 4 chunks] of 16 B (8 d each), chunk c of
         // row R stored at position c ^ (R & 7).  Round 6: the first form ([query][d block] rows of 144 B, ds_write_b64 straight from
@@ -495,7 +524,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
                 const int qq = (lane >> 3) + 8 * it, ch = lane & 7;
                 const int q = q0 + qq;
                 if (q < nqe) {
-                    const int64_t orow = obase + (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl);
+                    const int64_t orow = obase + (VARLEN ? (int64_t)q : (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl));
                     const size_t o = blk_off<true>(orow, h * 64 + d * 32, orows);
                     *reinterpret_cast<uint4*>(p.O_hi + o + ch * 8) = *reinterpret_cast<const uint4*>(wl + (d * 32 + qq) * 128 + ((ch ^ (qq & 7)) << 4));
                 }
@@ -504,7 +533,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
         const int q = q0 + l31;
         if (q < nqe) {
             RangeAcc ra;
-            const int64_t orow = obase + (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl);
+            const int64_t orow = obase + (VARLEN ? (int64_t)q : (q < nq ? (int64_t)sl * nq + q : (int64_t)Sg * nq + sl));
 #pragma unroll
             for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -531,4 +560,11 @@ template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void attn_mixed_kernel(const AttnMixedParams mp) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body<SPLIT, true>(mp.a, mp.b, smem);
+}
+
+// One group per sequence (AttnVarlenParams): batch entries with their own token counts in one launch
+template <bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_varlen_kernel(const AttnVarlenParams vp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    attn_body<SPLIT, false, true>(vp.a, AttnGroupB{}, smem, &vp);
 }

@@ -493,6 +493,95 @@ __global__ __launch_bounds__(256) void rope_tokens_kernel(RopeTokParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// sta_decode_varlen: every sequence has its own token count.  The sequence structure of a call, in the kernel arguments: tok0[s] =
+// patch tokens of the sequences before s (side 1's entries, then side 2's), tok0[S] = all of them; sequence s has n_s = tok0[s + 1]
+// - tok0[s] tokens.  Decoder rows (x and every plane buffer derived from it) are packed [n_s patch rows | pose row] per sequence:
+// sequence s starts at row tok0[s] + s.  A thread finds its sequence by a scan over at most SEQ_MAX entries.
+#define SEQ_MAX 32
+struct SeqTable { int S; int tok0[SEQ_MAX + 1]; };
+__device__ __forceinline__ int seq_of_row(const SeqTable& t, int64_t row) {      // row in the packed order above
+    int s = 0;
+    for (int i = 1; i < t.S; ++i) if ((int64_t)t.tok0[i] + i <= row) s = i;
+    return s;
+}
+
+// emb [tok0[S], D] (the embedded patch tokens, packed) -> x in the decoder's row order, each sequence's pose row filled with the
+// pose token (fill_pose_token_kernel's job in the equal-count forms)
+__global__ void place_tokens_varlen_kernel(const float* emb, SeqTable t, int D, const float* tok, float* x) {
+    const int d4 = D / 4;
+    const int64_t total = ((int64_t)t.tok0[t.S] + t.S) * d4, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int c = (int)(i % d4); const int64_t r = i / d4;
+        const int s = seq_of_row(t, r);
+        const int64_t tk = r - s;                          // packed token index, were this a patch row
+        reinterpret_cast<float4*>(x)[i] = tk < t.tok0[s + 1] ? reinterpret_cast<const float4*>(emb + tk * D)[c] : reinterpret_cast<const float4*>(tok)[c];
+    }
+}
+
+// emit_tokens_kernel for sequences [s0, s0 + B) of the packed order: out [sum(n_s + 1), D], entry by entry with the pose token FIRST
+// (the reference's order); the same rows as x's, only the pose row moves from the end of its sequence to the front
+__global__ void emit_tokens_varlen_kernel(const float* x, SeqTable t, int s0, int B, int D, float* out) {
+    const int d4 = D / 4;
+    const int64_t row0 = (int64_t)t.tok0[s0] + s0;
+    const int64_t total = ((int64_t)t.tok0[s0 + B] + s0 + B - row0) * d4, step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += step) {
+        const int c = (int)(i % d4); const int64_t r = row0 + i / d4;
+        const int s = seq_of_row(t, r);
+        const int64_t first = (int64_t)t.tok0[s] + s, n = t.tok0[s + 1] - t.tok0[s];
+        const int64_t src = r == first ? first + n : r - 1;
+        reinterpret_cast<float4*>(out)[i] = reinterpret_cast<const float4*>(x + src * D)[c];
+    }
+}
+
+// rope_tokens_kernel with one token count per sequence: up to three Q / K buffers [S][heads][npad][64] in one launch (blockIdx.y =
+// buffer), sequence s rotating its n_s tokens by the packed positions table pos[tok0[s] .. tok0[s + 1])[2] and its pose token (token
+// index n_s) by position -1; rows (n_s, npad) of a sequence are never touched.  Thread decomposition and arithmetic as
+// rope_tokens_kernel: one thread = eight frequencies of one (sequence, head, token, y | x half).
+struct RopeVarlenParams {
+    f16* hi[3]; f16* lo[3];
+    int heads, npad;
+    const int* pos; const float* tab; unsigned long long* rng;
+    SeqTable t;
+};
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void rope_varlen_kernel(RopeVarlenParams p) {
+    const int b = blockIdx.y;
+    f16* hi = b == 0 ? p.hi[0] : (b == 1 ? p.hi[1] : p.hi[2]);
+    f16* lo = b == 0 ? p.lo[0] : (b == 1 ? p.lo[1] : p.lo[2]);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rows = ((int64_t)p.t.tok0[p.t.S] + p.t.S) * p.heads;       // (sequence, head, token) rows, sequence-major
+    if (i >= rows * 4) return;
+    const int j = (int)(i & 3), xp = j >> 1, f0 = (j & 1) * 8;
+    int64_t r = i >> 2;
+    int s = 0;
+    for (int q = 1; q < p.t.S; ++q) if (((int64_t)p.t.tok0[q] + q) * p.heads <= r) s = q;
+    r -= ((int64_t)p.t.tok0[s] + s) * p.heads;
+    const int ntok = p.t.tok0[s + 1] - p.t.tok0[s];
+    const int tk = (int)(r % (ntok + 1)), hd = (int)(r / (ntok + 1));
+    const int ps = tk < ntok ? p.pos[((int64_t)p.t.tok0[s] + tk) * 2 + xp] : -1;
+    const float4* tab = reinterpret_cast<const float4*>(p.tab + ((size_t)(ps + 1) * 16 + f0) * 2);
+    const int64_t o = (((int64_t)s * p.heads + hd) * p.npad + tk) * 64 + xp * 32 + f0;
+    union { float4 v[4]; float2 e[8]; } cs;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) cs.v[q] = tab[q];
+    H8 h0, h1, l0, l1;
+    h0.u = ldg16(hi + o); h1.u = ldg16(hi + o + 16);
+    if (SPLIT) { l0.u = ldg16(lo + o); l1.u = ldg16(lo + o + 16); }
+    RangeAcc ra;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float v0 = (float)h0.e[e], v1 = (float)h1.e[e];
+        if (SPLIT) { v0 += (float)l0.e[e]; v1 += (float)l1.e[e]; }
+        const float r0 = v0 * cs.e[e].x - v1 * cs.e[e].y, r1 = v1 * cs.e[e].x + v0 * cs.e[e].y;
+        if (SPLIT) { split_f16(r0, h0.e[e], l0.e[e], ra); split_f16(r1, h1.e[e], l1.e[e], ra); }
+        else { h0.e[e] = to_f16_sat(r0, ra); h1.e[e] = to_f16_sat(r1, ra); }
+    }
+    *reinterpret_cast<uint4*>(hi + o) = h0.u; *reinterpret_cast<uint4*>(hi + o + 16) = h1.u;
+    if (SPLIT) { *reinterpret_cast<uint4*>(lo + o) = l0.u; *reinterpret_cast<uint4*>(lo + o + 16) = l1.u; }
+    ra.flush(p.rng);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Bilinear x2 upsample, align_corners=True (dpt_block.py:215-216,320), NHWC fp16 planes.
 // Output may be cropped to (Hc,Wc) <= (2Hi,2Wi) (dpt_head.py:58); interpolation ratios always use
 // the full (2Hi,2Wi) grid.  One workgroup = NR consecutive output rows of one image: the rows' taps / weights are block-uniform

@@ -118,6 +118,12 @@ struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks;
 struct AttnPlan { int pose, prefetch, stages, lds_bytes, grid, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; };
 // the two-group launch (attn_mixed_plan): stages / lds_bytes / grid of the launch, then what each group runs
 struct AttnMixedPlan { int stages, lds_bytes, grid, nwg_a; struct Group { int pose, prefetch, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; } g[2]; };
+// the per-sequence launch (attn_varlen_plan): the launch's numbers, then per sequence what attn_plan would decide for it plus where
+// it sits in the grid and in the output (AttnSeq: blk0, pose_blk0, orow0)
+struct AttnVarlenPlan {
+    int S, stages, lds_bytes, grid, nwg, pose_blocks, orows;
+    struct Seq { int nq, nk, pose, prefetch, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch, blk0, pose_blk0, orow0; } s[ATT_MAX_SEQ];
+};
 struct sta_handle {
     sta_config cfg;
     int device = 0;
@@ -150,6 +156,7 @@ struct sta_handle {
     GemmPlan last_plan{};   // the plan of the last launch_gemm / paired launch (sta_debug_last_gemm_plan)
     AttnPlan last_attn{};   // the plan of the last run_attn (sta_debug_last_attn_plan)
     AttnMixedPlan last_attn_mixed{};   // ... of the last run_attn_mixed (sta_debug_last_attn_mixed_plan)
+    AttnVarlenPlan last_attn_varlen{};   // ... of the last run_attn_varlen (sta_debug_last_attn_varlen_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
     // sta_decode_pos / sta_decode_tokens, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and
@@ -814,6 +821,50 @@ extern "C" int sta_decode_tokens(sta_handle* h, const float* feat1, const float*
             h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return decode_mixed_impl(h, ws, feat1, feat2, B, 1, N1, 1, N2, x, out1, out2, st);
+    });
+}
+
+// _decode_stereo on a batch whose entries have their own token counts (decode_varlen_impl).  n1 / n2 are HOST arrays: they size the
+// launches.  The packed positions of both sides become one int32 table [sum(n1)*2 | sum(n2)*2] in the workspace (the same kernel as
+// sta_decode_tokens: the same clamping), the QKV epilogues rotate by the identity table and rope_varlen_kernel rotates afterwards.
+extern "C" int sta_decode_varlen(sta_handle* h, const float* feat1, const float* feat2, const int64_t* pos1, const int64_t* pos2,
+                                 const int* n1, const int* n2, int B, int pos_max, float* const* out1, float* const* out2, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    CHK(check_ready(h, B, 16, 16));
+    REQUIRE(feat1 && feat2 && pos1 && pos2, "null device pointer");
+    REQUIRE(n1 && n2, "null token-count array");
+    REQUIRE(B <= SEQ_MAX / 2, "batch %d out of range (1 .. %d entries per call)", B, SEQ_MAX / 2);
+    REQUIRE(pos_max >= 0 && pos_max < (1 << 20), "bad argument (pos_max %d)", pos_max);
+    SeqTable t; memset(&t, 0, sizeof t);
+    t.S = 2 * B;
+    int64_t acc = 0; int nmax = 0;
+    for (int s = 0; s < 2 * B; ++s) {
+        const int n = s < B ? n1[s] : n2[s - B];
+        REQUIRE(n >= 1, "bad argument (entry %d has %d tokens on side %d)", s % B, n, s / B + 1);
+        t.tok0[s] = (int)acc; acc += n; nmax = std::max(nmax, n);
+        REQUIRE(acc + 2 * B < ((int64_t)1 << 31), "too many decoder rows (%lld or more)", (long long)(acc + 2 * B));
+    }
+    t.tok0[2 * B] = (int)acc;
+    const int64_t rows = acc + 2 * B;
+    hipStream_t st = (hipStream_t)stream;
+    CHK(ensure_rope(h, pos_max + 1));
+    const int64_t xbytes = rows * h->cfg.dec_embed_dim * 4;
+    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
+    h->rope_foreign = true;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        float* x = (float*)ws.take(xbytes);
+        const int64_t c1 = (int64_t)t.tok0[B] * 2, c2 = (acc - t.tok0[B]) * 2;
+        int* rp = (int*)ws.take((c1 + c2) * 4);
+        const int64_t n_ident = (int64_t)(nmax + 2) * 16;      // each sequence is the grid 1 x n: table rows 0 .. max(n) + 1
+        float2* ident = (float2*)ws.take(n_ident * 8);
+        if (!h->dry) {
+            hipLaunchKernelGGL(rope_tokens_table_kernel<int64_t>, dim3((unsigned)((c1 + c2 + n_ident + 255) / 256)), dim3(256), 0, st,
+                               pos1, pos2, c1, c2, pos_max, rp, ident, n_ident);
+            HIPCHK(hipGetLastError());
+            h->rope_pos = rp; h->rope_ident = (const float*)ident;
+        }
+        return decode_varlen_impl(h, ws, feat1, feat2, t, B, x, out1, out2, st);
     });
 }
 

@@ -276,6 +276,89 @@ extern "C" int sta_debug_attention_mixed(sta_handle* h, const float* q_a, const 
     return 0;
 }
 
+// The per-sequence form (attn_varlen_kernel / run_attn_varlen).  nq / nk: HOST arrays [S].  q fp32: sequence after sequence
+// [heads, nq[s] + 1, 64]; k / v: [heads, nk[s] + 1, 64], pose token LAST.  k / v of a sequence are the keys IT READS: the entry stores
+// those of sequence s at buffer sequence (s + kv_shift) % S, where the kernel looks for them.  out fp32 [sum(nq[s] + 1), heads*64]:
+// per sequence its patch rows, then its pose row.  Poisoning as in sta_debug_attention_mixed: V^T padding zero; K padding, dead Q
+// rows and the output planes 0xFF.  Directly behind the output planes lies a guard block of 64 rows, every byte 0x3C, which is
+// returned as rows [sum(nq[s] + 1), + 64) of out: a store to an output row at or past the launch's last one lands in the next column
+// block (a wrong row of the output) or, from the last column block, in the guard.
+extern "C" int sta_debug_attn_varlen(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads,
+                                     const int* nq, const int* nk, int kv_shift, float* out, void* stream) {
+    REQUIRE(h && q && k && v && out && nq && nk && S > 0 && S <= ATT_MAX_SEQ && heads > 0, "bad argument");
+    REQUIRE(kv_shift >= 0 && kv_shift < S, "bad kv_shift");
+    int nmax = 0; int64_t M = 0;
+    for (int s = 0; s < S; ++s) { REQUIRE(nq[s] > 0 && nk[s] > 0, "bad argument (sequence %d)", s); nmax = std::max(nmax, std::max(nq[s], nk[s])); M += nq[s] + 1; }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int npad = rup(nmax + 1, 64);
+    const int64_t seq = (int64_t)heads * npad * 64, hsz = S * seq;
+    const int G = 64;                                                   // guard rows
+    CHK(ensure_ws(h, (3 * hsz + (M + G) * heads * 64) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
+    Planes ao = ws.act(M + G, heads * 64, split);                       // one allocation: the output planes of M rows, then the guard's of G rows
+    ao.rp = M;
+    Planes guard = slice_rows(ao, M * (heads * 64 / 32)); guard.rp = G;
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    HIPCHK(hipMemsetAsync(o.vt.hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(o.vt.lo, 0, hsz * 2, st));
+    CHK(dbg_poison_planes(o.k, hsz, st));
+    CHK(dbg_poison_planes(o.q, hsz, st));
+    CHK(dbg_poison_act(ao, M, heads * 64, st));
+    HIPCHK(hipMemsetAsync(guard.hi, 0x3C, (size_t)G * heads * 64 * (split ? 4 : 2), st));
+    auto at = [&](const Planes& p, int64_t s) { Planes r = p; r.hi = p.hi + s * seq; if (p.lo) r.lo = p.lo + s * seq; return r; };
+    for (int s = 0; s < S; ++s) {
+        const int nqt = nq[s] + 1, nkt = nk[s] + 1, skv = (s + kv_shift) % S;
+        CHK(run_rows_to_planes(h, q, (int64_t)nqt * 64, heads, nqt, 64, at(o.q, s), st, npad));
+        CHK(run_rows_to_planes(h, k, (int64_t)nkt * 64, heads, nkt, 64, at(o.k, skv), st, npad));
+        const Planes vt = at(o.vt, skv);
+        hipLaunchKernelGGL(pack_vt_kernel, dim3((unsigned)(((int64_t)heads * nkt * 64 + 255) / 256)), dim3(256), 0, st,
+                           v, heads, nkt, npad, vt.hi, vt.lo, h->range);
+        HIPCHK(hipGetLastError());
+        q += (int64_t)heads * nqt * 64; k += (int64_t)heads * nkt * 64; v += (int64_t)heads * nkt * 64;
+    }
+    CHK(run_attn_varlen(h, o, ao, heads * 64, S, heads, nq, nk, kv_shift, st));
+    CHK(dbg_planes_to_f32(h, ao, 0, 1, (int)M, heads * 64, out, st));
+    CHK(dbg_planes_to_f32(h, guard, 0, 1, G, heads * 64, out + M * heads * 64, st));
+    return 0;
+}
+
+// The rotation step of sta_decode_varlen alone.  n: HOST array [S] of token counts.  bufs: nbuf (<= 3) fp32 device buffers
+// [S*heads + 1][npad][64], npad = roundup(max(n) + 1, 64): the decoder's Q / K layout plus ONE guard block behind the last head of
+// the last sequence.  EVERY row, the guard's too, is split to planes, rotated in place and returned as hi + lo, so a row the kernel
+// must not touch comes back as it went in.  pos_i32: device int32 [sum(n)*2] (y, x), packed, clamped to [-1, pos_max] into a copy first.
+extern "C" int sta_debug_rope_varlen(sta_handle* h, float* const* bufs, int nbuf, int S, int heads, const int* n, const int* pos_i32,
+                                     int pos_max, void* stream) {
+    REQUIRE(h && bufs && pos_i32 && n && nbuf >= 1 && nbuf <= 3 && S > 0 && S <= SEQ_MAX && heads > 0, "bad argument");
+    REQUIRE(pos_max >= 0 && pos_max < (1 << 20), "bad argument (pos_max %d)", pos_max);
+    for (int b = 0; b < nbuf; ++b) REQUIRE(bufs[b], "null buffer %d", b);
+    SeqTable t; memset(&t, 0, sizeof t);
+    t.S = S;
+    int nmax = 0;
+    for (int s = 0; s < S; ++s) { REQUIRE(n[s] > 0 && n[s] < (1 << 20), "bad argument (sequence %d)", s); t.tok0[s + 1] = t.tok0[s] + n[s]; nmax = std::max(nmax, n[s]); }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int npad = rup(nmax + 1, 64);
+    const int64_t hsz = ((int64_t)S * heads + 1) * npad * 64;          // with the guard block
+    const int64_t np = (int64_t)t.tok0[S] * 2;
+    CHK(ensure_rope(h, pos_max + 1));
+    CHK(ensure_ws(h, nbuf * hsz * 4 + np * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes pl[3]; const Planes* pp[3];
+    for (int b = 0; b < nbuf; ++b) { pl[b] = ws.planes(hsz, split); pp[b] = &pl[b]; }
+    int* pos = (int*)ws.take(np * 4);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    hipLaunchKernelGGL(rope_tokens_table_kernel<int>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st,
+                       pos_i32, pos_i32, np, (int64_t)0, pos_max, pos, (float2*)nullptr, (int64_t)0);
+    HIPCHK(hipGetLastError());
+    for (int b = 0; b < nbuf; ++b) CHK(run_rows_to_planes(h, bufs[b], (int64_t)npad * 64, S * heads + 1, npad, 64, pl[b], st, npad));
+    CHK(rope_varlen_launch(h, pp, nbuf, t, heads, npad, pos, st));
+    for (int b = 0; b < nbuf; ++b) CHK(dbg_planes_to_f32(h, pl[b], npad, S * heads + 1, npad, 64, bufs[b], st));
+    return 0;
+}
+
 // The rotation step of sta_decode_tokens alone.  bufs: nbuf (<= 3) fp32 device buffers [S1 + S2][heads][npad][64], npad =
 // roundup(max(ntok_a, ntok_b) + 1, 64): EVERY row is split to planes (the rows past a sequence's pose token too), rotated in place and
 // returned as hi + lo, so a row the kernel must not touch comes back as it went in.  pos_i32: device int32 [S1*ntok_a*2 | S2*ntok_b*2]

@@ -319,6 +319,103 @@ static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ decoder, one token count per entry
+// _decode_stereo on a batch whose entries have DIFFERENT token counts (sta_decode_varlen): entry b has n1[b] tokens on side 1 and
+// n2[b] on side 2.  Batch entries never interact in the reference (sta_model.py:177-244; attention is per sample), so entry b is
+// what a B = 1 call on it alone returns.  Sequences: s = b for side 1, B + b for side 2 (S = 2B <= 32), counts in a SeqTable that
+// travels in the kernel arguments (the counts are host values: nothing is copied to the device, nothing is synchronised).
+// Row order of x and every plane buffer derived from it: packed, no padded rows,
+//     [n_0 patch rows | pose row] [n_1 patch rows | pose row] ... for s = 0 .. S - 1      (sequence s starts at row tok0[s] + s)
+// LayerNorm, proj, cproj, fc1, fc2 and the residual epilogues: ONE launch over all rows, as in decode_mixed_impl.  What knows the
+// sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SEQUENCE on its contiguous rows with the existing EPI_QKV
+// (one sequence of ntok = n_s, pose_base = n_s: exactly the launch of a B = 1 sta_decode_tokens call; Q / K / V^T planes advanced by s
+// sequences of the shared npad); the rotation is rope_varlen_kernel from the packed positions table; attention is the per-sequence
+// launch (run_attn_varlen: kv_shift = 0 self attention of all sequences, kv_shift = B both cross directions).  One lane, outside
+// sta_reserve's coverage.  want1[i] [sum(n1) + B, D] / want2[i] [sum(n2) + B, D]: entry by entry, pose token first, or NULL.
+static int decode_varlen_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, const SeqTable& t, int B,
+                              float* x, float* const* want1, float* const* want2, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim, Hh = c.dec_num_heads, S = 2 * B;
+    int n[SEQ_MAX], nmax = 0;
+    for (int s = 0; s < S; ++s) { n[s] = t.tok0[s + 1] - t.tok0[s]; nmax = std::max(nmax, n[s]); }
+    const int Mp = t.tok0[S], Mp1 = t.tok0[B], M = Mp + S, npad = rup(nmax + 1, 64);
+    auto row0 = [&](int s) { return (int64_t)t.tok0[s] + s; };
+    Planes fp = ws.act(Mp, E, split);
+    float* emb = (float*)ws.take((int64_t)Mp * D * 4);
+    Planes a1 = ws.act(M, D, split);
+    Planes ay = ws.act(M, D, split);
+    Planes ao = ws.act(M, D, split);
+    Planes f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
+    f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
+    QKVOut qkv; qkv.npad = npad;
+    const int64_t ssz = (int64_t)Hh * npad * 64, hsz = S * ssz;       // one sequence; all S
+    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split);
+    QKVOut cqkv; cqkv.npad = npad;
+    cqkv.q = ws.planes(hsz, split); cqkv.k = ws.planes(hsz, split);
+    qkv.vt = ws.planes(hsz, split); cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
+    { const Planes* z[2] = {&qkv.vt, &cqkv.vt}; CHK(zero_planes(z, 2, hsz, split, st)); }
+    auto seq_planes = [&](const Planes& p, int s) { Planes q = p; q.hi = p.hi + s * ssz; if (p.lo) q.lo = p.lo + s * ssz; return q; };
+    auto seq_qkv = [&](const QKVOut& o, int s) { QKVOut q; q.npad = o.npad; q.q = seq_planes(o.q, s); q.k = seq_planes(o.k, s); q.vt = seq_planes(o.vt, s); return q; };
+
+    // patch embedding of all tokens in one GEMM on the packed rows, then into the row order above with the pose tokens
+    CHK(run_rows_to_planes(h, feat1, (int64_t)Mp1 * E, 1, Mp1, E, fp, st));
+    CHK(run_rows_to_planes(h, feat2, (int64_t)(Mp - Mp1) * E, 1, Mp - Mp1, E, slice_rows(fp, Mp1), st));
+    CHK(gemm_f32(h, fp, h->dec_embed, Mp, emb, D, nullptr, st));
+    auto blocks_for = [](int64_t total4) { int64_t b = (total4 + 255) / 256; return (int)(b > 8192 ? 8192 : b); };
+    hipLaunchKernelGGL(place_tokens_varlen_kernel, dim3(blocks_for((int64_t)M * D / 4)), dim3(256), 0, st, emb, t, D, h->pose_tok, x);
+    HIPCHK(hipGetLastError());
+    auto emit = [&](int idx, const float* src) -> int {
+        for (int side = 0; side < 2; ++side) {
+            float* dst = side == 0 ? (want1 ? want1[idx] : nullptr) : (want2 ? want2[idx] : nullptr);
+            if (!dst) continue;
+            const int64_t rows = row0(side * B + B) - row0(side * B);
+            hipLaunchKernelGGL(emit_tokens_varlen_kernel, dim3(blocks_for(rows * D / 4)), dim3(256), 0, st, src, t, side * B, B, D, dst);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    };
+    // one QKV-epilogue GEMM per sequence: its n_s + 1 rows of A -> its sequence of the Q / K / V^T buffers
+    auto qkv_seqs = [&](const Planes& A, const Lin& W, int nq, int nk, int nv, const QKVOut& o) -> int {
+        for (int s = 0; s < S; ++s)
+            CHK(gemm_qkv(h, slice_rows(A, row0(s)), W, n[s] + 1, nq, nk, nv, seq_qkv(o, s), n[s], Hh, n[s], 0, st, n[s]));
+        return 0;
+    };
+    int nx[SEQ_MAX];                                    // cross attention: sequence s reads the keys of the other side's entry
+    for (int s = 0; s < S; ++s) nx[s] = n[(s + B) % S];
+    auto rope = [&](const Planes* const* bufs, int nbuf) -> int { return rope_varlen_launch(h, bufs, nbuf, t, Hh, npad, h->rope_pos, st); };
+    CHK(emit(0, x));
+    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, a1, &h->dec[0].ny, &ay, nullptr, st));
+    for (int i = 0; i < c.dec_depth; ++i) {
+        const DecBlk& b = h->dec[i];
+        CHK(qkv_seqs(a1, b.qkv, D, D, D, qkv));
+        CHK(qkv_seqs(ay, b.ckv, 0, D, D, cqkv));         // K / V of a sequence's OWN tokens: the other side's queries read them (kv_shift = B)
+        { const Planes* rot[3] = {&qkv.q, &qkv.k, &cqkv.k}; CHK(rope(rot, 3)); }      // the epilogues above rotated by the identity
+        CHK(run_attn_varlen(h, qkv, ao, D, S, Hh, n, n, 0, st));
+        CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
+        CHK(qkv_seqs(a1, b.cq, D, 0, 0, cqkv));
+        { const Planes* rot[1] = {&cqkv.q}; CHK(rope(rot, 1)); }
+        CHK(run_attn_varlen(h, cqkv, ao, D, S, Hh, n, nx, B, st));
+        CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
+        CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));
+        if (i + 1 < c.dec_depth) {
+            const DecBlk& nb = h->dec[i + 1];
+            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, &nb.n1, &a1, &nb.ny, &ay, st));
+            CHK(emit(i + 1, x));
+        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
+            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
+            if ((want1 && want1[i + 1]) || (want2 && want2[i + 1])) {
+                Planes none;
+                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, x, st));          // x is dead after the last layer: in place
+                CHK(emit(i + 1, x));
+            }
+        }
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ pose head
 // pose2 / conf2 (optional): the last B - split samples write there (the two sides of a pair: one set of four launches)
 static int pose_impl(sta_handle* h, Bump& ws, const float* tok, int B, int64_t stride, float* pose, float* conf, hipStream_t st,

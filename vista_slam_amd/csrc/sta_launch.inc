@@ -981,6 +981,140 @@ static int run_attn_mixed(sta_handle* h, const QKVOut& qkv, const Planes& out, i
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------ per-sequence attention (decode_varlen_impl)
+// The plan of attn_varlen_kernel, pure like attn_plan: S <= ATT_MAX_SEQ sequences in the decoder's pose-token form, sequence s with
+// nq[s] queries over nk[s] keys (the caller resolves kv_shift: nk[s] is the count of the sequence s reads).  Per sequence exactly
+// attn_plan's rules on its own numbers - pose mode from its nq, tiles and tail from its nk, pose-query scratch from its nk -; the
+// prefetch decision uses the grid of the WHOLE launch and the launch carries the LDS of the hungriest sequence (attn_mixed_plan's
+// reasoning: 4 stages as soon as one sequence prefetches, the grid is <= 256 workgroups then).  Logical query-block ids and pose
+// blocks are handed out in sequence order; output rows are packed [nq patch rows | pose row] per sequence.  Sequences [0, S1) equal
+// and [S1, S) equal reduce to attn_mixed_plan field by field (tests/test_attention_varlen_plan.py).
+static_assert(ATT_MAX_SEQ == SEQ_MAX, "the attention table (attention.h) and the row table (elementwise.h) hold the same sequences of one call");
+static int attn_varlen_plan(int S, int heads, const int* nq, const int* nk, bool split, bool no_prefetch, AttnVarlenPlan& out) {
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && heads > 0 && nq && nk, "per-sequence attention takes 1 .. %d sequences", ATT_MAX_SEQ);
+    AttnVarlenPlan m{};
+    m.S = S;
+    int64_t nwg = 0, npose = 0, orows = 0;
+    for (int i = 0; i < S; ++i) {
+        REQUIRE(nq[i] > 0 && nk[i] > 0, "empty attention (sequence %d)", i);
+        AttnVarlenPlan::Seq& a = m.s[i];
+        a.nq = nq[i]; a.nk = nk[i];
+        a.pose = nq[i] % 128 != 0 ? 2 : 1;
+        a.pose_blocks = a.pose == 1 ? heads : 0;
+        a.qblocks = (nq[i] + (a.pose == 2 ? 1 : 0) + 127) / 128;
+        a.ntiles = (nk[i] + ATT_KV - 1) / ATT_KV; a.nfull = nk[i] / ATT_KV;
+        a.pose_scratch = (rup(nk[i] + 1, 64) + 8 + 256) * 4;
+        REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+        REQUIRE(nwg + npose < ((int64_t)1 << 30) && orows < ((int64_t)1 << 31) - nq[i] - 1, "attention launch too large");
+        a.blk0 = (int)nwg; a.pose_blk0 = (int)npose; a.orow0 = (int)orows;
+        nwg += (int64_t)a.qblocks * heads; npose += a.pose_blocks; orows += (int64_t)nq[i] + 1;
+    }
+    REQUIRE(nwg + npose < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)(nwg + npose));
+    m.nwg = (int)nwg; m.pose_blocks = (int)npose; m.grid = (int)(nwg + npose); m.orows = (int)orows;
+    m.stages = 2;
+    for (int i = 0; i < S; ++i) {
+        AttnVarlenPlan::Seq& a = m.s[i];
+        a.prefetch = (nk[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
+        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
+        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
+    }
+    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
+    out = m;
+    return 0;
+}
+#ifdef STA_TEST_HOOKS
+static void attn_varlen_plan_out(const AttnVarlenPlan& m, int* out) {
+    const int hd[7] = {m.S, m.stages, m.lds_bytes, m.grid, m.nwg, m.pose_blocks, m.orows};
+    for (int j = 0; j < 7; ++j) out[j] = hd[j];
+    for (int i = 0; i < m.S; ++i) {
+        const AttnVarlenPlan::Seq& a = m.s[i];
+        const int v[11] = {a.pose, a.prefetch, a.pose_blocks, a.qblocks, a.ntiles, a.nfull, a.tail_stage, a.pose_scratch, a.blk0, a.pose_blk0, a.orow0};
+        for (int j = 0; j < 11; ++j) out[7 + 11 * i + j] = v[j];
+    }
+}
+// out[7 + 11 * S] = {S, LDS stages, LDS bytes, grid, query-block workgroups, pose blocks, output rows, then per sequence {pose mode,
+// prefetch, pose blocks, query blocks, ntiles, nfull, tail stage, pose scratch bytes, first logical id, first pose block, first output row}}
+extern "C" int sta_debug_attn_varlen_plan(int S, int heads, const int* nq, const int* nk, int split, int no_prefetch, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnVarlenPlan m;
+    CHK(attn_varlen_plan(S, heads, nq, nk, split != 0, no_prefetch != 0, m));
+    attn_varlen_plan_out(m, out);
+    return 0;
+}
+extern "C" int sta_debug_last_attn_varlen_plan(sta_handle* h, int* out) {
+    REQUIRE(h && out, "bad argument");
+    attn_varlen_plan_out(h->last_attn_varlen, out);
+    return 0;
+}
+// The workgroup -> (sequence, head, query block) map of attn_varlen_kernel's query-block workgroups by the kernel's arithmetic
+// (attn_block_map, then the scan over the plan's first logical ids): out[3 * b + {0, 1, 2}] for workgroup b of the plan's nwg.
+extern "C" int sta_debug_attn_varlen_block_map(int S, int heads, const int* nq, const int* nk, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnVarlenPlan m;
+    CHK(attn_varlen_plan(S, heads, nq, nk, true, false, m));
+    for (int b = 0; b < m.nwg; ++b) {
+        int logical = attn_block_map(b, m.nwg), s = 0;
+        for (int i = 1; i < S; ++i) if (m.s[i].blk0 <= logical) s = i;
+        logical -= m.s[s].blk0;
+        out[3 * b] = s; out[3 * b + 1] = (logical / m.s[s].qblocks) % heads; out[3 * b + 2] = logical % m.s[s].qblocks;
+    }
+    return 0;
+}
+#endif
+
+// out: [nq[s] patch rows | pose row] per sequence (decode_varlen_impl's row order), out.rp rows in all.  nq[s]: queries of sequence s;
+// nk[s]: the keys it reads, which are those of buffer sequence (s + kv_shift) % S.
+static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* nq, const int* nk, int kv_shift, hipStream_t st) {
+    if (h->dry) return 0;
+    const bool split = h->prec != STA_PREC_F16;
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && kv_shift >= 0 && kv_shift < S, "internal: per-sequence attention arguments");
+    int nmax = 0;
+    for (int s = 0; s < S; ++s) nmax = std::max(nmax, std::max(nq[s], nk[s]));
+    AttnVarlenPlan m;
+    CHK(attn_varlen_plan(S, heads, nq, nk, split, h->opt[5] == 1, m));
+    h->last_attn_varlen = m;
+    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: per-sequence attention needs max(n) < npad, npad %% 64 == 0");
+    REQUIRE(out.rp == m.orows, "internal: per-sequence attention output of %d rows in planes of %lld", m.orows, (long long)out.rp);
+    AttnVarlenParams vp; memset(&vp, 0, sizeof vp);
+    AttnParams& p = vp.a;
+    p.range = h->range;
+    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
+    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
+    p.S = S; p.heads = heads; p.npad = qkv.npad; p.kv_shift = kv_shift;
+    p.scale_log2e = 0.125f * 1.44269504088896340736f;
+    vp.nwg = m.nwg; vp.npose_blocks = m.pose_blocks; vp.orows = m.orows;
+    for (int s = 0; s < S; ++s) {
+        const AttnVarlenPlan::Seq& a = m.s[s];
+        vp.seq[s] = AttnSeq{a.nq, a.nk, a.pose, a.prefetch, a.blk0, a.pose_blk0, a.orow0, 0};
+    }
+    const dim3 grid((unsigned)m.grid);
+    if (split) {
+        static unsigned attr_done = 0;      // one bit per device
+        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_varlen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
+        hipLaunchKernelGGL(attn_varlen_kernel<true>, grid, dim3(256), m.lds_bytes, st, vp);
+    } else {
+        STA_F16ONLY(hipLaunchKernelGGL(attn_varlen_kernel<false>, grid, dim3(256), m.lds_bytes, st, vp));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// sta_decode_varlen: rotate nbuf (<= 3) Q / K buffers [S][heads][npad][64] in place, sequence s by its slice of the packed positions
+// table (SeqTable): one launch of rope_varlen_kernel
+static int rope_varlen_launch(sta_handle* h, const Planes* const* bufs, int nbuf, const SeqTable& t, int heads, int npad, const int* pos, hipStream_t st) {
+    REQUIRE(nbuf >= 1 && nbuf <= 3 && pos && h->rope_tab && t.S >= 1 && t.S <= SEQ_MAX, "internal: rope_varlen_launch arguments");
+    for (int s = 0; s < t.S; ++s) REQUIRE(t.tok0[s + 1] - t.tok0[s] >= 1 && t.tok0[s + 1] - t.tok0[s] + 1 <= npad, "internal: rope_varlen_launch rows exceed npad");
+    RopeVarlenParams p;
+    for (int b = 0; b < 3; ++b) { p.hi[b] = bufs[b < nbuf ? b : 0]->hi; p.lo[b] = bufs[b < nbuf ? b : 0]->lo; }
+    p.heads = heads; p.npad = npad; p.pos = pos; p.tab = h->rope_tab; p.rng = h->range; p.t = t;
+    const int64_t total = ((int64_t)t.tok0[t.S] + t.S) * heads * 4;
+    const dim3 grid((unsigned)((total + 255) / 256), nbuf);
+    if (bufs[0]->lo) hipLaunchKernelGGL(rope_varlen_kernel<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(rope_varlen_kernel<false>, grid, dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 static int run_rows_to_planes(sta_handle* h, const float* x, int64_t bstride, int nb, int rows, int C, const Planes& o, hipStream_t st, int64_t obstride = 0, bool mx = false) {
     if (h->dry) return 0;
     int64_t total4 = (int64_t)nb * rows * C / 4;

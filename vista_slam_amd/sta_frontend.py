@@ -633,6 +633,111 @@ class STAFrontend:
             res.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"], "relative_pose_conf": pose["conf"]})
         return res[0], res[1]
 
+    # ------------------------------------------------------------------ one token count per batch entry
+    @staticmethod
+    def pack_varlen(feats: Sequence[torch.Tensor], poss: Sequence[torch.Tensor], E: int, device=None):
+        """One side of a varlen call: lists of [n_b, E] features and [n_b, 2] integer (y, x) positions, one pair per entry ->
+        (feat [sum n, E] float32, pos [sum n, 2] int64, counts [B]) packed entry-major.  Entry b's tokens are rows
+        [sum(counts[:b]), sum(counts[:b + 1])) of both."""
+        assert len(feats) == len(poss) and len(feats) >= 1, "one positions tensor per features tensor, at least one entry"
+        counts = []
+        for b, (f, q) in enumerate(zip(feats, poss)):
+            assert f.dim() == 2 and f.shape[1] == E, f"entry {b}: features must be [n, {E}] (got {tuple(f.shape)})"
+            assert f.shape[0] >= 1, f"entry {b}: every side needs at least one token"
+            assert tuple(q.shape) == (f.shape[0], 2), f"entry {b}: positions must be [{f.shape[0]}, 2] (got {tuple(q.shape)})"
+            assert not q.dtype.is_floating_point, "positions are integer (y, x) coordinates (PositionGetter, sta_blocks.py:241-247)"
+            counts.append(int(f.shape[0]))
+        dev = feats[0].device if device is None else device
+        feat = torch.cat([f.to(dev, torch.float32) for f in feats], 0).contiguous()
+        pos = torch.cat([q.to(dev, torch.int64) for q in poss], 0).contiguous()
+        return feat, pos, counts
+
+    @staticmethod
+    def varlen_offsets(counts: Sequence[int]):
+        """First row of every entry in a packed decoder output [sum(n) + B, D] (entry b: counts[b] + 1 rows, pose token first),
+        and the total: (offsets [B], rows)."""
+        offs, r = [], 0
+        for n in counts:
+            offs.append(r)
+            r += int(n) + 1
+        return offs, r
+
+    def decode_stereo_varlen(self, feats1: Sequence[torch.Tensor], feats2: Sequence[torch.Tensor], pos1: Sequence[torch.Tensor],
+                             pos2: Sequence[torch.Tensor], layers: Sequence[int] | None = None):
+        """`_decode_stereo` on a batch whose entries have their OWN token counts: feats1[b] [n1_b, E] with positions pos1[b]
+        [n1_b, 2], feats2[b] [n2_b, E] with pos2[b] [n2_b, 2] - lists over the B <= 16 entries.  Entry b of the result is what the
+        reference returns for that entry alone at B = 1 (batch entries never interact); nothing is padded.  Returns two lists over
+        the dec_depth+1 layers; each element is None (layer not in `layers`) or a list of B views [n_b + 1, D] (pose token first)
+        into one packed buffer.  One sta_decode_varlen call."""
+        B = len(feats1)
+        assert len(feats2) == B and len(pos1) == B and len(pos2) == B, "both views need the same number of entries"
+        assert 1 <= B <= 16, f"1 .. 16 entries per call (got {B})"
+        E, D = self.cfg.enc_embed_dim, self.cfg.dec_embed_dim
+        f1, q1, n1 = self.pack_varlen(feats1, pos1, E, self.device)
+        f2, q2, n2 = self.pack_varlen(feats2, pos2, E, self.device)
+        lo, hi = torch.stack(torch.aminmax(torch.cat([q1, q2]))).tolist()          # (one device sync)
+        if lo < -1:
+            raise ValueError(f"positions below -1 ({lo}) are not served (-1 is the pose token's position; the reference's python RoPE "
+                             "indexes its cos / sin tables with the position)")
+        L = self.cfg.dec_depth + 1
+        want = range(L) if layers is None else layers
+        out1: List[List[torch.Tensor] | None] = [None] * L
+        out2: List[List[torch.Tensor] | None] = [None] * L
+        p1 = (C.c_void_p * L)()
+        p2 = (C.c_void_p * L)()
+        (o1, r1), (o2, r2) = self.varlen_offsets(n1), self.varlen_offsets(n2)
+        for i in want:
+            b1 = torch.empty(r1, D, device=self.device, dtype=torch.float32)
+            b2 = torch.empty(r2, D, device=self.device, dtype=torch.float32)
+            p1[i], p2[i] = b1.data_ptr(), b2.data_ptr()
+            out1[i] = [b1[o:o + n + 1] for o, n in zip(o1, n1)]
+            out2[i] = [b2[o:o + n + 1] for o, n in zip(o2, n2)]
+        _lib.check(self.lib.sta_decode_varlen(self._h, f1.data_ptr(), f2.data_ptr(), q1.data_ptr(), q2.data_ptr(),
+                                              (C.c_int * B)(*n1), (C.c_int * B)(*n2), B, max(hi, 0), p1, p2, self._stream()))
+        return out1, out2
+
+    def forward_pairs_tokens(self, imgs_a: Sequence[torch.Tensor], imgs_b: Sequence[torch.Tensor], pos_a: Sequence[torch.Tensor],
+                             pos_b: Sequence[torch.Tensor]):
+        """`forward_pair_tokens` for B pairs whose token subsets differ in size: imgs_a[b] [3, H, W] (any frame size per entry) with
+        pos_a[b] [n, 2] int64 (y, x) patch positions, the same for side b.  Encoder: `encode_tokens`, entries of equal count and
+        frame size sharing one call; decoder: ONE `decode_stereo_varlen` call; pose head: once over all 2B pose rows; DPT head: per
+        entry and side, where that side is a row-major rectangle of patches.  Returns (main, support): two lists of B dicts with
+        pts3d_pred / conf ([16 h, 16 w, 3] / [16 h, 16 w], or None), relative_pose [4, 4], relative_pose_conf []."""
+        B = len(imgs_a)
+        assert len(imgs_b) == B and len(pos_a) == B and len(pos_b) == B and B >= 1, "one frame and one positions tensor per entry and side"
+        hooks = self.cfg.hooks
+        layers = sorted({hk - 1 for hk in hooks[1:]})
+        sides = []
+        for imgs, poss in ((imgs_a, pos_a), (imgs_b, pos_b)):
+            groups: Dict[tuple, List[int]] = {}
+            for b, (im, q) in enumerate(zip(imgs, poss)):
+                assert im.dim() == 3 and im.shape[0] == 3, f"entry {b}: a frame is [3, H, W] (got {tuple(im.shape)})"
+                groups.setdefault((int(q.shape[0]), int(im.shape[1]), int(im.shape[2])), []).append(b)
+            feats: List[torch.Tensor | None] = [None] * B
+            qs: List[torch.Tensor | None] = [None] * B
+            for members in groups.values():
+                f, q = self.encode_tokens(torch.stack([self._f32(imgs[b]) for b in members]),
+                                          pos=torch.stack([torch.as_tensor(poss[b]).cpu() for b in members]))
+                for j, b in enumerate(members):
+                    feats[b], qs[b] = f[j], q[j]
+            sides.append((feats, qs))
+        d1, d2 = self.decode_stereo_varlen(sides[0][0], sides[1][0], sides[0][1], sides[1][1], layers=layers)
+        pose = self.head_pose_s(torch.stack([t[0] for d in (d1, d2) for t in d[-1]]))
+        res = []
+        for k, ((feats, qs), dec) in enumerate(zip(sides, (d1, d2))):
+            outs = []
+            for b in range(B):
+                rect = self._rectangle_of(qs[b][None])
+                pts = {"pts3d": None, "conf": None}
+                if rect is not None:
+                    toks = [feats[b][None]] + [None if t is None else t[b][None, 1:, :] for t in dec]
+                    pts = self.head_pts(toks, [[16 * rect[0], 16 * rect[1]]])
+                    pts = {key: v[0] for key, v in pts.items()}
+                outs.append({"pts3d_pred": pts["pts3d"], "conf": pts["conf"], "relative_pose": pose["pose"][k * B + b],
+                             "relative_pose_conf": pose["conf"][k * B + b]})
+            res.append(outs)
+        return res[0], res[1]
+
     def forward_pair_u8hwc(self, img_a: torch.Tensor, img_b: torch.Tensor):
         """`forward_pair` on uint8 HWC frames [B,H,W,3]."""
         assert img_a.dtype == torch.uint8 and img_b.dtype == torch.uint8 and img_a.shape == img_b.shape
