@@ -9,6 +9,7 @@ import torch
 
 import helpers as HP
 from helpers import load_golden, rel_l2, max_rel, rope2d_ref, grid_pos
+from range_cases import range_class
 from vista_slam_amd import _lib
 from vista_slam_amd import weights as W
 from vista_slam_amd.sta_frontend import STAFrontend, rope2d_inplace
@@ -580,9 +581,10 @@ def _cached(key, make):
     return _conv_cache[kind][1]
 
 
-def conv_launch(precision, case, x, w, b, res):
+def conv_launch(precision, case, x, w, b, res, expect_range=(0, 0)):
     """Run the case's launch (sta_debug_conv3x3_r2) on numpy NHWC inputs -> (output [n, Ho, Wo, Co] float32, the class the launch ran
-    under).  The output buffer starts as NaN and the entry poisons the output planes: an element no workgroup stored is a NaN."""
+    under).  The output buffer starts as NaN and the entry poisons the output planes: an element no workgroup stored is a NaN.
+    expect_range: which of the two range counters the launch must leave non-zero (range_class); default: none."""
     import conv_cases as CC
     cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
     assert len(res) == nres
@@ -601,7 +603,7 @@ def conv_launch(precision, case, x, w, b, res):
     finally:
         _lib.check(lib.sta_set_gemm_variant(h, 0))
     rng = tuple(m.range_report(reset=True))
-    assert rng == (0, 0), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}"
+    assert range_class(rng) == range_class(expect_range), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}, expected class {range_class(expect_range)}"
     return out.cpu().numpy(), CC.conv_class(plan, Cin, stride, CC.EPI_NAME[(relu_in, act, nres)])
 
 
@@ -657,9 +659,9 @@ def check_conv_classes(precision, case, seed=32):
     return {"class": ran, "nan": int(np.isnan(got).sum()), "rel_l2": rel_l2(got, ref), "errs": errs, "worst": HP.worst_class(errs)}
 
 
-def tail_launch(precision, hcase, nA, x, w2, b2, w4, b4):
+def tail_launch(precision, hcase, nA, x, w2, b2, w4, b4, expect_range=(0, 0)):
     """sta_debug_conv3_head on numpy inputs -> (pts [n, H, W, 3], conf [n, H, W], class).  The two output pairs are separate
-    allocations of exactly nA and n - nA images, NaN before the launch."""
+    allocations of exactly nA and n - nA images, NaN before the launch.  expect_range: as conv_launch."""
     import conv_cases as CC
     cid, n, H, W_, variant, w4scale, cls = hcase
     m, lib, h = kernel_handle(precision, variant)
@@ -675,7 +677,7 @@ def tail_launch(precision, hcase, nA, x, w2, b2, w4, b4):
     finally:
         _lib.check(lib.sta_set_gemm_variant(h, 0))
     rng = tuple(m.range_report(reset=True))
-    assert rng == (0, 0), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}"
+    assert range_class(rng) == range_class(expect_range), f"{cid} {precision}: range events (fp16 saturations, fp8 correction saturations) = {rng}, expected class {range_class(expect_range)}"
     return torch.cat([pa, pb]).cpu().numpy(), torch.cat([ca, cb]).cpu().numpy(), CC.conv_class(plan, 128, 1, "head")
 
 
@@ -732,3 +734,123 @@ def check_tail_exact(precision, hcase, nA):
     up, wp = ulps(pts, rp)
     uc, wc = ulps(conf, rc)
     return {"class": ran, "nan": int(np.isnan(pts).sum() + np.isnan(conf).sum()), "pts_ulp": up, "pts_worst": wp, "conf_ulp": uc, "conf_worst": wc}
+
+
+# ---- tests/test_range_gpu.py: one launch of a debug entry between two resets of the handle's range counters
+def with_range(m, launch):
+    """Reset the range counters, run launch(), synchronise -> (what launch returned, (fp16 events, fp8 events))."""
+    m.range_report(reset=True)
+    r = launch()
+    torch.cuda.synchronize()
+    return r, tuple(m.range_report(reset=True))
+
+
+def range_gemm(precision, A, Wt, b, act=0, via_f16=1, variant=0):
+    """sta_debug_gemm on numpy operands -> (out [M, N] float32, report, plan of the launch)."""
+    m, lib, h = kernel_handle(precision, variant)
+    M, K = A.shape
+    N = Wt.shape[0]
+    Ad, Wd, bd = dev(A), dev(Wt), dev(b)
+    out = torch.full((M, N), float("nan"), device=DEV)
+    try:
+        _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_gemm(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, act, via_f16,
+                                                                     None, out.data_ptr(), st())))
+        plan = last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    return out.cpu().numpy(), rng, plan
+
+
+def range_convt(precision, x, w, b, k):
+    """sta_debug_convt on numpy NHWC x, w [C, C, k, k], b [C] -> (out [n, kH, kW, C], report, plan)."""
+    m, lib, h = kernel_handle(precision)
+    n, H, W_, Cd = x.shape
+    xd, wd, bd = dev(x), dev(w), dev(b)
+    out = torch.full((n, H * k, W_ * k, Cd), float("nan"), device=DEV)
+    _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_convt(h, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), n, H, W_, Cd, k, out.data_ptr(), st())))
+    return out.cpu().numpy(), rng, last_plan(lib, h)
+
+
+def range_up2(precision, x, Hc, Wc):
+    """sta_debug_up2 on numpy NHWC x -> (out [n, Hc, Wc, C], report)."""
+    m, lib, h = kernel_handle(precision)
+    n, H, W_, Cd = x.shape
+    xd = dev(x)
+    out = torch.full((n, Hc, Wc, Cd), float("nan"), device=DEV)
+    _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_up2(h, xd.data_ptr(), n, H, W_, Cd, Hc, Wc, out.data_ptr(), st())))
+    return out.cpu().numpy(), rng
+
+
+def range_layernorm(precision, x, g, b, eps):
+    """sta_debug_layernorm (ln_kernel) -> (fp32 output, value of the planes, report)."""
+    m, lib, h = kernel_handle(precision)
+    M, Cd = x.shape
+    xd, gd, bd = dev(x), dev(g), dev(b)
+    o32 = torch.zeros(M, Cd, device=DEV); op = torch.zeros(M, Cd, device=DEV)
+    _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_layernorm(h, xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), M, Cd, eps,
+                                                                      o32.data_ptr(), op.data_ptr(), st())))
+    return o32.cpu().numpy(), op.cpu().numpy(), rng
+
+
+def range_resid_ln(precision, A, Wt, b, x, g1, b1, eps):
+    """sta_debug_gemm_resid_ln with one affine set -> (x' [M, N], value of the planes, report, plan)."""
+    m, lib, h = kernel_handle(precision)
+    M, K = A.shape
+    N = Wt.shape[0]
+    Ad, Wd, bd, xd, gd, b1d = dev(A), dev(Wt), dev(b), dev(x.copy()), dev(g1), dev(b1)
+    o1 = torch.zeros(M, N, device=DEV)
+    _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_gemm_resid_ln(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), xd.data_ptr(), M, N, K,
+                                                                          gd.data_ptr(), b1d.data_ptr(), None, None, eps, o1.data_ptr(), None, st())))
+    return xd.cpu().numpy(), o1.cpu().numpy(), rng, last_plan(lib, h)
+
+
+def range_qkv_rope(precision, x, Wt, b, S, ntok, Cdim, wp):
+    """sta_debug_qkv_rope in the decoder's row order (x = [S*ntok patch rows | S pose rows]) -> (q, k [S, heads, ntok + 1, 64],
+    v^T [S, heads, 64, npad], report, plan)."""
+    m, lib, h = kernel_handle(precision)
+    K = x.shape[1]
+    heads, nt = Cdim // 64, ntok + 1
+    npad = (nt + 63) // 64 * 64
+    q = torch.full((S, heads, nt, 64), float("nan"), device=DEV)
+    k = torch.full_like(q, float("nan"))
+    vt = torch.full((S * heads * 64, npad), float("nan"), device=DEV)
+    xd, Wd, bd = dev(x), dev(Wt), dev(b)
+    _, rng = with_range(m, lambda: _lib.check(lib.sta_debug_qkv_rope(h, xd.data_ptr(), Wd.data_ptr(), bd.data_ptr(), S, ntok, K, Cdim, wp, 2,
+                                                                     q.data_ptr(), k.data_ptr(), vt.data_ptr(), st())))
+    return q.cpu().numpy(), k.cpu().numpy(), vt.cpu().numpy().reshape(S, heads, 64, npad), rng, last_plan(lib, h)
+
+
+def range_attention(precision, q, k, v, pose=False):
+    """sta_debug_attention (q [S, heads, nq, 64], k / v [S, heads, nk, 64] -> out [S, nq, heads*64]) or, pose=True,
+    sta_debug_attention_pose (q, k, v [S, heads, n + 1, 64] -> out [S*n + S, heads*64]) -> (out, report)."""
+    m, lib, h = kernel_handle(precision)
+    S, heads, nq, _ = q.shape
+    nk = k.shape[2]
+    qd, kd, vd = dev(q), dev(k), dev(v)
+    if pose:
+        out = torch.full((S * nq, heads * 64), float("nan"), device=DEV)
+        fn = lambda: _lib.check(lib.sta_debug_attention_pose(h, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), S, heads, nq - 1, 0, out.data_ptr(), st()))
+    else:
+        out = torch.full((S, nq, heads * 64), float("nan"), device=DEV)
+        fn = lambda: _lib.check(lib.sta_debug_attention(h, qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), S, heads, nq, nk, 0, out.data_ptr(), st()))
+    _, rng = with_range(m, fn)
+    return out.cpu().numpy(), rng
+
+
+def range_rope(precision, entry, bufs, pos, pos_max, **kw):
+    """One of the three rotation entries on numpy buffers (rotated in place, returned as hi + lo) -> ([buffers], report).
+    entry "tokens" (S1, S2, heads, na, nb, which), "enc" (S, heads, ntok), "varlen" (S, heads, n: list)."""
+    m, lib, h = kernel_handle(precision)
+    d = [dev(b) for b in bufs]
+    table = dev(np.ascontiguousarray(pos, np.int32))
+    ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in d])
+    if entry == "tokens":
+        fn = lambda: _lib.check(lib.sta_debug_rope_tokens(h, ptrs, len(d), kw["S1"], kw["S2"], kw["heads"], kw["na"], kw["nb"], table.data_ptr(),
+                                                          pos_max, kw["which"], st()))
+    elif entry == "enc":
+        fn = lambda: _lib.check(lib.sta_debug_rope_enc_tokens(h, ptrs, len(d), kw["S"], kw["heads"], kw["ntok"], table.data_ptr(), pos_max, 0, st()))
+    else:
+        n = (C.c_int * len(kw["n"]))(*kw["n"])
+        fn = lambda: _lib.check(lib.sta_debug_rope_varlen(h, ptrs, len(d), kw["S"], kw["heads"], n, table.data_ptr(), pos_max, st()))
+    _, rng = with_range(m, fn)
+    return [t.cpu().numpy() for t in d], rng
