@@ -143,6 +143,7 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
  * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_decode_varlen (a plan per set of counts), sta_encode_tokens[_u8hwc] (a plan per token count),
+ * sta_encode_varlen[_u8hwc] (a plan per set of counts; its RoPE table grows with the largest patch grid of a call),
  * sta_view_consistency (pair matrices per view count and window),
  * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
  * sta_ray_depth (one K^-1 per view). */
@@ -214,6 +215,25 @@ STA_API int sta_encode(sta_handle* h, const float* img_dev, int B, int H, int W,
  * pointers, N < 1, H / W not multiples of 16, or 2^31 or more rows. */
 STA_API int sta_encode_tokens(sta_handle* h, const float* img_dev, const int64_t* pos, int B, int H, int W, int N,
                       float* feat_dev, void* stream);
+
+/* sta_encode_tokens on a batch whose ENTRIES differ in token count and frame size: the encoder in front of sta_decode_varlen.  Batch
+ * entries of the reference's encoder never interact (attention is per sample), so entry b is what sta_encode_tokens computes for that
+ * entry alone at B = 1 (patch_embed, the gather, every Block with the gathered positions: sta_model.py:163-174,
+ * sta_blocks.py:129-148,166-169); nothing is padded and no token attends to another entry's.
+ * imgs / H / W / n: HOST arrays [B] (they size the launches and travel in the kernel arguments: the call copies nothing to the device
+ * for them and does not synchronise it).  imgs[b]: device pointer to entry b's own frame, fp32 [3, H[b], W[b]]; n[b] >= 1 its token
+ * count.  pos: device int64 [sum(n), 2] of (y, x), packed entry-major; entry b's positions live in its own grid H[b]/16 x W[b]/16, any
+ * order, repeats allowed, each axis clamped into that grid as in sta_encode_tokens.  feat_dev [sum(n), enc_dim], packed the same way,
+ * no final norm.  1 <= B <= 32.
+ * Implementation: rows are packed, so the gather, the patch embedding, every LayerNorm, proj, the MLP and the residual epilogues are one
+ * launch over all rows.  Per layer the QKV projection is ONE dense GEMM over all rows into an fp32 workspace; a sequence-aware finishing
+ * kernel rotates Q / K from the positions table and writes the head-major Q / K / V^T buffers, one sequence after the other; attention
+ * is one launch for all sequences, each with its own count and schedule (attn_varlen_kernel, encoder form: no pose token).
+ * Like sta_encode_tokens / sta_decode_varlen the call runs on one lane and is NOT covered by sta_reserve: the first call of a set of
+ * counts may allocate.  Returns -1 with a message for null pointers, a count below 1, B outside [1, 32], H or W not multiples of 16,
+ * or 2^31 or more rows. */
+STA_API int sta_encode_varlen(sta_handle* h, const float* const* imgs, const int* H, const int* W, const int64_t* pos, const int* n,
+                      int B, float* feat_dev, void* stream);
 
 /* enc_norm (the encoder's final LayerNorm) on `rows` token rows of enc_dim floats: what
  * _encode_image(normalize=True) adds after the blocks (sta_model.py:172-173).  The forward / SLAM paths call
@@ -309,6 +329,10 @@ STA_API int sta_encode_u8hwc(sta_handle* h, const uint8_t* img_dev, int B, int H
  * to sta_encode_tokens on the normalised fp32 NCHW tensor. */
 STA_API int sta_encode_tokens_u8hwc(sta_handle* h, const uint8_t* img_dev, const int64_t* pos, int B, int H, int W, int N,
                             float* feat_dev, void* stream);
+/* sta_encode_varlen on camera-format frames: imgs[b] [H[b], W[b], 3] uint8, 16-byte aligned; bit-identical to sta_encode_varlen on the
+ * normalised fp32 frames. */
+STA_API int sta_encode_varlen_u8hwc(sta_handle* h, const uint8_t* const* imgs, const int* H, const int* W, const int64_t* pos, const int* n,
+                            int B, float* feat_dev, void* stream);
 STA_API int sta_forward_pair_u8hwc(sta_handle* h, const uint8_t* img_a, const uint8_t* img_b, int B, int H, int W,
                            float* const pts[2], float* const conf[2],
                            float* const pose[2], float* const pose_conf[2], void* stream);

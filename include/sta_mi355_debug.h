@@ -131,6 +131,34 @@ STA_API int sta_debug_attn_varlen_plan(int S, int heads, const int* nq, const in
 STA_API int sta_debug_last_attn_varlen_plan(sta_handle* h, int* out);
 STA_API int sta_debug_attn_varlen_block_map(int S, int heads, const int* nq, const int* nk, int* out);
 
+/* Encoder form of the per-sequence attention (sta_encode_varlen: attn_varlen_kernel under attn_encv_plan): S <= 32 sequences, sequence s
+ * with n[s] queries over its own n[s] keys (HOST array), NO pose token.  q / k / v: sequence after sequence [heads, n[s], 64].  The
+ * buffers are the encoder's, npad = roundup(max(n), 64): n[s] may equal npad.  out [sum(n) + 64, heads*64]: the packed rows, then a guard
+ * block that lies directly behind the output planes, every byte 0x3C on entry.  Poisons like sta_debug_attn_varlen. */
+STA_API int sta_debug_attn_encv(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads, const int* n,
+                                float* out, void* stream);
+/* Its launch plan (pure host function; sta_launch.inc: attn_encv_plan) in the record of sta_debug_attn_varlen_plan - pose mode, pose
+ * blocks, pose scratch and first pose block are 0, output rows are packed n[s] per sequence -; the record of the handle's last such
+ * launch; and the kernel's workgroup map: out[3*b + 0..2] = (sequence, head, query block) of query-block workgroup b. */
+STA_API int sta_debug_attn_encv_plan(int S, int heads, const int* n, int split, int no_prefetch, int* out);
+STA_API int sta_debug_last_attn_encv_plan(sta_handle* h, int* out);
+STA_API int sta_debug_attn_encv_block_map(int S, int heads, const int* n, int* out);
+
+/* The QKV finisher of sta_encode_varlen alone (qkv_finish_kernel, VARLEN form): n HOST array [S] of token counts; slab device fp32
+ * [sum(n), 3*heads*64] = the q | k | v rows a dense QKV GEMM left; bias device fp32 [3*heads*64] or NULL; pos_i32 device int32
+ * [sum(n)*2] of (y, x), packed, clamped to [0, pos_max].  q / k: fp32 [S*heads + 1][npad][64], vt: fp32 [S*heads + 1][64][npad], npad =
+ * roundup(max(n), 64) - the encoder's Q / K / V^T layout and ONE guard block behind each; every element (the guards' too) is split to fp16
+ * planes inside, the kernel writes the planes and everything is returned as hi + lo.  Rows [n[s], npad) of Q / K, columns [n[s], npad)
+ * of V^T (NOT zeroed by this entry) and the guards are not touched. */
+STA_API int sta_debug_qkv_finish_varlen(sta_handle* h, const float* slab, const float* bias, const int* pos_i32, int S, int heads,
+                                        const int* n, int pos_max, float* q, float* k, float* vt, void* stream);
+
+/* The gather of sta_encode_varlen alone: imgs / H / W / n HOST arrays [B] as in sta_encode_varlen (u8hwc != 0: uint8 HWC frames);
+ * pos_i32 device int32 [sum(n)*2] of (y, x), packed, already inside each entry's grid; out fp32 [sum(n), 768] = the patch rows as
+ * hi + lo.  which = 0: the varlen form (one launch); 1: sta_encode_tokens' form of the same kernel, one launch per entry. */
+STA_API int sta_debug_patch_gather_varlen(sta_handle* h, const void* const* imgs, int u8hwc, const int* H, const int* W,
+                                          const int* pos_i32, const int* n, int B, int which, float* out, void* stream);
+
 /* The rotation step of sta_decode_varlen alone (rope_varlen_kernel): n HOST array [S] of token counts.  bufs[b] (nbuf 1..3): fp32
  * [S*heads + 1][npad][64], npad = roundup(max(n) + 1, 64) - the decoder's Q / K layout and ONE guard block behind it; every row (the
  * guard's too) is split to fp16 planes inside, the buffer is rotated IN PLACE and everything is returned as hi + lo.  Token index n[s]
@@ -170,7 +198,9 @@ STA_API int sta_debug_attn_block_map(int nwg, int* out);
  * f16x3h - the kernels that precision uses inside the head.  A/B switches of round-4 choices: 1 = 1 small-grid K slices by the
  * old rule; 2 = 1 small-grid GEMMs always on 4 waves; 5 = 1 attention without the 4-stage prefetch schedule; 6 = 1 no side
  * lanes (2: always); 7 = 1 bilinear one output row per workgroup; 3 = 1 sta_decode_tokens rotates Q / K by per-buffer
- * rope_planes_kernel launches (one per buffer and side: eight per decoder layer) instead of the two rope_tokens_kernel launches. */
+ * rope_planes_kernel launches (one per buffer and side: eight per decoder layer) instead of the two rope_tokens_kernel launches;
+ * 8 = 1 sta_encode_varlen runs its QKV GEMM once per sequence with the fused epilogue plus one no-pose rope_varlen_kernel launch per
+ * layer (sta_decode_varlen's way) instead of one dense GEMM and the varlen finisher. */
 STA_API int sta_debug_set_option(sta_handle* h, int idx, int value);
 
 /* Row-tail hint for the dense GEMMs (what the decoder sets to its 2B pose-token rows): the last `rows` (<= 32) rows of the

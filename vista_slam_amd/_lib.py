@@ -60,6 +60,8 @@ SIGNATURES = {
     "sta_encode_u8hwc": (_i, [_vp, _fp, _i, _i, _i, _fp, _vp]),
     "sta_encode_tokens": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _fp, _vp]),
     "sta_encode_tokens_u8hwc": (_i, [_vp, _fp, _vp, _i, _i, _i, _i, _fp, _vp]),
+    "sta_encode_varlen": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), _i, _fp, _vp]),
+    "sta_encode_varlen_u8hwc": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), _i, _fp, _vp]),
     "sta_encoder_norm": (_i, [_vp, _fp, C.c_int64, _fp, _vp]),
     "sta_forward_pair_u8hwc": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                     C.POINTER(_vp), _vp]),
@@ -119,6 +121,12 @@ TEST_SIGNATURES = {
     "sta_debug_attn_varlen_plan": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_i)]),
     "sta_debug_last_attn_varlen_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_attn_varlen_block_map": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "sta_debug_attn_encv": (_i, [_vp, _fp, _fp, _fp, _i, _i, C.POINTER(_i), _fp, _vp]),
+    "sta_debug_attn_encv_plan": (_i, [_i, _i, C.POINTER(_i), _i, _i, C.POINTER(_i)]),
+    "sta_debug_last_attn_encv_plan": (_i, [_vp, C.POINTER(_i)]),
+    "sta_debug_attn_encv_block_map": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "sta_debug_qkv_finish_varlen": (_i, [_vp, _fp, _fp, _vp, _i, _i, C.POINTER(_i), _i, _fp, _fp, _fp, _vp]),
+    "sta_debug_patch_gather_varlen": (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), _i, _i, _fp, _vp]),
     "sta_debug_rope_varlen": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, C.POINTER(_i), _vp, _i, _vp]),
     "sta_debug_rope_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sta_debug_rope_enc_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _vp]),

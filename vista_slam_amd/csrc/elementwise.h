@@ -4,6 +4,7 @@
 // All reductions are wave64 shuffles; all loads/stores are 8-16 B per lane.
 #pragma once
 #include "sta_common.h"
+#include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm (eps inside sqrt, affine) over fp32 rows -> fp16 hi/lo planes; up to two affine sets
@@ -298,20 +299,53 @@ __global__ __launch_bounds__(256) void enc_tokens_table_kernel(const int64_t* po
     } else if (i - n < n_ident) ident[i - n] = make_float2(1.f, 0.f);
 }
 
+// sta_encode_varlen: the entries of a call in the kernel arguments - entry s has its own frame img[s] of H[s] x W[s] pixels and the
+// tokens [t.tok0[s], t.tok0[s + 1]) of the packed order.  A thread finds the entry of a token by a scan over at most SEQ_MAX entries
+// (uniform indices: scalar loads of the argument segment).  NoEntries: the equal-count forms, which carry no table.
+struct NoEntries {};
+struct EncEntries { SeqTable t; const void* img[SEQ_MAX]; int H[SEQ_MAX]; int W[SEQ_MAX]; };
+
+// sta_encode_varlen: enc_tokens_table_kernel with one grid per entry: pos [tok0[S]*2] int64 (y, x), packed entry-major -> int32, entry
+// s clamped into ITS grid H[s]/16 x W[s]/16; the tail of the grid fills the identity cos / sin table (the per-sequence QKV route).
+__global__ __launch_bounds__(256) void enc_varlen_table_kernel(const int64_t* pos, EncEntries e, int* out, float2* ident, int64_t n_ident) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, n = (int64_t)e.t.tok0[e.t.S] * 2;
+    if (i < n) {
+        const int64_t tok = i >> 1;
+        int H = e.H[0], W = e.W[0];
+        for (int q = 1; q < e.t.S; ++q) if (e.t.tok0[q] <= tok) { H = e.H[q]; W = e.W[q]; }
+        const int64_t hi = (i & 1) ? W / 16 - 1 : H / 16 - 1;
+        int64_t v = pos[i];
+        v = v < 0 ? 0 : (v > hi ? hi : v);
+        out[i] = (int)v;
+    } else if (i - n < n_ident) ident[i - n] = make_float2(1.f, 0.f);
+}
+
 // sta_encode_tokens: patch_gather_kernel for a token SUBSET.  Token tok = b * N + t of the output is the patch at pos[tok] = (py, px)
 // of image b (int32 table [B][N][2], already inside the grid: enc_tokens_table_kernel); only the selected patches are read.  Same
 // thread decomposition, accesses and arithmetic as patch_gather_kernel: equal pixel values give equal planes.
-template <bool SPLIT>
-__global__ void patch_gather_tokens_kernel(const float* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng) {
-    const int64_t total = (int64_t)n * N * 48;
+// V = EncEntries (sta_encode_varlen): the packed tokens of entries with their own frames - img / n / N / H / W are not read, a token
+// takes frame and frame size from its entry of the table `ent`.
+template <bool SPLIT, typename V = NoEntries>
+__global__ void patch_gather_tokens_kernel(const float* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng, V ent = V{}) {
+    constexpr bool VARLEN = std::is_same<V, EncEntries>::value;
+    int64_t total = (int64_t)n * N * 48;
+    if constexpr (VARLEN) total = (int64_t)ent.t.tok0[ent.t.S] * 48;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
     for (; i < total; i += step) {
         int ck = (int)(i % 48); int64_t tok = i / 48;
         int c = ck / 16, ky = ck % 16;
         const int2 yx = *reinterpret_cast<const int2*>(pos + tok * 2);
-        const int py = yx.x, px = yx.y; const int b = (int)(tok / N);
-        const float* src = img + (((int64_t)b * 3 + c) * H + py * 16 + ky) * W + px * 16;
+        const int py = yx.x, px = yx.y;
+        const float* src;
+        if constexpr (VARLEN) {
+            const void* im = ent.img[0]; int He = ent.H[0], We = ent.W[0];
+            for (int q = 1; q < ent.t.S; ++q) if (ent.t.tok0[q] <= tok) { im = ent.img[q]; He = ent.H[q]; We = ent.W[q]; }
+            src = (const float*)im + ((int64_t)c * He + py * 16 + ky) * We + px * 16;
+        } else {
+            const int b = (int)(tok / N);
+            src = img + (((int64_t)b * 3 + c) * H + py * 16 + ky) * W + px * 16;
+        }
         H8 h0, h1, l0, l1;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -333,16 +367,27 @@ __global__ void patch_gather_tokens_kernel(const float* img, const int* pos, int
 
 // ... and patch_gather_u8hwc_kernel for a token subset: one thread = one (token, ky) row of 48 contiguous bytes, the ImgNorm fused
 // with the same operation order, so the result is bit-identical to patch_gather_tokens_kernel on the normalised fp32 NCHW image.
-template <bool SPLIT>
-__global__ void patch_gather_tokens_u8hwc_kernel(const uint8_t* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng) {
-    const int64_t total = (int64_t)n * N * 16;
+template <bool SPLIT, typename V = NoEntries>
+__global__ void patch_gather_tokens_u8hwc_kernel(const uint8_t* img, const int* pos, int n, int N, int H, int W, f16* o_hi, f16* o_lo, int64_t orows, unsigned long long* rng, V ent = V{}) {
+    constexpr bool VARLEN = std::is_same<V, EncEntries>::value;
+    int64_t total = (int64_t)n * N * 16;
+    if constexpr (VARLEN) total = (int64_t)ent.t.tok0[ent.t.S] * 16;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
     for (; i < total; i += step) {
         const int ky = (int)(i % 16); const int64_t tok = i / 16;
         const int2 yx = *reinterpret_cast<const int2*>(pos + tok * 2);
-        const int py = yx.x, px = yx.y; const int b = (int)(tok / N);
-        const uint8_t* src = img + (((int64_t)b * H + py * 16 + ky) * W + px * 16) * 3;   // 48 B, 16-B aligned (W % 16 == 0)
+        const int py = yx.x, px = yx.y;
+        const uint8_t* src;
+        if constexpr (VARLEN) {
+            const void* im = ent.img[0]; int He = ent.H[0], We = ent.W[0];
+            for (int q = 1; q < ent.t.S; ++q) if (ent.t.tok0[q] <= tok) { im = ent.img[q]; He = ent.H[q]; We = ent.W[q]; }
+            src = (const uint8_t*)im + (((int64_t)py * 16 + ky) * We + px * 16) * 3;
+            (void)He;
+        } else {
+            const int b = (int)(tok / N);
+            src = img + (((int64_t)b * H + py * 16 + ky) * W + px * 16) * 3;   // 48 B, 16-B aligned (W % 16 == 0)
+        }
         union { uint4 v[3]; uint8_t e[48]; } raw;
         raw.v[0] = ldg16(src); raw.v[1] = ldg16(src + 16); raw.v[2] = ldg16(src + 32);
 #pragma unroll
@@ -497,8 +542,7 @@ __global__ __launch_bounds__(256) void rope_tokens_kernel(RopeTokParams p) {
 // patch tokens of the sequences before s (side 1's entries, then side 2's), tok0[S] = all of them; sequence s has n_s = tok0[s + 1]
 // - tok0[s] tokens.  Decoder rows (x and every plane buffer derived from it) are packed [n_s patch rows | pose row] per sequence:
 // sequence s starts at row tok0[s] + s.  A thread finds its sequence by a scan over at most SEQ_MAX entries.
-#define SEQ_MAX 32
-struct SeqTable { int S; int tok0[SEQ_MAX + 1]; };
+// (SEQ_MAX, SeqTable: sta_common.h)
 __device__ __forceinline__ int seq_of_row(const SeqTable& t, int64_t row) {      // row in the packed order above
     int s = 0;
     for (int i = 1; i < t.S; ++i) if ((int64_t)t.tok0[i] + i <= row) s = i;
@@ -543,22 +587,26 @@ struct RopeVarlenParams {
     const int* pos; const float* tab; unsigned long long* rng;
     SeqTable t;
 };
-template <bool SPLIT>
+// POSE = false (sta_encode_varlen, per-sequence QKV route): the encoder's buffers have no pose row - exactly n_s rows per (sequence,
+// head), every one from the table (rope_tokens_kernel's POSE = false, and for the same reason: with n_s == npad row n_s is another
+// head's row 0).  POSE = true is the decoder's form (the same instructions as before the flag existed).
+template <bool SPLIT, bool POSE = true>
 __global__ __launch_bounds__(256) void rope_varlen_kernel(RopeVarlenParams p) {
+    constexpr int PR = POSE ? 1 : 0;                   // rows per (sequence, head): n_s + PR
     const int b = blockIdx.y;
     f16* hi = b == 0 ? p.hi[0] : (b == 1 ? p.hi[1] : p.hi[2]);
     f16* lo = b == 0 ? p.lo[0] : (b == 1 ? p.lo[1] : p.lo[2]);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t rows = ((int64_t)p.t.tok0[p.t.S] + p.t.S) * p.heads;       // (sequence, head, token) rows, sequence-major
+    const int64_t rows = ((int64_t)p.t.tok0[p.t.S] + p.t.S * PR) * p.heads;       // (sequence, head, token) rows, sequence-major
     if (i >= rows * 4) return;
     const int j = (int)(i & 3), xp = j >> 1, f0 = (j & 1) * 8;
     int64_t r = i >> 2;
     int s = 0;
-    for (int q = 1; q < p.t.S; ++q) if (((int64_t)p.t.tok0[q] + q) * p.heads <= r) s = q;
-    r -= ((int64_t)p.t.tok0[s] + s) * p.heads;
+    for (int q = 1; q < p.t.S; ++q) if (((int64_t)p.t.tok0[q] + q * PR) * p.heads <= r) s = q;
+    r -= ((int64_t)p.t.tok0[s] + s * PR) * p.heads;
     const int ntok = p.t.tok0[s + 1] - p.t.tok0[s];
-    const int tk = (int)(r % (ntok + 1)), hd = (int)(r / (ntok + 1));
-    const int ps = tk < ntok ? p.pos[((int64_t)p.t.tok0[s] + tk) * 2 + xp] : -1;
+    const int tk = (int)(r % (ntok + PR)), hd = (int)(r / (ntok + PR));
+    const int ps = (!POSE || tk < ntok) ? p.pos[((int64_t)p.t.tok0[s] + tk) * 2 + xp] : -1;
     const float4* tab = reinterpret_cast<const float4*>(p.tab + ((size_t)(ps + 1) * 16 + f0) * 2);
     const int64_t o = (((int64_t)s * p.heads + hd) * p.npad + tk) * 64 + xp * 32 + f0;
     union { float4 v[4]; float2 e[8]; } cs;

@@ -20,6 +20,7 @@
 // and the curope rotary kernel (pos_embed/curope/kernels.cu:17-82) fused into the QK epilogue.
 #pragma once
 #include "sta_common.h"
+#include <type_traits>
 
 enum { A_DENSE = 0, A_CONV3 = 1 };
 enum { EPI_F32 = 0, EPI_F16 = 1, EPI_QKV = 2, EPI_CONVT = 3,
@@ -559,8 +560,109 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const floatx1
 // bias, rotates Q / K (RoPE pairs (d, d+16) sit in lanes l and l^16 of a wave: a wave is one 64-column head of one row) and
 // writes head-major Q / K and V^T exactly like epilogue_qkv_tile.  Threads [0, M*(nq+nk)): one Q/K element each;
 // threads after that: one V column x 4 consecutive rows each (one 8-byte run of V^T).
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void qkv_finish_kernel(const GemmParams p) {
+//
+// The VARLEN form (P = QkvVarlenParams; sta_encode_varlen): the finisher of ONE dense QKV GEMM over the packed rows of sequences with
+// their own token counts.  The GEMM left fp32 q | k | v rows in `slab` ([M, 3E], row stride lds; the bias already added, or in `bias`);
+// this kernel writes what the fused epilogue cannot write across sequence boundaries: Q and K [S][heads][npad][64], rotated by the
+// int32 positions table (packed like the rows), and V^T [S][heads][64][npad] - the encoder's layout, no pose row.  Grid (tiles x
+// heads, 3): blockIdx.y = 0: Q, 1: K, 2: V; a tile is 64 tokens x 64 dims of one head and never straddles a sequence - tile index ->
+// (sequence, first token) by a scan of the SeqTable over sum_s ceil(n_s / 64) tiles (block-uniform: scalar registers).
+//   Q / K: rope_tokens_kernel's decomposition - one thread = eight frequencies of one (token, y | x half): 4 x 32 B of fp32 in, the
+//          eight (cos, sin) entries as four 16-byte loads of one table row, two 16-byte stores per plane out.
+//   V:     a thread reads float4s (four d of one token), the tile is transposed in LDS ([d][token], 144-byte rows) and V^T leaves as
+//          16-byte runs of eight tokens: 128 contiguous bytes per d row and plane.  The only arithmetic on that path is + bias.
+// Rows [n_s, npad) of Q and K and columns [n_s, npad) of V^T are not written (the caller zeroes the V^T planes once per call).
+struct QkvVarlenParams {
+    const float* slab; int64_t lds;                      // fp32 [M, 3E], row stride in floats
+    const float* bias;                                   // [3E], or nullptr: the GEMM added it
+    int E, heads, npad;
+    const int* pos; const float* rope_tab;               // [M][2] (y, x) inside the table; [(pos + 1)][16][2] cos, sin
+    f16* Q_hi; f16* Q_lo; f16* K_hi; f16* K_lo; f16* Vt_hi; f16* Vt_lo;
+    unsigned long long* range;
+    SeqTable t;
+};
+template <bool SPLIT, typename P = GemmParams>
+__global__ __launch_bounds__(256) void qkv_finish_kernel(const P p) {
+    if constexpr (std::is_same<P, QkvVarlenParams>::value) {
+        __shared__ __attribute__((aligned(16))) f16 vt_lds[2][64][72];
+        const int tid = threadIdx.x, head = blockIdx.x % p.heads, tile = blockIdx.x / p.heads, seg = blockIdx.y;
+        int s = 0, tile0 = 0, acc = 0;
+        for (int q = 0; q < p.t.S; ++q) {
+            if (acc <= tile) { s = q; tile0 = acc; }
+            acc += (p.t.tok0[q + 1] - p.t.tok0[q] + 63) >> 6;
+        }
+        const int n = p.t.tok0[s + 1] - p.t.tok0[s], t0 = (tile - tile0) * 64;
+        const int live = n - t0 < 64 ? n - t0 : 64;                   // tokens of this tile: 1 .. 64
+        const int64_t row0 = (int64_t)p.t.tok0[s] + t0;               // packed row of the tile's first token
+        RangeAcc ra;
+        if (seg < 2) {
+            const int tk = tid >> 2, j = tid & 3, xp = j >> 1, f0 = (j & 1) * 8;
+            if (tk < live) {
+                const int col = seg * p.E + head * 64 + xp * 32 + f0;
+                const float* src = p.slab + (row0 + tk) * p.lds + col;
+                union { float4 v[2]; float e[8]; } a, b;              // pair (d, d + 16): a = d f0 .. f0 + 7 of the half, b = the partners
+                a.v[0] = *reinterpret_cast<const float4*>(src); a.v[1] = *reinterpret_cast<const float4*>(src + 4);
+                b.v[0] = *reinterpret_cast<const float4*>(src + 16); b.v[1] = *reinterpret_cast<const float4*>(src + 20);
+                if (p.bias) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { a.e[e] += p.bias[col + e]; b.e[e] += p.bias[col + 16 + e]; }
+                }
+                const int ps = p.pos[(row0 + tk) * 2 + xp];
+                const float4* tab = reinterpret_cast<const float4*>(p.rope_tab + ((size_t)(ps + 1) * 16 + f0) * 2);
+                union { float4 v[4]; float2 e[8]; } cs;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) cs.v[q] = tab[q];
+                H8 h0, h1, l0, l1;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v0 = a.e[e], v1 = b.e[e];
+                    const float r0 = v0 * cs.e[e].x - v1 * cs.e[e].y, r1 = v1 * cs.e[e].x + v0 * cs.e[e].y;
+                    if (SPLIT) { split_f16(r0, h0.e[e], l0.e[e], ra); split_f16(r1, h1.e[e], l1.e[e], ra); }
+                    else { h0.e[e] = to_f16_sat(r0, ra); h1.e[e] = to_f16_sat(r1, ra); }
+                }
+                f16* const dh = seg == 0 ? p.Q_hi : p.K_hi;
+                f16* const dl = seg == 0 ? p.Q_lo : p.K_lo;
+                const int64_t o = (((int64_t)s * p.heads + head) * p.npad + t0 + tk) * 64 + xp * 32 + f0;
+                *reinterpret_cast<uint4*>(dh + o) = h0.u; *reinterpret_cast<uint4*>(dh + o + 16) = h1.u;
+                if (SPLIT) { *reinterpret_cast<uint4*>(dl + o) = l0.u; *reinterpret_cast<uint4*>(dl + o + 16) = l1.u; }
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int idx = tid + 256 * k, tk = idx >> 4, d4 = (idx & 15) * 4;
+                if (tk < live) {
+                    const int col = 2 * p.E + head * 64 + d4;
+                    union { float4 v; float e[4]; } x;
+                    x.v = *reinterpret_cast<const float4*>(p.slab + (row0 + tk) * p.lds + col);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float val = p.bias ? x.e[e] + p.bias[col + e] : x.e[e];
+                        f16 hh, ll;
+                        if (SPLIT) split_f16(val, hh, ll, ra); else { hh = to_f16_sat(val, ra); ll = (f16)0; }
+                        vt_lds[0][d4 + e][tk] = hh;
+                        if (SPLIT) vt_lds[1][d4 + e][tk] = ll;
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int idx = tid + 256 * k, d = idx >> 3, c8 = (idx & 7) * 8;          // eight tokens c8 .. c8 + 7 of row d
+                const int64_t o = (((int64_t)s * p.heads + head) * 64 + d) * p.npad + t0 + c8;
+                if (c8 + 8 <= live) {
+                    *reinterpret_cast<uint4*>(p.Vt_hi + o) = *reinterpret_cast<const uint4*>(&vt_lds[0][d][c8]);
+                    if (SPLIT) *reinterpret_cast<uint4*>(p.Vt_lo + o) = *reinterpret_cast<const uint4*>(&vt_lds[1][d][c8]);
+                } else {
+                    for (int e = 0; c8 + e < live; ++e) {                              // the sequence's last run: columns >= n_s stay as they are
+                        p.Vt_hi[o + e] = vt_lds[0][d][c8 + e];
+                        if (SPLIT) p.Vt_lo[o + e] = vt_lds[1][d][c8 + e];
+                    }
+                }
+            }
+        }
+        ra.flush(p.range);
+        return;
+    } else {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int nqk = p.nq + p.nk;
     const int64_t n_qk = (int64_t)p.M * nqk;
@@ -621,6 +723,7 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(const GemmParams p) {
             }
         }
     }
+    }          // P = GemmParams
 }
 
 template <bool SPLIT, int AMODE, int EPI>

@@ -150,13 +150,14 @@ struct sta_handle {
     f16* zero_page = nullptr;
     unsigned long long* range = nullptr;   // the two range counters (sta_range_report): 16 B of device memory, per handle
     int small_grid_mode = 0;  // tools/tile_table.py only (sta_set_gemm_variant 10 / 11): 1 = never the small-grid family, 2 = 4x the product threshold
-    int opt[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // experiment switches (sta_debug_set_option; 0 = product behaviour)
+    int opt[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // experiment switches (sta_debug_set_option; 0 = product behaviour)
     int tail_hint = 0;      // decode_impl: the last tail_hint rows of every dense GEMM are pose-token rows (GemmParams::m_tail)
     int gemm_variant = 0;   // tests / tools: 0 auto, 1..4 forced GEMM families, 8 = conv3h wherever legal, 9 = auto WITHOUT conv3h (A/B)
     GemmPlan last_plan{};   // the plan of the last launch_gemm / paired launch (sta_debug_last_gemm_plan)
     AttnPlan last_attn{};   // the plan of the last run_attn (sta_debug_last_attn_plan)
     AttnMixedPlan last_attn_mixed{};   // ... of the last run_attn_mixed (sta_debug_last_attn_mixed_plan)
     AttnVarlenPlan last_attn_varlen{};   // ... of the last run_attn_varlen (sta_debug_last_attn_varlen_plan)
+    AttnVarlenPlan last_attn_encv{};     // ... of the last run_attn_encv (sta_debug_last_attn_encv_plan)
     // rope table
     float* rope_tab = nullptr; int rope_P = 0;
     // sta_decode_pos / sta_decode_tokens, for the duration of the call: the decoder's QKV epilogues rotate by the identity table and
@@ -712,6 +713,56 @@ extern "C" int sta_encode_tokens(sta_handle* h, const float* img_dev, const int6
 }
 extern "C" int sta_encode_tokens_u8hwc(sta_handle* h, const uint8_t* img_dev, const int64_t* pos, int B, int H, int W, int N, float* feat_dev, void* stream) {
     return encode_tokens_any(h, img_dev, true, pos, B, H, W, N, feat_dev, stream);
+}
+
+// _encode_image(normalize=False) on a batch whose ENTRIES differ in token count and frame size (encode_varlen_impl).  imgs / H / W / n
+// are HOST arrays [B]: they size the launches and travel in the kernel arguments.  The packed positions become one int32 table in the
+// workspace, every entry clamped into its own grid (enc_varlen_table_kernel); the tail of that launch fills the identity table the
+// per-sequence QKV route (experiment switch 8) rotates by in its epilogues.
+static int encode_varlen_any(sta_handle* h, const void* const* imgs, bool u8hwc, const int* H, const int* W, const int64_t* pos, const int* n, int B,
+                             float* feat_dev, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    REQUIRE(B >= 1 && B <= SEQ_MAX, "batch %d out of range (1 .. %d entries per call)", B, SEQ_MAX);
+    REQUIRE(imgs && H && W && n, "null entry array (imgs, H, W and n are host arrays of B entries)");
+    REQUIRE(pos && feat_dev, "null device pointer");
+    EncEntries e; memset(&e, 0, sizeof e);
+    e.t.S = B;
+    int64_t acc = 0; int nmax = 0, pmax = 0;
+    for (int b = 0; b < B; ++b) {
+        CHK(check_ready(h, B, H[b], W[b]));
+        REQUIRE(imgs[b], "null device pointer (frame of entry %d)", b);
+        REQUIRE(!u8hwc || ((uintptr_t)imgs[b] & 15) == 0, "u8 HWC image must be 16-byte aligned (entry %d)", b);
+        REQUIRE(n[b] >= 1, "bad argument (entry %d has %d tokens): a token subset has at least one token", b, n[b]);
+        e.img[b] = imgs[b]; e.H[b] = H[b]; e.W[b] = W[b];
+        e.t.tok0[b] = (int)acc; acc += n[b]; nmax = std::max(nmax, n[b]);
+        pmax = std::max(pmax, std::max(H[b], W[b]) / 16);
+        REQUIRE(acc < ((int64_t)1 << 31), "too many encoder rows (%lld or more)", (long long)acc);
+    }
+    e.t.tok0[B] = (int)acc;
+    hipStream_t st = (hipStream_t)stream;
+    CHK(ensure_rope(h, pmax));
+    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
+    h->rope_foreign = true;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        int* rp = (int*)ws.take(acc * 2 * 4);
+        const int64_t n_ident = (int64_t)(nmax + 2) * 16;        // each sequence is the grid 1 x n: table rows 0 .. max(n) + 1
+        float2* ident = (float2*)ws.take(n_ident * 8);
+        if (!h->dry) {
+            hipLaunchKernelGGL(enc_varlen_table_kernel, dim3((unsigned)((acc * 2 + n_ident + 255) / 256)), dim3(256), 0, st, pos, e, rp, ident, n_ident);
+            HIPCHK(hipGetLastError());
+            h->rope_pos = rp; h->rope_ident = (const float*)ident;
+        }
+        return encode_varlen_impl(h, ws, e, u8hwc, feat_dev, st);
+    });
+}
+extern "C" int sta_encode_varlen(sta_handle* h, const float* const* imgs, const int* H, const int* W, const int64_t* pos, const int* n, int B,
+                                 float* feat_dev, void* stream) {
+    return encode_varlen_any(h, (const void* const*)imgs, false, H, W, pos, n, B, feat_dev, stream);
+}
+extern "C" int sta_encode_varlen_u8hwc(sta_handle* h, const uint8_t* const* imgs, const int* H, const int* W, const int64_t* pos, const int* n, int B,
+                                       float* feat_dev, void* stream) {
+    return encode_varlen_any(h, (const void* const*)imgs, true, H, W, pos, n, B, feat_dev, stream);
 }
 
 extern "C" int sta_encoder_norm(sta_handle* h, const float* feat_dev, int64_t rows, float* out_dev, void* stream) {

@@ -171,3 +171,8 @@ __device__ __forceinline__ void store_mx1(f16* base, size_t o, float x, unsigned
 
 union H8 { uint4 u; half8 h; f16 e[8]; };
 union H4 { uint2 u; half4 h; f16 e[4]; };
+
+// The sequence structure of a varlen call (sta_decode_varlen, sta_encode_varlen), in the kernel arguments: tok0[s] = tokens of the
+// sequences before s, tok0[S] = all of them; sequence s has n_s = tok0[s + 1] - tok0[s] tokens (elementwise.h says how rows follow).
+#define SEQ_MAX 32
+struct SeqTable { int S; int tok0[SEQ_MAX + 1]; };

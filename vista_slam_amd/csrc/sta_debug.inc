@@ -359,6 +359,135 @@ extern "C" int sta_debug_rope_varlen(sta_handle* h, float* const* bufs, int nbuf
     return 0;
 }
 
+// The encoder form of the per-sequence attention (run_attn_encv): n HOST array [S]; q / k / v fp32, sequence after sequence
+// [heads, n[s], 64], NO pose token; every sequence reads its own keys.  npad = roundup(max(n), 64), so a sequence with n[s] == npad
+// fills its blocks exactly.  out fp32 [sum(n) + 64, heads*64]: the packed rows, then the guard block behind the output planes (every
+// byte 0x3C on entry).  Poisoning as in sta_debug_attn_varlen; the Q / K / V^T allocations carry one more (sequence, head) block than the
+// launch uses - K and Q poisoned, V^T zero - so the row behind the last head of the last sequence is poison, not another tensor.
+extern "C" int sta_debug_attn_encv(sta_handle* h, const float* q, const float* k, const float* v, int S, int heads, const int* n,
+                                   float* out, void* stream) {
+    REQUIRE(h && q && k && v && out && n && S > 0 && S <= ATT_MAX_SEQ && heads > 0, "bad argument");
+    int nmax = 0; int64_t M = 0;
+    for (int s = 0; s < S; ++s) { REQUIRE(n[s] > 0, "bad argument (sequence %d)", s); nmax = std::max(nmax, n[s]); M += n[s]; }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int npad = rup(nmax, 64);
+    const int64_t seq = (int64_t)heads * npad * 64, hsz = S * seq + (int64_t)npad * 64;      // with the spare block
+    const int G = 64;                                                   // guard rows
+    CHK(ensure_ws(h, (3 * hsz + (M + G) * heads * 64) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
+    Planes ao = ws.act(M + G, heads * 64, split);
+    ao.rp = M;
+    Planes guard = slice_rows(ao, M * (heads * 64 / 32)); guard.rp = G;
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    HIPCHK(hipMemsetAsync(o.vt.hi, 0, hsz * 2, st)); if (split) HIPCHK(hipMemsetAsync(o.vt.lo, 0, hsz * 2, st));
+    CHK(dbg_poison_planes(o.k, hsz, st));
+    CHK(dbg_poison_planes(o.q, hsz, st));
+    CHK(dbg_poison_act(ao, M, heads * 64, st));
+    HIPCHK(hipMemsetAsync(guard.hi, 0x3C, (size_t)G * heads * 64 * (split ? 4 : 2), st));
+    auto at = [&](const Planes& p, int64_t s) { Planes r = p; r.hi = p.hi + s * seq; if (p.lo) r.lo = p.lo + s * seq; return r; };
+    for (int s = 0; s < S; ++s) {
+        CHK(run_rows_to_planes(h, q, (int64_t)n[s] * 64, heads, n[s], 64, at(o.q, s), st, npad));
+        CHK(run_rows_to_planes(h, k, (int64_t)n[s] * 64, heads, n[s], 64, at(o.k, s), st, npad));
+        const Planes vt = at(o.vt, s);
+        hipLaunchKernelGGL(pack_vt_kernel, dim3((unsigned)(((int64_t)heads * n[s] * 64 + 255) / 256)), dim3(256), 0, st,
+                           v, heads, n[s], npad, vt.hi, vt.lo, h->range);
+        HIPCHK(hipGetLastError());
+        q += (int64_t)heads * n[s] * 64; k += (int64_t)heads * n[s] * 64; v += (int64_t)heads * n[s] * 64;
+    }
+    CHK(run_attn_encv(h, o, ao, heads * 64, S, heads, n, st));
+    CHK(dbg_planes_to_f32(h, ao, 0, 1, (int)M, heads * 64, out, st));
+    CHK(dbg_planes_to_f32(h, guard, 0, 1, G, heads * 64, out + M * heads * 64, st));
+    return 0;
+}
+
+// The QKV finisher of sta_encode_varlen alone (qkv_finish_kernel, VARLEN form).  n: HOST array [S]; slab: device fp32 [sum(n), 3E], E =
+// heads*64 (q | k | v columns); bias: device fp32 [3E] or NULL; pos_i32: device int32 [sum(n)*2] (y, x), packed, clamped to [0, pos_max]
+// into a copy first.  q / k: fp32 device buffers [S*heads + 1][npad][64], vt: [S*heads + 1][64][npad], npad = roundup(max(n), 64) - the
+// encoder's layout plus ONE guard block behind each.  EVERY element, the guards' too, is split to planes, the kernel runs on the planes,
+// and everything is returned as hi + lo: what the kernel must not touch - rows [n[s], npad) of Q / K, columns [n[s], npad) of V^T (the
+// entry does NOT zero them), the guards - comes back as it went in.
+extern "C" int sta_debug_qkv_finish_varlen(sta_handle* h, const float* slab, const float* bias, const int* pos_i32, int S, int heads,
+                                           const int* n, int pos_max, float* q, float* k, float* vt, void* stream) {
+    REQUIRE(h && slab && pos_i32 && n && q && k && vt && S > 0 && S <= SEQ_MAX && heads > 0, "bad argument");
+    REQUIRE(pos_max >= 0 && pos_max < (1 << 20), "bad argument (pos_max %d)", pos_max);
+    SeqTable t; memset(&t, 0, sizeof t);
+    t.S = S;
+    int nmax = 0;
+    for (int s = 0; s < S; ++s) { REQUIRE(n[s] > 0 && n[s] < (1 << 20), "bad argument (sequence %d)", s); t.tok0[s + 1] = t.tok0[s] + n[s]; nmax = std::max(nmax, n[s]); }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int npad = rup(nmax, 64);
+    const int64_t hsz = ((int64_t)S * heads + 1) * npad * 64;          // with the guard block
+    const int64_t np = (int64_t)t.tok0[S] * 2;
+    CHK(ensure_rope(h, pos_max + 1));
+    CHK(ensure_ws(h, 3 * hsz * 4 + np * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    QKVOut o; o.npad = npad; o.q = ws.planes(hsz, split); o.k = ws.planes(hsz, split); o.vt = ws.planes(hsz, split);
+    int* pos = (int*)ws.take(np * 4);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    hipLaunchKernelGGL(rope_tokens_table_kernel<int>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st,
+                       pos_i32, pos_i32, np, (int64_t)0, pos_max, pos, (float2*)nullptr, (int64_t)0);
+    HIPCHK(hipGetLastError());
+    float* io[3] = {q, k, vt}; const Planes* pl[3] = {&o.q, &o.k, &o.vt};
+    for (int b = 0; b < 3; ++b) CHK(run_rows_to_planes(h, io[b], hsz, 1, (int)(hsz / 64), 64, *pl[b], st));      // flat: both layouts are [.][64] rows
+    CHK(qkv_finish_varlen(h, slab, bias, heads * 64, heads, t, o, pos, st));
+    for (int b = 0; b < 3; ++b) CHK(dbg_planes_to_f32(h, *pl[b], 0, 1, (int)(hsz / 64), 64, io[b], st));
+    return 0;
+}
+
+// The gather of sta_encode_varlen alone.  imgs / H / W / n: HOST arrays [B] as in sta_encode_varlen (u8hwc != 0: uint8 HWC frames);
+// pos_i32: device int32 [sum(n)*2] (y, x), packed, ALREADY inside each entry's grid.  out: fp32 [sum(n), 768], the patch rows the
+// patch-embed GEMM reads, hi + lo; the planes are poisoned first.  which = 0: the VARLEN form, one launch over all entries; which = 1:
+// the equal-count form of the same kernel (sta_encode_tokens'), one launch per entry on its rows.
+extern "C" int sta_debug_patch_gather_varlen(sta_handle* h, const void* const* imgs, int u8hwc, const int* H, const int* W, const int* pos_i32,
+                                             const int* n, int B, int which, float* out, void* stream) {
+    REQUIRE(h && imgs && H && W && pos_i32 && n && out && B >= 1 && B <= SEQ_MAX && (which == 0 || which == 1), "bad argument");
+    EncEntries e; memset(&e, 0, sizeof e);
+    e.t.S = B;
+    for (int b = 0; b < B; ++b) {
+        REQUIRE(imgs[b] && n[b] > 0 && n[b] < (1 << 20) && H[b] > 0 && W[b] > 0 && H[b] % 16 == 0 && W[b] % 16 == 0, "bad argument (entry %d)", b);
+        REQUIRE(!u8hwc || ((uintptr_t)imgs[b] & 15) == 0, "u8 HWC image must be 16-byte aligned (entry %d)", b);
+        e.img[b] = imgs[b]; e.H[b] = H[b]; e.W[b] = W[b]; e.t.tok0[b + 1] = e.t.tok0[b] + n[b];
+    }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const bool split = h->prec != STA_PREC_F16;
+    const int64_t M = e.t.tok0[B];
+    CHK(ensure_ws(h, M * 768 * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes patches = ws.act(M, 768, split);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    CHK(dbg_poison_act(patches, M, 768, st));
+    const int per = u8hwc ? 16 : 48;
+    if (which == 0) {
+        const int blocks = (int)((M * per + 255) / 256);
+        if (u8hwc) {
+            if (split) hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, pos_i32, 0, 0, 0, 0, patches.hi, patches.lo, M, h->range, e);
+            else hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, pos_i32, 0, 0, 0, 0, patches.hi, patches.lo, M, h->range, e);
+        } else if (split) hipLaunchKernelGGL((patch_gather_tokens_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, pos_i32, 0, 0, 0, 0, patches.hi, patches.lo, M, h->range, e);
+        else hipLaunchKernelGGL((patch_gather_tokens_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, pos_i32, 0, 0, 0, 0, patches.hi, patches.lo, M, h->range, e);
+        HIPCHK(hipGetLastError());
+    } else {
+        for (int b = 0; b < B; ++b) {
+            const int blocks = (int)(((int64_t)n[b] * per + 255) / 256);
+            f16* hi = patches.hi + (int64_t)e.t.tok0[b] * (split ? 64 : 32);          // row tok0[b] of every column block (blk_off)
+            const int* pb = pos_i32 + (int64_t)e.t.tok0[b] * 2;
+            if (u8hwc) {
+                if (split) hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<true>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)imgs[b], pb, 1, n[b], H[b], W[b], hi, patches.lo, M, h->range);
+                else hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<false>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)imgs[b], pb, 1, n[b], H[b], W[b], hi, patches.lo, M, h->range);
+            } else if (split) hipLaunchKernelGGL(patch_gather_tokens_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)imgs[b], pb, 1, n[b], H[b], W[b], hi, patches.lo, M, h->range);
+            else hipLaunchKernelGGL(patch_gather_tokens_kernel<false>, dim3(blocks), dim3(256), 0, st, (const float*)imgs[b], pb, 1, n[b], H[b], W[b], hi, patches.lo, M, h->range);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    CHK(dbg_planes_to_f32(h, patches, 0, 1, (int)M, 768, out, st));
+    return 0;
+}
+
 // The rotation step of sta_decode_tokens alone.  bufs: nbuf (<= 3) fp32 device buffers [S1 + S2][heads][npad][64], npad =
 // roundup(max(ntok_a, ntok_b) + 1, 64): EVERY row is split to planes (the rows past a sequence's pose token too), rotated in place and
 // returned as hi + lo, so a row the kernel must not touch comes back as it went in.  pos_i32: device int32 [S1*ntok_a*2 | S2*ntok_b*2]
@@ -439,8 +568,10 @@ extern "C" int sta_debug_rope_enc_tokens(sta_handle* h, float* const* bufs, int 
 //   4 = 1: debug GEMM entry points in the f16mx arithmetic                5 = 1: attention without the 4-stage prefetch schedule
 //   6 = 1: no side lanes, 2: side lanes even under a multi-stream caller  7 = 1: bilinear one output row per workgroup
 //   3 = 1: sta_decode_tokens rotates by per-buffer rope_planes_kernel launches (eight per layer) instead of rope_tokens_kernel (two)
+//   8 = 1: sta_encode_varlen runs its QKV GEMM once PER SEQUENCE (fused epilogue, identity table) plus one no-pose rope_varlen_kernel launch
+//          per layer, as decode_varlen_impl does, instead of one dense GEMM and the varlen finisher (tools/encode_varlen_bench.py)
 extern "C" int sta_debug_set_option(sta_handle* h, int idx, int value) {
-    REQUIRE(h && idx >= 0 && idx < 8, "bad argument");
+    REQUIRE(h && idx >= 0 && idx < 9, "bad argument");
     h->opt[idx] = value;
     return 0;
 }

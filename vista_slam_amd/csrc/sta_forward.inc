@@ -93,6 +93,70 @@ static int encode_tokens_impl(sta_handle* h, Bump& ws, const void* img, bool u8h
     return 0;
 }
 
+// The encoder on a batch whose ENTRIES differ in token count and frame size (sta_encode_varlen): entry s has its own frame e.img[s] of
+// e.H[s] x e.W[s] pixels and n_s = tok0[s + 1] - tok0[s] tokens at its own positions.  Batch entries never interact in the reference
+// (attention is per sample), so entry s is what encode_tokens_impl returns for it alone at B = 1.  Rows are packed, M = sum n_s, sequence
+// s the rows [tok0[s], tok0[s + 1]); nothing is padded.  The gather, the patch-embed GEMM, every LayerNorm, proj, fc1, fc2 and the
+// residual epilogues: ONE launch over all rows - encode_tokens_impl's calls with M = sum n_s.  What knows the sequence structure, per
+// layer: (1) the QKV GEMM, dense over all rows, fp32 + bias into a workspace [M, 3E] (its fused epilogue cannot write Q / K / V^T
+// across sequence boundaries); (2) qkv_finish_kernel's VARLEN form: rotation by each sequence's slice of the positions table, Q / K
+// [S][heads][npad][64], V^T [S][heads][64][npad], npad = roundup(max n_s, 64), no pose row; (3) attn_varlen_kernel under attn_encv_plan.
+// Experiment switch 8: (1) + (2) as S gemm_qkv calls (identity table) + one no-pose rope_varlen_kernel launch, decode_varlen_impl's way.
+// h->rope_pos: the int32 table [M][2], each entry clamped into its own grid (enc_varlen_table_kernel).  One lane, outside sta_reserve.
+static int encode_varlen_impl(sta_handle* h, Bump& ws, const EncEntries& e, bool u8hwc, float* feat, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, Hh = c.enc_num_heads, S = e.t.S;
+    const bool per_seq = h->opt[8] == 1;
+    int n[SEQ_MAX], nmax = 0;
+    for (int s = 0; s < S; ++s) { n[s] = e.t.tok0[s + 1] - e.t.tok0[s]; nmax = std::max(nmax, n[s]); }
+    const int M = e.t.tok0[S], npad = rup(nmax, 64);
+    Planes patches = ws.act(M, 768, split);
+    Planes lnp = ws.act(M, E, split);
+    Planes ao = ws.act(M, E, split);
+    Planes f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
+    f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);
+    float* qkv32 = per_seq ? nullptr : (float*)ws.take((int64_t)M * 3 * E * 4);
+    QKVOut qkv; qkv.npad = npad;
+    const int64_t ssz = (int64_t)Hh * npad * 64, hsz = S * ssz;       // one sequence; all S
+    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split); qkv.vt = ws.planes(hsz, split);
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
+    { const Planes* z[1] = {&qkv.vt}; CHK(zero_planes(z, 1, hsz, split, st)); }
+    {
+        const int per = u8hwc ? 16 : 48;
+        const int blocks = (int)(((int64_t)M * per + 255) / 256);
+        if (u8hwc) {
+            if (split) hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
+            else hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
+        } else if (split) hipLaunchKernelGGL((patch_gather_tokens_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
+        else hipLaunchKernelGGL((patch_gather_tokens_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
+        HIPCHK(hipGetLastError());
+    }
+    auto seq_planes = [&](const Planes& p, int s) { Planes q = p; q.hi = p.hi + s * ssz; if (p.lo) q.lo = p.lo + s * ssz; return q; };
+    auto seq_qkv = [&](const QKVOut& o, int s) { QKVOut q; q.npad = o.npad; q.q = seq_planes(o.q, s); q.k = seq_planes(o.k, s); q.vt = seq_planes(o.vt, s); return q; };
+    CHK(gemm_f32(h, patches, h->patch, M, feat, E, nullptr, st));
+    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, lnp, nullptr, nullptr, nullptr, st));
+    for (int i = 0; i < c.enc_depth; ++i) {
+        const EncBlk& b = h->enc[i];
+        if (per_seq) {
+            for (int s = 0; s < S; ++s)          // the grid 1 x n_s, identity table: exactly the launch of a B = 1 sta_encode_tokens call
+                CHK(gemm_qkv(h, slice_rows(lnp, e.t.tok0[s]), b.qkv, n[s], E, E, E, seq_qkv(qkv, s), n[s], Hh, n[s], 0, st));
+            const Planes* rot[2] = {&qkv.q, &qkv.k};
+            CHK(rope_varlen_launch(h, rot, 2, e.t, Hh, npad, h->rope_pos, st, false));
+        } else {
+            CHK(gemm_f32(h, lnp, b.qkv, M, qkv32, 3 * E, nullptr, st));
+            CHK(qkv_finish_varlen(h, qkv32, nullptr, E, Hh, e.t, qkv, h->rope_pos, st));
+        }
+        CHK(run_attn_encv(h, qkv, ao, E, S, Hh, n, st));
+        CHK(gemm_resid_ln(h, ao, b.proj, M, feat, E, &b.n2, &lnp, nullptr, nullptr, st));
+        CHK(gemm_f16(h, lnp, b.fc1, M, f1, ACT_GELU, st, f1.mx));
+        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &lnp, nullptr, nullptr, st));
+        else CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
+    }
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ decoder
 // Row order of the decoder's residual stream x (fp32, [2B*N + 2B, D]) and of every plane buffer derived from it:
 //     rows [0, 2B*N)        patch tokens, sequence-major (sequence s = side * B + b, token t: row s*N + t)

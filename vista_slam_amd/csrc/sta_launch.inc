@@ -1062,6 +1062,7 @@ extern "C" int sta_debug_attn_varlen_block_map(int S, int heads, const int* nq, 
 }
 #endif
 
+static int launch_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int heads, const AttnVarlenPlan& m, int kv_shift, hipStream_t st);
 // out: [nq[s] patch rows | pose row] per sequence (decode_varlen_impl's row order), out.rp rows in all.  nq[s]: queries of sequence s;
 // nk[s]: the keys it reads, which are those of buffer sequence (s + kv_shift) % S.
 static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* nq, const int* nk, int kv_shift, hipStream_t st) {
@@ -1074,6 +1075,13 @@ static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, 
     CHK(attn_varlen_plan(S, heads, nq, nk, split, h->opt[5] == 1, m));
     h->last_attn_varlen = m;
     REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: per-sequence attention needs max(n) < npad, npad %% 64 == 0");
+    return launch_attn_varlen(h, qkv, out, ldo, heads, m, kv_shift, st);
+}
+// attn_varlen_kernel under a plan: attn_varlen_plan's (the decoder's pose-token form) or attn_encv_plan's (the encoder's, pose = 0)
+static int launch_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int heads, const AttnVarlenPlan& m, int kv_shift, hipStream_t st) {
+    const bool split = h->prec != STA_PREC_F16;
+    const int S = m.S;
+    {
     REQUIRE(out.rp == m.orows, "internal: per-sequence attention output of %d rows in planes of %lld", m.orows, (long long)out.rp);
     AttnVarlenParams vp; memset(&vp, 0, sizeof vp);
     AttnParams& p = vp.a;
@@ -1096,21 +1104,124 @@ static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, 
         STA_F16ONLY(hipLaunchKernelGGL(attn_varlen_kernel<false>, grid, dim3(256), m.lds_bytes, st, vp));
     }
     HIPCHK(hipGetLastError());
+    }
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ per-sequence attention, encoder form (encode_varlen_impl)
+// attn_varlen_kernel on the ENCODER's buffers: sequence s is n[s] queries over its own n[s] keys, no pose token anywhere - pose = 0
+// for every sequence, no pose blocks, no pose scratch, and npad may EQUAL n[s] (the decoder's form reads token index nk as the pose
+// key: here that is row 0 of the next head, or the end of the buffer).  Per sequence attn_plan(pose = false)'s rules on its own count;
+// the prefetch decision uses the grid of the whole launch and the launch carries the LDS of the hungriest sequence, as in
+// attn_varlen_plan.  Output rows packed [n[s]] per sequence: orow0 = the prefix sum of n.  All sequences equal reduces to
+// attn_plan(S, heads, n, n, pose = false) field by field (tests/test_encode_varlen_cpu.py).
+static int attn_encv_plan(int S, int heads, const int* n, bool split, bool no_prefetch, AttnVarlenPlan& out) {
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && heads > 0 && n, "per-sequence attention takes 1 .. %d sequences", ATT_MAX_SEQ);
+    AttnVarlenPlan m{};
+    m.S = S;
+    int64_t nwg = 0, orows = 0;
+    for (int i = 0; i < S; ++i) {
+        REQUIRE(n[i] > 0, "empty attention (sequence %d)", i);
+        AttnVarlenPlan::Seq& a = m.s[i];
+        a.nq = a.nk = n[i];
+        a.qblocks = (n[i] + 127) / 128;
+        a.ntiles = (n[i] + ATT_KV - 1) / ATT_KV; a.nfull = n[i] / ATT_KV;
+        REQUIRE(nwg < ((int64_t)1 << 30) && orows < ((int64_t)1 << 31) - n[i], "attention launch too large");
+        a.blk0 = (int)nwg; a.orow0 = (int)orows;
+        nwg += (int64_t)a.qblocks * heads; orows += n[i];
+    }
+    m.nwg = m.grid = (int)nwg; m.orows = (int)orows;
+    m.stages = 2;
+    for (int i = 0; i < S; ++i) {
+        AttnVarlenPlan::Seq& a = m.s[i];
+        a.prefetch = (n[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
+        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
+        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
+    }
+    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
+    out = m;
+    return 0;
+}
+#ifdef STA_TEST_HOOKS
+// out[7 + 11 * S]: the record of sta_debug_attn_varlen_plan (pose mode, pose blocks, pose scratch and first pose block are 0 here)
+extern "C" int sta_debug_attn_encv_plan(int S, int heads, const int* n, int split, int no_prefetch, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnVarlenPlan m;
+    CHK(attn_encv_plan(S, heads, n, split != 0, no_prefetch != 0, m));
+    attn_varlen_plan_out(m, out);
+    return 0;
+}
+extern "C" int sta_debug_last_attn_encv_plan(sta_handle* h, int* out) {
+    REQUIRE(h && out, "bad argument");
+    attn_varlen_plan_out(h->last_attn_encv, out);
+    return 0;
+}
+// The workgroup -> (sequence, head, query block) map under attn_encv_plan, by the kernel's arithmetic: out[3 * b + {0, 1, 2}]
+extern "C" int sta_debug_attn_encv_block_map(int S, int heads, const int* n, int* out) {
+    REQUIRE(out, "bad argument");
+    AttnVarlenPlan m;
+    CHK(attn_encv_plan(S, heads, n, true, false, m));
+    for (int b = 0; b < m.nwg; ++b) {
+        int logical = attn_block_map(b, m.nwg), s = 0;
+        for (int i = 1; i < S; ++i) if (m.s[i].blk0 <= logical) s = i;
+        logical -= m.s[s].blk0;
+        out[3 * b] = s; out[3 * b + 1] = (logical / m.s[s].qblocks) % heads; out[3 * b + 2] = logical % m.s[s].qblocks;
+    }
+    return 0;
+}
+#endif
+// out: [n[s] rows] per sequence, packed (encode_varlen_impl's row order), out.rp = sum(n) rows
+static int run_attn_encv(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* n, hipStream_t st) {
+    if (h->dry) return 0;
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ, "internal: per-sequence attention arguments");
+    int nmax = 0;
+    for (int s = 0; s < S; ++s) nmax = std::max(nmax, n[s]);
+    AttnVarlenPlan m;
+    CHK(attn_encv_plan(S, heads, n, h->prec != STA_PREC_F16, h->opt[5] == 1, m));
+    h->last_attn_encv = m;
+    REQUIRE(nmax <= qkv.npad && qkv.npad % 64 == 0, "internal: encoder per-sequence attention needs max(n) <= npad, npad %% 64 == 0");
+    return launch_attn_varlen(h, qkv, out, ldo, heads, m, 0, st);
 }
 
 // sta_decode_varlen: rotate nbuf (<= 3) Q / K buffers [S][heads][npad][64] in place, sequence s by its slice of the packed positions
 // table (SeqTable): one launch of rope_varlen_kernel
-static int rope_varlen_launch(sta_handle* h, const Planes* const* bufs, int nbuf, const SeqTable& t, int heads, int npad, const int* pos, hipStream_t st) {
+// pose = false (sta_encode_varlen's per-sequence QKV route): buffers without a pose row, n_s rows per (sequence, head)
+static int rope_varlen_launch(sta_handle* h, const Planes* const* bufs, int nbuf, const SeqTable& t, int heads, int npad, const int* pos, hipStream_t st, bool pose = true) {
     REQUIRE(nbuf >= 1 && nbuf <= 3 && pos && h->rope_tab && t.S >= 1 && t.S <= SEQ_MAX, "internal: rope_varlen_launch arguments");
-    for (int s = 0; s < t.S; ++s) REQUIRE(t.tok0[s + 1] - t.tok0[s] >= 1 && t.tok0[s + 1] - t.tok0[s] + 1 <= npad, "internal: rope_varlen_launch rows exceed npad");
+    const int pr = pose ? 1 : 0;
+    for (int s = 0; s < t.S; ++s) REQUIRE(t.tok0[s + 1] - t.tok0[s] >= 1 && t.tok0[s + 1] - t.tok0[s] + pr <= npad, "internal: rope_varlen_launch rows exceed npad");
     RopeVarlenParams p;
     for (int b = 0; b < 3; ++b) { p.hi[b] = bufs[b < nbuf ? b : 0]->hi; p.lo[b] = bufs[b < nbuf ? b : 0]->lo; }
     p.heads = heads; p.npad = npad; p.pos = pos; p.tab = h->rope_tab; p.rng = h->range; p.t = t;
-    const int64_t total = ((int64_t)t.tok0[t.S] + t.S) * heads * 4;
+    const int64_t total = ((int64_t)t.tok0[t.S] + t.S * pr) * heads * 4;
     const dim3 grid((unsigned)((total + 255) / 256), nbuf);
-    if (bufs[0]->lo) hipLaunchKernelGGL(rope_varlen_kernel<true>, grid, dim3(256), 0, st, p);
+    if (!pose) {
+        if (bufs[0]->lo) hipLaunchKernelGGL((rope_varlen_kernel<true, false>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((rope_varlen_kernel<false, false>), grid, dim3(256), 0, st, p);
+    } else if (bufs[0]->lo) hipLaunchKernelGGL(rope_varlen_kernel<true>, grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL(rope_varlen_kernel<false>, grid, dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// sta_encode_varlen: qkv_finish_kernel's VARLEN form on the fp32 rows [tok0[S], 3E] of one dense QKV GEMM (bias: nullptr when the
+// GEMM added it).  sum_s ceil(n_s / 64) x heads tiles, times three (Q, K, V).
+static int qkv_finish_varlen(sta_handle* h, const float* slab, const float* bias, int E, int heads, const SeqTable& t, const QKVOut& o, const int* pos, hipStream_t st) {
+    REQUIRE(slab && pos && h->rope_tab && t.S >= 1 && t.S <= SEQ_MAX && E == heads * 64, "internal: qkv_finish_varlen arguments");
+    int64_t tiles = 0;
+    for (int s = 0; s < t.S; ++s) {
+        const int n = t.tok0[s + 1] - t.tok0[s];
+        REQUIRE(n >= 1 && n <= o.npad, "internal: qkv_finish_varlen rows exceed npad");
+        tiles += (n + 63) / 64;
+    }
+    REQUIRE(o.npad % 64 == 0 && tiles * heads < ((int64_t)1 << 31), "internal: qkv_finish_varlen grid");
+    QkvVarlenParams p;
+    p.slab = slab; p.lds = (int64_t)3 * E; p.bias = bias; p.E = E; p.heads = heads; p.npad = o.npad; p.pos = pos; p.rope_tab = h->rope_tab;
+    p.Q_hi = o.q.hi; p.Q_lo = o.q.lo; p.K_hi = o.k.hi; p.K_lo = o.k.lo; p.Vt_hi = o.vt.hi; p.Vt_lo = o.vt.lo;
+    p.range = h->range; p.t = t;
+    const dim3 grid((unsigned)(tiles * heads), 3);
+    if (o.q.lo) hipLaunchKernelGGL((qkv_finish_kernel<true, QkvVarlenParams>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((qkv_finish_kernel<false, QkvVarlenParams>), grid, dim3(256), 0, st, p);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -662,6 +662,59 @@ class STAFrontend:
             r += int(n) + 1
         return offs, r
 
+    def _encode_varlen(self, frames: List[torch.Tensor], sizes: List[tuple], entry, pos, index):
+        """The shared part of `encode_tokens_varlen[_u8hwc]`: per-entry selection checks, then ONE C call over the packed positions."""
+        B = len(frames)
+        sel = pos if pos is not None else index
+        if (pos is None) == (index is None):
+            raise ValueError("give exactly one of pos (a list of [n, 2] (y, x) patch positions) and index (a list of [n] indices into each entry's row-major patch grid)")
+        if len(sel) != B:
+            raise ValueError(f"one selection per frame: {B} frames, {len(sel)} selections")
+        if not 1 <= B <= 32:
+            raise ValueError(f"1 .. 32 entries per call (got {B})")
+        qs = []
+        for b, (H, W_) in enumerate(sizes):
+            self._check_hw(H, W_, self.patch_size)
+            one = torch.as_tensor(sel[b])
+            if one.dim() == (2 if pos is not None else 1) and one.shape[0] == 0:
+                raise ValueError(f"entry {b}: a token subset has at least one token")
+            try:          # the rules and refusals of encode_tokens, on this entry alone in its OWN grid
+                qs.append(self._subset_positions(1, H // 16, W_ // 16, one[None] if pos is not None else None, one[None] if index is not None else None)[0])
+            except (ValueError, AssertionError) as err:
+                raise type(err)(f"entry {b}: {err}") from None
+        counts = [int(q.shape[0]) for q in qs]
+        q = torch.cat(qs, 0).contiguous()
+        feat = torch.empty(sum(counts), self.cfg.enc_embed_dim, device=self.device, dtype=torch.float32)
+        ptrs = (C.c_void_p * B)(*[f.data_ptr() for f in frames])
+        Hs, Ws = (C.c_int * B)(*[hw[0] for hw in sizes]), (C.c_int * B)(*[hw[1] for hw in sizes])
+        _lib.check(entry(self._h, ptrs, Hs, Ws, q.data_ptr(), (C.c_int * B)(*counts), B, feat.data_ptr(), self._stream()))
+        offs = [0]
+        for n in counts:
+            offs.append(offs[-1] + n)
+        return [feat[offs[b]:offs[b + 1]] for b in range(B)], [q[offs[b]:offs[b + 1]] for b in range(B)]
+
+    def encode_tokens_varlen(self, images: Sequence[torch.Tensor], pos=None, index=None):
+        """`encode_tokens` for B <= 32 entries that differ in token count AND frame size, in ONE call: images[b] [3, H_b, W_b]; exactly
+        one of `pos` (a list of [n_b, 2] int64 (y, x) patch positions) and `index` (a list of [n_b] int64 indices into entry b's own
+        row-major patch grid), selected and refused per entry exactly as `encode_tokens` does.  Entry b is what `encode_tokens` returns
+        for it alone at B = 1; nothing is padded, no token attends to another entry's.  -> (feats, poss): lists of per-entry views
+        [n_b, E] / [n_b, 2] into one packed buffer each - what `decode_stereo_varlen` takes."""
+        frames = []
+        for b, im in enumerate(images):
+            im = self._f32(im).contiguous()
+            assert im.dim() == 3 and im.shape[0] == 3, f"entry {b}: a frame is [3, H, W] (got {tuple(im.shape)})"
+            frames.append(im)
+        return self._encode_varlen(frames, [(int(f.shape[1]), int(f.shape[2])) for f in frames], self.lib.sta_encode_varlen, pos, index)
+
+    def encode_tokens_varlen_u8hwc(self, images_u8: Sequence[torch.Tensor], pos=None, index=None):
+        """`encode_tokens_varlen` on uint8 HWC camera frames [H_b, W_b, 3] with the fused ImgNorm of `encode_u8hwc`: bit-identical to
+        `encode_tokens_varlen` on the normalised [3, H_b, W_b] tensors."""
+        frames = []
+        for b, im in enumerate(images_u8):
+            assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[-1] == 3, f"entry {b}: a camera frame is uint8 [H, W, 3] (got {im.dtype} {tuple(im.shape)})"
+            frames.append(im.to(self.device).contiguous())
+        return self._encode_varlen(frames, [(int(f.shape[0]), int(f.shape[1])) for f in frames], self.lib.sta_encode_varlen_u8hwc, pos, index)
+
     def decode_stereo_varlen(self, feats1: Sequence[torch.Tensor], feats2: Sequence[torch.Tensor], pos1: Sequence[torch.Tensor],
                              pos2: Sequence[torch.Tensor], layers: Sequence[int] | None = None):
         """`_decode_stereo` on a batch whose entries have their OWN token counts: feats1[b] [n1_b, E] with positions pos1[b]
@@ -697,18 +750,30 @@ class STAFrontend:
         return out1, out2
 
     def forward_pairs_tokens(self, imgs_a: Sequence[torch.Tensor], imgs_b: Sequence[torch.Tensor], pos_a: Sequence[torch.Tensor],
-                             pos_b: Sequence[torch.Tensor]):
+                             pos_b: Sequence[torch.Tensor], encode: str = "grouped"):
         """`forward_pair_tokens` for B pairs whose token subsets differ in size: imgs_a[b] [3, H, W] (any frame size per entry) with
-        pos_a[b] [n, 2] int64 (y, x) patch positions, the same for side b.  Encoder: `encode_tokens`, entries of equal count and
-        frame size sharing one call; decoder: ONE `decode_stereo_varlen` call; pose head: once over all 2B pose rows; DPT head: per
-        entry and side, where that side is a row-major rectangle of patches.  Returns (main, support): two lists of B dicts with
-        pts3d_pred / conf ([16 h, 16 w, 3] / [16 h, 16 w], or None), relative_pose [4, 4], relative_pose_conf []."""
+        pos_a[b] [n, 2] int64 (y, x) patch positions, the same for side b.  Encoder: encode="grouped" (default): `encode_tokens`,
+        entries of equal count and frame size sharing one call; encode="varlen": all 2B frames through `encode_tokens_varlen` - one
+        call where 2B <= 32, else one per side.  Decoder: ONE `decode_stereo_varlen` call; pose head: once over all 2B pose rows; DPT
+        head: per entry and side, where that side is a row-major rectangle of patches.  Returns (main, support): two lists of B dicts
+        with pts3d_pred / conf ([16 h, 16 w, 3] / [16 h, 16 w], or None), relative_pose [4, 4], relative_pose_conf []."""
         B = len(imgs_a)
         assert len(imgs_b) == B and len(pos_a) == B and len(pos_b) == B and B >= 1, "one frame and one positions tensor per entry and side"
+        if encode not in ("grouped", "varlen"):
+            raise ValueError(f'encode must be "grouped" or "varlen" (got {encode!r})')
         hooks = self.cfg.hooks
         layers = sorted({hk - 1 for hk in hooks[1:]})
         sides = []
-        for imgs, poss in ((imgs_a, pos_a), (imgs_b, pos_b)):
+        if encode == "varlen":
+            for imgs in (imgs_a, imgs_b):
+                for b, im in enumerate(imgs):
+                    assert im.dim() == 3 and im.shape[0] == 3, f"entry {b}: a frame is [3, H, W] (got {tuple(im.shape)})"
+            if 2 * B <= 32:
+                f, q = self.encode_tokens_varlen(list(imgs_a) + list(imgs_b), pos=list(pos_a) + list(pos_b))
+                sides = [(f[:B], q[:B]), (f[B:], q[B:])]
+            else:
+                sides = [self.encode_tokens_varlen(list(imgs), pos=list(poss)) for imgs, poss in ((imgs_a, pos_a), (imgs_b, pos_b))]
+        for imgs, poss in ((imgs_a, pos_a), (imgs_b, pos_b)) if encode == "grouped" else ():
             groups: Dict[tuple, List[int]] = {}
             for b, (im, q) in enumerate(zip(imgs, poss)):
                 assert im.dim() == 3 and im.shape[0] == 3, f"entry {b}: a frame is [3, H, W] (got {tuple(im.shape)})"
