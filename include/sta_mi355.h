@@ -144,6 +144,7 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
  * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_decode_varlen (a plan per set of counts), sta_encode_tokens[_u8hwc] (a plan per token count),
  * sta_encode_varlen[_u8hwc] (a plan per set of counts; its RoPE table grows with the largest patch grid of a call),
+ * sta_regress_views_tokens[_begin] (a plan per set of selections and frame sizes, both phases in it; its RoPE table likewise),
  * sta_view_consistency (pair matrices per view count and window),
  * sta_symmetric_geo_mask (error plane per edge count), sta_geo_valid_mask (error plane per batch) and sta_local_pointclouds /
  * sta_ray_depth (one K^-1 per view). */
@@ -471,10 +472,50 @@ STA_API int sta_regress_views_begin(sta_handle* h, const float* feat_i, const fl
 STA_API int sta_regress_views_finish(sta_handle* h, const uint8_t* adjacent, float rel_pose_thres,
                              float* pose_conf_host, int* slot_host, int* n_accepted,
                              float* pts, float* conf, float* K, float* depth, void* stream);
-/* Give up a call that was begun on `stream` and will not be finished (a host-side error between the phases): waits for
+/* Give up a call that was begun on `stream` (by sta_regress_views_begin or sta_regress_views_tokens_begin) and will not be finished (a host-side error between the phases): waits for
  * phase A's confidence copy, clears the pending state, the stream's scratch context is usable again.  Nothing pending on
  * `stream`: returns 0.  (vista_slam_amd.slam_scheduler.PendingEdges calls it from close() / __del__ / its context manager.) */
 STA_API int sta_regress_views_abort(sta_handle* h, void* stream);
+
+/* The keyframe scheduler on TOKEN SUBSETS: sta_regress_views with a SELECTION per edge and side, and every candidate with its own
+ * frame size.  feat_i [Ni,E] is keyframe i's cached whole-frame encoding at Hi x Wi, feat_j[e] [Nj_e,E] candidate e's at Hj[e] x
+ * Wj[e] (device, 16-byte aligned; Hj / Wj host arrays [k]).  Per side a HOST window array [k][4] = (y0, x0, h, w) in patches of that
+ * frame's grid, row-major - the whole frame is (0, 0, hp, wp) -; h * w == 0 makes the side an INDEX LIST of cnt[e] >= 1 int64 indices
+ * into the frame's row-major patch grid (any order, repeats allowed, out-of-grid values are clamped into the grid), read from that
+ * side's packed DEVICE array idx_*: the lists of the index-list edges follow each other in edge order.  cnt_* (host [k]) is read for
+ * index-list sides only; cnt_* / idx_* may be NULL when the side has none.  Selecting means SLICING the cached encoding (the tokens
+ * have attended to the whole frame) and the positions are the tokens' (y, x) in their own frame's grid.
+ * Edge e is regress_two_views (slam.py:153-189) at B = 1 on the two slices: _decode_stereo, head_pose_s on side i's pose token ->
+ * pose [k,16] (device) and pose_conf_host[k]; REJECTED iff pose_conf < rel_pose_thres and !adjacent[e]; for an accepted edge each
+ * WINDOW side runs head_pts at the shape (16 h, 16 w); an index-list side has no maps.  Host outputs, valid on return:
+ * pose_conf_host[k], accepted_host[k] (0 / 1), n_accepted, k_valid_host[k].
+ * pts / conf / depth: ONE device buffer each, the maps of the window sides of ALL k edges in (edge, side) order, so the offsets follow
+ * from the shapes the caller passed: a window side of h x w patches occupies 256 h w pixels (x 3 floats in pts), image orientation
+ * [16 h, 16 w]; an index-list side occupies nothing.  The ranges of rejected edges are NOT written.  An accepted edge whose two sides
+ * are windows of one (h, w) has its two maps adjacent in the reference's [ij, ji] order (slam.py:182) and gets the pair-shared
+ * intrinsics K[e] [3,3] with k_valid_host[e] = 1: estimate_intrinsic_from_pts3d of those two maps, i.e. the principal point is the
+ * centre of the WINDOW's image (8 w, 8 h), not of the frame; h > w follows the portrait rule of sta_regress_views.  Every other edge
+ * has k_valid_host[e] = 0 and K[e] untouched (the reference concatenates the two maps, which two shapes do not allow).
+ * Two phases like sta_regress_views_begin / _finish, on the same pending state: a begin of either kind fails while a call of either
+ * kind is pending on the stream, a finish of the other kind fails and leaves the call pending, sta_regress_views_abort releases both.
+ * One lane of decode; NOT covered by sta_reserve (like sta_decode_varlen: the first call of a set of counts plans and may grow the
+ * stream's workspace).  Returns -1 for: null pointers, k outside [1, 16], H or W not a multiple of 16, a window that leaves its
+ * grid, a count below 1, features not 16-byte aligned, 2^31 or more decoder rows. */
+STA_API int sta_regress_views_tokens(sta_handle* h, const float* feat_i, int Hi, int Wi,
+                             const float* const* feat_j, const int* Hj, const int* Wj, int k,
+                             const int* win_i, const int* cnt_i, const int64_t* idx_i,
+                             const int* win_j, const int* cnt_j, const int64_t* idx_j,
+                             const uint8_t* adjacent, float rel_pose_thres,
+                             float* pose, float* pose_conf_host, int* accepted_host, int* n_accepted,
+                             float* pts, float* conf, float* depth, float* K, int* k_valid_host, void* stream);
+STA_API int sta_regress_views_tokens_begin(sta_handle* h, const float* feat_i, int Hi, int Wi,
+                                   const float* const* feat_j, const int* Hj, const int* Wj, int k,
+                                   const int* win_i, const int* cnt_i, const int64_t* idx_i,
+                                   const int* win_j, const int* cnt_j, const int64_t* idx_j,
+                                   float* pose, void* stream);
+STA_API int sta_regress_views_tokens_finish(sta_handle* h, const uint8_t* adjacent, float rel_pose_thres,
+                                    float* pose_conf_host, int* accepted_host, int* n_accepted,
+                                    float* pts, float* conf, float* depth, float* K, int* k_valid_host, void* stream);
 
 /* the compact per-pair record of one step's all-gather (vista_slam_amd/parallel.py; what a SLAM consumer
  * reads of a pair, slam.py:165-185), packed from the outputs of sta_forward_pair* in one launch.  Row b of out_dev

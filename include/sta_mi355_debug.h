@@ -159,6 +159,19 @@ STA_API int sta_debug_qkv_finish_varlen(sta_handle* h, const float* slab, const 
 STA_API int sta_debug_patch_gather_varlen(sta_handle* h, const void* const* imgs, int u8hwc, const int* H, const int* W,
                                           const int* pos_i32, const int* n, int B, int which, float* out, void* stream);
 
+/* The gather of sta_regress_views_tokens alone (gather_tokens_varlen_kernel): S <= 32 sequences (S even: the first half is side i,
+ * the second side j).  srcs [S] device pointers to cached frames [hp[s]*wp[s], E] fp32, 16-byte aligned; hp / wp [S]; win [S][4] =
+ * (y0, x0, h, w) in patches, h * w == 0 = index list of cnt[s] tokens; idx_i / idx_j: packed device int64 indices of the index-list
+ * sequences of each half, in sequence order (out-of-grid values are clamped).  All arrays but idx_* are HOST arrays.  feat_out fp32
+ * [sum(n), E] and pos_out int32 [sum(n), 2] of (y, x): the packed rows in sequence order. */
+STA_API int sta_debug_gather_tokens(sta_handle* h, const float* const* srcs, const int* hp, const int* wp, const int* win, const int* cnt,
+                                    const int64_t* idx_i, const int64_t* idx_j, int S, int E, float* feat_out, int* pos_out, void* stream);
+
+/* sta_head_pose with the samples named by a HOST row table: sample b (b < k <= 16) is row rows[b] of tok (rows of tok_stride floats).
+ * Bit-identical to sta_head_pose on a stacked copy of those rows. */
+STA_API int sta_debug_pose_rows(sta_handle* h, const float* tok, int64_t tok_stride, const int64_t* rows, int k, float* pose, float* conf,
+                                void* stream);
+
 /* The rotation step of sta_decode_varlen alone (rope_varlen_kernel): n HOST array [S] of token counts.  bufs[b] (nbuf 1..3): fp32
  * [S*heads + 1][npad][64], npad = roundup(max(n) + 1, 64) - the decoder's Q / K layout and ONE guard block behind it; every row (the
  * guard's too) is split to fp16 planes inside, the buffer is rotated IN PLACE and everything is returned as hi + lo.  Token index n[s]

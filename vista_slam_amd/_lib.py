@@ -81,6 +81,13 @@ SIGNATURES = {
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),
     "sta_regress_views_finish": (_i, [_vp, C.c_char_p, _f, C.POINTER(C.c_float), C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_abort": (_i, [_vp, _vp]),
+    "sta_regress_views_tokens": (_i, [_vp, _fp, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i,
+                                      C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), _vp, C.c_char_p, _f,
+                                      _fp, C.POINTER(C.c_float), C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, C.POINTER(_i), _vp]),
+    "sta_regress_views_tokens_begin": (_i, [_vp, _fp, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i,
+                                            C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), C.POINTER(_i), _vp, _fp, _vp]),
+    "sta_regress_views_tokens_finish": (_i, [_vp, C.c_char_p, _f, C.POINTER(C.c_float), C.POINTER(_i), C.POINTER(_i),
+                                             _fp, _fp, _fp, _fp, C.POINTER(_i), _vp]),
     "sta_pack_compact": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _i, _i, _i, _fp, _i64, _vp]),
     "sta_rope2d_inplace": (_i, [_fp, _i64, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "sta_rope2d_inplace_dtype": (_i, [_vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _f, _f, _vp]),
@@ -127,6 +134,8 @@ TEST_SIGNATURES = {
     "sta_debug_attn_encv_block_map": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sta_debug_qkv_finish_varlen": (_i, [_vp, _fp, _fp, _vp, _i, _i, C.POINTER(_i), _i, _fp, _fp, _fp, _vp]),
     "sta_debug_patch_gather_varlen": (_i, [_vp, C.POINTER(_vp), _i, C.POINTER(_i), C.POINTER(_i), _vp, C.POINTER(_i), _i, _i, _fp, _vp]),
+    "sta_debug_gather_tokens": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _vp, _vp, _i, _i, _fp, _vp, _vp]),
+    "sta_debug_pose_rows": (_i, [_vp, _fp, _i64, C.POINTER(_i64), _i, _fp, _fp, _vp]),
     "sta_debug_rope_varlen": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, C.POINTER(_i), _vp, _i, _vp]),
     "sta_debug_rope_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "sta_debug_rope_enc_tokens": (_i, [_vp, C.POINTER(_vp), _i, _i, _i, _i, _vp, _i, _i, _vp]),

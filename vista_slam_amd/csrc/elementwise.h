@@ -629,6 +629,39 @@ __global__ __launch_bounds__(256) void rope_varlen_kernel(RopeVarlenParams p) {
     ra.flush(p.rng);
 }
 
+// sta_regress_views_tokens: both packed sides of a varlen decode, sliced out of cached whole-frame encodings in ONE launch.  Sequence
+// s (s = e side i, k + e side j, the order of decode_varlen_impl) selects n_s = tok0[s + 1] - tok0[s] tokens of the frame src[s]
+// ([hp[s] * wp[s], E] fp32, row-major patch grid): a WINDOW (ww[s] > 0: token r is the grid cell (y0 + r / ww, x0 + r % ww), no index
+// memory) or an INDEX LIST (ww[s] == 0: idx[s][r], device int64, any order, repeats allowed, clamped into the grid like the other
+// entries clamp positions).  Everything per sequence travels in the kernel arguments: nothing is copied to the device beforehand.
+// One workgroup = one output row at a time, so the table scan and the source row are block-uniform (scalar registers); the threads
+// move the row in 16-byte accesses and thread 0 writes its (y, x) into the int32 positions table the decoder rotates by - the form
+// rope_tokens_table_kernel builds from caller positions.  fp32 in, fp32 out: no plane is written here.
+struct TokenSel {
+    SeqTable t;
+    const float* src[SEQ_MAX]; const int64_t* idx[SEQ_MAX];
+    int hp[SEQ_MAX], wp[SEQ_MAX], y0[SEQ_MAX], x0[SEQ_MAX], ww[SEQ_MAX];
+};
+__global__ __launch_bounds__(256) void gather_tokens_varlen_kernel(TokenSel g, int E, float* feat, int* pos) {
+    const int e4 = E / 4, rows = g.t.tok0[g.t.S];
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+        int s = 0;
+        for (int i = 1; i < g.t.S; ++i) if (g.t.tok0[i] <= row) s = i;
+        const int r = row - g.t.tok0[s], wp = g.wp[s], ww = g.ww[s];
+        int64_t cell;
+        if (ww > 0) cell = (int64_t)(g.y0[s] + r / ww) * wp + g.x0[s] + r % ww;
+        else {
+            const int64_t last = (int64_t)g.hp[s] * wp - 1;
+            cell = g.idx[s][r];
+            cell = cell < 0 ? 0 : (cell > last ? last : cell);
+        }
+        const float4* in = reinterpret_cast<const float4*>(g.src[s] + cell * E);
+        float4* out = reinterpret_cast<float4*>(feat + (int64_t)row * E);
+        for (int c = threadIdx.x; c < e4; c += 256) out[c] = in[c];
+        if (threadIdx.x == 0) *reinterpret_cast<int2*>(pos + (int64_t)row * 2) = make_int2((int)(cell / wp), (int)(cell % wp));
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Bilinear x2 upsample, align_corners=True (dpt_block.py:215-216,320), NHWC fp16 planes.
 // Output may be cropped to (Hc,Wc) <= (2Hi,2Wi) (dpt_head.py:58); interpolation ratios always use
@@ -878,6 +911,23 @@ __global__ __launch_bounds__(256) void pose_layer_kernel(const float* in, int64_
     if (n >= N) return;
     const float4* wr = reinterpret_cast<const float4*>(w + (size_t)n * K);
     const float4* xr = reinterpret_cast<const float4*>(in + (size_t)b * in_stride);
+    float s = 0.f;
+    for (int k = lane; k < K / 4; k += 64) { float4 a = wr[k], x = xr[k]; s += (a.x * x.x + a.y * x.y) + (a.z * x.z + a.w * x.w); }
+    s = wave_sum(s);
+    if (lane == 0) { s += bias[n]; out[(size_t)b * N + n] = relu ? fmaxf(s, 0.f) : s; }
+}
+
+// pose_layer_kernel's FIRST layer with the samples named by a row table in the kernel arguments: sample b reads row rows[b] of `in`
+// (rows of in_stride floats) - the pose rows of a packed varlen decode sit at irregular offsets (sta_regress_views_tokens: entry e at
+// row sum(n[:e]) + e).  The same lanes, the same order of sums as pose_layer_kernel on a stacked copy of those rows: bit-identical.
+struct PoseRows { int64_t row[16]; };
+__global__ __launch_bounds__(256) void pose_layer_rows_kernel(const float* in, int64_t in_stride, PoseRows rows, const float* w, const float* bias,
+                                                              float* out, int K, int N, int relu) {
+    const int lane = threadIdx.x & 63;
+    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+    if (n >= N) return;
+    const float4* wr = reinterpret_cast<const float4*>(w + (size_t)n * K);
+    const float4* xr = reinterpret_cast<const float4*>(in + rows.row[b] * in_stride);
     float s = 0.f;
     for (int k = lane; k < K / 4; k += 64) { float4 a = wr[k], x = xr[k]; s += (a.x * x.x + a.y * x.y) + (a.z * x.z + a.w * x.w); }
     s = wave_sum(s);

@@ -101,6 +101,11 @@ struct StreamCtx {
     bool rv_open = false; int rv_k = 0, rv_H = 0, rv_W = 0;
     float* rv_conf = nullptr;         // pinned host copy of the k pose confidences (async D2H in begin, read in finish)
     hipEvent_t rv_ev = nullptr;       // recorded behind that copy
+    // rv_kind: which scheduler the pending call belongs to - 0 whole frames (sta_regress_views_begin), 1 token subsets
+    // (sta_regress_views_tokens_begin), whose per-sequence counts and map grids phase B needs again (RvtState, sequence s = e
+    // side i, k + e side j: n tokens; mh x mw patches of a window side, 0 for an index-list side, which has no maps)
+    int rv_kind = 0;
+    struct RvtState { int n[SEQ_MAX], mh[SEQ_MAX], mw[SEQ_MAX]; } rvt{};
     // side lane of the DPT head (dpt_impl): an internal second stream for the branches of the head that do not lie on its
     // critical chain, with its own split-K scratch; forked from and joined back into `st` inside the call
     hipStream_t side = nullptr; float* side_skbuf = nullptr; hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};

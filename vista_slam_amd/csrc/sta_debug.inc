@@ -791,3 +791,31 @@ extern "C" int sta_debug_svd_orthogonalize(sta_handle* h, const float* m, float*
     HIPCHK(hipGetLastError());
     return 0;
 }
+
+// The gather of sta_regress_views_tokens alone (gather_tokens_varlen_kernel).  srcs / hp / wp / win / cnt: HOST arrays over S <= 32
+// sequences (S even: the first half is side i, the second side j, as in the entry); idx_i / idx_j: the packed device int64 index
+// arrays of the two halves.  feat_out fp32 [sum(n), E], pos_out int32 [sum(n), 2]: written by the one launch, nothing else is touched.
+extern "C" int sta_debug_gather_tokens(sta_handle* h, const float* const* srcs, const int* hp, const int* wp, const int* win, const int* cnt,
+                                       const int64_t* idx_i, const int64_t* idx_j, int S, int E, float* feat_out, int* pos_out, void* stream) {
+    REQUIRE(h && srcs && hp && wp && win && feat_out && pos_out, "bad argument");
+    REQUIRE(S >= 2 && S <= SEQ_MAX && S % 2 == 0 && E >= 4 && E % 4 == 0, "bad argument (S %d, E %d)", S, E);
+    REQUIRE(((uintptr_t)feat_out & 15) == 0 && ((uintptr_t)pos_out & 7) == 0, "misaligned output");
+    DEV_SCOPE(h->device);
+    TokenSel g; int mh[SEQ_MAX], mw[SEQ_MAX];
+    const int64_t* const idx_side[2] = {idx_i, idx_j};
+    CHK(build_token_sel(srcs, hp, wp, win, cnt, idx_side, S, &g, mh, mw));
+    return launch_gather_tokens(g, E, feat_out, pos_out, (hipStream_t)stream);
+}
+
+// The pose head with its samples named by a row table (pose_layer_rows_kernel in front of the unchanged layers): sample b reads row
+// rows[b] (HOST int64 [k], k <= 16) of tok, rows of tok_stride floats.
+extern "C" int sta_debug_pose_rows(sta_handle* h, const float* tok, int64_t tok_stride, const int64_t* rows, int k, float* pose, float* conf, void* stream) {
+    REQUIRE(h && h->finalized, "handle not ready");
+    REQUIRE(tok && rows && pose && conf && k >= 1 && k <= 16, "bad argument");
+    REQUIRE(tok_stride % 4 == 0 && ((uintptr_t)tok & 15) == 0, "tok must be 16-byte aligned with a stride that is a multiple of 4 floats");
+    DEV_SCOPE(h->device);
+    PoseRows pr;
+    for (int e = 0; e < 16; ++e) { pr.row[e] = e < k ? rows[e] : 0; REQUIRE(pr.row[e] >= 0, "negative row"); }
+    hipStream_t st = (hipStream_t)stream;
+    return plan_and_run(h, st, [&](Bump& ws) { return pose_impl(h, ws, tok, k, tok_stride, pose, conf, st, nullptr, nullptr, 0, &pr); });
+}

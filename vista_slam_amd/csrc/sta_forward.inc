@@ -482,8 +482,9 @@ static int decode_varlen_impl(sta_handle* h, Bump& ws, const float* feat1, const
 
 // ------------------------------------------------------------------------------------------ pose head
 // pose2 / conf2 (optional): the last B - split samples write there (the two sides of a pair: one set of four launches)
+// rows (optional, B <= 16): sample b is row rows->row[b] of tok (rows of `stride` floats) instead of row b - pose_layer_rows_kernel
 static int pose_impl(sta_handle* h, Bump& ws, const float* tok, int B, int64_t stride, float* pose, float* conf, hipStream_t st,
-                     float* pose2 = nullptr, float* conf2 = nullptr, int split = 0) {
+                     float* pose2 = nullptr, float* conf2 = nullptr, int split = 0, const PoseRows* rows = nullptr) {
     const int D = h->cfg.dec_embed_dim, Hd = 512;
     float* f0 = (float*)ws.take((int64_t)B * Hd * 4);
     float* f1 = (float*)ws.take((int64_t)B * Hd * 4);
@@ -495,7 +496,8 @@ static int pose_impl(sta_handle* h, Bump& ws, const float* tok, int B, int64_t s
     p.wt = h->pt.w; p.bt = h->pt.b; p.wr = h->pr.w; p.br = h->pr.b; p.wc = h->pc.w; p.bc = h->pc.b;
     p.pose = pose; p.conf = conf; p.pose2 = pose2; p.conf2 = conf2; p.split = split;
     dim3 grid(Hd / 4, B);
-    hipLaunchKernelGGL(pose_layer_kernel, grid, dim3(256), 0, st, tok, stride, p.w0, p.b0, f0, D, Hd, 1);
+    if (rows) hipLaunchKernelGGL(pose_layer_rows_kernel, grid, dim3(256), 0, st, tok, stride, *rows, p.w0, p.b0, f0, D, Hd, 1);
+    else hipLaunchKernelGGL(pose_layer_kernel, grid, dim3(256), 0, st, tok, stride, p.w0, p.b0, f0, D, Hd, 1);
     hipLaunchKernelGGL(pose_layer_kernel, grid, dim3(256), 0, st, f0, (int64_t)Hd, p.w1, p.b1, f1, Hd, Hd, 1);
     hipLaunchKernelGGL(pose_layer_kernel, grid, dim3(256), 0, st, f1, (int64_t)Hd, p.w2, p.b2, f0, Hd, Hd, 1);
     hipLaunchKernelGGL(pose_final_kernel, dim3(B), dim3(256), 0, st, p, f0);

@@ -473,7 +473,7 @@ extern "C" int sta_regress_views_begin(sta_handle* h, const float* feat_i, const
     if (r != 0) return r;
     if (h->reserve_only) return 0;                      // sta_reserve: both phases are planned and allocated, nothing is pending
     StreamCtx& c = *h->cur;
-    c.rv_open = true; c.rv_k = k; c.rv_H = H; c.rv_W = W;
+    c.rv_open = true; c.rv_kind = 0; c.rv_k = k; c.rv_H = H; c.rv_W = W;
     return 0;
 }
 
@@ -487,6 +487,7 @@ extern "C" int sta_regress_views_finish(sta_handle* h, const uint8_t* adjacent, 
     CHK(stream_ctx(h, st));
     StreamCtx& c = *h->cur;
     REQUIRE(c.rv_open, "sta_regress_views_finish: no scheduler call was begun on this stream");
+    REQUIRE(c.rv_kind == 0, "sta_regress_views_finish: the call pending on this stream was begun with sta_regress_views_tokens_begin: finish it with sta_regress_views_tokens_finish (or abort it)");
     c.rv_open = false;                                  // (also on an error below: the call is over either way)
     const int k = c.rv_k, H = c.rv_H, W = c.rv_W;
     const RvDims d = rv_dims(h, k, H, W);
@@ -519,6 +520,260 @@ extern "C" int sta_regress_views(sta_handle* h, const float* feat_i, const float
     REQUIRE(adjacent && pose_conf_host && slot_host && n_accepted && pts && conf && K && depth, "null argument");
     CHK(sta_regress_views_begin(h, feat_i, feat_j, k, H, W, pose, stream));
     return sta_regress_views_finish(h, adjacent, rel_pose_thres, pose_conf_host, slot_host, n_accepted, pts, conf, K, depth, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// f2 on TOKEN SUBSETS (sta_regress_views_tokens): the scheduler contract above with a SELECTION per edge and side - the whole frame, a
+// window of its patch grid, or an index list -, every candidate with its own frame size.  Selecting = slicing the cached whole-frame
+// encoding (gather_tokens_varlen_kernel: both packed sides and the positions table in one launch), then ONE varlen decode
+// (decode_varlen_impl: sequence e = side i of edge e, k + e = side j), the pose head on the k pose rows of side i through a row table
+// (pose_layer_rows_kernel), the k confidences to the host, and for the accepted edges the DPT head per window side at that side's
+// token shape: one call with n = 2 where both sides of an edge share a shape (then also the pair-shared intrinsics, slam.py:182-185),
+// else one per window side.  The head reads its inputs where the decode left them - a window's rows are contiguous in the packed
+// features and in the emitted hooks (pose row first, skipped) -, the two images of an n = 2 call lie one pointer difference apart.
+//
+// Builds the per-sequence table from the HOST arrays of an entry and checks them.  srcs / hp / wp: [S]; win: [S][4] (y0, x0, h, w),
+// h * w == 0 = index list of cnt[s] tokens taken from idx_side[s < S / 2 ? 0 : 1], whose slices follow each other in sequence order.
+static int build_token_sel(const float* const* srcs, const int* hp, const int* wp, const int* win, const int* cnt,
+                           const int64_t* const idx_side[2], int S, TokenSel* out, int* mh, int* mw) {
+    TokenSel& g = *out; memset(&g, 0, sizeof g);
+    g.t.S = S;
+    int64_t acc = 0, ioff[2] = {0, 0};
+    for (int s = 0; s < S; ++s) {
+        const int side = s < S / 2 ? 0 : 1, e = s % (S / 2);
+        const int y0 = win[4 * s], x0 = win[4 * s + 1], wh = win[4 * s + 2], ww = win[4 * s + 3];
+        REQUIRE(srcs[s] && ((uintptr_t)srcs[s] & 15) == 0, "features of edge %d side %d null or not 16-byte aligned", e, side);
+        REQUIRE(hp[s] >= 1 && wp[s] >= 1, "bad frame grid %d x %d (edge %d side %d)", hp[s], wp[s], e, side);
+        int n;
+        if ((int64_t)wh * ww != 0) {
+            REQUIRE(wh >= 1 && ww >= 1 && y0 >= 0 && x0 >= 0 && (int64_t)y0 + wh <= hp[s] && (int64_t)x0 + ww <= wp[s],
+                    "window (%d, %d, %d, %d) leaves the %d x %d grid (edge %d side %d)", y0, x0, wh, ww, hp[s], wp[s], e, side);
+            n = wh * ww; mh[s] = wh; mw[s] = ww;
+            g.y0[s] = y0; g.x0[s] = x0; g.ww[s] = ww;
+        } else {
+            REQUIRE(cnt && cnt[s] >= 1, "bad argument (edge %d side %d: an index list has at least one token)", e, side);
+            REQUIRE(idx_side[side], "null index array (edge %d side %d selects by index)", e, side);
+            n = cnt[s]; mh[s] = 0; mw[s] = 0;
+            g.idx[s] = idx_side[side] + ioff[side]; ioff[side] += n;
+        }
+        g.src[s] = srcs[s]; g.hp[s] = hp[s]; g.wp[s] = wp[s];
+        g.t.tok0[s] = (int)acc; acc += n;
+        REQUIRE(acc + S < ((int64_t)1 << 31), "too many decoder rows (%lld or more)", (long long)(acc + S));
+    }
+    g.t.tok0[S] = (int)acc;
+    return 0;
+}
+static int launch_gather_tokens(const TokenSel& g, int E, float* feat, int* pos, hipStream_t st) {
+    int gx = g.t.tok0[g.t.S]; if (gx > 65536) gx = 65536;
+    hipLaunchKernelGGL(gather_tokens_varlen_kernel, dim3(gx), dim3(256), 0, st, g, E, feat, pos);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+struct RvtLayout { float *F, *x, *hk[3][2], *cdev; int* rp; float2* ident; int64_t n_ident, mark; };
+static RvtLayout rvt_layout(Bump& ws, const SeqTable& t, int k, int E, int D) {
+    RvtLayout L;
+    const int64_t Mp = t.tok0[2 * k], Mp1 = t.tok0[k];
+    int nmax = 0;
+    for (int s = 0; s < 2 * k; ++s) nmax = std::max(nmax, t.tok0[s + 1] - t.tok0[s]);
+    L.F = (float*)ws.take(Mp * E * 4);                  // packed features: side i's k selections, then side j's
+    L.rp = (int*)ws.take(Mp * 2 * 4);
+    L.n_ident = (int64_t)(nmax + 2) * 16;               // each sequence is the grid 1 x n: table rows 0 .. max(n) + 1 (sta_decode_varlen)
+    L.ident = (float2*)ws.take(L.n_ident * 8);
+    L.x = (float*)ws.take((Mp + 2 * k) * D * 4);
+    for (int q = 0; q < 3; ++q) {                       // emitted hooks per side, entry by entry, pose row first (decode_varlen_impl)
+        L.hk[q][0] = (float*)ws.take((Mp1 + k) * D * 4);
+        L.hk[q][1] = (float*)ws.take((Mp - Mp1 + k) * D * 4);
+    }
+    L.cdev = (float*)ws.take(k * 4);
+    L.mark = ws.off;
+    return L;
+}
+// phase A: gather -> varlen decode -> pose head on the pose rows of side i -> confidences on their way to the host
+static int rvt_phase_a(sta_handle* h, Bump& ws, const TokenSel& g, int k, float* pose, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim, dd = c.dec_depth;
+    const int hidx[3] = {dd * 2 / 4, dd * 3 / 4, dd};
+    RvtLayout L = rvt_layout(ws, g.t, k, E, D);
+    if (!h->dry) {
+        REQUIRE(!ws.overflow, "internal: scheduler workspace overflow");
+        CHK(launch_gather_tokens(g, E, L.F, L.rp, st));
+        hipLaunchKernelGGL(rope_tokens_table_kernel<int64_t>, dim3((unsigned)((L.n_ident + 255) / 256)), dim3(256), 0, st,
+                           (const int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int64_t)0, 0, L.rp, L.ident, L.n_ident);    // the identity table alone
+        HIPCHK(hipGetLastError());
+        h->rope_pos = L.rp; h->rope_ident = (const float*)L.ident;
+    }
+    std::vector<float*> w1(dd + 1, nullptr), w2(dd + 1, nullptr);
+    for (int q = 0; q < 3; ++q) { w1[hidx[q]] = L.hk[q][0]; w2[hidx[q]] = L.hk[q][1]; }
+    CHK(decode_varlen_impl(h, ws, L.F, L.F + (size_t)g.t.tok0[k] * E, g.t, k, L.x, w1.data(), w2.data(), st));
+    ws.rewind(L.mark);
+    PoseRows rows;
+    for (int e = 0; e < 16; ++e) rows.row[e] = e < k ? (int64_t)g.t.tok0[e] + e : 0;      // pose_ij only (slam.py:165)
+    CHK(pose_impl(h, ws, L.hk[2][0], k, (int64_t)D, pose, L.cdev, st, nullptr, nullptr, 0, &rows));
+    if (!h->dry) {
+        StreamCtx& cx = *h->cur;
+        HIPCHK(hipMemcpyAsync(cx.rv_conf, L.cdev, (size_t)k * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(cx.rv_ev, st));
+    }
+    return 0;
+}
+// phase B: acceptance on the host -> per accepted edge the DPT head of its window sides, depths, and K where both sides share a shape.
+// Map buffers: (edge, side) order over the WINDOW sides of all k edges, offsets from the host-known shapes; what belongs to a rejected
+// edge or to no side at all is not written.  Planning pass (dry): every edge accepted.
+static int rvt_phase_b(sta_handle* h, Bump& ws, const SeqTable& t, const StreamCtx::RvtState& rs, int k, const uint8_t* adjacent, float rel_pose_thres,
+                       float* pose_conf_host, int* accepted_host, int* n_accepted, float* pts, float* conf, float* depth, float* K,
+                       int* k_valid_host, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim;
+    RvtLayout L = rvt_layout(ws, t, k, E, D);
+    bool acc[16];
+    for (int e = 0; e < k; ++e) acc[e] = true;
+    if (!h->dry) {
+        StreamCtx& cx = *h->cur;
+        HIPCHK(hipEventSynchronize(cx.rv_ev));                 // the reference syncs here too (slam.py:169)
+        int na = 0;
+        for (int e = 0; e < k; ++e) {
+            pose_conf_host[e] = cx.rv_conf[e];
+            acc[e] = !(pose_conf_host[e] < rel_pose_thres && !adjacent[e]);        // slam.py:169
+            accepted_host[e] = acc[e] ? 1 : 0; k_valid_host[e] = 0;
+            na += acc[e] ? 1 : 0;
+        }
+        *n_accepted = na;
+    }
+    const int Mp1 = t.tok0[k];
+    int64_t pix = 0;                                           // pixels of the window sides before this one
+    for (int e = 0; e < k; ++e) {
+        const int si = e, sj = k + e;
+        const bool pair = rs.mh[si] > 0 && rs.mh[si] == rs.mh[sj] && rs.mw[si] == rs.mw[sj];
+        const float* enc[2] = {L.F + (size_t)t.tok0[si] * E, L.F + (size_t)t.tok0[sj] * E};
+        const float* hk[3][2];
+        for (int q = 0; q < 3; ++q) {                          // the side's patch rows of hook q: behind the entry's pose row
+            hk[q][0] = L.hk[q][0] + (size_t)(t.tok0[si] + e + 1) * D;
+            hk[q][1] = L.hk[q][1] + (size_t)(t.tok0[sj] - Mp1 + e + 1) * D;
+        }
+        for (int side = 0; side < 2; ++side) {
+            const int s = side ? sj : si;
+            if (rs.mh[s] == 0) continue;
+            const int H = 16 * rs.mh[s], W = 16 * rs.mw[s], n = pair ? 2 : 1;
+            const int64_t hw = (int64_t)H * W;
+            if (acc[e]) {
+                ws.rewind(L.mark);
+                CHK(dpt_impl(h, ws, enc[side], enc[1] - enc[0], hk[0][side], hk[0][1] - hk[0][0], hk[1][side], hk[1][1] - hk[1][0],
+                             hk[2][side], hk[2][1] - hk[2][0], n, H, W, pts ? pts + pix * 3 : nullptr, conf ? conf + pix : nullptr, n, nullptr, nullptr, st));
+                ws.rewind(L.mark);
+                int nblk = (int)((hw + 256 * 8 - 1) / (256 * 8)); if (nblk > 256) nblk = 256; if (nblk < 1) nblk = 1;
+                double* partial = (double*)ws.take((int64_t)n * nblk * 5 * 8);
+                if (!h->dry) {
+                    REQUIRE(!ws.overflow, "internal: workspace overflow");
+                    hipLaunchKernelGGL(intrinsics_partial_kernel, dim3(nblk, n), dim3(256), 0, st, pts + pix * 3, conf + pix, n, H, W, depth + pix, partial, nblk, H > W);
+                    if (pair) {
+                        hipLaunchKernelGGL(intrinsics_final_kernel, dim3(1), dim3(64), 0, st, partial, 2, nblk, H, W, 2, K + (size_t)e * 9, (float*)nullptr, H > W);
+                        k_valid_host[e] = 1;
+                    }
+                    HIPCHK(hipGetLastError());
+                }
+            }
+            pix += n * hw;
+            if (pair) break;                                   // both sides went in one call
+        }
+    }
+    return 0;
+}
+
+// Host arrays of the entry -> per-sequence arrays (s = e side i, k + e side j) for build_token_sel
+static int rvt_table(sta_handle* h, const float* feat_i, int Hi, int Wi, const float* const* feat_j, const int* Hj, const int* Wj, int k,
+                     const int* win_i, const int* cnt_i, const int64_t* idx_i, const int* win_j, const int* cnt_j, const int64_t* idx_j,
+                     TokenSel* g, StreamCtx::RvtState* rs, int* pmax) {
+    REQUIRE(k >= 1 && k <= 16, "1 .. 16 candidate edges per keyframe (got %d)", k);
+    REQUIRE(feat_i && feat_j && Hj && Wj && win_i && win_j, "null argument");
+    const float* srcs[SEQ_MAX]; int hp[SEQ_MAX], wp[SEQ_MAX], win[SEQ_MAX * 4], cnt[SEQ_MAX];
+    CHK(check_ready(h, k, Hi, Wi));
+    *pmax = std::max(Hi, Wi) / 16;
+    for (int e = 0; e < k; ++e) {
+        CHK(check_ready(h, k, Hj[e], Wj[e]));
+        *pmax = std::max(*pmax, std::max(Hj[e], Wj[e]) / 16);
+        srcs[e] = feat_i; hp[e] = Hi / 16; wp[e] = Wi / 16;
+        srcs[k + e] = feat_j[e]; hp[k + e] = Hj[e] / 16; wp[k + e] = Wj[e] / 16;
+        for (int q = 0; q < 4; ++q) { win[4 * e + q] = win_i[4 * e + q]; win[4 * (k + e) + q] = win_j[4 * e + q]; }
+        cnt[e] = cnt_i ? cnt_i[e] : 0; cnt[k + e] = cnt_j ? cnt_j[e] : 0;
+    }
+    const int64_t* const idx_side[2] = {idx_i, idx_j};
+    memset(rs, 0, sizeof *rs);
+    CHK(build_token_sel(srcs, hp, wp, win, cnt, idx_side, 2 * k, g, rs->mh, rs->mw));
+    for (int s = 0; s < 2 * k; ++s) rs->n[s] = g->t.tok0[s + 1] - g->t.tok0[s];
+    return 0;
+}
+
+extern "C" int sta_regress_views_tokens_begin(sta_handle* h, const float* feat_i, int Hi, int Wi,
+                                              const float* const* feat_j, const int* Hj, const int* Wj, int k,
+                                              const int* win_i, const int* cnt_i, const int64_t* idx_i,
+                                              const int* win_j, const int* cnt_j, const int64_t* idx_j,
+                                              float* pose, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    TokenSel g; StreamCtx::RvtState rs; int pmax = 0;
+    CHK(rvt_table(h, feat_i, Hi, Wi, feat_j, Hj, Wj, k, win_i, cnt_i, idx_i, win_j, cnt_j, idx_j, &g, &rs, &pmax));
+    REQUIRE(pose, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    CHK(ensure_rope(h, pmax));
+    CHK(stream_ctx(h, st));
+    REQUIRE(!h->cur->rv_open, "sta_regress_views_tokens_begin: the previous scheduler call on this stream has not been finished");
+    if (!h->cur->rv_conf) {
+        HIPCHK(hipHostMalloc((void**)&h->cur->rv_conf, 16 * sizeof(float), hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&h->cur->rv_ev, hipEventDisableTiming));
+        h->n_alloc += 2;
+    }
+    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
+    h->rope_foreign = true;
+    // one plan for both phases (phase B sized for k accepted edges), then phase A runs
+    int r = plan_and_run(h, st, [&](Bump& ws) -> int {
+        if (h->dry) {
+            CHK(rvt_phase_a(h, ws, g, k, pose, st));
+            ws.rewind(0);
+            return rvt_phase_b(h, ws, g.t, rs, k, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, st);
+        }
+        return rvt_phase_a(h, ws, g, k, pose, st);
+    });
+    if (r != 0) return r;
+    if (h->reserve_only) return 0;
+    StreamCtx& c = *h->cur;
+    c.rv_open = true; c.rv_kind = 1; c.rv_k = k; c.rvt = rs;
+    return 0;
+}
+
+extern "C" int sta_regress_views_tokens_finish(sta_handle* h, const uint8_t* adjacent, float rel_pose_thres,
+                                               float* pose_conf_host, int* accepted_host, int* n_accepted,
+                                               float* pts, float* conf, float* depth, float* K, int* k_valid_host, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    REQUIRE(adjacent && pose_conf_host && accepted_host && n_accepted && pts && conf && depth && K && k_valid_host, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    CHK(stream_ctx(h, st));
+    StreamCtx& c = *h->cur;
+    REQUIRE(c.rv_open, "sta_regress_views_tokens_finish: no scheduler call was begun on this stream");
+    REQUIRE(c.rv_kind == 1, "sta_regress_views_tokens_finish: the call pending on this stream was begun with sta_regress_views_begin: finish it with sta_regress_views_finish (or abort it)");
+    c.rv_open = false;                                  // (also on an error below: the call is over either way)
+    const int k = c.rv_k;
+    SeqTable t; memset(&t, 0, sizeof t);
+    t.S = 2 * k;
+    for (int s = 0; s < 2 * k; ++s) t.tok0[s + 1] = t.tok0[s] + c.rvt.n[s];
+    *n_accepted = 0;
+    h->dry = false;
+    Bump ws = cur_bump(h);                              // the workspace phase A planned and filled
+    return rvt_phase_b(h, ws, t, c.rvt, k, adjacent, rel_pose_thres, pose_conf_host, accepted_host, n_accepted, pts, conf, depth, K, k_valid_host, st);
+}
+
+extern "C" int sta_regress_views_tokens(sta_handle* h, const float* feat_i, int Hi, int Wi,
+                                        const float* const* feat_j, const int* Hj, const int* Wj, int k,
+                                        const int* win_i, const int* cnt_i, const int64_t* idx_i,
+                                        const int* win_j, const int* cnt_j, const int64_t* idx_j,
+                                        const uint8_t* adjacent, float rel_pose_thres,
+                                        float* pose, float* pose_conf_host, int* accepted_host, int* n_accepted,
+                                        float* pts, float* conf, float* depth, float* K, int* k_valid_host, void* stream) {
+    REQUIRE(h, "null handle");
+    REQUIRE(adjacent && pose_conf_host && accepted_host && n_accepted && pts && conf && depth && K && k_valid_host, "null argument");
+    CHK(sta_regress_views_tokens_begin(h, feat_i, Hi, Wi, feat_j, Hj, Wj, k, win_i, cnt_i, idx_i, win_j, cnt_j, idx_j, pose, stream));
+    return sta_regress_views_tokens_finish(h, adjacent, rel_pose_thres, pose_conf_host, accepted_host, n_accepted, pts, conf, depth, K, k_valid_host, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -93,6 +93,44 @@ def regress_two_views_split(frontend: STAFrontend, feat_i, feat_j, pos_i, pos_j,
     return EdgeResult(head["pose"][0], conf, True, conf_maps, K, pts[..., 2], pts)
 
 
+def regress_two_views_tokens_split(frontend: STAFrontend, feat_i, size_i, feat_j, size_j, sel_i, sel_j, adjacent: bool,
+                                   rel_pose_thres: float) -> EdgeResult:
+    """One edge (i, j) on TOKEN SUBSETS through the split entry points at B = 1 - the sequence one `regress_views_tokens` call
+    replaces for k edges: slice the cached encodings (`select_tokens`), `decode_stereo_tokens`, `head_pose_s`, the host-side accept /
+    reject test, `head_pts` per window side (j first, like slam.py:179-180) and, where both sides are windows of one shape, the
+    pair-shared intrinsics.  Arguments and result as one edge of `slam_scheduler.regress_views_tokens`."""
+    from .slam_scheduler import _selection
+    sides = []
+    for feat, (H, W), sel in ((feat_i, size_i, sel_i), (feat_j, size_j, sel_j)):
+        hp, wp = int(H) // 16, int(W) // 16
+        feat = feat.to(frontend.device, torch.float32).reshape(1, hp * wp, -1)
+        win, index = _selection(sel, hp, wp)
+        if index is None:
+            index = STAFrontend.window_index((hp, wp), win, 1)[0]
+        f, p = STAFrontend.select_tokens(feat, frontend._positions(1, hp, wp), index.to(frontend.device))
+        sides.append((f, p, None if win[2] == 0 else (16 * win[2], 16 * win[3])))
+    layers = sorted({hk - 1 for hk in frontend.cfg.hooks[1:]})
+    tokens_i, tokens_j = frontend.decode_stereo_tokens(sides[0][0], sides[1][0], sides[0][1], sides[1][1], layers=layers)
+    head = frontend.head_pose_s(tokens_i[-1][:, 0, :])
+    conf = float(head["conf"][0])
+    if not adjacent and conf < rel_pose_thres:
+        return EdgeResult(head["pose"][0], conf, False)
+    maps = [None, None]
+    for side in (1, 0):
+        f, _p, shape = sides[side]
+        if shape is not None:
+            toks = tokens_j if side else tokens_i
+            maps[side] = frontend.head_pts([f] + [None if t is None else t[:, 1:, :] for t in toks], [list(shape)])
+    if maps[0] is not None and maps[1] is not None and sides[0][2] == sides[1][2]:
+        pts = torch.cat([maps[0]["pts3d"], maps[1]["pts3d"]], dim=0)
+        conf_maps = torch.cat([maps[0]["conf"], maps[1]["conf"]], dim=0)
+        K = estimate_intrinsic_from_pts3d(frontend, pts, conf_maps, shared_intrinsic=True)
+        return EdgeResult(head["pose"][0], conf, True, conf_maps, K, pts[..., 2], pts)
+    confs = [None if m is None else m["conf"][0] for m in maps]
+    ptss = [None if m is None else m["pts3d"][0] for m in maps]
+    return EdgeResult(head["pose"][0], conf, True, confs, None, [None if q is None else q[..., 2] for q in ptss], ptss)
+
+
 def replay(frontend: STAFrontend, n_keyframes: int, add_view: Callable[[int], Tuple[torch.Tensor, Optional[torch.Tensor]]],
            edge_list: Callable[[int], Sequence[int]], rel_pose_thres: float, H: int, W: int, schedule: str = "batched",
            streams: Optional[Sequence[torch.cuda.Stream]] = None, timeline: Optional[Dict[str, list]] = None,
