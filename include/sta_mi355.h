@@ -168,6 +168,16 @@ STA_API int sta_pipeline_streams(sta_handle* h, int n, void** streams_out, int* 
 #define STA_LANES_ON 1
 STA_API int sta_set_side_lanes(sta_handle* h, int mode);
 
+/* sta_set_varlen_heads: how sta_regress_views_tokens / sta_regress_views_tokens_finish run the DPT head, read when the heads are
+ * enqueued (at finish time).  The call's workspace is planned at begin time, for the varlen pass only when the switch is on THEN: a
+ * caller who never sets it plans and allocates exactly what it did before.  Set it before begin; switching it on between begin and
+ * finish makes finish fail with a message (the call is over, the stream serves the next one), switching it off there is served.  0 (default): once per accepted edge and window side (one call for the two sides of an edge whose sides
+ * share a shape), as before.  1: the window sides of ALL accepted edges through ONE sta_head_pts_varlen pass that writes straight into
+ * the pts / conf layout those entry points define; ranges of rejected edges stay unwritten, the per-edge reductions (depth, the shared
+ * K of same-shape pairs) stay per edge.  Same decisions; maps within 1e-4 of mode 0 (tests/test_regress_tokens_varlen_gpu.py).  The three
+ * scheduler signatures do not change. */
+STA_API int sta_set_varlen_heads(sta_handle* h, int on);
+
 /* Range report.  Activations travel between kernels as fp16 planes (hi + residual), the f16mx arithmetic of the DPT head adds
  * fp8 correction bytes (activations e5m2, weights e4m3): values beyond +-65504 (or NaN) SATURATE when they are written to a
  * plane, activation correction bytes saturate at +-57344, weight bytes at |w| > 28 (the result then degrades towards
@@ -314,6 +324,25 @@ STA_API int sta_head_pts(sta_handle* h,
                  const float* hook2, int64_t hook2_bstride,
                  const float* hook3, int64_t hook3_bstride,
                  int B, int H, int W, float* pts, float* conf, void* stream);
+
+/* sta_head_pts on B <= 32 entries whose patch rectangles DIFFER, in one call: entry b is hp[b] x wp[b] patches (hp, wp >= 1), and what
+ * sta_head_pts computes for that entry alone at (16 hp[b], 16 wp[b]) - the reference's head_pts on it at B = 1.  Nothing is padded and
+ * no pixel reads another entry's pixels (no halo, no bilinear tap, no tile spans two entries): at each of the head's six resolutions
+ * the pixels of all entries are packed entry-major, and every launch carries the per-entry geometry in its kernel arguments.
+ * enc_row, hook_row, hp, wp, out_pix are HOST arrays [B]; the call copies nothing to the device for them and does not synchronise.
+ *   enc_row[b]   first patch row of entry b in enc_feat ([rows, enc_dim], dense rows)
+ *   hook_row[b]  first patch row of entry b in EACH hook buffer ([rows, dec_dim], dense rows)
+ * - so the packed output of sta_decode_varlen (a pose row in front of each entry) and the scheduler's (edge, side) subsets feed the head
+ * in place.  out_pix[b]: pixel offset of entry b in pts (x 3 floats) and conf; NULL = packed, 256 * sum_{b' < b} hp wp.  Outputs are in
+ * image orientation, [16 hp, 16 wp].  Tile families come from the cost model on the packed rows of each level; the halo-tiled family 8
+ * runs its varlen form where it is forced (sta_set_gemm_variant 8), the register-staged family 1 has none: the automatic choice
+ * never takes it here, and forcing it makes the call fail with a message.  Precisions f16x3, f16x3h, f16x3m; plain f16 is refused.  Like
+ * the other varlen calls it runs on one lane and is NOT covered by sta_reserve: the first call of a set of shapes may allocate.
+ * Returns -1 with a message for null pointers, B outside [1, 32], hp or wp below 1, 2^31 or more rows at any level, features that
+ * are not 16-byte aligned. */
+STA_API int sta_head_pts_varlen(sta_handle* h, const float* enc_feat, const int64_t* enc_row,
+                        const float* hook1, const float* hook2, const float* hook3, const int64_t* hook_row,
+                        const int* hp, const int* wp, int B, float* pts, float* conf, const int64_t* out_pix, void* stream);
 
 /* Monolithic two-view forward.  Outputs index 0 = main view (img_a), 1 = support (img_b):
  * pts[k] [B,H,W,3], conf[k] [B,H,W], pose[k] [B,16], pose_conf[k] [B]. */

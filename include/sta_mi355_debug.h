@@ -299,6 +299,27 @@ STA_API int sta_bench_attention(sta_handle* h, int S, int heads, int nq, int nk,
 STA_API int sta_bench_attention_mixed(sta_handle* h, int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift,
                                       int iters, float* ms_out, void* stream);
 
+/* The varlen DPT head (sta_head_pts_varlen), kernel by kernel: B <= 32 entries of different size in ONE launch, inputs and outputs
+ * packed entry-major (entry b: H[b] x W[b] pixels, NHWC fp32).  H / W / Hc / Wc: HOST arrays.  Arguments otherwise as
+ * sta_debug_conv3x3_r2 / _conv3_head / _convt / _up2.  guard (device, 4096 bytes, may be NULL) receives the 4096 bytes that start at the
+ * byte behind the output planes' last row, filled with 0xA5 before the launch.  Precision f16 is refused.  sta_debug_conv3_head_varlen: the fused tail as an
+ * implicit GEMM on 192x128 tiles, or the halo form under forced family 8; fails on a small grid (fewer than 192 tiles) and under
+ * another forced family, as the head itself falls back to conv + head_final there. */
+STA_API int sta_debug_conv3x3_varlen(sta_handle* h, const float* x, const float* w, const float* bias, int B, const int* H, const int* W,
+                                     int Cin, int Co, int stride, int relu_in, int act, const float* resid, const float* resid2,
+                                     float* out, void* guard, void* stream);
+STA_API int sta_debug_conv3_head_varlen(sta_handle* h, const float* x, const float* w2, const float* b2, const float* w4, const float* b4,
+                                        int B, const int* H, const int* W, float* pts, float* conf, void* stream);
+STA_API int sta_debug_convt_varlen(sta_handle* h, const float* x, const float* w, const float* bias, int B, const int* H, const int* W,
+                                   int C, int k, float* out, void* guard, void* stream);
+STA_API int sta_debug_up2_varlen(sta_handle* h, const float* x, int B, const int* H, const int* W, int C, const int* Hc, const int* Wc,
+                                 float* out, void* guard, void* stream);
+/* Host only: the packing of the varlen head's six levels - level 0 .. 5 = (ceil(h/2), ceil(w/2)), (h, w), (2h, 2w), (4h, 4w), (8h, 8w),
+ * (16h, 16w).  off [6][B + 1]: first packed pixel of every entry, then the level's size; hw [6][B][2]: the entry's (rows, columns).
+ * ntiles [6], tiles [cap][3] (both may be NULL): the tile map of the halo-tiled convolution at every level, level after level: tile ->
+ * (entry, y0, x0), tiles of 8 rows x 32 pixels of one entry, decoded by the function the kernel uses; -1 when cap is too small. */
+STA_API int sta_debug_dpt_varlen_plan(int B, const int* hp, const int* wp, long long* off, int* hw, int* ntiles, int* tiles, int cap);
+
 #ifdef __cplusplus
 }
 #endif

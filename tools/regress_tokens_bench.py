@@ -12,7 +12,8 @@ random (the cost does not depend on their values).
     384x512, pruned       loop candidates: a random half of the tokens on both sides (index lists: no maps)
 
 Quantities (median of 21 single calls after 3 warm-up calls, device events around each call):
-    (a) tokens     one regress_views_tokens call
+    (a) tokens     one regress_views_tokens call (heads="entry": the DPT head once per edge)
+    (a') varlen    the same call with heads="varlen": the window sides of all edges through one varlen head pass
     (b) split      the k regress_two_views_tokens_split sequences it replaces (decode_stereo_tokens, head_pose_s, a host read, head_pts)
     (c) whole      regress_views on the whole frames: what a caller without subsets pays (it computes something else)
 """
@@ -57,7 +58,9 @@ def config(H, Wd, kind, win):
 
     def whole():
         return regress_views(m, feats[0], feats[1:], adjacent, 0.0, H, Wd)
-    return {"(a) tokens": tokens, "(b) split": split, "(c) whole": whole}
+    def tokens_varlen():
+        return regress_views_tokens(m, feats[0], size, feats[1:], [size] * K, sel_i, sel_j, adjacent, 0.0, heads="varlen")
+    return {"(a) tokens": tokens, "(a') varlen": tokens_varlen, "(b) split": split, "(c) whole": whole}
 
 
 def median_us(f):
@@ -89,3 +92,5 @@ for name, H, Wd, kind, win in CONFIGS:
         med[key], lo, hi = median_us(f)
         print(f"  {key:12s} median {med[key]:9.1f} us   (min {lo:9.1f}, max {hi:9.1f})")
     print(f"  (a) / (b) = {med['(a) tokens'] / med['(b) split']:.3f}    (a) / (c) = {med['(a) tokens'] / med['(c) whole']:.3f}")
+    av = med["(a') varlen"]
+    print(f"  (a') / (b) = {av / med['(b) split']:.3f}    (a') / (c) = {av / med['(c) whole']:.3f}    (a') / (a) = {av / med['(a) tokens']:.3f}")

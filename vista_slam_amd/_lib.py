@@ -40,6 +40,7 @@ SIGNATURES = {
     "sta_set_precision": (_i, [_vp, _i]),
     "sta_set_deterministic": (_i, [_vp, _i]),
     "sta_set_side_lanes": (_i, [_vp, _i]),
+    "sta_set_varlen_heads": (_i, [_vp, _i]),
     "sta_pipeline_streams": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i)]),
     "sta_reserve": (_i, [_vp, _i, _i, _i, _i, C.POINTER(_vp), _i]),
     "sta_alloc_stats": (_i, [_vp, C.POINTER(_i64)]),
@@ -54,6 +55,8 @@ SIGNATURES = {
     "sta_decode_tokens": (_i, [_vp, _fp, _fp, _vp, _vp, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_decode_varlen": (_i, [_vp, _fp, _fp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), _i, _i, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     "sta_head_pose": (_i, [_vp, _fp, _i, _i64, _fp, _fp, _vp]),
+    "sta_head_pts_varlen": (_i, [_vp, _fp, C.POINTER(_i64), _fp, _fp, _fp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i), _i, _fp, _fp,
+                                 C.POINTER(_i64), _vp]),
     "sta_head_pts": (_i, [_vp, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _i, _i, _i, _fp, _fp, _vp]),
     "sta_forward_pair": (_i, [_vp, _fp, _fp, _i, _i, _i, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                               C.POINTER(_vp), _vp]),
@@ -159,6 +162,11 @@ TEST_SIGNATURES = {
     "sta_debug_gemm_resid_ln": (_i, [_vp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _f, _fp, _fp, _vp]),
     "sta_debug_head_final": (_i, [_vp, _fp, _fp, _fp, _i64, _fp, _fp, _vp]),
     "sta_debug_svd_orthogonalize": (_i, [_vp, _fp, _fp, _i, _vp]),
+    "sta_debug_conv3x3_varlen": (_i, [_vp, _fp, _fp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp, _vp]),
+    "sta_debug_conv3_head_varlen": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _fp, _fp, _vp]),
+    "sta_debug_convt_varlen": (_i, [_vp, _fp, _fp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _fp, _vp, _vp]),
+    "sta_debug_up2_varlen": (_i, [_vp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_i), _fp, _vp, _vp]),
+    "sta_debug_dpt_varlen_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i]),
 }
 
 _lib = None

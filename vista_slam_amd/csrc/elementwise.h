@@ -188,6 +188,31 @@ __global__ void rows_to_planes_kernel(const float* x, int64_t bstride, int rows,
     }
 }
 
+// The row-table form (sta_head_pts_varlen): entry b's t.tok0[b + 1] - t.tok0[b] rows start at row src_row[b] of x ([., C], dense rows)
+// and go to rows [t.tok0[b], t.tok0[b + 1]) of the blocked planes - the packed output of sta_decode_varlen (a pose row in front of
+// each entry) and the scheduler's subsets feed the head in place.
+struct RowSrc { SeqTable t; int64_t src_row[SEQ_MAX]; };
+template <bool SPLIT, class ROWS>
+__global__ void rows_to_planes_kernel(const float* x, const ROWS rs, int C, int64_t total4, f16* o_hi, int64_t orows, int mx, unsigned long long* rng) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    const int c4 = C / 4;
+    for (; i < total4; i += step) {
+        const int64_t r = i / c4; const int c = (int)(i - r * c4) * 4;
+        int64_t src = rs.src_row[0] + r;
+        for (int b = 1; b < rs.t.S; ++b) if (rs.t.tok0[b] <= r) src = rs.src_row[b] + (r - rs.t.tok0[b]);
+        const float4 v = *reinterpret_cast<const float4*>(x + src * C + c);
+        float y[4] = {v.x, v.y, v.z, v.w};
+        H4 h, l;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { if (SPLIT) split_f16(y[e], h.e[e], l.e[e], rng); else h.e[e] = to_f16_sat(y[e], rng); }
+        if (SPLIT && mx) { store_mx4(o_hi, blk_off<SPLIT>(r, c, orows), split_mx4<false>(y, rng)); continue; }      // (counts as the one-shape form does)
+        const size_t o = blk_off<SPLIT>(r, c, orows);
+        *reinterpret_cast<uint2*>(o_hi + o) = h.u;
+        if (SPLIT) *reinterpret_cast<uint2*>(o_hi + o + 32) = l.u;
+    }
+}
+
 // planes [nb, rows(+pad), C] -> fp32 [nb, rows, C]  (test/debug taps only)
 __global__ void planes_to_f32_kernel(const f16* hi, const f16* lo, int64_t ibstride_rows, int rows, int C,
                                      int64_t total, float* out, int64_t irows /* blocked planes with irows rows; 0 = row-major */,
@@ -784,6 +809,86 @@ __global__ __launch_bounds__(256) void bilinear_up2_kernel(const f16* i_hi, cons
                 emit(k, top, bot);
             }
         }
+    }
+}
+
+// The varlen form (sta_head_pts_varlen; GEO = VlGeo, sta_common.h): entries of different size in one launch, input and output pixels
+// packed entry-major.  One workgroup = ONE output row of one entry (NR = 1: at window scale the four-row form has no grid to fill);
+// workgroup -> (entry, row) by a scan over the entries' output rows (block-uniform), in the same XCD band order.  ry / rx, the clamp
+// of the second tap and the crop (ho <= 2 hi, wo <= 2 wi) are the entry's own: Hi = 1 / Wi = 1 give ratio 0, every tap the one pixel.
+// The arithmetic of a pixel is that of the one-shape kernel's one-row form, term for term.
+template <bool SPLIT, int NR, class GEO>
+__global__ __launch_bounds__(256) void bilinear_up2_kernel(const f16* i_hi, const f16* i_lo, const GEO g, int C, int64_t irows, int64_t orows,
+                                                           f16* o_hi, f16* o_lo, int mx, unsigned long long* rng) {
+    static_assert(NR == 1, "the varlen bilinear has the one-row form only");
+    const int c8 = C / 8;
+    int bid;
+    {
+        const int nwg = gridDim.x, q = nwg / 8, r = nwg % 8, xcd = blockIdx.x % 8;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blockIdx.x / 8;
+    }
+    int b = 0, row0 = 0;
+    for (int i = 0; i + 1 < g.B; ++i) { if (bid >= row0 + g.ho[i]) { row0 += g.ho[i]; b = i + 1; } else break; }
+    const int y = bid - row0;
+    const int Hi = g.hi[b], Wi = g.wi[b], Hc = g.ho[b], Wc = g.wo[b];
+    if (y >= Hc) return;                                       // (a grid larger than the sum of the rows)
+    const size_t ibase = (size_t)g.in0[b], obase = (size_t)g.out0[b];
+    const float ry = Hi > 1 ? (float)(Hi - 1) / (float)(2 * Hi - 1) : 0.f;
+    const float rx = Wi > 1 ? (float)(Wi - 1) / (float)(2 * Wi - 1) : 0.f;
+    const float sy = ry * y;
+    const int y0 = (int)sy, y1 = y0 + (y0 < Hi - 1);
+    const float fy = sy - y0;
+    const bool pow2 = (c8 & (c8 - 1)) == 0;
+    const int sh = __ffs(c8) - 1;
+    const int per_row = Wc * c8;
+    for (int i = threadIdx.x; i < per_row; i += 256) {
+        const int x = pow2 ? i >> sh : i / c8;
+        const int c = (i - x * c8) * 8;
+        const float sx = rx * x;
+        const int x0 = (int)sx, x1 = x0 + (x0 < Wi - 1);
+        const float fx = sx - x0;
+        float row_top[2][8];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (r == 1 && y1 == y0) continue;
+            const size_t rb = ibase + (size_t)(r == 0 ? y0 : y1) * Wi;
+            const size_t oa = blk_off<SPLIT>(rb + x0, c, irows), ob = blk_off<SPLIT>(rb + x1, c, irows);
+            H8 a, b_, al, bl;
+            a.u = ldg16(i_hi + oa); b_.u = ldg16(i_hi + ob);
+            if (SPLIT) { al.u = ldg16(i_hi + oa + 32); bl.u = ldg16(i_hi + ob + 32); }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float v0 = (float)a.e[e], v1 = (float)b_.e[e];
+                if (SPLIT && mx) {
+                    constexpr float KL = 1.0f / (float)(1 << STA_MX_A_SLO);
+                    v0 += __builtin_amdgcn_cvt_f32_bf8(reinterpret_cast<const unsigned short*>(&al)[e], 1) * KL;
+                    v1 += __builtin_amdgcn_cvt_f32_bf8(reinterpret_cast<const unsigned short*>(&bl)[e], 1) * KL;
+                } else if (SPLIT) { v0 += (float)al.e[e]; v1 += (float)bl.e[e]; }
+                row_top[r][e] = (1.f - fx) * v0 + fx * v1;
+            }
+        }
+        H8 oh, ol;
+        float vout[8];
+        RangeAcc ra;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float bot = y1 == y0 ? row_top[0][e] : row_top[1][e];
+            const float v = (1.f - fy) * row_top[0][e] + fy * bot;
+            vout[e] = v;
+            if (SPLIT && mx) continue;
+            if (SPLIT) split_f16(v, oh.e[e], ol.e[e], ra); else oh.e[e] = to_f16_sat(v, ra);
+        }
+        const size_t o = blk_off<SPLIT>(obase + (size_t)y * Wc + x, c, orows);
+        if (SPLIT && mx) {
+            const MX4 m0 = split_mx4<false>(vout, ra), m1 = split_mx4<false>(vout + 4, ra);
+            *reinterpret_cast<uint4*>(o_hi + o) = make_uint4(m0.hi.x, m0.hi.y, m1.hi.x, m1.hi.y);
+            *reinterpret_cast<uint4*>(o_hi + o + 32) = make_uint4(m0.pairs.x, m0.pairs.y, m1.pairs.x, m1.pairs.y);
+            ra.flush(rng);
+            continue;
+        }
+        ra.flush(rng);
+        *reinterpret_cast<uint4*>(o_hi + o) = oh.u;
+        if (SPLIT) *reinterpret_cast<uint4*>(o_hi + o + 32) = ol.u;
     }
 }
 

@@ -301,9 +301,10 @@ __device__ __forceinline__ void epilogue_qkv_tile(const GemmParams& p, const flo
 // of the tile lies beyond the row's end); default: the GEMM's M.
 #define QKV_LDS_BYTES (2 * 32 * 80)      // per-wave LDS scratch of the V^T transpose in epilogue_qkv_tile
 #define EPI_LDS_BYTES 5120               // per-wave LDS scratch of the epilogues (>= QKV_LDS_BYTES, >= 32 x 144 for the plane tiles)
-template <bool SPLIT, int EPI>
+// GEO = VlGeo (EPI_CONVT only): the scatter of the varlen DPT head - a row is an input pixel of ITS entry (sta_common.h)
+template <bool SPLIT, int EPI, class GEO = NoGeo>
 __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const floatx16& acc, int row0, int col, int lane,
-                                              int kslice = 0, int mlim = -1, char* wave_lds = nullptr) {
+                                              int kslice = 0, int mlim = -1, char* wave_lds = nullptr, const GEO& geo = GEO{}) {
     const bool first_slice = kslice == 0;
     const int M_ = mlim >= 0 ? mlim : p.M;
     RangeAcc ra;                      // range report (sta_common.h): one flush per tile - for the plane epilogues of the DPT head
@@ -541,9 +542,16 @@ __device__ __forceinline__ void epilogue_tile(const GemmParams& p, const floatx1
         for (int r = 0; r < 16; ++r) {
             if (!ok[r]) continue;
             const int row = row0 + 4 * lhi + (r & 3) + 8 * (r >> 2);
+            size_t opix;
+            if constexpr (!std::is_same<GEO, NoGeo>::value) {
+                const VlEntry en = vl_entry<false>(geo, row);
+                const int rem = row - en.in0, y = rem / en.wi, x = rem - y * en.wi;
+                opix = (size_t)en.out0 + (size_t)(y * p.ct_k + dy) * (en.wi * p.ct_k) + (x * p.ct_k + dx);
+            } else {
             const int img = row / hw, rem = row - img * hw;
             const int y = rem / p.ct_w, x = rem - y * p.ct_w;
-            const size_t opix = ((size_t)img * (p.ct_h * p.ct_k) + (y * p.ct_k + dy)) * (p.ct_w * p.ct_k) + (x * p.ct_k + dx);
+            opix = ((size_t)img * (p.ct_h * p.ct_k) + (y * p.ct_k + dy)) * (p.ct_w * p.ct_k) + (x * p.ct_k + dx);
+            }
             const size_t o = blk_off<SPLIT>(opix, co, p.c_rp);
             const float v = acc[r] + bv;
             if (SPLIT && p.c_mx) store_mx1<false>(p.C_hi, o, v, ra);

@@ -295,8 +295,13 @@ __device__ __forceinline__ void gemm2_tail(const GemmParams& p, const int tb, ch
 #ifndef STA_RING_ABL
 #define STA_RING_ABL 0      // probe builds (tools/ring_ablate.py): the ablation mask below applied to the ring family inside the product flow
 #endif
-template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, int ABL_ = 0, int NSTG = 2, bool MX = false>
-__device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_id_in) {
+// GEO = VlGeo: the varlen form (sta_head_pts_varlen) of the two places that decode image geometry from a row - the 3x3 tap loader
+// (the row's own entry gives image base, Hi, Wi and the tap mask: no tap leaves the entry) and the EPI_CONVT scatter.  Everything else
+// works on packed rows and is the same code.
+template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, int ABL_ = 0, int NSTG = 2, bool MX = false, class GEO = NoGeo>
+__device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_id_in, const GEO& geo = GEO{}) {
+    constexpr bool VL = !std::is_same<GEO, NoGeo>::value;
+    static_assert(!VL || AMODE == A_CONV3 || EPI == EPI_CONVT, "the varlen form exists where geometry is decoded");
     constexpr int ABL = ABL_ | (NSTG > 2 ? STA_RING_ABL : 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = WAVES_M * WAVES_N;
@@ -367,6 +372,8 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
     // address of every tap used to be rebuilt from (image, y, x) with two exec-masked bounds branches and 64-bit multiplies per
     // slot plus a scalar division per K tile: ~400 issue cycles per K tile next to 512 cycles of f16mx MFMAs)
     int cv_pix0[SA]; unsigned cv_mask[SA], cv_coff[SA];
+    // (varlen: bits 9 .. 31 of the mask hold the row pitch Wi of the slot's own entry - tap (ky, kx) is ky * Wi + kx pixels away;
+    //  the launcher checks Wi < 2^23)
 #pragma unroll
     for (int s = 0; s < SA; ++s) {
         const int row = RPS * (wave + NW * s) + row_in;                      // tile row
@@ -379,18 +386,28 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         } else {
             const bool rok = gm < p.M;
             const int gmc = rok ? gm : 0;
-            const int hw = p.Ho * p.Wo;
-            const int img = gmc / hw;
-            const int rem = gmc - img * hw;
-            const int y0 = (rem / p.Wo) * p.cstride - 1, x0 = (rem % p.Wo) * p.cstride - 1;
-            cv_pix0[s] = (img * p.Hi + y0) * p.Wi + x0;
+            int y0, x0, Hi_, Wi_;
+            if constexpr (VL) {
+                const VlEntry en = vl_entry<true>(geo, gmc);
+                const int rem = gmc - en.out0, yo = rem / en.wo;
+                y0 = yo * p.cstride - 1; x0 = (rem - yo * en.wo) * p.cstride - 1;
+                Hi_ = en.hi; Wi_ = en.wi;
+                cv_pix0[s] = en.in0 + y0 * en.wi + x0;
+            } else {
+                const int hw = p.Ho * p.Wo;
+                const int img = gmc / hw;
+                const int rem = gmc - img * hw;
+                y0 = (rem / p.Wo) * p.cstride - 1; x0 = (rem % p.Wo) * p.cstride - 1;
+                Hi_ = p.Hi; Wi_ = p.Wi;
+                cv_pix0[s] = (img * p.Hi + y0) * p.Wi + x0;
+            }
             unsigned mk = 0;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int yi = y0 + t / 3, xi = x0 + t % 3;
-                if (rok && yi >= 0 && yi < p.Hi && xi >= 0 && xi < p.Wi) mk |= 1u << t;
+                if (rok && yi >= 0 && yi < Hi_ && xi >= 0 && xi < Wi_) mk |= 1u << t;
             }
-            cv_mask[s] = mk;
+            cv_mask[s] = VL ? mk | ((unsigned)Wi_ << 9) : mk;
             cv_coff[s] = (unsigned)chunk * 16u;
             a_src[s] = 0;
         }
@@ -415,8 +432,10 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         // conv: K tile kt = (tap, channel block); the tiles are issued in increasing kt, so the pair is carried as a counter
         // (cv_tap / cv_cb, set for kt0 before the first call) instead of being re-derived by a division per call
         int tap_off = 0; const char* a_cb = nullptr;
+        int tap_ky = 0, tap_kx = 0;
         if (AMODE == A_CONV3) {
             const int ky = cv_tap >= 6 ? 2 : (cv_tap >= 3 ? 1 : 0), kx = cv_tap - 3 * ky;
+            tap_ky = ky; tap_kx = kx;
             tap_off = ky * p.Wi + kx;
             a_cb = reinterpret_cast<const char*>(p.A_hi) + (size_t)cv_cb * p.a_rp * (A_ES * 2);
         }
@@ -429,6 +448,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
                 asm volatile("" : "+v"(o));      // opaque: keeps the 32-bit offset form (hipcc would hoist base + offset into a VGPR pair)
                 glds16(a_run + o, dst);
             } else {
+                if constexpr (VL) tap_off = tap_ky * (int)(cv_mask[s] >> 9) + tap_kx;
                 const unsigned off = (unsigned)(cv_pix0[s] + tap_off) * (unsigned)(A_ES * 2) + cv_coff[s];     // (pixels x 128 B < 2^32: checked by the launcher)
                 const bool ok = (cv_mask[s] >> cv_tap) & 1u;
                 glds16(ok ? static_cast<const void*>(a_cb + off) : static_cast<const void*>(p.zero_page), dst);
@@ -751,7 +771,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         for (int j = 0; j < NT; ++j)
 #pragma unroll
             for (int i = 0; i < MT; ++i)
-                { epilogue_tile<SPLIT, EPI>(p, acc[i][j], m0 + wm * WM + i * 32, n0 + wn * WN + j * 32 + l31, lane, kslice, -1, wave_lds); if (EPI == EPI_F16 || EPI == EPI_CONVT) STA_EPI_TILE_FENCE(); }
+                { epilogue_tile<SPLIT, EPI>(p, acc[i][j], m0 + wm * WM + i * 32, n0 + wn * WN + j * 32 + l31, lane, kslice, -1, wave_lds, geo); if (EPI == EPI_F16 || EPI == EPI_CONVT) STA_EPI_TILE_FENCE(); }
     }
     if (p.stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the epilogue's stores acknowledged
@@ -769,6 +789,12 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
 template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, int ABL = 0, int NSTG = 2, bool MX = false>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm2_kernel(const GemmParams p) {
     gemm2_body<SPLIT, AMODE, EPI, BM, BN, WAVES_M, WAVES_N, ABL, NSTG, MX>(p, blockIdx.x);
+}
+
+// the varlen form (gemm2_body): the geometry table travels next to the parameters
+template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, int ABL, int NSTG, bool MX, class GEO>
+__global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void gemm2_kernel(const GemmParams p, const GEO geo) {
+    gemm2_body<SPLIT, AMODE, EPI, BM, BN, WAVES_M, WAVES_N, ABL, NSTG, MX, GEO>(p, blockIdx.x, geo);
 }
 
 // Two independent GEMMs of the same tile family in ONE launch: blocks [0, tiles_a) work on `pa`, the rest on `pb`.

@@ -105,7 +105,7 @@ struct StreamCtx {
     // (sta_regress_views_tokens_begin), whose per-sequence counts and map grids phase B needs again (RvtState, sequence s = e
     // side i, k + e side j: n tokens; mh x mw patches of a window side, 0 for an index-list side, which has no maps)
     int rv_kind = 0;
-    struct RvtState { int n[SEQ_MAX], mh[SEQ_MAX], mw[SEQ_MAX]; } rvt{};
+    struct RvtState { int n[SEQ_MAX], mh[SEQ_MAX], mw[SEQ_MAX]; int plan_v; } rvt{};      // plan_v: the begin-time plan holds the varlen head pass (sta_set_varlen_heads was on)
     // side lane of the DPT head (dpt_impl): an internal second stream for the branches of the head that do not lie on its
     // critical chain, with its own split-K scratch; forked from and joined back into `st` inside the call
     hipStream_t side = nullptr; float* side_skbuf = nullptr; hipEvent_t side_ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -182,6 +182,7 @@ struct sta_handle {
     int pre_key[6] = {0, 0, 0, 0, 0, 0}; int* pre_tab = nullptr; int64_t pre_cap = 0; int pre_meta[12] = {0};
     bool dry = false;   // planning pass: run the orchestration without launching to size the workspace
     int lanes_mode = STA_LANES_AUTO;   // sta_set_side_lanes
+    bool varlen_heads = false;         // sta_set_varlen_heads: sta_regress_views_tokens[_finish] runs ONE sta_head_pts_varlen over the accepted edges' window sides
     std::vector<hipStream_t> pipe_streams; int pipe_verified = 0;   // sta_pipeline_streams: library-owned streams probed to overlap pairwise
     int lane = 0;       // 1 while dpt_impl enqueues on the context's side stream (launch_gemm then hands out the side lane's split-K scratch)
     // sta_reserve / sta_alloc_stats: device allocations (hipMalloc / hipFree / hipHostMalloc / stream and event creation count as
@@ -516,6 +517,11 @@ extern "C" int sta_set_precision(sta_handle* h, int precision) {
 extern "C" int sta_set_deterministic(sta_handle* h, int on) {
     REQUIRE(h, "null handle");
     h->deterministic = on != 0;
+    return 0;
+}
+extern "C" int sta_set_varlen_heads(sta_handle* h, int on) {
+    REQUIRE(h && (on == 0 || on == 1), "sta_set_varlen_heads: bad argument");
+    h->varlen_heads = on != 0;
     return 0;
 }
 extern "C" int sta_set_side_lanes(sta_handle* h, int mode) {
@@ -945,6 +951,34 @@ extern "C" int sta_head_pts(sta_handle* h, const float* enc_feat, int64_t enc_bs
     return plan_and_run(h, st, [&](Bump& ws) {
         return dpt_impl(h, ws, enc_feat, enc_bstride, hook1, hook1_bstride, hook2, hook2_bstride, hook3, hook3_bstride,
                         B, H, W, pts, conf, B, nullptr, nullptr, st);
+    });
+}
+
+extern "C" int sta_head_pts_varlen(sta_handle* h, const float* enc_feat, const int64_t* enc_row,
+                                   const float* hook1, const float* hook2, const float* hook3, const int64_t* hook_row,
+                                   const int* hp, const int* wp, int B, float* pts, float* conf, const int64_t* out_pix, void* stream) {
+    REQUIRE(h, "null handle");
+    DEV_SCOPE(h->device);
+    REQUIRE(h->finalized, "weights not finalized (call sta_finalize_weights)");
+    REQUIRE(enc_feat && hook1 && hook2 && hook3 && pts && conf, "null device pointer");
+    REQUIRE(enc_row && hook_row && hp && wp, "null host array");
+    REQUIRE(B >= 1 && B <= SEQ_MAX, "bad argument (B = %d): sta_head_pts_varlen takes 1 .. %d entries", B, SEQ_MAX);
+    REQUIRE(h->prec != STA_PREC_F16, "sta_head_pts_varlen has no precision-f16 form (f16x3, f16x3h and f16x3m have one)");
+    REQUIRE((((uintptr_t)enc_feat | (uintptr_t)hook1 | (uintptr_t)hook2 | (uintptr_t)hook3) & 15) == 0, "misaligned features: enc_feat and the hooks must be 16-byte aligned");
+    int64_t rows[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < B; ++b) {
+        REQUIRE(hp[b] >= 1 && wp[b] >= 1, "bad argument (entry %d is %d x %d patches): a patch rectangle has at least one row and one column", b, hp[b], wp[b]);
+        REQUIRE(enc_row[b] >= 0 && hook_row[b] >= 0 && (!out_pix || out_pix[b] >= 0), "bad argument (entry %d has a negative row or pixel offset)", b);
+        const int64_t n = (int64_t)hp[b] * wp[b];
+        const int64_t lv[6] = {(int64_t)((hp[b] + 1) / 2) * ((wp[b] + 1) / 2), n, 4 * n, 16 * n, 64 * n, 256 * n};
+        for (int k = 0; k < 6; ++k) {
+            rows[k] += lv[k];
+            REQUIRE(rows[k] < ((int64_t)1 << 31), "too many rows (2^31 or more at the head's level %d)", k);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    return plan_and_run(h, st, [&](Bump& ws) {
+        return dpt_varlen_impl(h, ws, enc_feat, enc_row, hook1, hook2, hook3, hook_row, hp, wp, B, pts, conf, out_pix, st);
     });
 }
 

@@ -176,3 +176,43 @@ union H4 { uint2 u; half4 h; f16 e[4]; };
 // sequences before s, tok0[S] = all of them; sequence s has n_s = tok0[s + 1] - tok0[s] tokens (elementwise.h says how rows follow).
 #define SEQ_MAX 32
 struct SeqTable { int S; int tok0[SEQ_MAX + 1]; };
+
+// The geometry of one launch of the varlen DPT head (sta_head_pts_varlen), in the kernel arguments: B <= SEQ_MAX entries, entry b an
+// image of hi[b] x wi[b] input pixels and ho[b] x wo[b] output pixels; both sides packed entry-major, row-major inside an entry, no
+// padding: entry b's input pixels are plane rows [in0[b], in0[b + 1]), its output pixels [out0[b], out0[b + 1]).  A 3x3 convolution has
+// ho = (hi - 1) / stride + 1, a ConvTranspose with k = stride ho = k hi, the x2 bilinear ho <= 2 hi (the crop).  Host values: nothing
+// is copied to the device for them.  NoGeo: the one-shape forms, which carry no table.
+struct NoGeo {};
+struct VlGeo { int B; int hi[SEQ_MAX], wi[SEQ_MAX], ho[SEQ_MAX], wo[SEQ_MAX]; int in0[SEQ_MAX + 1], out0[SEQ_MAX + 1]; };
+struct VlEntry { int e, hi, wi, ho, wo, in0, out0; };
+// entry of a packed row (OUT = true: an output pixel, else an input pixel): a scan with uniform indices (scalar loads of the
+// argument segment) that keeps the last entry starting at or before the row
+template <bool OUT>
+__device__ __forceinline__ VlEntry vl_entry(const VlGeo& g, int row) {
+    VlEntry r{0, g.hi[0], g.wi[0], g.ho[0], g.wo[0], 0, 0};
+    for (int i = 1; i < g.B; ++i) {
+        if ((OUT ? g.out0[i] : g.in0[i]) <= row) { r.e = i; r.hi = g.hi[i]; r.wi = g.wi[i]; r.ho = g.ho[i]; r.wo = g.wo[i]; r.in0 = g.in0[i]; r.out0 = g.out0[i]; }
+    }
+    return r;
+}
+
+// The halo-tiled convolution (conv3h.h) on a varlen launch: entry b is cut into ceil(ho / TR) x ceil(wo / 32) tiles of TR rows x 32 pixels
+// of ITS image, the tiles of all entries numbered entry-major, row-major inside an entry.  vl_tiles: how many; vl_tile: tile index ->
+// (entry, first row, first column) by a scan of the per-entry tile prefix sums.  ONE definition for the kernel, its launcher and the
+// host-only plan (sta_debug_dpt_varlen_plan).
+__host__ __device__ inline int vl_entry_tiles(const VlGeo& g, int b, int TR) { return ((g.wo[b] + 31) >> 5) * ((g.ho[b] + TR - 1) / TR); }
+__host__ __device__ inline int vl_tiles(const VlGeo& g, int TR) {
+    int n = 0;
+    for (int b = 0; b < g.B; ++b) n += vl_entry_tiles(g, b, TR);
+    return n;
+}
+__host__ __device__ inline void vl_tile(const VlGeo& g, int TR, int tile, int& e, int& y0, int& x0) {
+    int t0 = 0;
+    e = 0;
+    for (int b = 0; b + 1 < g.B; ++b) {
+        const int nt = vl_entry_tiles(g, b, TR);
+        if (tile >= t0 + nt) { t0 += nt; e = b + 1; } else break;
+    }
+    const int tx = (g.wo[e] + 31) >> 5, trem = tile - t0;
+    y0 = (trem / tx) * TR; x0 = (trem % tx) * 32;
+}

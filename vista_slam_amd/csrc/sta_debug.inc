@@ -819,3 +819,165 @@ extern "C" int sta_debug_pose_rows(sta_handle* h, const float* tok, int64_t tok_
     hipStream_t st = (hipStream_t)stream;
     return plan_and_run(h, st, [&](Bump& ws) { return pose_impl(h, ws, tok, k, tok_stride, pose, conf, st, nullptr, nullptr, 0, &pr); });
 }
+
+// ------------------------------------------------------------------------------------------ varlen DPT head: kernel-level hooks
+// The varlen siblings of sta_debug_conv3x3_r2 / _conv3_head / _convt / _up2: B <= 32 entries of different size in ONE launch, inputs
+// and outputs packed entry-major (entry b: H[b] x W[b] pixels, NHWC fp32).  H / W (/ Hc / Wc): HOST arrays.  guard (device, 4096 B, may
+// be NULL): receives the 4096 bytes that lie right behind the output planes in the workspace, filled with 0xA5 before the launch - a
+// store past the last packed row of the last channel block lands there.
+#define DBG_GUARD_BYTES 4096
+static int dbg_vl_check(sta_handle* h, int B, const int* H, const int* W) {
+    REQUIRE(h && H && W && B >= 1 && B <= SEQ_MAX, "bad argument");
+    REQUIRE(h->prec != STA_PREC_F16, "the varlen forms have no precision-f16 kernels");
+    for (int b = 0; b < B; ++b) REQUIRE(H[b] >= 1 && W[b] >= 1, "bad argument (entry %d is %d x %d)", b, H[b], W[b]);
+    return 0;
+}
+// (o: the output planes, allocated LAST before this call: the guard starts at their last byte + 1, inside the allocator's slack and
+//  alignment gap, so a store one row past the last packed row of the last channel block lands in it)
+static int dbg_guard_arm(Bump& ws, const Planes& o, int64_t rows, int64_t cols, char** g, hipStream_t st) {
+    char* end = (char*)o.hi + rows * ((cols + 31) & ~int64_t(31)) * (o.lo ? 4 : 2);
+    char* tail = (char*)ws.take(DBG_GUARD_BYTES + 1024);
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    REQUIRE(end <= tail && tail - end <= 1024, "internal: the guard does not follow the output planes");
+    *g = end;
+    HIPCHK(hipMemsetAsync(end, 0xA5, DBG_GUARD_BYTES, st));
+    return 0;
+}
+static int dbg_guard_read(const char* g, void* out, hipStream_t st) {
+    if (out) HIPCHK(hipMemcpyAsync(out, g, DBG_GUARD_BYTES, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+extern "C" int sta_debug_conv3x3_varlen(sta_handle* h, const float* x, const float* w, const float* bias, int B, const int* H, const int* W,
+                                        int Cin, int Co, int stride, int relu_in, int act, const float* resid, const float* resid2,
+                                        float* out, void* guard, void* stream) {
+    CHK(dbg_vl_check(h, B, H, W));
+    REQUIRE(x && w && out && Cin > 0 && Co > 0 && (stride == 1 || stride == 2) && (resid || !resid2), "bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int ho[SEQ_MAX], wo[SEQ_MAX];
+    for (int b = 0; b < B; ++b) { ho[b] = (H[b] - 1) / stride + 1; wo[b] = (W[b] - 1) / stride + 1; }
+    const VlGeo g = vl_geo(B, H, W, ho, wo);
+    const int64_t pin = g.in0[B], pout = g.out0[B];
+    CHK(ensure_ws(h, (pin * Cin + (int64_t)2 * Co * Cin * 9 + 3 * pout * Co) * 4 + (1 << 17), st));
+    Bump ws = cur_bump(h);
+    Planes xi = ws.act(pin, Cin, true), r = ws.act(pout, Co, true), r2 = ws.act(pout, Co, true);
+    const bool mx = dbg_mx(h) && Co % 64 == 0;
+    Lin L; CHK(dbg_make_lin(h, ws, w, bias, Co, Cin * 9, 1, Co, Cin, 3, 3, L, st, mx));
+    Planes o = ws.act(pout, Co, true);
+    char* gd; CHK(dbg_guard_arm(ws, o, pout, Co, &gd, st));
+    xi.mx = o.mx = r.mx = r2.mx = mx;
+    CHK(run_rows_to_planes(h, x, pin * Cin, 1, (int)pin, Cin, xi, st, 0, mx));
+    if (resid) CHK(run_rows_to_planes(h, resid, pout * Co, 1, (int)pout, Co, r, st, 0, mx));
+    if (resid2) CHK(run_rows_to_planes(h, resid2, pout * Co, 1, (int)pout, Co, r2, st, 0, mx));
+    CHK(dbg_poison_act(o, pout, Co, st));
+    CHK(conv3_vl(h, xi, g, Cin, L, stride, relu_in != 0, act, o, resid ? &r : nullptr, resid2 ? &r2 : nullptr, st));
+    CHK(dbg_planes_to_f32(h, o, 0, 1, (int)pout, Co, out, st));
+    return dbg_guard_read(gd, guard, st);
+}
+// the fused tail on packed pixels (conv3_head_vl: implicit GEMM on 192x128 tiles; fails on a small grid, as sta_debug_conv3_head does)
+extern "C" int sta_debug_conv3_head_varlen(sta_handle* h, const float* x, const float* w2, const float* b2, const float* w4, const float* b4,
+                                           int B, const int* H, const int* W, float* pts, float* conf, void* stream) {
+    CHK(dbg_vl_check(h, B, H, W));
+    REQUIRE(x && w2 && b2 && w4 && b4 && pts && conf, "bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const VlGeo g = vl_geo(B, H, W, H, W);
+    const int64_t npix = g.in0[B];
+    CHK(ensure_ws(h, (npix * 128 + (int64_t)2 * 128 * 128 * 9) * 4 + (1 << 16), st));
+    Bump ws = cur_bump(h);
+    Planes xi = ws.act(npix, 128, true);
+    const bool mx = dbg_mx(h);
+    xi.mx = mx;
+    Lin L; CHK(dbg_make_lin(h, ws, w2, b2, 128, 128 * 9, 1, 128, 128, 3, 3, L, st, mx));
+    REQUIRE(!ws.overflow, "debug ws overflow");
+    REQUIRE((auto_family(h) && !small_grid(h, npix, 128)) || h->gemm_variant == 8, "the fused varlen tail does not run at %lld pixels under tile family %d", (long long)npix, h->gemm_variant);
+    F32Lin L4; L4.w = const_cast<float*>(w4); L4.b = const_cast<float*>(b4);
+    std::vector<float> w4h(4 * 128);
+    HIPCHK(hipMemcpyAsync(w4h.data(), w4, w4h.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    struct ScaleGuard {
+        float* dst; float keep[4];
+        explicit ScaleGuard(float* d) : dst(d) { for (int o = 0; o < 4; ++o) keep[o] = d[o]; }
+        ~ScaleGuard() { for (int o = 0; o < 4; ++o) dst[o] = keep[o]; }
+    } restore_scales(h->head4_scale);
+    head4_row_scales(w4h.data(), h->head4_scale);
+    CHK(run_rows_to_planes(h, x, npix * 128, 1, (int)npix, 128, xi, st, 0, mx));
+    CHK(dbg_poison(pts, npix * 12, st)); CHK(dbg_poison(conf, npix * 4, st));
+    return conv3_head_vl(h, xi, g, 128, L, L4, pts, conf, st);
+}
+extern "C" int sta_debug_convt_varlen(sta_handle* h, const float* x, const float* w, const float* bias, int B, const int* H, const int* W,
+                                      int C, int k, float* out, void* guard, void* stream) {
+    CHK(dbg_vl_check(h, B, H, W));
+    REQUIRE(x && w && bias && out && C > 0 && (k == 2 || k == 4), "bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int ho[SEQ_MAX], wo[SEQ_MAX];
+    for (int b = 0; b < B; ++b) { ho[b] = k * H[b]; wo[b] = k * W[b]; }
+    const VlGeo g = vl_geo(B, H, W, ho, wo);
+    const int64_t pin = g.in0[B], pout = g.out0[B];
+    CHK(ensure_ws(h, (pin * C + (int64_t)2 * C * C * k * k + pout * C) * 4 + (int64_t)C * k * k * 4 + (1 << 17), st));
+    Bump ws = cur_bump(h);
+    Planes xi = ws.act(pin, C, true);
+    float* eb = (float*)ws.take((int64_t)C * k * k * 4);
+    const bool mx = dbg_mx(h) && (k * k * C) % 64 == 0;
+    Lin L; CHK(dbg_make_lin(h, ws, w, eb, k * k * C, C, 2, C, C, k, k, L, st, mx));
+    Planes o = ws.act(pout, C, true);
+    char* gd; CHK(dbg_guard_arm(ws, o, pout, C, &gd, st));
+    xi.mx = o.mx = mx;
+    hipLaunchKernelGGL(expand_bias_kernel, dim3((C * k * k + 255) / 256), dim3(256), 0, st, bias, eb, C, k * k);
+    CHK(run_rows_to_planes(h, x, pin * C, 1, (int)pin, C, xi, st, 0, mx));
+    CHK(dbg_poison_act(o, pout, C, st));
+    CHK(gemm_convt_vl(h, xi, L, g, k, C, o, st));
+    CHK(dbg_planes_to_f32(h, o, 0, 1, (int)pout, C, out, st));
+    return dbg_guard_read(gd, guard, st);
+}
+extern "C" int sta_debug_up2_varlen(sta_handle* h, const float* x, int B, const int* H, const int* W, int C, const int* Hc, const int* Wc,
+                                    float* out, void* guard, void* stream) {
+    CHK(dbg_vl_check(h, B, H, W));
+    REQUIRE(x && out && Hc && Wc && C % 8 == 0, "bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const VlGeo g = vl_geo(B, H, W, Hc, Wc);
+    const int64_t pin = g.in0[B], pout = g.out0[B];
+    CHK(ensure_ws(h, (pin + pout) * C * 4 + (1 << 17), st));
+    Bump ws = cur_bump(h);
+    Planes xi = ws.act(pin, C, true), o = ws.act(pout, C, true);
+    char* gd; CHK(dbg_guard_arm(ws, o, pout, C, &gd, st));
+    xi.mx = o.mx = dbg_mx(h);
+    CHK(run_rows_to_planes(h, x, pin * C, 1, (int)pin, C, xi, st, 0, xi.mx));
+    CHK(dbg_poison_act(o, pout, C, st));
+    CHK(run_up2_vl(h, xi, g, C, o, st));
+    CHK(dbg_planes_to_f32(h, o, 0, 1, (int)pout, C, out, st));
+    return dbg_guard_read(gd, guard, st);
+}
+// Host only: the packing of the varlen head's six levels for B entries of hp[b] x wp[b] patches.  Level 0 .. 5 = (ceil(h/2), ceil(w/2)),
+// (h, w), (2h, 2w), (4h, 4w), (8h, 8w), (16h, 16w).  off [6][B + 1]: first packed pixel of each entry, and the level's size; hw [6][B][2].
+// ntiles [6] and tiles [cap][3] (both may be NULL): the halo-tiled convolution's tile map of every level, level after level - tile t of a
+// level -> (entry, y0, x0), 8 rows x 32 pixels, from vl_tile (sta_common.h), the function the kernel decodes its block index with.
+extern "C" int sta_debug_dpt_varlen_plan(int B, const int* hp, const int* wp, long long* off, int* hw, int* ntiles, int* tiles, int cap) {
+    REQUIRE(hp && wp && off && hw && B >= 1 && B <= SEQ_MAX && (!tiles || (ntiles && cap >= 0)), "bad argument");
+    int64_t used = 0;
+    for (int k = 0; k < 6; ++k) {
+        int lh[SEQ_MAX], lw[SEQ_MAX];
+        for (int b = 0; b < B; ++b) {
+            REQUIRE(hp[b] >= 1 && wp[b] >= 1, "bad argument (entry %d)", b);
+            lh[b] = k == 0 ? (hp[b] - 1) / 2 + 1 : hp[b] << (k - 1); lw[b] = k == 0 ? (wp[b] - 1) / 2 + 1 : wp[b] << (k - 1);
+            hw[(k * B + b) * 2] = lh[b]; hw[(k * B + b) * 2 + 1] = lw[b];
+        }
+        int64_t a = 0;
+        for (int b = 0; b < B; ++b) { off[k * (B + 1) + b] = a; a += (int64_t)lh[b] * lw[b]; }
+        off[k * (B + 1) + B] = a;
+        REQUIRE(a < ((int64_t)1 << 31), "too many rows at level %d", k);
+        if (ntiles) {
+            const VlGeo g = vl_geo(B, lh, lw, lh, lw);
+            const int nt = vl_tiles(g, 8);
+            ntiles[k] = nt;
+            if (tiles) {
+                REQUIRE(used + nt <= cap, "tile map: %lld tiles do not fit the %d given", (long long)(used + nt), cap);
+                for (int t = 0; t < nt; ++t) { int* o = tiles + (used + t) * 3; vl_tile(g, 8, t, o[0], o[1], o[2]); }
+            }
+            used += nt;
+        }
+    }
+    return 0;
+}

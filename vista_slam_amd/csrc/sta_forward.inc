@@ -644,3 +644,129 @@ static int dpt_impl(sta_handle* h, Bump& ws, const float* enc, int64_t enc_bs,
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------------------ DPT head, one patch rectangle per entry
+// dpt_impl on B <= SEQ_MAX entries of DIFFERENT size in one call (sta_head_pts_varlen): entry b is hp[b] x wp[b] patches, and what
+// dpt_impl computes for it alone at (16 hp[b], 16 wp[b]).  Nothing is padded and no pixel reads another entry's pixels.  At each of the
+// head's six resolutions - (ceil(h/2), ceil(w/2)), (h, w), (2h, 2w), (4h, 4w), (8h, 8w), (16h, 16w) - the pixels of all entries are
+// packed entry-major, row-major inside an entry; what dpt_impl derives from one (H, W) - h3s / w3s, the crop of refinenet4's x2
+// output to (h, w), the align_corners ratios - is per entry, in the VlGeo table of each launch (kernel arguments; host values:
+// nothing is copied to the device, nothing is synchronised).  The same launch sequence as dpt_impl, one launch per step: the row-wise
+// steps (rows -> planes through the row table, every 1x1 GEMM, the split-K finisher, head_final_kernel) run once over the packed rows
+// as they are; the geometry-decoding steps run their varlen forms (conv3_vl, gemm_convt_vl, run_up2_vl).  Tile families: the cost
+// model on the packed M of each level (the halo-tiled family 8, whose cost the model counts per image size, only where it is forced).  One lane.
+// enc_row / hook_row: first patch row of entry b in enc / in each hook buffer.  out_pix: pixel offset of entry b in pts / conf, or
+// nullptr = packed (256 x the patches before it).
+static int dpt_varlen_impl(sta_handle* h, Bump& ws, const float* enc, const int64_t* enc_row, const float* h1, const float* h2, const float* h3,
+                           const int64_t* hook_row, const int* hp, const int* wp, int B, float* pts, float* conf, const int64_t* out_pix, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim;
+    const bool dmx = (h->mx_mask & CLS_HEAD) != 0;
+    auto act = [&](int64_t rows, int64_t cols, bool mx) { Planes q = ws.act(rows, cols, split); q.mx = mx; return q; };
+    // the six levels: index 0 .. 3 as dpt_impl's Hs / Ws (4x, 2x, 1x, 1/2x), 4 = 8x, 5 = 16x
+    int lh[6][SEQ_MAX], lw[6][SEQ_MAX], ch[SEQ_MAX], cw[SEQ_MAX];
+    int64_t P[6] = {0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < B; ++b) {
+        const int hh = hp[b], ww = wp[b];
+        lh[0][b] = 4 * hh; lw[0][b] = 4 * ww; lh[1][b] = 2 * hh; lw[1][b] = 2 * ww; lh[2][b] = hh; lw[2][b] = ww;
+        lh[3][b] = (hh - 1) / 2 + 1; lw[3][b] = (ww - 1) / 2 + 1;
+        lh[4][b] = 8 * hh; lw[4][b] = 8 * ww; lh[5][b] = 16 * hh; lw[5][b] = 16 * ww;
+        for (int k = 0; k < 6; ++k) P[k] += (int64_t)lh[k][b] * lw[k][b];
+        ch[b] = std::min(2 * lh[3][b], hh); cw[b] = std::min(2 * lw[3][b], ww);      // refinenet4's x2 output, cropped (dpt_head.py:58)
+    }
+    const int M = (int)P[2];
+    auto same = [&](int k) { return vl_geo(B, lh[k], lw[k], lh[k], lw[k]); };
+    auto step = [&](int ki, int ko) { return vl_geo(B, lh[ki], lw[ki], lh[ko], lw[ko]); };
+    RowSrc re, rh; memset(&re, 0, sizeof re); memset(&rh, 0, sizeof rh);
+    re.t.S = rh.t.S = B;
+    { int acc = 0; for (int b = 0; b < B; ++b) { re.t.tok0[b] = rh.t.tok0[b] = acc; re.src_row[b] = enc_row[b]; rh.src_row[b] = hook_row[b]; acc += hp[b] * wp[b]; } re.t.tok0[B] = rh.t.tok0[B] = acc; }
+
+    Planes t0 = act(M, E, use_mx(h, h->act0_0)), t1 = act(M, D, dmx), t2 = act(M, D, dmx), t3 = act(M, D, dmx);
+    Planes a0 = act(M, 96, dmx), l0 = act(P[0], 96, dmx);
+    Planes a1 = act(M, 192, dmx), l1 = act(P[1], 192, dmx);
+    Planes l2 = act(M, 384, dmx), a3 = act(M, 768, dmx), l3 = act(P[3], 768, dmx);
+    const int Cs[4] = {96, 192, 384, 768};
+    Planes lin[4] = {l0, l1, l2, l3}, r[4], c1o[4];
+    for (int k = 0; k < 4; ++k) {
+        r[k] = act(P[k], 256, dmx);
+        if (k < 3) c1o[k] = act(P[k], 256, dmx);
+    }
+    REQUIRE(!ws.overflow, "internal: dpt workspace overflow (stage 1)");
+    // reassembly, in dpt_impl's order: level 3 (1x1, then 3x3 stride 2), 2 (1x1), 1 (1x1, ConvT k = 2), 0 (1x1, ConvT k = 4); layer_rn
+    CHK(run_rows_to_planes_src(h, h3, rh, D, t3, st, t3.mx));
+    CHK(gemm_f16(h, t3, h->act3_0, M, a3, ACT_NONE, st, a3.mx));
+    CHK(conv3_vl(h, a3, step(2, 3), 768, h->act3_1, 2, false, ACT_NONE, l3, nullptr, nullptr, st));
+    CHK(conv3_vl(h, l3, same(3), Cs[3], h->rn[3], 1, false, ACT_NONE, r[3], nullptr, nullptr, st));
+    for (int k = 2; k >= 0; --k) {
+        if (k == 2) {
+            CHK(run_rows_to_planes_src(h, h2, rh, D, t2, st, t2.mx));
+            CHK(gemm_f16(h, t2, h->act2_0, M, l2, ACT_NONE, st, l2.mx));
+        } else if (k == 1) {
+            CHK(run_rows_to_planes_src(h, h1, rh, D, t1, st, t1.mx));
+            CHK(gemm_f16(h, t1, h->act1_0, M, a1, ACT_NONE, st, a1.mx));
+            CHK(gemm_convt_vl(h, a1, h->act1_1, step(2, 1), 2, 192, l1, st));
+        } else {
+            CHK(run_rows_to_planes_src(h, enc, re, E, t0, st, t0.mx));
+            CHK(gemm_f16(h, t0, h->act0_0, M, a0, ACT_NONE, st, a0.mx));
+            CHK(gemm_convt_vl(h, a0, h->act0_1, step(2, 0), 4, 96, l0, st));
+        }
+        CHK(conv3_vl(h, lin[k], same(k), Cs[k], h->rn[k], 1, false, ACT_NONE, r[k], nullptr, nullptr, st));
+        CHK(conv3_vl(h, r[k], same(k), 256, h->ref[k].u1.c1, 1, true, ACT_RELU, c1o[k], nullptr, nullptr, st));
+    }
+    // refinenet4 .. refinenet1 (out_conv before the x2 upsample, as in dpt_impl)
+    Planes path;
+    for (int k = 3; k >= 0; --k) {
+        const Refine& rf = h->ref[k];
+        const VlGeo g = same(k);
+        const int64_t el = P[k];
+        Planes tmp = act(el, 256, dmx), cur = r[k];
+        if (k < 3) {
+            Planes sum = act(el, 256, dmx);
+            REQUIRE(!ws.overflow, "internal: dpt workspace overflow (fusion)");
+            REQUIRE(h->dry || path.rp == el, "internal: refinenet size mismatch at level %d", k);
+            CHK(conv3_vl(h, c1o[k], g, 256, rf.u1.c2, 1, false, ACT_NONE, sum, &r[k], &path, st));
+            cur = sum;
+        }
+        Planes y = act(el, 256, dmx), z = act(el, 256, dmx);
+        REQUIRE(!ws.overflow, "internal: dpt workspace overflow (rcu2)");
+        CHK(conv3_vl(h, cur, g, 256, rf.u2.c1, 1, true, ACT_RELU, tmp, nullptr, nullptr, st));
+        CHK(conv3_vl(h, tmp, g, 256, rf.u2.c2, 1, false, ACT_NONE, y, &cur, nullptr, st));
+        CHK(gemm_f16(h, y, rf.out, (int)el, z, ACT_NONE, st, z.mx));
+        // k == 3: 2 h3s x 2 w3s cropped to (h, w); the other levels land on the next level's size: lh[k - 1] (k = 0: level 4, 8x)
+        const VlGeo ug = k == 3 ? vl_geo(B, lh[3], lw[3], ch, cw) : step(k, k == 0 ? 4 : k - 1);
+        Planes up = act(ug.out0[B], 256, dmx);
+        REQUIRE(!ws.overflow, "internal: dpt workspace overflow (up)");
+        if (k == 3) for (int b = 0; b < B; ++b) REQUIRE(ch[b] == lh[2][b] && cw[b] == lw[2][b], "internal: refinenet4 crop of entry %d", b);
+        CHK(run_up2_vl(h, z, ug, 256, up, st));
+        path = up;
+    }
+    // head: 3x3 256 -> 128 at 8x, up x2, 3x3 128 -> 128 + ReLU, 1x1 128 -> 4 + postprocess
+    Planes h0 = act(P[4], 128, dmx), h0u = act(P[5], 128, dmx);
+    bool packed_out = true;
+    if (out_pix) { int64_t o = 0; for (int b = 0; b < B; ++b) { packed_out = packed_out && out_pix[b] == o; o += (int64_t)lh[5][b] * lw[5][b]; } }
+    // the fused tail on the packed pixels (conv3_head_ok's rule: implicit GEMM on 192x128, the halo form where forced), packed outputs
+    const bool fused_tail = packed_out && h->head2.N == 128 && ((auto_family(h) && !small_grid(h, P[5], h->head2.N)) || h->gemm_variant == 8);
+    // (planning pass: always with the [pixels, 128] map of the unfused tail - the scheduler plans with every edge accepted, i.e. packed
+    //  outputs, and runs with whatever was accepted: a rejected edge in front of an accepted one leaves a gap, and the tail unfused)
+    Planes h2o; if (!fused_tail || h->dry) h2o = act(P[5], 128, dmx);
+    REQUIRE(!ws.overflow, "internal: dpt workspace overflow (head)");
+    CHK(conv3_vl(h, path, same(4), 256, h->head0, 1, false, ACT_NONE, h0, nullptr, nullptr, st));
+    CHK(run_up2_vl(h, h0, step(4, 5), 128, h0u, st));
+    if (fused_tail) return conv3_head_vl(h, h0u, same(5), 128, h->head2, h->head4, pts + (out_pix ? out_pix[0] * 3 : 0), conf + (out_pix ? out_pix[0] : 0), st);
+    CHK(conv3_vl(h, h0u, same(5), 128, h->head2, 1, false, ACT_RELU, h2o, nullptr, nullptr, st));
+    if (h->dry) return 0;
+    // head_final_kernel: once over all packed pixels, or once per run of entries whose outputs are contiguous (out_pix with gaps)
+    const VlGeo g5 = same(5);
+    for (int b0 = 0; b0 < B;) {
+        int b1 = b0 + 1;
+        int64_t o0 = out_pix ? out_pix[b0] : g5.out0[b0];
+        while (b1 < B && (out_pix ? out_pix[b1] : (int64_t)g5.out0[b1]) == o0 + (g5.out0[b1] - g5.out0[b0])) ++b1;
+        const int64_t pix0 = g5.out0[b0], npix = g5.out0[b1] - g5.out0[b0];
+        int blocks = (int)((npix * 16 + 255) / 256); if (blocks > 16384) blocks = 16384;
+        hipLaunchKernelGGL(head_final_kernel<true>, dim3(blocks), dim3(256), 0, st, h2o.hi, h2o.lo, pix0, h2o.rp, npix, h->head4.w, h->head4.b, pts + o0 * 3, conf + o0, h2o.mx ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        b0 = b1;
+    }
+    return 0;
+}

@@ -2,9 +2,23 @@
 // wrappers the orchestration code calls.  Included by sta_api.hip (one translation unit; needs its types and macros).
 // ------------------------------------------------------------------------------------------ launch helpers
 template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WMS, int WNS, int NSTG = 2, bool MX = false>
-static int launch_gemm2(const GemmParams& p, hipStream_t st, int dev = 0) {
+static int launch_gemm2(const GemmParams& p, hipStream_t st, int dev = 0, const VlGeo* geo = nullptr) {
     static unsigned attr_done = 0;        // one bit per device: the attribute is set on the current device's copy of the function
     constexpr int smem = gemm2_smem_bytes<SPLIT, BM, BN>(NSTG);
+    if (geo) {      // the varlen form of the same tile family (sta_head_pts_varlen): same grid, the geometry table next to the parameters
+        if constexpr (SPLIT && (AMODE == A_CONV3 || EPI == EPI_CONVT)) {
+            static unsigned attr_done_v = 0;
+            auto kern = gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX, VlGeo>;
+            if (!(attr_done_v >> (dev & 31) & 1u)) {
+                HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+                attr_done_v |= 1u << (dev & 31);
+            }
+            REQUIRE(p.m_tail == 0, "internal: a varlen launch has no row tail");
+            const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN, ks = p.ksplit > 1 ? p.ksplit : 1;
+            hipLaunchKernelGGL(kern, dim3((unsigned)(tm * tn * ks)), dim3(WMS * WNS * 64), smem, st, p, *geo);
+            return 0;
+        } else REQUIRE(false, "internal: no varlen form of this GEMM (precision f16, or an epilogue that decodes no geometry)");
+    }
     if (!(attr_done >> (dev & 31) & 1u)) {
         HIPCHK(hipFuncSetAttribute((const void*)gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX>,
                                    hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -18,10 +32,24 @@ static int launch_gemm2(const GemmParams& p, hipStream_t st, int dev = 0) {
 }
 
 template <bool SPLIT, int EPI, int BM, int BN, bool MX, int WMS = 4, int WNS = 4>
-static int launch_conv3h(const GemmParams& p, hipStream_t st, int dev) {
+static int launch_conv3h(const GemmParams& p, hipStream_t st, int dev, const VlGeo* geo = nullptr) {
     static unsigned attr_done = 0;        // one bit per device
     constexpr int smem = conv3h_smem_bytes<SPLIT, BM, BN>();
     static_assert(smem <= 160 * 1024, "conv3h: LDS budget");
+    if (geo) {      // the varlen form: tiles = the sum of every entry's own tiles
+        if constexpr (SPLIT) {
+            static unsigned attr_done_v = 0;
+            auto kv = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX, VlGeo>;
+            if (!(attr_done_v >> (dev & 31) & 1u)) {
+                HIPCHK(hipFuncSetAttribute((const void*)kv, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+                attr_done_v |= 1u << (dev & 31);
+            }
+            const int64_t tiles = (int64_t)vl_tiles(*geo, BM / 32) * ((p.N + BN - 1) / BN);
+            REQUIRE(tiles > 0 && tiles < ((int64_t)1 << 31), "internal: conv3h varlen grid");
+            hipLaunchKernelGGL(kv, dim3((unsigned)tiles), dim3(WMS * WNS * 64), smem, st, p, *geo);
+            return 0;
+        } else REQUIRE(false, "internal: the varlen halo-tiled convolution has no precision-f16 form");
+    }
     auto kern = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX>;
     if (!(attr_done >> (dev & 31) & 1u)) {
         HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
@@ -317,7 +345,7 @@ extern "C" int sta_debug_conv_plan(int epi, int M, int N, int K, int precision, 
 static int no_mx_kernel(int family, int epi) { return set_err("internal: tile family %d has no f16mx form for epilogue %d", family, epi); }
 // slab_ks_out: K slices a slab GEMM wrote (0: it did not take the slab path) - the caller's finisher sums exactly those
 template <int AMODE, int EPI>
-static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, int* slab_ks_out = nullptr) {
+static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, int* slab_ks_out = nullptr, const VlGeo* geo = nullptr) {
     GemmParams p = p_in;
     p.range = h->range;
     if (slab_ks_out) *slab_ks_out = 0;
@@ -331,8 +359,16 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
     if (AMODE == A_CONV3) REQUIRE((int64_t)p.a_rp * 128 < ((int64_t)1 << 32), "convolution input of %lld pixels exceeds the 32-bit offset range of the tap loader", (long long)p.a_rp);
     if (h->dry) return 0;
     const bool split = h->prec != STA_PREC_F16;
+    // varlen launches (geo): every family but the register-staged family 1 has the form; forcing that one is refused here
+    REQUIRE(!geo || h->gemm_variant != 1, "tile family %d has no varlen form (sta_head_pts_varlen runs on families 2 / 3 / 5 / 6 / 8)", h->gemm_variant);
     GemmPlan g;
-    CHK(gemm_plan(plan_query(h, AMODE, EPI, p), g));
+    if (geo && h->gemm_variant == 8 && AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD) && p.cstride == 1 && (p.N == 128 || (p.N == 256 && EPI == EPI_F16))) {
+        // the halo-tiled family on a varlen launch (forced: the cost model, which counts the tiles of ONE image size, never proposes it
+        // there): 8 rows x 32 pixels of one ENTRY per tile, the tiles of all entries in one grid
+        const int tm = vl_tiles(*geo, 8);          // (fewer than 2^31 / 8 tiles: every level has fewer than 2^31 pixels)
+        const int bn = p.N == 128 ? 128 : 256;
+        g = GemmPlan{8, 256, bn, 0, tm, (p.N + bn - 1) / bn, 1, 0};
+    } else CHK(gemm_plan(plan_query(h, AMODE, EPI, p), g));
     h->last_plan = g;
     const int variant = g.family;
     p.m_tail = g.m_tail;
@@ -364,17 +400,18 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
     }
     if (timed && variant == 5) p.clk_dbg = h->clk_buf;   // effective-clock probe (bench only)
     if (timed && h->kstamp_on && h->kn <= KSTAMP_LAUNCHES) p.stamps = h->kstamp + (size_t)(h->kn - 1) * KSTAMP_WG * 4;
+    REQUIRE(!geo || variant != 1, "internal: tile family %d planned for a varlen launch", variant);
     if constexpr (AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD)) {
         if (variant == 8) {
-            REQUIRE((int64_t)p.Ho * p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0, "internal: conv3h needs whole images");
+            REQUIRE(geo || ((int64_t)p.Ho * p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0), "internal: conv3h needs whole images");
             if (p.N == 128) {
-                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 128, true>(p, st, h->device)));
-                else if (split) CHK((launch_conv3h<true, EPI, 256, 128, false>(p, st, h->device)));
-                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 128, false>(p, st, h->device))));
+                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 128, true>(p, st, h->device, geo)));
+                else if (split) CHK((launch_conv3h<true, EPI, 256, 128, false>(p, st, h->device, geo)));
+                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 128, false>(p, st, h->device, geo))));
             } else if constexpr (EPI == EPI_F16) {
-                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 256, true>(p, st, h->device)));
-                else if (split) CHK((launch_conv3h<true, EPI, 256, 256, false>(p, st, h->device)));
-                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 256, false>(p, st, h->device))));
+                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 256, true>(p, st, h->device, geo)));
+                else if (split) CHK((launch_conv3h<true, EPI, 256, 256, false>(p, st, h->device, geo)));
+                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 256, false>(p, st, h->device, geo))));
             } else REQUIRE(false, "internal: no halo-tiled convolution for epilogue %d at N = %d", EPI, p.N);
         }
     }
@@ -386,26 +423,26 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
     } else
     if constexpr (EPI == EPI_HEAD) {      // exists for the 192x128 family only (conv3_head checks the shape)
         REQUIRE(variant == 5 && p.N == 128, "internal: fused head epilogue on a tile family without it");
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device))));
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
+        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo)));
+        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo))));
     } else
     if (variant == 2) {
       if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_256) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device))));
+        if (p.mx) { if constexpr (MX_256) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
+        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device, geo)));
+        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device, geo))));
       } else REQUIRE(false, "internal: no 256x256 RoPE epilogue");
     } else if (variant == 3) {
       if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device))));
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
+        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device, geo)));
+        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device, geo))));
       } else REQUIRE(false, "internal: no 192x256 RoPE epilogue");
     } else if (variant == 5) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device))));
+        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
+        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo)));
+        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo))));
     } else if (variant == 6) {
         // A grid of <= 256 workgroups leaves every workgroup alone on its CU: with 4 waves (one per SIMD) the barrier, the DMA
         // issue, the fragment reads and the MFMAs of a K tile simply add up (ablations, tools/ring_ablate.py: 0.12 + 0.14 + 0.09 +
@@ -416,13 +453,13 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
         const bool lone = sg_grid <= (h->opt[2] > 1 ? h->opt[2] : 256) && h->opt[2] != 1;
         if (p.mx) {
             if constexpr (MX_EPI) {
-                if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3, true>(p, st, h->device)));
-                else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3, true>(p, st, h->device)));
+                if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3, true>(p, st, h->device, geo)));
+                else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3, true>(p, st, h->device, geo)));
             } else return no_mx_kernel(variant, EPI);
         } else if (split) {
-            if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3>(p, st, h->device)));
-            else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device)));
-        } else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device))));
+            if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3>(p, st, h->device, geo)));
+            else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device, geo)));
+        } else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device, geo))));
         if (EPI == EPI_QKV && p.ksplit > 1) {
             const int64_t nthr = (int64_t)p.M * (p.nq + p.nk) + (int64_t)((p.M + 3) / 4) * p.nv;
             const int blocks = (int)((nthr + 255) / 256);
@@ -1251,6 +1288,94 @@ static int run_up2(sta_handle* h, const Planes& in, int n, int Hi, int Wi, int C
     } else {
         STA_F16ONLY(hipLaunchKernelGGL((bilinear_up2_kernel<false, 1>), dim3(blocks), dim3(256), 0, st, in.hi, in.lo, n, Hi, Wi, C, Hc, Wc, out.hi, out.lo, 0, h->range));
     }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------ varlen DPT head: launch forms
+// One launch over the packed pixels of B entries of different size (sta_head_pts_varlen; geometry table: VlGeo, sta_common.h).
+// vl_geo: entry b is hi[b] x wi[b] input pixels -> ho[b] x wo[b] output pixels; offsets = prefix sums (host values).
+static VlGeo vl_geo(int B, const int* hi, const int* wi, const int* ho, const int* wo) {
+    VlGeo g; memset(&g, 0, sizeof g);
+    g.B = B;
+    int64_t a = 0, o = 0;
+    for (int b = 0; b < B; ++b) {
+        g.hi[b] = hi[b]; g.wi[b] = wi[b]; g.ho[b] = ho[b]; g.wo[b] = wo[b];
+        g.in0[b] = (int)a; g.out0[b] = (int)o;
+        a += (int64_t)hi[b] * wi[b]; o += (int64_t)ho[b] * wo[b];
+    }
+    g.in0[B] = (int)a; g.out0[B] = (int)o;      // (the callers check that every level has fewer than 2^31 rows)
+    return g;
+}
+// 3x3 conv, pad 1, stride 1 or 2, every entry on its own (no tap leaves the entry): conv3 with per-entry geometry
+static int conv3_vl(sta_handle* h, const Planes& in, const VlGeo& g, int Cin, const Lin& W, int stride,
+                    bool relu_in, int act, const Planes& out, const Planes* r1, const Planes* r2, hipStream_t st) {
+    GemmParams p; memset(&p, 0, sizeof p);
+    p.A_hi = in.hi; p.A_lo = in.lo; p.a_rp = in.rp;
+    p.Cin = Cin; p.cstride = stride; p.relu_in = relu_in ? 1 : 0;       // Hi / Wi / Ho / Wo stay 0: the table has them, and no family that needs ONE image size is chosen
+    const bool mx = use_mx(h, W);
+    REQUIRE(h->dry || in.mx == mx, "internal: conv input format mismatch");
+    p.mx = mx ? 1 : 0;
+    p.B_hi = mx ? W.wmx.hi : W.w.hi; p.B_lo = mx ? W.wmx.lo : W.w.lo; p.bias = W.bias;
+    p.M = g.out0[g.B]; p.N = W.N; p.K = W.K;
+    REQUIRE(W.K == 9 * Cin, "conv weight K mismatch");
+    for (int b = 0; b < g.B; ++b)
+        REQUIRE(g.ho[b] == (g.hi[b] - 1) / stride + 1 && g.wo[b] == (g.wi[b] - 1) / stride + 1, "internal: varlen conv geometry of entry %d", b);
+    for (int b = 0; b < g.B; ++b) REQUIRE(g.wi[b] < (1 << 23), "entry %d is %d pixels wide: the varlen tap loader takes rows of fewer than 2^23 pixels", b, g.wi[b]);
+    p.C_hi = out.hi; p.C_lo = out.lo; p.ldc16 = W.N; p.act = act; p.c_rp = out.rp; p.c_mx = out.mx ? 1 : 0;
+    REQUIRE(h->dry || (g.in0[g.B] == in.rp && out.rp == p.M), "internal: conv plane rows mismatch");
+    if (r1) { p.R1_hi = r1->hi; p.R1_lo = r1->lo; p.r_mx = r1->mx ? 1 : 0; REQUIRE(h->dry || r1->rp == out.rp, "internal: residual rows mismatch"); }
+    if (r2) { p.R2_hi = r2->hi; p.R2_lo = r2->lo; REQUIRE(h->dry || (r2->rp == out.rp && (!r1 || r1->mx == r2->mx)), "internal: residual rows / format mismatch"); p.r_mx = r2->mx ? 1 : 0; }
+    return launch_gemm<A_CONV3, EPI_F16>(h, p, st, nullptr, &g);
+}
+// the fused tail (conv3_head) on packed pixels: pixel i of the pack -> pts[3 i], conf[i] (the implied packing only)
+static int conv3_head_vl(sta_handle* h, const Planes& in, const VlGeo& g, int Cin, const Lin& W, const F32Lin& W4, float* pts, float* conf, hipStream_t st) {
+    GemmParams p; memset(&p, 0, sizeof p);
+    p.A_hi = in.hi; p.A_lo = in.lo; p.a_rp = in.rp;
+    p.Cin = Cin; p.cstride = 1; p.relu_in = 0;
+    const bool mx = use_mx(h, W);
+    REQUIRE(h->dry || in.mx == mx, "internal: conv input format mismatch");
+    p.mx = mx ? 1 : 0;
+    p.B_hi = mx ? W.wmx.hi : W.w.hi; p.B_lo = mx ? W.wmx.lo : W.w.lo; p.bias = W.bias;
+    p.M = g.out0[g.B]; p.N = W.N; p.K = W.K;
+    REQUIRE(W.K == 9 * Cin && W.N == 128, "conv weight shape mismatch (fused head)");
+    REQUIRE(h->dry || g.in0[g.B] == in.rp, "internal: conv plane rows mismatch");
+    for (int b = 0; b < g.B; ++b) REQUIRE(g.wi[b] < (1 << 23), "entry %d is %d pixels wide: the varlen tap loader takes rows of fewer than 2^23 pixels", b, g.wi[b]);
+    p.hw4 = W4.w; p.hb4 = W4.b; for (int o = 0; o < 4; ++o) p.hw4_scale[o] = h->head4_scale[o];
+    p.hptsA = pts; p.hconfA = conf; p.hptsB = nullptr; p.hconfB = nullptr; p.hsplit = p.M;
+    return launch_gemm<A_CONV3, EPI_HEAD>(h, p, st, nullptr, &g);
+}
+// ConvTranspose2d with kernel = stride = k: entry b's hi x wi pixels scatter into ITS k hi x k wi output pixels
+static int gemm_convt_vl(sta_handle* h, const Planes& A, const Lin& W, const VlGeo& g, int k, int cout, const Planes& out, hipStream_t st) {
+    GemmParams p = gp_dense(A, W.K, W, g.in0[g.B], use_mx(h, W));
+    REQUIRE(h->dry || A.mx == (p.mx != 0), "internal: ConvT input format mismatch");
+    for (int b = 0; b < g.B; ++b) REQUIRE(g.ho[b] == k * g.hi[b] && g.wo[b] == k * g.wi[b], "internal: varlen ConvT geometry of entry %d", b);
+    REQUIRE(h->dry || (out.rp == g.out0[g.B] && A.rp == g.in0[g.B]), "internal: ConvT plane rows mismatch");
+    p.C_hi = out.hi; p.C_lo = out.lo; p.ct_k = k; p.ct_cout = cout; p.c_rp = out.rp; p.c_mx = out.mx ? 1 : 0;
+    return launch_gemm<A_DENSE, EPI_CONVT>(h, p, st, nullptr, &g);
+}
+// bilinear x2 (align_corners), entry b: hi x wi -> ho x wo <= 2 hi x 2 wi (the crop); one workgroup per output row of an entry
+static int run_up2_vl(sta_handle* h, const Planes& in, const VlGeo& g, int C, const Planes& out, hipStream_t st) {
+    if (h->dry) return 0;
+    REQUIRE(in.mx == out.mx && C % 8 == 0, "internal: bilinear format mismatch");
+    REQUIRE(h->prec != STA_PREC_F16, "internal: the varlen bilinear has no precision-f16 form");
+    int64_t rows = 0;
+    for (int b = 0; b < g.B; ++b) {
+        REQUIRE(g.ho[b] >= 1 && g.wo[b] >= 1 && g.ho[b] <= 2 * g.hi[b] && g.wo[b] <= 2 * g.wi[b], "internal: varlen bilinear geometry of entry %d", b);
+        rows += g.ho[b];
+    }
+    REQUIRE(in.rp == g.in0[g.B] && out.rp == g.out0[g.B], "internal: bilinear plane rows mismatch");
+    hipLaunchKernelGGL((bilinear_up2_kernel<true, 1, VlGeo>), dim3((unsigned)rows), dim3(256), 0, st, in.hi, in.lo, g, C, in.rp, out.rp, out.hi, out.lo, in.mx ? 1 : 0, h->range);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// fp32 rows -> planes through a row table (RowSrc, elementwise.h): one launch for the rows of every entry
+static int run_rows_to_planes_src(sta_handle* h, const float* x, const RowSrc& rs, int C, const Planes& o, hipStream_t st, bool mx) {
+    if (h->dry) return 0;
+    REQUIRE(h->prec != STA_PREC_F16, "internal: the row-table form has no precision-f16 form");
+    const int64_t total4 = (int64_t)rs.t.tok0[rs.t.S] * C / 4;
+    int blocks = (int)((total4 + 255) / 256); if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL((rows_to_planes_kernel<true, RowSrc>), dim3(blocks), dim3(256), 0, st, x, rs, C, total4, o.hi, o.rp, mx ? 1 : 0, h->range);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -582,8 +582,8 @@ static RvtLayout rvt_layout(Bump& ws, const SeqTable& t, int k, int E, int D) {
     L.ident = (float2*)ws.take(L.n_ident * 8);
     L.x = (float*)ws.take((Mp + 2 * k) * D * 4);
     for (int q = 0; q < 3; ++q) {                       // emitted hooks per side, entry by entry, pose row first (decode_varlen_impl)
-        L.hk[q][0] = (float*)ws.take((Mp1 + k) * D * 4);
-        L.hk[q][1] = (float*)ws.take((Mp - Mp1 + k) * D * 4);
+        L.hk[q][0] = (float*)ws.take((Mp + 2 * k) * D * 4);      // both sides in ONE block of dense rows: the varlen head reads side j through
+        L.hk[q][1] = L.hk[q][0] + (size_t)(Mp1 + k) * D;         // row offsets from side i's base (sta_set_varlen_heads)
     }
     L.cdev = (float*)ws.take(k * 4);
     L.mark = ws.off;
@@ -642,6 +642,30 @@ static int rvt_phase_b(sta_handle* h, Bump& ws, const SeqTable& t, const StreamC
     }
     const int Mp1 = t.tok0[k];
     int64_t pix = 0;                                           // pixels of the window sides before this one
+    // The switch is read HERE, at finish time.  The workspace was planned at begin time: for the varlen pass only when the switch was on
+    // THEN (rs.plan_v) - a caller who never sets it plans, and allocates, what the per-edge route needs and no more.  Switching it on
+    // between begin and finish is refused; switching it off is served (the per-edge route is planned always).
+    const bool vheads = h->dry ? rs.plan_v != 0 : h->varlen_heads;
+    REQUIRE(h->dry || !vheads || rs.plan_v, "sta_set_varlen_heads(h, 1) came after sta_regress_views_tokens_begin: the call's workspace was planned there, for the per-edge heads; set the switch before begin");
+    if (vheads) {      // ONE varlen head pass over the window sides of all accepted edges, written straight into the layout below
+        int64_t erow[SEQ_MAX], hrow[SEQ_MAX], opix[SEQ_MAX]; int hp[SEQ_MAX], wp[SEQ_MAX], nb = 0;
+        int64_t px = 0;
+        for (int e = 0; e < k; ++e)
+            for (int side = 0; side < 2; ++side) {
+                const int s = side ? k + e : e;
+                if (rs.mh[s] == 0) continue;
+                if (acc[e]) {
+                    erow[nb] = t.tok0[s];                                              // L.F: both sides packed, no pose rows
+                    hrow[nb] = (int64_t)t.tok0[s] + (side ? k : 0) + e + 1;              // hooks: a pose row in front of every entry, side j behind side i
+                    hp[nb] = rs.mh[s]; wp[nb] = rs.mw[s]; opix[nb] = px; ++nb;
+                }
+                px += (int64_t)256 * rs.mh[s] * rs.mw[s];
+            }
+        if (nb > 0 && (h->dry || (pts && conf))) {
+            ws.rewind(L.mark);
+            CHK(dpt_varlen_impl(h, ws, L.F, erow, L.hk[0][0], L.hk[1][0], L.hk[2][0], hrow, hp, wp, nb, pts, conf, opix, st));
+        }
+    }
     for (int e = 0; e < k; ++e) {
         const int si = e, sj = k + e;
         const bool pair = rs.mh[si] > 0 && rs.mh[si] == rs.mh[sj] && rs.mw[si] == rs.mw[sj];
@@ -658,7 +682,7 @@ static int rvt_phase_b(sta_handle* h, Bump& ws, const SeqTable& t, const StreamC
             const int64_t hw = (int64_t)H * W;
             if (acc[e]) {
                 ws.rewind(L.mark);
-                CHK(dpt_impl(h, ws, enc[side], enc[1] - enc[0], hk[0][side], hk[0][1] - hk[0][0], hk[1][side], hk[1][1] - hk[1][0],
+                if (!vheads || h->dry) CHK(dpt_impl(h, ws, enc[side], enc[1] - enc[0], hk[0][side], hk[0][1] - hk[0][0], hk[1][side], hk[1][1] - hk[1][0],
                              hk[2][side], hk[2][1] - hk[2][0], n, H, W, pts ? pts + pix * 3 : nullptr, conf ? conf + pix : nullptr, n, nullptr, nullptr, st));
                 ws.rewind(L.mark);
                 int nblk = (int)((hw + 256 * 8 - 1) / (256 * 8)); if (nblk > 256) nblk = 256; if (nblk < 1) nblk = 1;
@@ -713,6 +737,7 @@ extern "C" int sta_regress_views_tokens_begin(sta_handle* h, const float* feat_i
     DEV_SCOPE(h->device);
     TokenSel g; StreamCtx::RvtState rs; int pmax = 0;
     CHK(rvt_table(h, feat_i, Hi, Wi, feat_j, Hj, Wj, k, win_i, cnt_i, idx_i, win_j, cnt_j, idx_j, &g, &rs, &pmax));
+    rs.plan_v = h->varlen_heads ? 1 : 0;
     REQUIRE(pose, "null argument");
     hipStream_t st = (hipStream_t)stream;
     CHK(ensure_rope(h, pmax));

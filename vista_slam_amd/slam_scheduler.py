@@ -43,7 +43,7 @@ class PendingEdges:
     leave the stream unusable: sta_regress_views_abort).  Close it EXPLICITLY: `__del__` is only a best-effort fallback and acts
     only on the thread that created the object - the abort may block in hipEventSynchronize and the handle is not thread-safe,
     so a garbage collection that happens to run on another thread must not enter the library."""
-    __slots__ = ("k", "H", "W", "stream", "pose", "pts", "conf", "K", "depth", "_keep", "_frontend", "_open", "_tid", "maps")
+    __slots__ = ("k", "H", "W", "stream", "pose", "pts", "conf", "K", "depth", "_keep", "_frontend", "_open", "_tid", "maps", "heads")
 
     def close(self):
         """Abort the call if it is still pending (idempotent)."""
@@ -169,11 +169,23 @@ def _pack_side(sels, dev):
     return win, cnt, (torch.cat(lists).contiguous() if lists else None)
 
 
+def _heads_on(frontend: STAFrontend, heads):
+    """heads keyword -> the switch value for one call: None = whatever `set_varlen_heads` left on the handle."""
+    if heads is None:
+        return getattr(frontend, "_varlen_heads", False)
+    if heads not in ("entry", "varlen"):
+        raise ValueError(f'heads must be "entry" or "varlen" (got {heads!r})')
+    return heads == "varlen"
+
+
 def regress_views_tokens_begin(frontend: STAFrontend, enc_feat_i: torch.Tensor, size_i: Tuple[int, int], enc_feats_j: Sequence[torch.Tensor],
-                               sizes_j: Sequence[Tuple[int, int]], sel_i: Sequence, sel_j: Sequence) -> PendingEdges:
+                               sizes_j: Sequence[Tuple[int, int]], sel_i: Sequence, sel_j: Sequence, heads: str | None = None) -> PendingEdges:
     """Phase 1 of `regress_views_tokens` on the CURRENT stream: slice + varlen decode + pose heads, no host synchronisation (index
     lists given on the CPU are checked there and copied).  Until `regress_views_tokens_finish` no other frontend call may run on this
-    stream.  The returned `PendingEdges` closes like the one of `regress_views_begin`."""
+    stream.  The returned `PendingEdges` closes like the one of `regress_views_begin`.  heads: "entry" | "varlen" | None (the handle's
+    `set_varlen_heads` setting) - the call's workspace is planned HERE, so a finish with heads="varlen" needs a begin with it; the
+    handle's own setting is put back before this returns."""
+    on = _heads_on(frontend, heads)
     k = len(enc_feats_j)
     assert 1 <= k <= 16, f"1 .. 16 candidate edges per keyframe (got {k})"
     assert len(sizes_j) == k and len(sel_i) == k and len(sel_j) == k, "one frame size and one selection per side for every edge"
@@ -211,29 +223,44 @@ def regress_views_tokens_begin(frontend: STAFrontend, enc_feat_i: torch.Tensor, 
     p._keep = (fi, fj, idx_i, idx_j)
     p._frontend, p._open, p._tid = frontend, False, threading.get_ident()
     ptrs = (C.c_void_p * k)(*[f.data_ptr() for f in fj])
-    _lib.check(frontend.lib.sta_regress_views_tokens_begin(
-        frontend._h, fi.data_ptr(), Hi, Wi, ptrs, (C.c_int * k)(*Hj), (C.c_int * k)(*Wj), k,
-        win_i, cnt_i, None if idx_i is None else idx_i.data_ptr(), win_j, cnt_j, None if idx_j is None else idx_j.data_ptr(),
-        p.pose.data_ptr(), p.stream))
+    p.heads = "varlen" if on else "entry"
+    prev = frontend.set_varlen_heads(on)
+    try:
+        _lib.check(frontend.lib.sta_regress_views_tokens_begin(
+            frontend._h, fi.data_ptr(), Hi, Wi, ptrs, (C.c_int * k)(*Hj), (C.c_int * k)(*Wj), k,
+            win_i, cnt_i, None if idx_i is None else idx_i.data_ptr(), win_j, cnt_j, None if idx_j is None else idx_j.data_ptr(),
+            p.pose.data_ptr(), p.stream))
+    finally:
+        frontend.set_varlen_heads(prev)
     p._open = True
     return p
 
 
-def regress_views_tokens_finish(frontend: STAFrontend, p: PendingEdges, adjacent: Sequence[bool], rel_pose_thres: float) -> List[EdgeResult]:
+def regress_views_tokens_finish(frontend: STAFrontend, p: PendingEdges, adjacent: Sequence[bool], rel_pose_thres: float,
+                                heads: str | None = None) -> List[EdgeResult]:
     """Phase 2: waits for the k pose confidences, accepts / rejects (slam.py:169), enqueues the DPT heads of the accepted edges' window
     sides and their reductions.  Per edge an `EdgeResult` whose confs / depths / pts3d are 2-LISTS [side i, side j] with None for an
     index-list side ([16 h, 16 w] maps; a window with h > w comes as the transposed view the reference's head wrapper returns).  An
     edge whose two sides are windows of one (h, w) additionally gets what `regress_views` returns: confs / depths / pts3d are the
     stacked [2, ..] tensors (indexing [0] / [1] gives the sides) and intri the pair-shared K - `estimate_intrinsic_from_pts3d` of
-    those two maps, so its principal point is the centre of the WINDOW's image, not of the frame.  Every other edge has intri None."""
+    those two maps, so its principal point is the centre of the WINDOW's image, not of the frame.  Every other edge has intri None.
+    heads="entry": the DPT head once per accepted edge and window side; heads="varlen": the window sides of ALL accepted edges through
+    one varlen head pass - same decisions, same layout, ranges of rejected edges unwritten; None (default): what the begin was given.
+    "varlen" needs a begin with heads="varlen" (the workspace is planned there; the library refuses otherwise); "entry" is served after
+    either.  The handle's own `set_varlen_heads` setting is put back before this returns."""
+    on = (p.heads == "varlen") if heads is None else _heads_on(frontend, heads)
     k = p.k
     assert k == len(adjacent)
     adj = bytes(bytearray(1 if a else 0 for a in adjacent))
     pconf, acc, kval, nacc = (C.c_float * k)(), (C.c_int * k)(), (C.c_int * k)(), C.c_int(0)
     assert p._open, "this scheduler call was already finished or aborted"
     p._open = False
-    rc = frontend.lib.sta_regress_views_tokens_finish(frontend._h, adj, float(rel_pose_thres), pconf, acc, C.byref(nacc),
-                                                      p.pts.data_ptr(), p.conf.data_ptr(), p.depth.data_ptr(), p.K.data_ptr(), kval, p.stream)
+    prev = frontend.set_varlen_heads(on)
+    try:
+        rc = frontend.lib.sta_regress_views_tokens_finish(frontend._h, adj, float(rel_pose_thres), pconf, acc, C.byref(nacc),
+                                                          p.pts.data_ptr(), p.conf.data_ptr(), p.depth.data_ptr(), p.K.data_ptr(), kval, p.stream)
+    finally:
+        frontend.set_varlen_heads(prev)
     if rc != 0:
         msg = frontend.lib.sta_last_error()
         frontend.lib.sta_regress_views_abort(frontend._h, p.stream)
@@ -266,14 +293,16 @@ def regress_views_tokens_finish(frontend: STAFrontend, p: PendingEdges, adjacent
 
 def regress_views_tokens(frontend: STAFrontend, enc_feat_i: torch.Tensor, size_i: Tuple[int, int], enc_feats_j: Sequence[torch.Tensor],
                          sizes_j: Sequence[Tuple[int, int]], sel_i: Sequence, sel_j: Sequence, adjacent: Sequence[bool],
-                         rel_pose_thres: float) -> List[EdgeResult]:
+                         rel_pose_thres: float, heads: str | None = None) -> List[EdgeResult]:
     """Edges (i, j_e), e < k <= 16, of one keyframe on TOKEN SUBSETS.  enc_feat_i: keyframe i's cached whole-frame encoding at size_i
     = (H, W); enc_feats_j[e] / sizes_j[e]: candidate e's, each with its own frame size.  sel_i[e] / sel_j[e] select the tokens of the
     two sides of edge e: None (the whole frame), a 4-tuple (y0, x0, h, w) (a window, in patches of that frame's grid, row-major) or
     an int64 tensor [n >= 1] of indices into the frame's row-major patch grid (any order, repeats allowed).  Selecting slices the
     cached encoding (`select_tokens` / `window_tokens`, the encode="frame" meaning); the positions are the tokens' (y, x) in their
     own frame.  Edge e is `regress_two_views` (slam.py:153-189) at B = 1 on the two slices; see `regress_views_tokens_finish` for
-    the result.  ValueError: indices outside the grid, an empty selection, a window outside its grid; AssertionError: dtype / shape."""
+    the result and for `heads`.  ValueError: indices outside the grid, an empty selection, a window outside its grid, an unknown `heads`;
+    AssertionError: dtype / shape."""
     assert len(enc_feats_j) == len(adjacent)
-    return regress_views_tokens_finish(frontend, regress_views_tokens_begin(frontend, enc_feat_i, size_i, enc_feats_j, sizes_j, sel_i, sel_j),
+    _heads_on(frontend, heads)
+    return regress_views_tokens_finish(frontend, regress_views_tokens_begin(frontend, enc_feat_i, size_i, enc_feats_j, sizes_j, sel_i, sel_j, heads=heads),
                                        adjacent, rel_pose_thres)

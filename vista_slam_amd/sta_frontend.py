@@ -116,6 +116,15 @@ class STAFrontend:
         """Bit-reproducible results (no split-K fp32 atomics at SLAM scale; include/sta_mi355.h)."""
         _lib.check(self.lib.sta_set_deterministic(self._h, int(on)))
 
+    def set_varlen_heads(self, on: bool):
+        """How `regress_views_tokens[_finish]` runs the DPT head (include/sta_mi355.h, sta_set_varlen_heads): False (default) once per
+        accepted edge and window side, True the window sides of all accepted edges in one varlen pass.  Read at finish time; the
+        workspace for the varlen pass is planned at begin time, so it has to be on at begin as well.  Returns the previous setting."""
+        prev = getattr(self, "_varlen_heads", False)
+        _lib.check(self.lib.sta_set_varlen_heads(self._h, 1 if on else 0))
+        self._varlen_heads = bool(on)
+        return prev
+
     def set_side_lanes(self, mode: str = "auto"):
         """The library's internal side streams (include/sta_mi355.h, sta_set_side_lanes): "auto" (default: on unless the
         application overlaps calls on several streams itself), "off", "on".  Results are bit-identical in all three."""
@@ -500,6 +509,76 @@ class STAFrontend:
             pts, conf = pts.swapaxes(1, 2), conf.swapaxes(1, 2)
         return {"pts3d": pts, "conf": conf}
 
+    def _row_table(self, rows: Sequence[torch.Tensor], Cdim: int):
+        """Per-entry row blocks [n_b, Cdim] -> (base tensor, first row of every entry in it).  In place where the entries are dense-row
+        views of ONE buffer whose offsets are whole rows (the packed outputs of the varlen calls); else one packed copy."""
+        ts = [self._f32(t) for t in rows]
+        for t in ts:
+            assert t.dim() == 2 and t.shape[1] == Cdim, f"bad token tensor shape {tuple(t.shape)}"
+        store = ts[0].untyped_storage().data_ptr()
+        base = min(t.data_ptr() for t in ts)
+        if all(t.untyped_storage().data_ptr() == store and t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) == Cdim) and
+               (t.data_ptr() - base) % (Cdim * 4) == 0 for t in ts) and base % 16 == 0:
+            return ts, base, [(t.data_ptr() - base) // (Cdim * 4) for t in ts]
+        buf = torch.cat([t.reshape(-1, Cdim) for t in ts]).contiguous()
+        offs, acc = [], 0
+        for t in ts:
+            offs.append(acc)
+            acc += int(t.shape[0])
+        return buf, buf.data_ptr(), offs
+
+    def head_pts_varlen(self, feats: Sequence[torch.Tensor], hooks: Sequence[Sequence[torch.Tensor]], rects: Sequence[Sequence[int]],
+                        out_pix: Sequence[int] | None = None, out: tuple | None = None):
+        """`head_pts` for B <= 32 entries whose patch rectangles differ, in ONE sta_head_pts_varlen call.  feats[b] [h_b w_b, E]: the
+        encoder features of entry b; hooks: three lists (decoder hooks d/2, 3d/4, d - dpt_head.py:112) of B tensors [h_b w_b, D], pose
+        row already skipped; rects[b] = (h_b, w_b) patches, row-major.  Views into one packed buffer (what `encode_tokens_varlen` /
+        `decode_stereo_varlen` return) are read in place through row tables; anything else is packed first.  Returns a list of B dicts
+        {"pts3d": [1, 16 h, 16 w, 3], "conf": [1, 16 h, 16 w]} - per entry exactly what `head_pts` returns for it alone, the transposed
+        views for h > w included (utils/misc.py:48-61).  out_pix / out = (pts [P, 3], conf [P]): the entries' pixel offsets in caller
+        buffers (default: a fresh packed pair)."""
+        B = len(feats)
+        assert 1 <= B <= 32, f"1 .. 32 entries per call (got {B})"
+        assert len(hooks) == 3 and all(len(hk) == B for hk in hooks) and len(rects) == B, "three hook lists and one rectangle per entry"
+        E, D = self.cfg.enc_embed_dim, self.cfg.dec_embed_dim
+        hp = [int(r[0]) for r in rects]
+        wp = [int(r[1]) for r in rects]
+        for b in range(B):
+            assert feats[b].shape[0] == hp[b] * wp[b] and all(hk[b].shape[0] == hp[b] * wp[b] for hk in hooks), \
+                f"entry {b}: {hp[b]} x {wp[b]} patches need {hp[b] * wp[b]} rows"
+        keep_e, enc_ptr, enc_row = self._row_table(feats, E)
+        tabs = [self._row_table(hk, D) for hk in hooks]
+        if any(t[2] != tabs[0][2] for t in tabs):          # the three hooks share ONE row table: pack them alike
+            tabs = []
+            for hk in hooks:
+                buf = torch.cat([self._f32(t).reshape(-1, D) for t in hk]).contiguous()
+                tabs.append((buf, buf.data_ptr(), [sum(hp[i] * wp[i] for i in range(b)) for b in range(B)]))
+        npix = [256 * hp[b] * wp[b] for b in range(B)]
+        if out is None:
+            assert out_pix is None, "out_pix names offsets in caller buffers: pass out=(pts, conf)"
+            pts = torch.empty(sum(npix), 3, device=self.device, dtype=torch.float32)
+            conf = torch.empty(sum(npix), device=self.device, dtype=torch.float32)
+        else:
+            pts, conf = out
+            assert pts.dtype == torch.float32 and conf.dtype == torch.float32 and pts.is_contiguous() and conf.is_contiguous()
+        offs = [sum(npix[:b]) for b in range(B)] if out_pix is None else [int(o) for o in out_pix]
+        for b in range(B):
+            assert 0 <= offs[b] and offs[b] + npix[b] <= conf.numel() and (offs[b] + npix[b]) * 3 <= pts.numel(), f"entry {b}: output range"
+        I64, I32 = C.c_int64 * B, C.c_int * B
+        _lib.check(self.lib.sta_head_pts_varlen(self._h, enc_ptr, I64(*enc_row), tabs[0][1], tabs[1][1], tabs[2][1], I64(*tabs[0][2]),
+                                                I32(*hp), I32(*wp), B, pts.data_ptr(), conf.data_ptr(),
+                                                None if out_pix is None else I64(*offs), self._stream()))
+        del keep_e
+        res = []
+        pf, cf = pts.view(-1, 3), conf.view(-1)
+        for b in range(B):
+            H, W_ = 16 * hp[b], 16 * wp[b]
+            p = pf[offs[b]:offs[b] + npix[b]].view(1, H, W_, 3)
+            c = cf[offs[b]:offs[b] + npix[b]].view(1, H, W_)
+            if H > W_:
+                p, c = p.swapaxes(1, 2), c.swapaxes(1, 2)
+            res.append({"pts3d": p, "conf": c})
+        return res
+
     # ------------------------------------------------------------------ monolithic paths
     @staticmethod
     def _landscape_views(outs, H: int, W_: int):
@@ -740,8 +819,8 @@ class STAFrontend:
         p2 = (C.c_void_p * L)()
         (o1, r1), (o2, r2) = self.varlen_offsets(n1), self.varlen_offsets(n2)
         for i in want:
-            b1 = torch.empty(r1, D, device=self.device, dtype=torch.float32)
-            b2 = torch.empty(r2, D, device=self.device, dtype=torch.float32)
+            both = torch.empty(r1 + r2, D, device=self.device, dtype=torch.float32)      # one buffer per layer: `head_pts_varlen` reads both sides in place
+            b1, b2 = both[:r1], both[r1:]
             p1[i], p2[i] = b1.data_ptr(), b2.data_ptr()
             out1[i] = [b1[o:o + n + 1] for o, n in zip(o1, n1)]
             out2[i] = [b2[o:o + n + 1] for o, n in zip(o2, n2)]
@@ -750,17 +829,20 @@ class STAFrontend:
         return out1, out2
 
     def forward_pairs_tokens(self, imgs_a: Sequence[torch.Tensor], imgs_b: Sequence[torch.Tensor], pos_a: Sequence[torch.Tensor],
-                             pos_b: Sequence[torch.Tensor], encode: str = "grouped"):
+                             pos_b: Sequence[torch.Tensor], encode: str = "grouped", heads: str = "entry"):
         """`forward_pair_tokens` for B pairs whose token subsets differ in size: imgs_a[b] [3, H, W] (any frame size per entry) with
         pos_a[b] [n, 2] int64 (y, x) patch positions, the same for side b.  Encoder: encode="grouped" (default): `encode_tokens`,
         entries of equal count and frame size sharing one call; encode="varlen": all 2B frames through `encode_tokens_varlen` - one
         call where 2B <= 32, else one per side.  Decoder: ONE `decode_stereo_varlen` call; pose head: once over all 2B pose rows; DPT
-        head: per entry and side, where that side is a row-major rectangle of patches.  Returns (main, support): two lists of B dicts
+        head, where a side is a row-major rectangle of patches: heads="entry" (default): `head_pts` per entry and side; heads="varlen":
+        every rectangular side of both sides through ONE `head_pts_varlen` call (chunks of 32).  Returns (main, support): two lists of B dicts
         with pts3d_pred / conf ([16 h, 16 w, 3] / [16 h, 16 w], or None), relative_pose [4, 4], relative_pose_conf []."""
         B = len(imgs_a)
         assert len(imgs_b) == B and len(pos_a) == B and len(pos_b) == B and B >= 1, "one frame and one positions tensor per entry and side"
         if encode not in ("grouped", "varlen"):
             raise ValueError(f'encode must be "grouped" or "varlen" (got {encode!r})')
+        if heads not in ("entry", "varlen"):
+            raise ValueError(f'heads must be "entry" or "varlen" (got {heads!r})')
         hooks = self.cfg.hooks
         layers = sorted({hk - 1 for hk in hooks[1:]})
         sides = []
@@ -789,11 +871,21 @@ class STAFrontend:
         d1, d2 = self.decode_stereo_varlen(sides[0][0], sides[1][0], sides[0][1], sides[1][1], layers=layers)
         pose = self.head_pose_s(torch.stack([t[0] for d in (d1, d2) for t in d[-1]]))
         res = []
+        vl = {}
+        if heads == "varlen":
+            ent = [(k, b, self._rectangle_of(qs[b][None]), feats[b], [dec[hk - 1][b][1:, :] for hk in hooks[1:]])
+                   for k, ((feats, qs), dec) in enumerate(zip(sides, (d1, d2))) for b in range(B)]
+            ent = [e for e in ent if e[2] is not None]
+            for c0 in range(0, len(ent), 32):
+                part = ent[c0:c0 + 32]
+                got = self.head_pts_varlen([e[3] for e in part], [[e[4][j] for e in part] for j in range(3)], [e[2] for e in part])
+                for e, g in zip(part, got):
+                    vl[(e[0], e[1])] = {key: v[0] for key, v in g.items()}
         for k, ((feats, qs), dec) in enumerate(zip(sides, (d1, d2))):
             outs = []
             for b in range(B):
-                rect = self._rectangle_of(qs[b][None])
-                pts = {"pts3d": None, "conf": None}
+                rect = self._rectangle_of(qs[b][None]) if heads == "entry" else None
+                pts = vl.get((k, b), {"pts3d": None, "conf": None})
                 if rect is not None:
                     toks = [feats[b][None]] + [None if t is None else t[b][None, 1:, :] for t in dec]
                     pts = self.head_pts(toks, [[16 * rect[0], 16 * rect[1]]])
