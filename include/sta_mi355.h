@@ -466,6 +466,43 @@ STA_API int sta_local_pointclouds(sta_handle* h, const float* depths, const floa
 STA_API int sta_ray_depth(sta_handle* h, const float* pts, const float* K, int k_batched, int B, int H, int W, float* out,
                   void* stream);
 
+/* Token selections from per-pixel maps: the producer of what sta_encode_varlen (index lists), sta_decode_varlen ((y, x) lists) and
+ * sta_regress_views_tokens (index lists, windows) take.  B in [1, 32] maps, entry b of its own size H[b] x W[b] (multiples of 16,
+ * hp_b x wp_b patches of 16x16 pixels, N_b = hp_b wp_b <= 8192, patch index y wp_b + x), are pooled to one int32 score per patch;
+ * a rule selects patches per entry; the selection comes out as an ascending index list, a (y, x) list, a count and a bounding
+ * window.  maps, H, W and top_k are HOST arrays read during the call (maps[b]: device memory, contiguous [H_b, W_b]); the geometry
+ * travels in the kernel arguments.  Two launches; no copy, no workspace, no allocation, no synchronisation, on the first call as on
+ * any later one (sta_alloc_stats does not move).  Everything is integer arithmetic: the result is defined bit for bit.
+ * Score (int32 >= 0 per patch, over its 256 pixels):
+ *   dtype 0 (uint8 / bool bytes), mode 0: the number of non-zero bytes (255 and 2 count like 1); with invert, of zero bytes.
+ *   dtype 1 (float32), mode 0: the number of pixels with v > thres - strict, false for a NaN v and for a NaN thres, true for +inf;
+ *     invert negates the predicate, so a NaN pixel counts under invert.
+ *   dtype 1, mode 1 (fixed-point sum; thres is ignored): sum of rint(clamp(v, 0, 32767) * 256), rounding half to even; the clamp
+ *     takes NaN, -inf and negatives to 0 and +inf to 32767.  The product is exact in fp32 and every term an integer, so the score
+ *     does not depend on summation order; its maximum is 256 * 8 388 352 = 2 147 418 112 < 2^31.
+ * Rule:
+ *   rule 0 (min_score = s >= 0): patch p is selected iff score[p] >= s; with margin = r in [0, 8] the selection is then dilated by r
+ *     patches in the Chebyshev metric inside the entry's own grid (a selected patch selects every existing patch with |dy| <= r and
+ *     |dx| <= r; nothing crosses the grid border or reaches another entry).  top_k may be NULL.
+ *   rule 1 (top_k[b] = k_b in [1, N_b]): exactly k_b patches, those with the largest scores; among equal scores the lower patch
+ *     index wins.  min_score is not used (pass 0).
+ * Outputs (device memory, the caller's; off_b = sum of N_a over a < b):
+ *   score  int32 [sum N_b]      entry b's grid, row-major, at off_b
+ *   index  int64 [sum N_b]      slot b starts at off_b: its first n_sel[b] values are the selected patch indices in ASCENDING
+ *                               order, the rest of the slot is -1
+ *   pos    int64 [sum N_b, 2]   the same slots: (y, x) of every selected patch, -1 in the tail
+ *   n_sel  int32 [B]            the counts (k_b under rule 1)
+ *   window int32 [B, 4]         (y0, x0, h, w), in patches: the bounding rectangle of the selected patches, after the margin;
+ *                               (0, 0, 0, 0) when nothing is selected - an empty selection is a result, not an error
+ * Refused (-1 and a message, nothing launched): a null pointer; B outside [1, 32]; H or W below 16 or no multiple of 16;
+ * N_b > 8192 (one workgroup keeps an entry's scores and flags in LDS; 8192 patches is a 2048 x 1024 frame); mode 1 with dtype 0 or
+ * with invert; rule 1 with margin != 0 or a top_k[b] outside [1, N_b]; min_score < 0; margin outside [0, 8]; a float32 map that is
+ * not 4-byte aligned.  A byte map may start at any address (a map that is not 16-byte aligned is read element by element). */
+STA_API int sta_select_patches(sta_handle* h, const void* const* maps, const int* H, const int* W, int B,
+                               int dtype /*0 uint8, 1 float32*/, int mode /*0 count, 1 fixed-point sum*/, float thres, int invert,
+                               int rule /*0 min_score, 1 top_k*/, int min_score, const int* top_k, int margin,
+                               int32_t* score, int64_t* index, int64_t* pos, int32_t* n_sel, int32_t* window, void* stream);
+
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one
  * batched launch sequence instead of k sequential B=1 calls, with the reference's early reject kept:

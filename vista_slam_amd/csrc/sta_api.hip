@@ -11,6 +11,7 @@
 #include "attention.h"
 #include "elementwise.h"
 #include "geo.h"
+#include "select.h"
 
 #include <algorithm>
 #include <cmath>

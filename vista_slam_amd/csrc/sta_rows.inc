@@ -296,6 +296,51 @@ extern "C" int sta_ray_depth(sta_handle* h, const float* pts, const float* K, in
     });
 }
 
+// Token selections from per-pixel maps (kernels in select.h; the contract is in include/sta_mi355.h).  The per-entry geometry is a
+// host table that travels in the kernel arguments, like sta_head_pts_varlen's: two launches, no memset, no workspace, no copy, no
+// synchronisation - on the first call of a set of shapes as on any later one.
+extern "C" int sta_select_patches(sta_handle* h, const void* const* maps, const int* H, const int* W, int B, int dtype, int mode,
+                                  float thres, int invert, int rule, int min_score, const int* top_k, int margin, int32_t* score,
+                                  int64_t* index, int64_t* pos, int32_t* n_sel, int32_t* window, void* stream) {
+    REQUIRE(h && maps && H && W && score && index && pos && n_sel && window, "null argument");
+    REQUIRE(B >= 1 && B <= SEQ_MAX, "bad argument (B = %d): sta_select_patches takes 1 .. %d maps", B, SEQ_MAX);
+    REQUIRE(dtype == 0 || dtype == 1, "dtype must be 0 (uint8) or 1 (float32) (got %d)", dtype);
+    REQUIRE(mode == 0 || mode == 1, "mode must be 0 (count) or 1 (fixed-point sum) (got %d)", mode);
+    REQUIRE(rule == 0 || rule == 1, "rule must be 0 (min_score) or 1 (top_k) (got %d)", rule);
+    REQUIRE(mode == 0 || dtype == 1, "the fixed-point sum (mode 1) is defined for float32 maps only");
+    REQUIRE(mode == 0 || !invert, "invert is refused with the fixed-point sum (mode 1)");
+    REQUIRE(margin >= 0 && margin <= SEL_MAX_MARGIN, "margin must lie in [0, %d] (got %d)", SEL_MAX_MARGIN, margin);
+    REQUIRE(min_score >= 0, "min_score must be >= 0 (got %d)", min_score);
+    if (rule == 1) {
+        REQUIRE(top_k, "null argument (top_k)");
+        REQUIRE(margin == 0, "margin is refused with top_k (the count would stop being known on the host; got margin = %d)", margin);
+    }
+    SelGeo g;
+    memset(&g, 0, sizeof(g));
+    int max_n = 0;
+    for (int b = 0; b < B; ++b) {
+        REQUIRE(maps[b], "null argument (maps[%d])", b);
+        REQUIRE(H[b] >= 16 && W[b] >= 16 && H[b] % 16 == 0 && W[b] % 16 == 0, "entry %d: H and W must be multiples of 16, at least 16 (got %d x %d)", b, H[b], W[b]);
+        const int64_t n = (int64_t)(H[b] / 16) * (W[b] / 16);
+        REQUIRE(n <= SEL_MAX_PATCHES, "entry %d: %d x %d is %lld patches, above the limit of %d per entry", b, H[b], W[b], (long long)n, SEL_MAX_PATCHES);
+        REQUIRE(dtype == 0 || ((uintptr_t)maps[b] & 3) == 0, "entry %d: a float32 map must be 4-byte aligned", b);
+        if (rule == 1) REQUIRE(top_k[b] >= 1 && top_k[b] <= n, "entry %d: top_k must lie in [1, %lld] (got %d)", b, (long long)n, top_k[b]);
+        g.map[b] = maps[b]; g.H[b] = H[b]; g.W[b] = W[b]; g.k[b] = rule == 1 ? top_k[b] : 0;
+        g.off[b + 1] = g.off[b] + (int)n;
+        max_n = (int)n > max_n ? (int)n : max_n;
+    }
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int want = (max_n + 15) / 16, gx = want < 256 ? want : 256;      // 16 patches per workgroup and step; larger entries stride
+    const dim3 grid(gx, B), block(256);
+    if (dtype == 0) hipLaunchKernelGGL(patch_score_kernel<SEL_U8>, grid, block, 0, st, g, thres, invert, score);
+    else if (mode == 0) hipLaunchKernelGGL(patch_score_kernel<SEL_F32_THRES>, grid, block, 0, st, g, thres, invert, score);
+    else hipLaunchKernelGGL(patch_score_kernel<SEL_F32_SUM>, grid, block, 0, st, g, thres, invert, score);
+    hipLaunchKernelGGL(patch_select_kernel, dim3(B), block, 0, st, g, rule, min_score, margin, score, index, pos, n_sel, window);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
