@@ -141,7 +141,8 @@ STA_API int sta_set_deterministic(sta_handle* h, int on);
  * allocations, frees and stream / event creations, out[1] = device-wide synchronisations the compute entry points have made
  * since sta_create (weight loading, sta_range_report, sta_destroy and the timing tools are not compute entry points).  Not covered
  * (their sizes depend on other arguments): sta_preprocess_frame (tables per source geometry: the first frame of a geometry
- * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_decode_pos (its RoPE table grows with pos_max and
+ * allocates and synchronises), sta_world_pointcloud (workspace per view count), sta_voxel_downsample (workspace per point count; it
+ * synchronises its stream twice like sta_world_pointcloud does once), sta_decode_pos (its RoPE table grows with pos_max and
  * its plan holds the positions table on top of sta_decode's), sta_decode_mixed / sta_decode_tokens (plans per pair of token counts), sta_decode_varlen (a plan per set of counts), sta_encode_tokens[_u8hwc] (a plan per token count),
  * sta_encode_varlen[_u8hwc] (a plan per set of counts; its RoPE table grows with the largest patch grid of a call),
  * sta_regress_views_tokens[_begin] (a plan per set of selections and frame sizes, both phases in it; its RoPE table likewise),
@@ -411,6 +412,40 @@ STA_API int sta_world_pointcloud(sta_handle* h, const float* depths, const float
                          const float* confs, const float* imgs, int N, int H, int W, float conf_thres,
                          float* pts_out, float* col_out, uint8_t* ply_records_out, int64_t* count_host, void* stream);
 STA_API int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream);
+
+/* sta_voxel_downsample: the cloud fused on a voxel grid - one row per occupied voxel, the mean of its points and colours.  It is
+ * what the reference reaches for Open3D for (eval/eval_recon.py:157-159 voxel_down_sample(0.05)) or avoids by dropping points at
+ * random (run.py:41-47); the rows are spatial bins with a per-voxel mean, not a nearest-neighbour structure.
+ * Inputs (device): pts [M,3] fp32; col [M,3] fp32 or NULL (colour sums are then 0); M < 2^30; voxel_size finite and > 0;
+ * origin = three doubles or NULL; min_points >= 1.
+ * Dropping: a point with a non-finite coordinate is dropped and counted in n_dropped.
+ * Grid: mn = the per-axis minimum of the kept points (fp32, exact).  origin == NULL: o = double(mn) - voxel_size * 0.5 - the rule
+ * Open3D documents for VoxelDownSample, restated from memory: Open3D was not available to check against.  Otherwise o = origin, so
+ * that two calls with one origin share one grid.
+ * Voxel index per axis: floor((double(p) - o) / voxel_size) - an IEEE fp64 subtraction and division, no multiply-add to contract
+ * and no fast-math build flag -, so numpy's float64 gives the same integer, also for a point exactly on a voxel face.  Indices may
+ * be negative with an explicit origin; they must fit int32.
+ * Limit: the extent index_max - index_min + 1 must be <= 2^21 per axis (a 63-bit key); a wider grid is refused with the extents in
+ * the message.
+ * Rows: one per occupied voxel with count >= min_points, in ascending lexicographic order of (iz, iy, ix).  Outputs (device, any
+ * may be NULL, row outputs sized for M rows): pts_out [V,3] fp32, col_out [V,3] fp32 = the means - sums in fp64, divided by the
+ * count in fp64, rounded once to fp32 -, counts_out [V] int32, index_out [V,3] int32 = the absolute voxel indices (ix, iy, iz),
+ * inverse_out [M] int32 = the output row of every input point, -1 where the point was dropped or its voxel filtered,
+ * ply_records_out [V,27] bytes = sta_world_pointcloud's vertex records of the means (double(fp32 mean), rint(clamp(c,0,1)*255)).
+ * count_host[0] = V, count_host[1] = n_dropped.  V = 0 (every point dropped, every voxel below min_points) is not an error; M = 0
+ * returns {0, 0} without touching the device.
+ * Determinism: no floating-point atomics.  A stable radix sort of (voxel key, input index) puts every voxel's points in ascending
+ * input order; a row of at most 1024 points is summed by 64 lanes - lane l adds points l, l + 64, ... in ascending order, then a
+ * fixed butterfly -, a longer row by 1024 threads the same way and the 16 wave sums in ascending order.  The order depends on the
+ * row's length alone, two calls on one input are bit-identical, inputs whose fp64 sums are exact give the exact mean, and any
+ * other input is within one fp32 step of any other order of summation.
+ * The call synchronises `stream` twice - after the bounds (the host must see them to refuse a grid and to choose the number of
+ * sort passes) and after the row count - and returns with the reduction enqueued: the outputs are complete for whatever runs on
+ * `stream` next.  Workspace (the stream's scratch context): about 36 bytes per point - two (key, index) buffers of 12 each, segment
+ * and row tables of 12 - plus 1 KiB of histogram per 1024 points and the scan tables. */
+STA_API int sta_voxel_downsample(sta_handle* h, const float* pts, const float* col, int64_t M, double voxel_size, const double* origin,
+                         int min_points, float* pts_out, float* col_out, int32_t* counts_out, int32_t* index_out, int32_t* inverse_out,
+                         uint8_t* ply_records_out, int64_t count_host[2] /* V, n_dropped */, void* stream);
 
 /* geometric consistency of the depth maps the path produced (vista_slam/utils/slam_utils.py; the CODE is the
  * definition where it disagrees with its docstring).  All pointers are device memory; H, W need not be multiples of 16 and

@@ -73,6 +73,8 @@ SIGNATURES = {
     "sta_preprocess_geometry": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i)]),
     "sta_preprocess_frame": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _vp]),
     "sta_world_pointcloud": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _fp, _fp, _fp, C.POINTER(_i64), _vp]),
+    "sta_voxel_downsample": (_i, [_vp, _fp, _fp, _i64, C.c_double, C.POINTER(C.c_double), _i, _fp, _fp, _fp, _fp, _fp, _fp,
+                                  C.POINTER(_i64), _vp]),
     "sta_mat_to_se3": (_i, [_vp, _fp, _i, _fp, _vp]),
     "sta_view_consistency": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _fp, _vp]),
     "sta_symmetric_geo_mask": (_i, [_vp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _vp]),

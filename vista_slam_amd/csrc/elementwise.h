@@ -1362,6 +1362,16 @@ __global__ __launch_bounds__(1024) void cloud_scan_kernel(CloudParams p) {
     int64_t run = part[threadIdx.x];
     for (int i = lo; i < hi; ++i) { p.offs[i] = run; run += p.counts[i]; }
 }
+// one PLY vertex record: double(fp32 coordinate) x 3, then rint(clamp(c, 0, 1) * 255) x 3 (also voxel.h's rows)
+__device__ __forceinline__ void cloud_write_record(uint8_t* r, float wx, float wy, float wz, float cr, float cg, float cb) {
+    const double dv[3] = {(double)wx, (double)wy, (double)wz};
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(dv);
+#pragma unroll
+    for (int q = 0; q < 24; ++q) r[q] = src[q];
+    r[24] = (uint8_t)rintf(fminf(fmaxf(cr, 0.f), 1.f) * 255.f);
+    r[25] = (uint8_t)rintf(fminf(fmaxf(cg, 0.f), 1.f) * 255.f);
+    r[26] = (uint8_t)rintf(fminf(fmaxf(cb, 0.f), 1.f) * 255.f);
+}
 __global__ __launch_bounds__(256) void cloud_emit_kernel(CloudParams p) {
     const int64_t hw = (int64_t)p.H * p.W, total = p.N * hw, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < total && p.conf[i] > p.thres;
@@ -1397,16 +1407,7 @@ __global__ __launch_bounds__(256) void cloud_emit_kernel(CloudParams p) {
     }
     if (p.pts) { p.pts[o * 3] = wx; p.pts[o * 3 + 1] = wy; p.pts[o * 3 + 2] = wz; }
     if (p.col) { p.col[o * 3] = cr; p.col[o * 3 + 1] = cg; p.col[o * 3 + 2] = cb; }
-    if (p.rec) {
-        uint8_t* r = p.rec + o * 27;
-        const double dv[3] = {(double)wx, (double)wy, (double)wz};
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(dv);
-#pragma unroll
-        for (int q = 0; q < 24; ++q) r[q] = src[q];
-        r[24] = (uint8_t)rintf(fminf(fmaxf(cr, 0.f), 1.f) * 255.f);
-        r[25] = (uint8_t)rintf(fminf(fmaxf(cg, 0.f), 1.f) * 255.f);
-        r[26] = (uint8_t)rintf(fminf(fmaxf(cb, 0.f), 1.f) * 255.f);
-    }
+    if (p.rec) cloud_write_record(p.rec + o * 27, wx, wy, wz, cr, cg, cb);
 }
 
 // pp.mat2SE3 (slam.py:166): [B,4,4] rigid transforms -> [B,7] = (tx,ty,tz, qx,qy,qz,qw), unit quaternion with the

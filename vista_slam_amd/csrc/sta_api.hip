@@ -12,6 +12,7 @@
 #include "elementwise.h"
 #include "geo.h"
 #include "select.h"
+#include "voxel.h"
 
 #include <algorithm>
 #include <cmath>

@@ -161,6 +161,126 @@ extern "C" int sta_world_pointcloud(sta_handle* h, const float* depths, const fl
     });
 }
 
+// Voxel-grid fusion of a cloud (kernels in voxel.h; the contract is in the header).  The host learns the bounds and the dropped
+// count after the first two kernels - it must, to refuse an over-wide grid and to choose the number of sort passes - and V before
+// the reduction: two copies that synchronise the stream.
+static double vox_index_host(double p, double o, double vs) {
+#pragma clang fp contract(off)
+    const double d = p - o;
+    return floor(d / vs);
+}
+static int vox_bit_length(long long v) { int n = 0; while (v > 0) { ++n; v >>= 1; } return n; }
+
+extern "C" int sta_voxel_downsample(sta_handle* h, const float* pts, const float* col, int64_t M, double voxel_size, const double* origin,
+                                    int min_points, float* pts_out, float* col_out, int32_t* counts_out, int32_t* index_out,
+                                    int32_t* inverse_out, uint8_t* ply_records_out, int64_t* count_host, void* stream) {
+    REQUIRE(h && count_host, "null argument");
+    REQUIRE(M >= 0 && M < (int64_t)1 << 30, "voxel_downsample takes fewer than 2^30 points (got %lld)", (long long)M);
+    REQUIRE(std::isfinite(voxel_size) && voxel_size > 0.0, "voxel_size must be finite and > 0 (got %g)", voxel_size);
+    REQUIRE(min_points >= 1, "min_points must be >= 1 (got %d)", min_points);
+    if (origin) REQUIRE(std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]), "origin must be finite");
+    count_host[0] = 0; count_host[1] = 0;
+    if (M == 0) return 0;
+    REQUIRE(pts, "null argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int m = (int)M;
+    const int nb256 = (m + 255) / 256, nbs = (m + VOX_TILE - 1) / VOX_TILE, nbb = nb256 < 1024 ? nb256 : 1024;
+    const int long_cap = m / VOX_LONG + 1;
+    return plan_and_run(h, st, [&](Bump& ws) -> int {
+        float* bpart = (float*)ws.take((int64_t)nbb * 32);
+        float* bout = (float*)ws.take(32);
+        unsigned long long* key[2] = {(unsigned long long*)ws.take((int64_t)m * 8), (unsigned long long*)ws.take((int64_t)m * 8)};
+        int* idx[2] = {(int*)ws.take((int64_t)m * 4), (int*)ws.take((int64_t)m * 4)};
+        int* hist = (int*)ws.take((int64_t)256 * nbs * 4);
+        int* dtot = (int*)ws.take(256 * 4);
+        int* cnt_h = (int*)ws.take((int64_t)nb256 * 4);
+        int64_t* off_h = (int64_t*)ws.take((int64_t)(nb256 + 1) * 8);
+        int* cnt_r = (int*)ws.take((int64_t)nb256 * 4);
+        int64_t* off_r = (int64_t*)ws.take((int64_t)(nb256 + 1) * 8);
+        int* seg = (int*)ws.take((int64_t)(m + 1) * 4);
+        int2* rows = (int2*)ws.take((int64_t)m * 8);
+        int* n_long = (int*)ws.take(4);
+        int* long_rows = (int*)ws.take((int64_t)long_cap * 4);
+        if (h->dry) return 0;
+        REQUIRE(!ws.overflow, "internal: workspace overflow");
+        // 1. bounds
+        hipLaunchKernelGGL(vox_bounds_kernel, dim3(nbb), dim3(256), 0, st, pts, m, bpart);
+        hipLaunchKernelGGL(vox_bounds_final_kernel, dim3(1), dim3(256), 0, st, (const float*)bpart, nbb, bout);
+        HIPCHK(hipGetLastError());
+        float bh[8];
+        HIPCHK(hipMemcpyAsync(bh, bout, 32, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        int dropped; memcpy(&dropped, &bh[6], 4);
+        const int n = m - dropped;                                  // the kept points: the first n sorted positions
+        count_host[1] = dropped;
+        if (inverse_out) HIPCHK(hipMemsetAsync(inverse_out, 0xff, (size_t)m * 4, st));      // -1 unless a row claims the point
+        if (n == 0) return 0;
+        VoxGrid g; g.vs = voxel_size;
+        long long ext[3];
+        for (int a = 0; a < 3; ++a) {
+            {
+#pragma clang fp contract(off)
+                const double half = voxel_size * 0.5;
+                g.o[a] = origin ? origin[a] : (double)bh[a] - half;
+            }
+            const double lo = vox_index_host((double)bh[a], g.o[a], voxel_size), hi = vox_index_host((double)bh[3 + a], g.o[a], voxel_size);
+            REQUIRE(lo >= -2147483648.0 && hi <= 2147483647.0, "voxel index outside int32 on axis %d: [%.17g, %.17g] at voxel_size %g", a, lo, hi,
+                    voxel_size);
+            g.lo[a] = (int)lo;
+            ext[a] = (long long)hi - (long long)lo + 1;
+        }
+        REQUIRE(ext[0] <= VOX_MAX_EXTENT && ext[1] <= VOX_MAX_EXTENT && ext[2] <= VOX_MAX_EXTENT,
+                "voxel grid too wide: %lld x %lld x %lld voxels at voxel_size %g (at most %d per axis)", ext[0], ext[1], ext[2], voxel_size,
+                VOX_MAX_EXTENT);
+        g.nx = vox_bit_length(ext[0] - 1); g.ny = vox_bit_length(ext[1] - 1);
+        const int bits = g.nx + g.ny + vox_bit_length(ext[2] - 1);
+        // the all-ones key of a dropped point must differ from every voxel's key in the digits that are sorted: a spare bit in the top
+        // digit does it, a key width that fills its digits takes one more pass
+        const int passes = (bits + 7) / 8 + (dropped > 0 && bits % 8 == 0 ? 1 : 0);
+        // 2. keys  3. sort
+        hipLaunchKernelGGL(vox_key_kernel, dim3(nb256), dim3(256), 0, st, pts, m, g, key[0], idx[0]);
+        for (int p = 0; p < passes; ++p) {
+            const int a = p & 1, b = a ^ 1;
+            hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)key[a], m, 8 * p, nbs, hist);
+            hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, hist, nbs, dtot);
+            hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)key[a], (const int*)idx[a], m, 8 * p, nbs,
+                               (const int*)hist, (const int*)dtot, key[b], idx[b]);
+        }
+        const unsigned long long* skey = key[passes & 1];
+        const int* sidx = idx[passes & 1];
+        // 4. heads, then rows
+        const int nbn = (n + 255) / 256;
+        CloudParams sc{};
+        sc.counts = cnt_h; sc.offs = off_h; sc.nblk = nbn;
+        hipLaunchKernelGGL(vox_head_count_kernel, dim3(nbn), dim3(256), 0, st, skey, n, cnt_h);
+        hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
+        hipLaunchKernelGGL(vox_head_emit_kernel, dim3(nbn), dim3(256), 0, st, skey, n, (const int64_t*)off_h, nbn, seg);
+        HIPCHK(hipMemsetAsync(n_long, 0, 4, st));
+        sc.counts = cnt_r; sc.offs = off_r;
+        hipLaunchKernelGGL(vox_row_count_kernel, dim3(nbn), dim3(256), 0, st, (const int*)seg, (const int64_t*)(off_h + nbn), min_points, cnt_r);
+        hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
+        hipLaunchKernelGGL(vox_row_emit_kernel, dim3(nbn), dim3(256), 0, st, (const int*)seg, (const int64_t*)(off_h + nbn), min_points,
+                           (const int64_t*)off_r, rows, n_long, long_rows);
+        HIPCHK(hipGetLastError());
+        int64_t V = 0;
+        HIPCHK(hipMemcpyAsync(&V, off_r + nbn, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        count_host[0] = V;
+        if (V == 0 || !(pts_out || col_out || counts_out || index_out || inverse_out || ply_records_out)) return 0;
+        // 5. reduce (stream-ordered: the outputs are complete for whatever the caller enqueues on `stream` next)
+        VoxOut o;
+        o.pts = pts; o.col = col; o.key = skey; o.idx = sidx; o.rows = rows; o.V = (int)V; o.g = g;
+        o.pts_out = pts_out; o.col_out = col_out; o.counts_out = counts_out; o.index_out = index_out; o.inverse_out = inverse_out;
+        o.rec = ply_records_out;
+        hipLaunchKernelGGL(vox_reduce_kernel, dim3(((int)V + 3) / 4), dim3(256), 0, st, o);
+        if (n > VOX_LONG)
+            hipLaunchKernelGGL(vox_reduce_long_kernel, dim3(long_cap < 256 ? long_cap : 256), dim3(1024), 0, st, o, (const int*)n_long, (const int*)long_rows);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // f5: geometric consistency of depth maps (slam_utils.py:269-419; kernels in geo.h).  Neither call synchronises or copies to
 // the host; the workspace comes from the stream's scratch context like f4's.

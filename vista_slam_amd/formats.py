@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -38,13 +38,121 @@ def mat_to_se3(frontend: STAFrontend, pose: torch.Tensor) -> torch.Tensor:
     return out
 
 
+MAX_VOXEL_EXTENT = 1 << 21     # voxels per axis: three 21-bit fields make the 63-bit sort key
+MAX_VOXEL_POINTS = (1 << 30) - 1
+
+
+class VoxelPlan(NamedTuple):
+    """What `sta_voxel_downsample` derives from the bounds of the kept points (`voxel_plan`)."""
+    origin: Tuple[float, float, float]        # the grid's corner o
+    index_min: Tuple[int, int, int]           # per axis (x, y, z): floor((bound - o) / voxel_size)
+    index_max: Tuple[int, int, int]
+    extent: Tuple[int, int, int]              # index_max - index_min + 1
+    bits: Tuple[int, int, int]                # key bits per axis = bit length of extent - 1
+    key_bits: int                             # their sum, <= 63
+    passes: int                               # 8-bit sort passes = ceil(key_bits / 8); the call runs one more when it dropped
+    #                                           non-finite points and key_bits is a multiple of 8 (their all-ones key needs a spare bit)
+
+
+def voxel_plan(bounds_min, bounds_max, voxel_size, origin=None) -> VoxelPlan:
+    """Host only: the grid of a `voxel_downsample` call whose finite points have the per-axis bounds `bounds_min` / `bounds_max`
+    (fp32 values).  origin=None: o = double(min) - voxel_size * 0.5 (the rule Open3D documents for VoxelDownSample, restated from
+    memory).  Raises ValueError with the message the library gives for a bad voxel_size, an index outside int32 and a grid wider
+    than 2^21 voxels on an axis."""
+    vs = float(voxel_size)
+    if not (np.isfinite(vs) and vs > 0.0):
+        raise ValueError("voxel_size must be finite and > 0 (got %g)" % vs)
+    mn = np.asarray(bounds_min, dtype=np.float32).astype(np.float64).reshape(3)
+    mx = np.asarray(bounds_max, dtype=np.float32).astype(np.float64).reshape(3)
+    if not (np.isfinite(mn).all() and np.isfinite(mx).all() and (mn <= mx).all()):
+        raise ValueError(f"bounds must be finite with min <= max (got {mn.tolist()} .. {mx.tolist()})")
+    if origin is None:
+        o = mn - vs * 0.5
+    else:
+        o = np.asarray(origin, dtype=np.float64).reshape(3)
+        if not np.isfinite(o).all():
+            raise ValueError("origin must be finite")
+    lo, hi = np.floor((mn - o) / vs), np.floor((mx - o) / vs)
+    for a in range(3):
+        if not (lo[a] >= -2147483648.0 and hi[a] <= 2147483647.0):
+            raise ValueError("voxel index outside int32 on axis %d: [%.17g, %.17g] at voxel_size %g" % (a, lo[a], hi[a], vs))
+    ilo, ihi = [int(v) for v in lo], [int(v) for v in hi]
+    ext = [ihi[a] - ilo[a] + 1 for a in range(3)]
+    if max(ext) > MAX_VOXEL_EXTENT:
+        raise ValueError("voxel grid too wide: %d x %d x %d voxels at voxel_size %g (at most %d per axis)"
+                         % (ext[0], ext[1], ext[2], vs, MAX_VOXEL_EXTENT))
+    bits = [(e - 1).bit_length() for e in ext]
+    return VoxelPlan(tuple(float(v) for v in o), tuple(ilo), tuple(ihi), tuple(ext), tuple(bits), sum(bits), (sum(bits) + 7) // 8)
+
+
+def voxel_downsample(frontend: STAFrontend, points, colors=None, *, voxel_size, origin=None, min_points: int = 1,
+                     return_counts: bool = False, return_index: bool = False, return_inverse: bool = False,
+                     want_records: bool = False):
+    """The cloud fused on a voxel grid (sta_voxel_downsample; the contract is in include/sta_mi355.h): one row per occupied voxel
+    with at least `min_points` points, in ascending (iz, iy, ix) order, holding the fp64 mean of its points and colours.
+
+    points [M,3], colors [M,3] or None -> (points [V,3] fp32, colors [V,3] fp32 or None [, counts [V] int32] [, index [V,3] int32]
+    [, inverse [M] int32, -1 for a dropped or filtered point] [, records [V] PLY_RECORD numpy array]), device tensors trimmed to
+    V rows.  Points with a non-finite coordinate are dropped.  origin (three floats) fixes the grid's corner, so that two calls
+    share one grid; by default the corner is min - voxel_size / 2.  ValueError for bad arguments and for a grid the library
+    refuses (`voxel_plan` gives the same answer on the host)."""
+    vs = float(voxel_size)
+    if not (np.isfinite(vs) and vs > 0.0):
+        raise ValueError("voxel_size must be finite and > 0 (got %g)" % vs)
+    if int(min_points) < 1:
+        raise ValueError(f"min_points must be >= 1 (got {int(min_points)})")
+    pts = _dev(frontend, points)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"points must be [M, 3] (got {tuple(pts.shape)})")
+    M = pts.shape[0]
+    if M > MAX_VOXEL_POINTS:
+        raise ValueError(f"voxel_downsample takes fewer than 2^30 points (got {M})")
+    col = _dev(frontend, colors, (M, 3)) if colors is not None else None
+    org = None
+    if origin is not None:
+        org = (C.c_double * 3)(*[float(v) for v in origin])
+        if not all(np.isfinite(v) for v in org):
+            raise ValueError("origin must be finite")
+    dev = frontend.device
+    out_p = torch.empty(M, 3, device=dev, dtype=torch.float32)
+    out_c = torch.empty(M, 3, device=dev, dtype=torch.float32) if col is not None else None
+    out_n = torch.empty(M, device=dev, dtype=torch.int32) if return_counts else None
+    out_i = torch.empty(M, 3, device=dev, dtype=torch.int32) if return_index else None
+    out_v = torch.empty(M, device=dev, dtype=torch.int32) if return_inverse else None
+    rec = torch.empty(M * 27, device=dev, dtype=torch.uint8) if want_records else None
+    cnt = (C.c_int64 * 2)(0, 0)
+
+    def ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+    try:
+        _lib.check(frontend.lib.sta_voxel_downsample(frontend._h, ptr(pts), ptr(col), M, vs, org, int(min_points), ptr(out_p), ptr(out_c),
+                                                     ptr(out_n), ptr(out_i), ptr(out_v), ptr(rec), cnt, frontend._stream()))
+    except _lib.StaError as e:
+        if str(e).startswith(("voxel grid too wide", "voxel index outside int32")):
+            raise ValueError(str(e)) from None
+        raise
+    V = cnt[0]
+    res = [out_p[:V], out_c[:V] if out_c is not None else None]
+    if return_counts:
+        res.append(out_n[:V])
+    if return_index:
+        res.append(out_i[:V])
+    if return_inverse:
+        res.append(out_v)
+    if want_records:
+        res.append(np.frombuffer(rec[:V * 27].cpu().numpy().tobytes(), dtype=PLY_RECORD))
+    return tuple(res)
+
+
 def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres: float,
-                     want_records: bool = False, counts=None, min_views: int = 0):
+                     want_records: bool = False, counts=None, min_views: int = 0, voxel_size=None, voxel_origin=None,
+                     min_points: int = 1):
     """slam.py:396-408 -> (points [M,3] fp32, colors [M,3] fp32 [, records [M] PLY_RECORD numpy array]).
 
     counts [N,H,W] (geo.view_consistency_check) with min_views > 0: a pixel is kept iff conf > conf_thres AND counts >= min_views
-    (the confidence of the other pixels is lowered to -inf on a copy before the same library call).  The defaults leave the
-    output unchanged."""
+    (the confidence of the other pixels is lowered to -inf on a copy before the same library call).  voxel_size: the cloud goes
+    through one `voxel_downsample` call (voxel_origin, min_points as there) before it is returned: one row per occupied voxel.
+    The defaults leave the output unchanged."""
     depths = _dev(frontend, depths)
     N, H, W = depths.shape
     scales = _dev(frontend, scales).reshape(N)
@@ -59,7 +167,7 @@ def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, c
     cap = N * H * W
     pts = torch.empty(cap, 3, device=frontend.device, dtype=torch.float32)
     col = torch.empty(cap, 3, device=frontend.device, dtype=torch.float32)
-    rec = torch.empty(cap * 27, device=frontend.device, dtype=torch.uint8) if want_records else None
+    rec = torch.empty(cap * 27, device=frontend.device, dtype=torch.uint8) if want_records and voxel_size is None else None
     cnt = C.c_int64(0)
     _lib.check(frontend.lib.sta_world_pointcloud(frontend._h, depths.data_ptr(), scales.data_ptr(), K.data_ptr(),
                                                  poses.data_ptr(), confs.data_ptr(),
@@ -67,6 +175,9 @@ def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, c
                                                  pts.data_ptr(), col.data_ptr(), rec.data_ptr() if rec is not None else None,
                                                  C.byref(cnt), frontend._stream()))
     M = cnt.value
+    if voxel_size is not None:
+        return voxel_downsample(frontend, pts[:M], col[:M], voxel_size=voxel_size, origin=voxel_origin, min_points=min_points,
+                                want_records=want_records)
     if want_records:
         records = np.frombuffer(rec[:M * 27].cpu().numpy().tobytes(), dtype=PLY_RECORD)
         return pts[:M], col[:M], records
@@ -102,11 +213,12 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
                   view_names: Optional[Sequence[str]] = None, save_view_graph=True, traj_name_postfix=None,
                   save_poses=True, save_images=True, save_scales=True, save_depths=True, save_intrinsics=True,
                   save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None,
-                  counts=None, min_views: int = 0):
+                  counts=None, min_views: int = 0, ply_voxel_size=None):
     """Same switches and files as OnlineSLAM.save_data_all (slam.py:338-421).  poses [N,4,4] (rotation + translation
     of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1].
     counts / min_views: pointcloud.ply keeps only pixels that at least min_views neighbouring views agree with
-    (world_pointcloud); every other file is unaffected."""
+    (world_pointcloud); ply_voxel_size: pointcloud.ply holds the cloud fused on a voxel grid of that size, one vertex per occupied
+    voxel (voxel_downsample); every other file is unaffected."""
     os.makedirs(output_folder, exist_ok=True)
 
     def host(t):
@@ -130,7 +242,7 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
         np.save(f"{output_folder}/intrinsics.npy", host(intrinsics))
     if save_ply:
         _, _, records = world_pointcloud(frontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres, want_records=True,
-                                         counts=counts, min_views=min_views)
+                                         counts=counts, min_views=min_views, voxel_size=ply_voxel_size)
         write_ply(f"{output_folder}/pointcloud.ply", records)
     if gt_poses is not None:
         np.save(f"{output_folder}/gt_poses.npy", np.array(gt_poses).astype(np.float32))
