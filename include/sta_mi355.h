@@ -538,6 +538,57 @@ STA_API int sta_select_patches(sta_handle* h, const void* const* maps, const int
                                int rule /*0 min_score, 1 top_k*/, int min_score, const int* top_k, int margin,
                                int32_t* score, int64_t* index, int64_t* pos, int32_t* n_sel, int32_t* window, void* stream);
 
+/* The keyframe gate: Shi-Tomasi corners on the last keyframe, tracked into the current frame with pyramidal Lucas-Kanade
+ * (vista_slam/flow_tracker.py:15-66, which calls OpenCV on the CPU).  The contract RESTATES OpenCV's documented algorithms
+ * (pyrDown, goodFeaturesToTrack, calcOpticalFlowPyrLK) in integer and float64 terms; the yardstick is the numpy restatement
+ * tests/flow_cases.py, it is NOT cv2, and keyframe decisions can differ from OpenCV's at the margin.
+ * Frame: uint8 [H,W] (dtype 0) or fp32 [H,W] in [0,1] (dtype 1), converted as the reference does (run.py:181):
+ * uint8(trunc(fp32(g) * 255.0f)).  H, W >= 8 (odd sizes are legal), H * W <= 2^21.  An image read outside its bounds uses periodic
+ * reflect-101: m = 2 (n - 1), i = ((i mod m) + m) mod m, i = m - i if i >= n; index 0 for n == 1.
+ * Pyramid: level 0 is the uint8 frame; level l + 1 has size ((H_l + 1) / 2, (W_l + 1) / 2) and pixel (y, x) =
+ * (sum_ab k[a] k[b] ext(2y + a - 2, 2x + b - 2) + 128) >> 8, k = [1,4,6,4,1]; a level is added while l < max_level (<= 3) and both of
+ * its dimensions exceed win.  A pyramid buffer holds its levels at the byte offsets sta_flow_plan reports (256-byte aligned);
+ * B frames are pyramid_bytes apart.
+ * sta_flow_plan (host only, no GPU): out = {levels, h[4], w[4], offset[4], pyramid_bytes, corner workspace_bytes, 0}.  Returns -1,
+ * with the numbers in sta_last_error(), for H or W < 8, H * W > 2^21, B outside [1, 32], win even or outside [3, 21], max_level
+ * outside [0, 3], max_corners < 1.
+ * sta_flow_pyramid: B frames [B,H,W] -> B pyramids.
+ * sta_flow_corners (image = a uint8 [H,W] frame, e.g. level 0 of a pyramid): Sobel 3x3 on the extended image -> gx, gy; box sums of
+ * block_size^2 (3, 5 or 7) over the reflect-101 extension of the product maps gx^2, gx gy, gy^2 -> a, b, c (int32);
+ * R = (a + c) - isqrt((a - c)^2 + 4 b^2) with the floor square root of the int64 argument.  A pixel is a candidate iff R > 0,
+ * double(R) >= quality * double(Rmax), and R equals the maximum of its 3x3 neighbourhood inside the image (ties keep both).  The
+ * candidates are ordered by R descending, the lower y * W + x first among equals, and suppressed greedily in that order: one is
+ * accepted iff no accepted one lies at dx^2 + dy^2 < min_distance^2 (min_distance in [1, 32]); the first max_corners accepted are
+ * written as (x, y) fp32 rows in rank order to corners [max_corners,2], their number to *n_out (device); later rows are not written.
+ * workspace: workspace_bytes of device memory, 8-byte aligned, contents free.
+ * sta_flow_track: the points pts [n,2] fp32 (x, y) of the frame behind prev_pyramid - any positions, not only corners - into each
+ * of the B frames behind next_pyramids.  n = min(*n_dev, n_cap) when n_dev (device) is given - e.g. sta_flow_corners' n_out, so
+ * that corners followed by track needs no synchronisation - and n_cap otherwise.  Per point and frame, float64 state, W_BITS = 14,
+ * half = (win - 1) / 2, FS = 2^-20, descale(s, k) = (s + 2^(k-1)) >> k, from the top level L down to 0:
+ *   p = pts 2^-l - half; the estimate q = pts 2^-L at the top, q <- 2 q below.  ip = floor(p); the level is SKIPPED (estimate
+ *   unchanged; at level 0 also status = 0) unless -win <= ip.x < W_l and -win <= ip.y < H_l.  Bilinear weights from the fractions
+ *   (al, be) of p: w00 = rint((1-al)(1-be) 2^14), w01 = rint(al (1-be) 2^14), w10 = rint((1-al) be 2^14) (float64 products, half to
+ *   even), w11 = 2^14 - w00 - w01 - w10.  Over the win^2 window: I = descale(sum w img, 9), Ix, Iy = descale(sum w grad, 14), grad =
+ *   Scharr (3, 10, 3) of the extended level image, 0 at positions outside the level.  A11, A12, A22 = FS x the exact integer sums of
+ *   Ix^2, Ix Iy, Iy^2; D = A11 A22 - A12 A12; e = (A11 + A22 - sqrt((A11 - A22)^2 + 4 A12^2)) / (2 win^2); the level is skipped if
+ *   e < min_eig or D < 2^-23.  q <- q - half, then up to max_iter rounds: iq = floor(q); outside the bounds above -> status = 0 at
+ *   level 0 and the loop ends; J = descale(sum w(q) next_img, 9); b1, b2 = FS x the exact sums of (J - I) Ix, (J - I) Iy;
+ *   d = ((A12 b2 - A22 b1) / D, (A12 b1 - A11 b2) / D); q <- q + d; stop if d.d <= eps^2; from the second round on, if
+ *   |d.x + dprev.x| < 0.01 and |d.y + dprev.y| < 0.01, q <- q - d / 2 and stop.  After the loop q <- q + half.
+ * Every float64 operation is one IEEE operation in the order written.  Outputs (device): next_pts [B,n_cap,2] = float32(q) at level
+ * 0, status [B,n_cap] uint8 (a rejection at a coarse level does not clear it, as in OpenCV), rows >= n are not written;
+ * stats [B,3] float64 = {n, n_good = points with status 1, sum over them of sqrt(dx^2 + dy^2) in float64 of the fp32 positions}.
+ * The mean and the comparison with the threshold are the host's (the reference's mean is float32: a stated difference).
+ * None of the three device calls allocates, copies to the host or synchronises. */
+STA_API int sta_flow_plan(int H, int W, int B, int win, int max_level, int max_corners, int64_t out[16]);
+STA_API int sta_flow_pyramid(sta_handle* h, const void* gray, int dtype /*0 uint8, 1 float32*/, int H, int W, int B, int win, int max_level,
+                             uint8_t* pyramid, void* stream);
+STA_API int sta_flow_corners(sta_handle* h, const uint8_t* image, int H, int W, int max_corners, double quality, int min_distance,
+                             int block_size, void* workspace, int64_t workspace_bytes, float* corners, int32_t* n_out, void* stream);
+STA_API int sta_flow_track(sta_handle* h, const uint8_t* prev_pyramid, const uint8_t* next_pyramids, int H, int W, int B, int win,
+                           int max_level, const float* pts, const int32_t* n_dev, int n_cap, int max_iter, double eps, double min_eig,
+                           float* next_pts, uint8_t* status, double* stats, void* stream);
+
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one
  * batched launch sequence instead of k sequential B=1 calls, with the reference's early reject kept:

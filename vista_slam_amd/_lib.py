@@ -83,6 +83,10 @@ SIGNATURES = {
     "sta_ray_depth": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _fp, _vp]),
     "sta_select_patches": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _f, _i, _i, _i, C.POINTER(_i), _i,
                                 _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sta_flow_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
+    "sta_flow_pyramid": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _vp]),
+    "sta_flow_corners": (_i, [_vp, _fp, _i, _i, _i, C.c_double, _i, _i, _fp, _i64, _fp, _fp, _vp]),
+    "sta_flow_track": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, C.c_double, C.c_double, _fp, _fp, _fp, _vp]),
     "sta_regress_views": (_i, [_vp, _fp, C.POINTER(_vp), _i, C.c_char_p, _f, _i, _i, _fp, C.POINTER(C.c_float),
                                C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),

@@ -13,6 +13,7 @@
 #include "geo.h"
 #include "select.h"
 #include "voxel.h"
+#include "flow.h"
 
 #include <algorithm>
 #include <cmath>

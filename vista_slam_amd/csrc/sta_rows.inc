@@ -461,6 +461,140 @@ extern "C" int sta_select_patches(sta_handle* h, const void* const* maps, const 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The keyframe gate (kernels in flow.h; the contract is in include/sta_mi355.h).  sta_flow_plan holds every size and refusal and is
+// host only; the three device calls take the caller's buffers, launch on `stream` and return: no allocation, no copy to the host, no
+// synchronisation - the corner count stays on the device and sta_flow_track reads it there.
+static int64_t flow_align(int64_t v) { return (v + 255) & ~(int64_t)255; }
+static int flow_levels(int H, int W, int win, int max_level, FlowLevels* lv) {
+    REQUIRE(H >= 8 && W >= 8, "flow: H and W must be at least 8 (got %d x %d)", H, W);
+    REQUIRE((int64_t)H * W <= FLOW_MAX_PIXELS, "flow: %d x %d is %lld pixels, above the limit of %d", H, W, (long long)H * W, FLOW_MAX_PIXELS);
+    REQUIRE(win >= 3 && win <= FLOW_MAX_WIN && win % 2 == 1, "flow: win must be odd and lie in [3, %d] (got %d)", FLOW_MAX_WIN, win);
+    REQUIRE(max_level >= 0 && max_level < FLOW_MAX_LEVELS, "flow: max_level must lie in [0, %d] (got %d)", FLOW_MAX_LEVELS - 1, max_level);
+    memset(lv, 0, sizeof(*lv));
+    lv->levels = 1; lv->h[0] = H; lv->w[0] = W; lv->off[0] = 0;
+    int64_t end = flow_align((int64_t)H * W);
+    while (lv->levels - 1 < max_level) {
+        const int l = lv->levels, nh = (lv->h[l - 1] + 1) / 2, nw = (lv->w[l - 1] + 1) / 2;
+        if (!(nh > win && nw > win)) break;
+        lv->h[l] = nh; lv->w[l] = nw; lv->off[l] = end;
+        end += flow_align((int64_t)nh * nw);
+        lv->levels = l + 1;
+    }
+    lv->bytes = end;
+    return 0;
+}
+static int flow_idx_bits(int N) { int n = 0; for (long long v = (long long)N - 1; v > 0; v >>= 1) ++n; return n; }
+// the corner workspace: R, cell, two key and two payload arrays of one word per pixel, the sort's histogram, three counters
+struct FlowWs { int *R, *cell, *idx[2], *hist, *dtot, *counters; unsigned long long* key[2]; int64_t bytes; };
+static FlowWs flow_workspace(void* base, int H, int W) {
+    const int64_t N = (int64_t)H * W, nbs = (N + VOX_TILE - 1) / VOX_TILE;
+    FlowWs w;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { void* p = (void*)((uintptr_t)base + (uintptr_t)o); o += flow_align(b); return p; };
+    w.key[0] = (unsigned long long*)take(N * 8); w.key[1] = (unsigned long long*)take(N * 8);
+    w.R = (int*)take(N * 4); w.cell = (int*)take(N * 4);
+    w.idx[0] = (int*)take(N * 4); w.idx[1] = (int*)take(N * 4);
+    w.hist = (int*)take(256 * nbs * 4); w.dtot = (int*)take(256 * 4); w.counters = (int*)take(16);
+    w.bytes = o;
+    return w;
+}
+
+extern "C" int sta_flow_plan(int H, int W, int B, int win, int max_level, int max_corners, int64_t out[16]) {
+    REQUIRE(out, "null argument");
+    FlowLevels lv;
+    CHK(flow_levels(H, W, win, max_level, &lv));
+    REQUIRE(B >= 1 && B <= FLOW_MAX_FRAMES, "flow: 1 .. %d frames per call (got B = %d)", FLOW_MAX_FRAMES, B);
+    REQUIRE(max_corners >= 1 && max_corners <= FLOW_MAX_PIXELS, "flow: max_corners must lie in [1, %d] (got %d)", FLOW_MAX_PIXELS, max_corners);
+    memset(out, 0, 16 * sizeof(int64_t));
+    out[0] = lv.levels;
+    for (int l = 0; l < lv.levels; ++l) { out[1 + l] = lv.h[l]; out[5 + l] = lv.w[l]; out[9 + l] = lv.off[l]; }
+    out[13] = lv.bytes;
+    out[14] = flow_workspace(nullptr, H, W).bytes;
+    return 0;
+}
+
+extern "C" int sta_flow_pyramid(sta_handle* h, const void* gray, int dtype, int H, int W, int B, int win, int max_level, uint8_t* pyramid,
+                                void* stream) {
+    REQUIRE(h && gray && pyramid, "null argument");
+    REQUIRE(dtype == 0 || dtype == 1, "flow: dtype must be 0 (uint8) or 1 (float32) (got %d)", dtype);
+    FlowLevels lv;
+    CHK(flow_levels(H, W, win, max_level, &lv));
+    REQUIRE(B >= 1 && B <= FLOW_MAX_FRAMES, "flow: 1 .. %d frames per call (got B = %d)", FLOW_MAX_FRAMES, B);
+    REQUIRE(dtype == 0 || ((uintptr_t)gray & 3) == 0, "flow: a float32 frame must be 4-byte aligned");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* up = lv.levels > 1 ? pyramid + lv.off[1] : nullptr;
+    const dim3 g0((W + 31) / 32, (H + 31) / 32, B);
+    if (dtype == 1)
+        hipLaunchKernelGGL(flow_pyrdown_kernel<true>, g0, dim3(256), 0, st, gray, (long long)H * W, H, W, pyramid, up, lv.h[1], lv.w[1], lv.bytes);
+    else
+        hipLaunchKernelGGL(flow_pyrdown_kernel<false>, g0, dim3(256), 0, st, gray, (long long)H * W, H, W, pyramid, up, lv.h[1], lv.w[1], lv.bytes);
+    for (int l = 2; l < lv.levels; ++l)
+        hipLaunchKernelGGL(flow_pyrdown_kernel<false>, dim3((lv.w[l - 1] + 31) / 32, (lv.h[l - 1] + 31) / 32, B), dim3(256), 0, st,
+                           (const void*)(pyramid + lv.off[l - 1]), lv.bytes, lv.h[l - 1], lv.w[l - 1], (uint8_t*)nullptr, pyramid + lv.off[l],
+                           lv.h[l], lv.w[l], lv.bytes);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_flow_corners(sta_handle* h, const uint8_t* image, int H, int W, int max_corners, double quality, int min_distance,
+                                int block_size, void* workspace, int64_t workspace_bytes, float* corners, int32_t* n_out, void* stream) {
+    REQUIRE(h && image && workspace && corners && n_out, "null argument");
+    FlowLevels lv;
+    CHK(flow_levels(H, W, FLOW_MAX_WIN, 0, &lv));
+    REQUIRE(max_corners >= 1 && max_corners <= FLOW_MAX_PIXELS, "flow: max_corners must lie in [1, %d] (got %d)", FLOW_MAX_PIXELS, max_corners);
+    REQUIRE(std::isfinite(quality) && quality > 0.0 && quality <= 1.0, "flow: quality must lie in (0, 1] (got %g)", quality);
+    REQUIRE(min_distance >= 1 && min_distance <= FLOW_MAX_MIN_DISTANCE, "flow: min_distance must lie in [1, %d] (got %d)", FLOW_MAX_MIN_DISTANCE, min_distance);
+    REQUIRE(block_size == 3 || block_size == 5 || block_size == 7, "flow: block_size must be 3, 5 or 7 (got %d)", block_size);
+    REQUIRE(((uintptr_t)workspace & 7) == 0, "flow: the workspace must be 8-byte aligned");
+    const FlowWs w = flow_workspace(workspace, H, W);
+    REQUIRE(workspace_bytes >= w.bytes, "flow: the workspace holds %lld bytes, %d x %d needs %lld", (long long)workspace_bytes, H, W, (long long)w.bytes);
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = H * W, nb256 = (N + 255) / 256, nbs = (N + VOX_TILE - 1) / VOX_TILE;
+    int* rmax = w.counters; int* n_cand = w.counters + 1;
+    HIPCHK(hipMemsetAsync(w.counters, 0, 16, st));
+    hipLaunchKernelGGL(flow_response_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, st, image, H, W, block_size / 2, w.R, rmax);
+    const int idx_bits = flow_idx_bits(N), bits = FLOW_R_BITS + idx_bits;
+    hipLaunchKernelGGL(flow_key_kernel, dim3(nb256), dim3(256), 0, st, (const int*)w.R, H, W, (const int*)rmax, quality, idx_bits, w.key[0], w.idx[0], n_cand);
+    // the all-ones key of a pixel that is no candidate must sort behind every candidate: a spare bit in the top digit does it
+    const int passes = (bits + 7) / 8 + (bits % 8 == 0 ? 1 : 0);
+    for (int p = 0; p < passes; ++p) {
+        const int a = p & 1, b = a ^ 1;
+        hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)w.key[a], N, 8 * p, nbs, w.hist);
+        hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, w.hist, nbs, w.dtot);
+        hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)w.key[a], (const int*)w.idx[a], N, 8 * p, nbs,
+                           (const int*)w.hist, (const int*)w.dtot, w.key[b], w.idx[b]);
+    }
+    const int* sidx = w.idx[passes & 1];
+    hipLaunchKernelGGL(flow_rank_kernel, dim3(nb256), dim3(256), 0, st, sidx, N, (const int*)n_cand, w.cell);
+    hipLaunchKernelGGL(flow_suppress_kernel, dim3(1), dim3(1024), 0, st, w.cell, sidx, (const int*)n_cand, H, W, min_distance, max_corners, corners, n_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_flow_track(sta_handle* h, const uint8_t* prev_pyramid, const uint8_t* next_pyramids, int H, int W, int B, int win,
+                              int max_level, const float* pts, const int32_t* n_dev, int n_cap, int max_iter, double eps, double min_eig,
+                              float* next_pts, uint8_t* status, double* stats, void* stream) {
+    REQUIRE(h && prev_pyramid && next_pyramids && stats, "null argument");
+    FlowTrack a;
+    CHK(flow_levels(H, W, win, max_level, &a.lv));
+    REQUIRE(B >= 1 && B <= FLOW_MAX_FRAMES, "flow: 1 .. %d frames per call (got B = %d)", FLOW_MAX_FRAMES, B);
+    REQUIRE(n_cap >= 0 && n_cap <= FLOW_MAX_PIXELS, "flow: n_cap must lie in [0, %d] (got %d)", FLOW_MAX_PIXELS, n_cap);
+    REQUIRE(n_cap == 0 || (pts && next_pts && status), "null argument");
+    REQUIRE(max_iter >= 1 && max_iter <= 1000, "flow: max_iter must lie in [1, 1000] (got %d)", max_iter);
+    REQUIRE(std::isfinite(eps) && eps >= 0.0 && std::isfinite(min_eig), "flow: eps must be finite and >= 0, min_eig finite");
+    a.prev = prev_pyramid; a.next = next_pyramids; a.pts = pts; a.n_dev = n_dev; a.n_cap = n_cap; a.win = win; a.max_iter = max_iter;
+    a.eps = eps; a.min_eig = min_eig; a.out = next_pts; a.status = status;
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_cap > 0) hipLaunchKernelGGL(flow_track_kernel, dim3(n_cap, B), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(flow_stats_kernel, dim3(B), dim3(256), 0, st, pts, n_dev, n_cap, (const float*)next_pts, (const uint8_t*)status, stats);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
