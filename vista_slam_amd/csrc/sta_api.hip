@@ -126,8 +126,8 @@ struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks;
 struct AttnPlan { int pose, prefetch, stages, lds_bytes, grid, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; };
 // the two-group launch (attn_mixed_plan): stages / lds_bytes / grid of the launch, then what each group runs
 struct AttnMixedPlan { int stages, lds_bytes, grid, nwg_a; struct Group { int pose, prefetch, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch; } g[2]; };
-// the per-sequence launch (attn_varlen_plan): the launch's numbers, then per sequence what attn_plan would decide for it plus where
-// it sits in the grid and in the output (AttnSeq: blk0, pose_blk0, orow0)
+// the per-sequence launch (attn_varlen_plan, both forms): the launch's numbers, then per sequence what it runs plus where it sits in
+// the grid and in the output (AttnSeq: blk0, pose_blk0, orow0)
 struct AttnVarlenPlan {
     int S, stages, lds_bytes, grid, nwg, pose_blocks, orows;
     struct Seq { int nq, nk, pose, prefetch, pose_blocks, qblocks, ntiles, nfull, tail_stage, pose_scratch, blk0, pose_blk0, orow0; } s[ATT_MAX_SEQ];
@@ -223,6 +223,23 @@ struct Bump {
         return p;
     }
 };
+
+// A call with caller positions (sta_handle::rope_foreign), from here to the end of the entry point
+struct RopeForeign {
+    sta_handle* h;
+    explicit RopeForeign(sta_handle* h_) : h(h_) { h->rope_foreign = true; }
+    ~RopeForeign() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; }
+};
+// ... inside its plan_and_run body: the int32 positions table (n_pos values) and the identity table (n_ident float2) from the
+// workspace, in that order; the real pass records them in the handle.  The entry point's own table kernel fills them.
+struct RopeTables { int* pos; float2* ident; };
+static RopeTables rope_tables(sta_handle* h, Bump& ws, int64_t n_pos, int64_t n_ident) {
+    RopeTables t;
+    t.pos = (int*)ws.take(n_pos * 4);
+    t.ident = (float2*)ws.take(n_ident * 8);
+    if (!h->dry) { h->rope_pos = t.pos; h->rope_ident = (const float*)t.ident; }
+    return t;
+}
 
 // The context of stream `st` becomes the current one (created on the first call on that stream: 2 x 16 MiB of split-K scratch;
 // the workspace grows with the first call of a shape).  At most MAX_STREAM_CTX contexts per handle: one more stream RECYCLES the
@@ -707,17 +724,14 @@ static int encode_tokens_any(sta_handle* h, const void* img_dev, bool u8hwc, con
     hipStream_t st = (hipStream_t)stream;
     const int hp = H / 16, wp = W / 16;
     CHK(ensure_rope(h, hp > wp ? hp : wp));
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     return plan_and_run(h, st, [&](Bump& ws) {
         const int64_t n = (int64_t)B * N * 2;
-        int* rp = (int*)ws.take(n * 4);
         const int64_t n_ident = (int64_t)(N + 2) * 16;            // the grid form of the call is 1 x N: table rows 0 .. N + 1
-        float2* ident = (float2*)ws.take(n_ident * 8);
+        const RopeTables t = rope_tables(h, ws, n, n_ident);
         if (!h->dry) {
-            hipLaunchKernelGGL(enc_tokens_table_kernel, dim3((unsigned)((n + n_ident + 255) / 256)), dim3(256), 0, st, pos, n, hp, wp, rp, ident, n_ident);
+            hipLaunchKernelGGL(enc_tokens_table_kernel, dim3((unsigned)((n + n_ident + 255) / 256)), dim3(256), 0, st, pos, n, hp, wp, t.pos, t.ident, n_ident);
             HIPCHK(hipGetLastError());
-            h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return encode_tokens_impl(h, ws, img_dev, u8hwc, B, H, W, N, feat_dev, st);
     });
@@ -756,16 +770,13 @@ static int encode_varlen_any(sta_handle* h, const void* const* imgs, bool u8hwc,
     e.t.tok0[B] = (int)acc;
     hipStream_t st = (hipStream_t)stream;
     CHK(ensure_rope(h, pmax));
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     return plan_and_run(h, st, [&](Bump& ws) {
-        int* rp = (int*)ws.take(acc * 2 * 4);
         const int64_t n_ident = (int64_t)(nmax + 2) * 16;        // each sequence is the grid 1 x n: table rows 0 .. max(n) + 1
-        float2* ident = (float2*)ws.take(n_ident * 8);
+        const RopeTables t = rope_tables(h, ws, acc * 2, n_ident);
         if (!h->dry) {
-            hipLaunchKernelGGL(enc_varlen_table_kernel, dim3((unsigned)((acc * 2 + n_ident + 255) / 256)), dim3(256), 0, st, pos, e, rp, ident, n_ident);
+            hipLaunchKernelGGL(enc_varlen_table_kernel, dim3((unsigned)((acc * 2 + n_ident + 255) / 256)), dim3(256), 0, st, pos, e, t.pos, t.ident, n_ident);
             HIPCHK(hipGetLastError());
-            h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return encode_varlen_impl(h, ws, e, u8hwc, feat_dev, st);
     });
@@ -838,18 +849,15 @@ extern "C" int sta_decode_pos(sta_handle* h, const float* feat1, const float* fe
     CHK(ensure_rope(h, pos_max + 1));
     const int D = h->cfg.dec_embed_dim;
     const int64_t xbytes = (int64_t)2 * B * (N + 1) * D * 4;
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     return plan_and_run(h, st, [&](Bump& ws) {
         float* x = (float*)ws.take(xbytes);
-        int* rp = (int*)ws.take((int64_t)2 * B * N * 2 * 4);
+        const int64_t n = (int64_t)B * N * 2;
         const int64_t n_ident = (int64_t)(N + 2) * 16;            // the grid form of the call is 1 x N: table rows 0 .. N + 1
-        float2* ident = (float2*)ws.take(n_ident * 8);
+        const RopeTables t = rope_tables(h, ws, 2 * n, n_ident);
         if (!h->dry) {
-            const int64_t n = (int64_t)B * N * 2;
-            hipLaunchKernelGGL(rope_pos_table_kernel, dim3((unsigned)((2 * n + n_ident + 255) / 256)), dim3(256), 0, st, pos1, pos2, n, pos_max, rp, ident, n_ident);
+            hipLaunchKernelGGL(rope_pos_table_kernel, dim3((unsigned)((2 * n + n_ident + 255) / 256)), dim3(256), 0, st, pos1, pos2, n, pos_max, t.pos, t.ident, n_ident);
             HIPCHK(hipGetLastError());
-            h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return decode_impl(h, ws, feat1, feat2, B, 1, N, x, out1, out2, true, st);
     });
@@ -871,19 +879,16 @@ extern "C" int sta_decode_tokens(sta_handle* h, const float* feat1, const float*
     hipStream_t st = (hipStream_t)stream;
     CHK(ensure_rope(h, pos_max + 1));
     const int64_t xbytes = rows * h->cfg.dec_embed_dim * 4;
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     return plan_and_run(h, st, [&](Bump& ws) {
         float* x = (float*)ws.take(xbytes);
         const int64_t n1 = (int64_t)B * N1 * 2, n2 = (int64_t)B * N2 * 2;
-        int* rp = (int*)ws.take((n1 + n2) * 4);
         const int64_t n_ident = (int64_t)(std::max(N1, N2) + 2) * 16;      // each side is the grid 1 x Nx: table rows 0 .. max(N1, N2) + 1
-        float2* ident = (float2*)ws.take(n_ident * 8);
+        const RopeTables t = rope_tables(h, ws, n1 + n2, n_ident);
         if (!h->dry) {
             hipLaunchKernelGGL(rope_tokens_table_kernel<int64_t>, dim3((unsigned)((n1 + n2 + n_ident + 255) / 256)), dim3(256), 0, st,
-                               pos1, pos2, n1, n2, pos_max, rp, ident, n_ident);
+                               pos1, pos2, n1, n2, pos_max, t.pos, t.ident, n_ident);
             HIPCHK(hipGetLastError());
-            h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return decode_mixed_impl(h, ws, feat1, feat2, B, 1, N1, 1, N2, x, out1, out2, st);
     });
@@ -915,19 +920,16 @@ extern "C" int sta_decode_varlen(sta_handle* h, const float* feat1, const float*
     hipStream_t st = (hipStream_t)stream;
     CHK(ensure_rope(h, pos_max + 1));
     const int64_t xbytes = rows * h->cfg.dec_embed_dim * 4;
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     return plan_and_run(h, st, [&](Bump& ws) {
         float* x = (float*)ws.take(xbytes);
         const int64_t c1 = (int64_t)t.tok0[B] * 2, c2 = (acc - t.tok0[B]) * 2;
-        int* rp = (int*)ws.take((c1 + c2) * 4);
         const int64_t n_ident = (int64_t)(nmax + 2) * 16;      // each sequence is the grid 1 x n: table rows 0 .. max(n) + 1
-        float2* ident = (float2*)ws.take(n_ident * 8);
+        const RopeTables rt = rope_tables(h, ws, c1 + c2, n_ident);
         if (!h->dry) {
             hipLaunchKernelGGL(rope_tokens_table_kernel<int64_t>, dim3((unsigned)((c1 + c2 + n_ident + 255) / 256)), dim3(256), 0, st,
-                               pos1, pos2, c1, c2, pos_max, rp, ident, n_ident);
+                               pos1, pos2, c1, c2, pos_max, rt.pos, rt.ident, n_ident);
             HIPCHK(hipGetLastError());
-            h->rope_pos = rp; h->rope_ident = (const float*)ident;
         }
         return decode_varlen_impl(h, ws, feat1, feat2, t, B, x, out1, out2, st);
     });

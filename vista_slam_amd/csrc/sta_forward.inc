@@ -1,164 +1,158 @@
 // Orchestration of the STA forward: encoder, cross-view decoder, pose head, DPT head (each a function over one stream's bump
 // workspace: the same code runs once dry to size the workspace and once for real, plan_and_run).  Included by sta_api.hip.
+// The encoder and the decoder each have ONE allocation function and ONE layer loop (encoder_layers / decoder_layers) that own every
+// row-wise launch; a ROUTE (whole frames, token subsets, one token count per entry) is a function that prepares the input rows and
+// hands the loop callables for what knows the sequence structure: the QKV producers, the rotation and the attention launch.
+
+// o's Q / K / V^T planes advanced by `off` elements: a whole number of sequences of the shared npad (per-side / per-sequence QKV GEMMs)
+static QKVOut qkv_at(const QKVOut& o, int64_t off) {
+    QKVOut q = o;
+    for (Planes* p : {&q.q, &q.k, &q.vt}) { p->hi += off; if (p->lo) p->lo += off; }
+    return q;
+}
+
 // ------------------------------------------------------------------------------------------ encoder
+struct EncPlanes { Planes patches, lnp, ao, f1; float* qkv32 = nullptr; QKVOut qkv; };
+// The encoder's activation planes for M rows in nseq sequences of npad rows; qkv32: also fp32 rows [M, 3E] for a dense QKV GEMM
+// (encode_varlen_impl).  Real pass: checks the workspace and zeroes the V^T padding.
+static int enc_planes(sta_handle* h, Bump& ws, int M, int nseq, int npad, bool qkv32, EncPlanes& P, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim;
+    P.patches = ws.act(M, 768, split);
+    P.lnp = ws.act(M, E, split);
+    P.ao = ws.act(M, E, split);
+    P.f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
+    P.f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);          // precision f16x3m: mlp.fc1's GELU epilogue writes f16mx rows for mlp.fc2
+    if (qkv32) P.qkv32 = (float*)ws.take((int64_t)M * 3 * E * 4);
+    P.qkv.npad = npad;
+    const int64_t hsz = (int64_t)nseq * c.enc_num_heads * npad * 64;
+    P.qkv.q = ws.planes(hsz, split); P.qkv.k = ws.planes(hsz, split); P.qkv.vt = ws.planes(hsz, split);
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
+    const Planes* z[1] = {&P.qkv.vt};
+    return zero_planes(z, 1, hsz, split, st);
+}
+// One patch-gather launch: launch(u8, split) is called with two std::bool_constant tags, the frame format and the call's precision
+template <class F>
+static int gather_dispatch(bool u8hwc, bool split, F&& launch) {
+    if (u8hwc) { if (split) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+    else if (split) launch(std::false_type{}, std::true_type{});
+    else launch(std::false_type{}, std::false_type{});
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Patch embedding of the gathered rows, then every Block.  step(b): lnp -> Q / K / V^T (rotated) -> attention of every sequence in ao.
+template <class Step>
+static int encoder_layers(sta_handle* h, const EncPlanes& P, int M, float* feat, hipStream_t st, Step&& step) {
+    const sta_config& c = h->cfg;
+    const int E = c.enc_embed_dim;
+    CHK(gemm_f32(h, P.patches, h->patch, M, feat, E, nullptr, st));
+    // every in-place residual GEMM is issued together with the LayerNorm that reads its result (gemm_resid_ln)
+    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, P.lnp, nullptr, nullptr, nullptr, st));
+    for (int i = 0; i < c.enc_depth; ++i) {
+        const EncBlk& b = h->enc[i];
+        CHK(step(b));
+        CHK(gemm_resid_ln(h, P.ao, b.proj, M, feat, E, &b.n2, &P.lnp, nullptr, nullptr, st));
+        CHK(gemm_f16(h, P.lnp, b.fc1, M, P.f1, ACT_GELU, st, P.f1.mx));
+        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, P.f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &P.lnp, nullptr, nullptr, st));
+        else CHK(gemm_resid_ln(h, P.f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
+    }
+    return 0;
+}
+
 // imgs: nsets pointers of B images each -> feat [nsets*B, N, E] (fp32, caller memory = residual stream)
 static int encode_impl(sta_handle* h, Bump& ws, const void* const* imgs, bool u8hwc, int nsets, int B, int H, int W,
                        float* feat, hipStream_t st) {
     const sta_config& c = h->cfg;
     const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, Hh = c.enc_num_heads, hp = H / 16, wp = W / 16, N = hp * wp;
-    const int n = nsets * B, M = n * N, npad = rup(N, 64);
-    Planes patches = ws.act(M, 768, split);
-    Planes lnp = ws.act(M, E, split);
-    Planes ao = ws.act(M, E, split);
-    Planes f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
-    f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);          // precision f16x3m: mlp.fc1's GELU epilogue writes f16mx rows for mlp.fc2
-    QKVOut qkv; qkv.npad = npad;
-    int64_t hsz = (int64_t)n * Hh * npad * 64;
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split); qkv.vt = ws.planes(hsz, split);
+    const int n = nsets * B, M = n * N;
+    EncPlanes P;
+    CHK(enc_planes(h, ws, M, n, rup(N, 64), false, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
-    { const Planes* z[1] = {&qkv.vt}; CHK(zero_planes(z, 1, hsz, split, st)); }
     for (int sidx = 0; sidx < nsets; ++sidx) {
-        int64_t total = (int64_t)B * N * 48;
-        int blocks = (int)((total + 255) / 256);
         const int64_t row0 = (int64_t)sidx * B * N;
-        if (u8hwc) {
-            const int b16 = (int)(((int64_t)B * N * 16 + 255) / 256);
-            if (split) hipLaunchKernelGGL(patch_gather_u8hwc_kernel<true>, dim3(b16), dim3(256), 0, st, (const uint8_t*)imgs[sidx], B, H, W, patches.hi, patches.lo, row0, (int64_t)M, h->range);
-            else hipLaunchKernelGGL(patch_gather_u8hwc_kernel<false>, dim3(b16), dim3(256), 0, st, (const uint8_t*)imgs[sidx], B, H, W, patches.hi, patches.lo, row0, (int64_t)M, h->range);
-        } else if (split) hipLaunchKernelGGL(patch_gather_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)imgs[sidx], B, H, W, patches.hi, patches.lo, row0, (int64_t)M, h->range);
-        else hipLaunchKernelGGL(patch_gather_kernel<false>, dim3(blocks), dim3(256), 0, st, (const float*)imgs[sidx], B, H, W, patches.hi, patches.lo, row0, (int64_t)M, h->range);
-        HIPCHK(hipGetLastError());
+        CHK(gather_dispatch(u8hwc, split, [&](auto u8, auto sp) {
+            const int blocks = (int)(((int64_t)B * N * (decltype(u8)::value ? 16 : 48) + 255) / 256);
+            if constexpr (decltype(u8)::value) hipLaunchKernelGGL(patch_gather_u8hwc_kernel<decltype(sp)::value>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)imgs[sidx], B, H, W, P.patches.hi, P.patches.lo, row0, (int64_t)M, h->range);
+            else hipLaunchKernelGGL(patch_gather_kernel<decltype(sp)::value>, dim3(blocks), dim3(256), 0, st, (const float*)imgs[sidx], B, H, W, P.patches.hi, P.patches.lo, row0, (int64_t)M, h->range);
+        }));
     }
-    CHK(gemm_f32(h, patches, h->patch, M, feat, E, nullptr, st));
-    // every in-place residual GEMM is issued together with the LayerNorm that reads its result (gemm_resid_ln)
-    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, lnp, nullptr, nullptr, nullptr, st));
-    for (int i = 0; i < c.enc_depth; ++i) {
-        const EncBlk& b = h->enc[i];
-        CHK(gemm_qkv(h, lnp, b.qkv, M, E, E, E, qkv, N, Hh, wp, 0, st));
-        CHK(run_attn(h, qkv, ao, E, n, Hh, N, N, 0, st));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, feat, E, &b.n2, &lnp, nullptr, nullptr, st));
-        CHK(gemm_f16(h, lnp, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &lnp, nullptr, nullptr, st));
-        else CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
-    }
-    return 0;
+    return encoder_layers(h, P, M, feat, st, [&](const EncBlk& b) -> int {
+        CHK(gemm_qkv(h, P.lnp, b.qkv, M, E, E, E, P.qkv, N, Hh, wp, 0, st));
+        return run_attn(h, P.qkv, P.ao, E, n, Hh, N, N, 0, st);
+    });
+}
+
+// The gather launch of a token-subset route, M rows.  V = NoEntries: B x N tokens of one frame size; V = EncEntries: the table's.
+template <class V = NoEntries>
+static int gather_tokens(sta_handle* h, const void* img, bool u8hwc, int B, int N, int H, int W, const EncPlanes& P, int M, hipStream_t st, const V& ent = V{}) {
+    return gather_dispatch(u8hwc, h->prec != STA_PREC_F16, [&](auto u8, auto sp) {
+        const int blocks = (int)(((int64_t)M * (decltype(u8)::value ? 16 : 48) + 255) / 256);
+        if constexpr (decltype(u8)::value) hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<decltype(sp)::value, V>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)img, h->rope_pos, B, N, H, W, P.patches.hi, P.patches.lo, (int64_t)M, h->range, ent);
+        else hipLaunchKernelGGL((patch_gather_tokens_kernel<decltype(sp)::value, V>), dim3(blocks), dim3(256), 0, st, (const float*)img, h->rope_pos, B, N, H, W, P.patches.hi, P.patches.lo, (int64_t)M, h->range, ent);
+    });
 }
 
 // The encoder on a TOKEN SUBSET (sta_encode_tokens): N tokens per image, token t of image b = the patch at pos[b][t] = (y, x), which is
 // also its RoPE position - the reference's module code on the gathered patch embeddings (patch_embed, then every Block with the
-// gathered positions: sta_model.py:163-174, sta_blocks.py:129-148,166-169).  encode_impl with M = B*N rows: the gather reads the
-// selected patches only, every QKV epilogue sees the grid 1 x N and rotates by the identity table (h->rope_foreign), one
-// rope_tokens_kernel<., false> launch per layer rotates Q and K from the positions table, attention runs with nq = nk = N.
+// gathered positions: sta_model.py:163-174, sta_blocks.py:129-148,166-169).  M = B*N rows: the gather reads the selected patches
+// only, every QKV epilogue sees the grid 1 x N and rotates by the identity table (h->rope_foreign), one rope_tokens_kernel<., false>
+// launch per layer rotates Q and K from the positions table, attention runs with nq = nk = N.
 // h->rope_pos: the int32 table [B][N][2] inside the grid (enc_tokens_table_kernel).
 static int encode_tokens_impl(sta_handle* h, Bump& ws, const void* img, bool u8hwc, int B, int H, int W, int N, float* feat, hipStream_t st) {
     const sta_config& c = h->cfg;
-    const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, Hh = c.enc_num_heads;
     const int M = B * N, npad = rup(N, 64);
-    Planes patches = ws.act(M, 768, split);
-    Planes lnp = ws.act(M, E, split);
-    Planes ao = ws.act(M, E, split);
-    Planes f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
-    f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);
-    QKVOut qkv; qkv.npad = npad;
-    int64_t hsz = (int64_t)B * Hh * npad * 64;
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split); qkv.vt = ws.planes(hsz, split);
+    EncPlanes P;
+    CHK(enc_planes(h, ws, M, B, npad, false, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
-    { const Planes* z[1] = {&qkv.vt}; CHK(zero_planes(z, 1, hsz, split, st)); }
-    {
-        const int per = u8hwc ? 16 : 48;
-        const int blocks = (int)(((int64_t)M * per + 255) / 256);
-        if (u8hwc) {
-            if (split) hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<true>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
-            else hipLaunchKernelGGL(patch_gather_tokens_u8hwc_kernel<false>, dim3(blocks), dim3(256), 0, st, (const uint8_t*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
-        } else if (split) hipLaunchKernelGGL(patch_gather_tokens_kernel<true>, dim3(blocks), dim3(256), 0, st, (const float*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
-        else hipLaunchKernelGGL(patch_gather_tokens_kernel<false>, dim3(blocks), dim3(256), 0, st, (const float*)img, h->rope_pos, B, N, H, W, patches.hi, patches.lo, (int64_t)M, h->range);
-        HIPCHK(hipGetLastError());
-    }
-    CHK(gemm_f32(h, patches, h->patch, M, feat, E, nullptr, st));
-    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, lnp, nullptr, nullptr, nullptr, st));
-    for (int i = 0; i < c.enc_depth; ++i) {
-        const EncBlk& b = h->enc[i];
-        CHK(gemm_qkv(h, lnp, b.qkv, M, E, E, E, qkv, N, Hh, N, 0, st));          // the grid 1 x N, identity table
-        CHK(rope_enc_tokens(h, qkv.q, qkv.k, B, Hh, npad, N, st));
-        CHK(run_attn(h, qkv, ao, E, B, Hh, N, N, 0, st));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, feat, E, &b.n2, &lnp, nullptr, nullptr, st));
-        CHK(gemm_f16(h, lnp, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &lnp, nullptr, nullptr, st));
-        else CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
-    }
-    return 0;
+    CHK(gather_tokens(h, img, u8hwc, B, N, H, W, P, M, st));
+    return encoder_layers(h, P, M, feat, st, [&](const EncBlk& b) -> int {
+        CHK(gemm_qkv(h, P.lnp, b.qkv, M, E, E, E, P.qkv, N, Hh, N, 0, st));          // the grid 1 x N, identity table
+        CHK(rope_enc_tokens(h, P.qkv.q, P.qkv.k, B, Hh, npad, N, st));
+        return run_attn(h, P.qkv, P.ao, E, B, Hh, N, N, 0, st);
+    });
 }
 
 // The encoder on a batch whose ENTRIES differ in token count and frame size (sta_encode_varlen): entry s has its own frame e.img[s] of
 // e.H[s] x e.W[s] pixels and n_s = tok0[s + 1] - tok0[s] tokens at its own positions.  Batch entries never interact in the reference
 // (attention is per sample), so entry s is what encode_tokens_impl returns for it alone at B = 1.  Rows are packed, M = sum n_s, sequence
-// s the rows [tok0[s], tok0[s + 1]); nothing is padded.  The gather, the patch-embed GEMM, every LayerNorm, proj, fc1, fc2 and the
-// residual epilogues: ONE launch over all rows - encode_tokens_impl's calls with M = sum n_s.  What knows the sequence structure, per
-// layer: (1) the QKV GEMM, dense over all rows, fp32 + bias into a workspace [M, 3E] (its fused epilogue cannot write Q / K / V^T
-// across sequence boundaries); (2) qkv_finish_kernel's VARLEN form: rotation by each sequence's slice of the positions table, Q / K
-// [S][heads][npad][64], V^T [S][heads][64][npad], npad = roundup(max n_s, 64), no pose row; (3) attn_varlen_kernel under attn_encv_plan.
+// s the rows [tok0[s], tok0[s + 1]); nothing is padded.  What knows the sequence structure, per layer: (1) the QKV GEMM, dense over all
+// rows, fp32 + bias into a workspace [M, 3E] (its fused epilogue cannot write Q / K / V^T across sequence boundaries);
+// (2) qkv_finish_kernel's VARLEN form: rotation by each sequence's slice of the positions table, Q / K [S][heads][npad][64], V^T
+// [S][heads][64][npad], npad = roundup(max n_s, 64), no pose row; (3) attn_varlen_kernel in the encoder form (run_attn_encv).
 // Experiment switch 8: (1) + (2) as S gemm_qkv calls (identity table) + one no-pose rope_varlen_kernel launch, decode_varlen_impl's way.
 // h->rope_pos: the int32 table [M][2], each entry clamped into its own grid (enc_varlen_table_kernel).  One lane, outside sta_reserve.
 static int encode_varlen_impl(sta_handle* h, Bump& ws, const EncEntries& e, bool u8hwc, float* feat, hipStream_t st) {
     const sta_config& c = h->cfg;
-    const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, Hh = c.enc_num_heads, S = e.t.S;
     const bool per_seq = h->opt[8] == 1;
     int n[SEQ_MAX], nmax = 0;
     for (int s = 0; s < S; ++s) { n[s] = e.t.tok0[s + 1] - e.t.tok0[s]; nmax = std::max(nmax, n[s]); }
     const int M = e.t.tok0[S], npad = rup(nmax, 64);
-    Planes patches = ws.act(M, 768, split);
-    Planes lnp = ws.act(M, E, split);
-    Planes ao = ws.act(M, E, split);
-    Planes f1 = ws.act(M, (int64_t)E * c.mlp_ratio, split);
-    f1.mx = c.enc_depth > 0 && use_mx(h, h->enc[0].fc2);
-    float* qkv32 = per_seq ? nullptr : (float*)ws.take((int64_t)M * 3 * E * 4);
-    QKVOut qkv; qkv.npad = npad;
-    const int64_t ssz = (int64_t)Hh * npad * 64, hsz = S * ssz;       // one sequence; all S
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split); qkv.vt = ws.planes(hsz, split);
+    const int64_t ssz = (int64_t)Hh * npad * 64;       // one sequence
+    EncPlanes P;
+    CHK(enc_planes(h, ws, M, S, npad, !per_seq, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: encode workspace overflow");
-    { const Planes* z[1] = {&qkv.vt}; CHK(zero_planes(z, 1, hsz, split, st)); }
-    {
-        const int per = u8hwc ? 16 : 48;
-        const int blocks = (int)(((int64_t)M * per + 255) / 256);
-        if (u8hwc) {
-            if (split) hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
-            else hipLaunchKernelGGL((patch_gather_tokens_u8hwc_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const uint8_t*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
-        } else if (split) hipLaunchKernelGGL((patch_gather_tokens_kernel<true, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
-        else hipLaunchKernelGGL((patch_gather_tokens_kernel<false, EncEntries>), dim3(blocks), dim3(256), 0, st, (const float*)nullptr, h->rope_pos, 0, 0, 0, 0, patches.hi, patches.lo, (int64_t)M, h->range, e);
-        HIPCHK(hipGetLastError());
-    }
-    auto seq_planes = [&](const Planes& p, int s) { Planes q = p; q.hi = p.hi + s * ssz; if (p.lo) q.lo = p.lo + s * ssz; return q; };
-    auto seq_qkv = [&](const QKVOut& o, int s) { QKVOut q; q.npad = o.npad; q.q = seq_planes(o.q, s); q.k = seq_planes(o.k, s); q.vt = seq_planes(o.vt, s); return q; };
-    CHK(gemm_f32(h, patches, h->patch, M, feat, E, nullptr, st));
-    if (c.enc_depth > 0) CHK(run_ln(h, feat, M, E, h->enc[0].n1, lnp, nullptr, nullptr, nullptr, st));
-    for (int i = 0; i < c.enc_depth; ++i) {
-        const EncBlk& b = h->enc[i];
+    CHK(gather_tokens(h, nullptr, u8hwc, 0, 0, 0, 0, P, M, st, e));
+    return encoder_layers(h, P, M, feat, st, [&](const EncBlk& b) -> int {
         if (per_seq) {
             for (int s = 0; s < S; ++s)          // the grid 1 x n_s, identity table: exactly the launch of a B = 1 sta_encode_tokens call
-                CHK(gemm_qkv(h, slice_rows(lnp, e.t.tok0[s]), b.qkv, n[s], E, E, E, seq_qkv(qkv, s), n[s], Hh, n[s], 0, st));
-            const Planes* rot[2] = {&qkv.q, &qkv.k};
+                CHK(gemm_qkv(h, slice_rows(P.lnp, e.t.tok0[s]), b.qkv, n[s], E, E, E, qkv_at(P.qkv, s * ssz), n[s], Hh, n[s], 0, st));
+            const Planes* rot[2] = {&P.qkv.q, &P.qkv.k};
             CHK(rope_varlen_launch(h, rot, 2, e.t, Hh, npad, h->rope_pos, st, false));
         } else {
-            CHK(gemm_f32(h, lnp, b.qkv, M, qkv32, 3 * E, nullptr, st));
-            CHK(qkv_finish_varlen(h, qkv32, nullptr, E, Hh, e.t, qkv, h->rope_pos, st));
+            CHK(gemm_f32(h, P.lnp, b.qkv, M, P.qkv32, 3 * E, nullptr, st));
+            CHK(qkv_finish_varlen(h, P.qkv32, nullptr, E, Hh, e.t, P.qkv, h->rope_pos, st));
         }
-        CHK(run_attn_encv(h, qkv, ao, E, S, Hh, n, st));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, feat, E, &b.n2, &lnp, nullptr, nullptr, st));
-        CHK(gemm_f16(h, lnp, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.enc_depth) CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, &h->enc[i + 1].n1, &lnp, nullptr, nullptr, st));
-        else CHK(gemm_resid_ln(h, f1, b.fc2, M, feat, E, nullptr, nullptr, nullptr, nullptr, st));
-    }
-    return 0;
+        return run_attn_encv(h, P.qkv, P.ao, E, S, Hh, n, st);
+    });
 }
 
 // ------------------------------------------------------------------------------------------ decoder
-// Row order of the decoder's residual stream x (fp32, [2B*N + 2B, D]) and of every plane buffer derived from it:
+// Row order of the decoder's residual stream x (fp32, [2B*N + 2B, D]) and of every plane buffer derived from it (decode_impl):
 //     rows [0, 2B*N)        patch tokens, sequence-major (sequence s = side * B + b, token t: row s*N + t)
 //     rows [2B*N, 2B*N+2B)  the pose tokens of the 2B sequences
 // (the reference prepends the pose token to every sequence, sta_model.py:206-213: M = 2B x (N + 1) interleaved rows.  Token
@@ -166,6 +160,71 @@ static int encode_varlen_impl(sta_handle* h, Bump& ws, const EncEntries& e, bool
 // the pose rows LAST the patch rows tile exactly: at 512x384, B = 8: 12288 = 64 x 192 rows + a 16-row tail that the GEMMs
 // serve with skinny tail blocks (GemmParams::m_tail) and the attention kernel with its pose path (AttnParams::pose),
 // instead of a 65th tile row, a 7th query block and a 13th key tile everywhere.)
+struct DecPlanes { Planes fp, a1, ay, ao, f1; float* emb = nullptr; QKVOut qkv, cqkv; };
+// The decoder's activation planes: fp_rows patch-feature rows, M rows of x in nseq sequences of npad rows; emb: also fp32 rows
+// [fp_rows, D] for the packed patch embedding (decode_varlen_impl).  Real pass: checks the workspace and zeroes both V^T paddings.
+static int dec_planes(sta_handle* h, Bump& ws, int64_t fp_rows, int M, int nseq, int npad, bool emb, DecPlanes& P, hipStream_t st) {
+    const sta_config& c = h->cfg;
+    const bool split = h->prec != STA_PREC_F16;
+    const int E = c.enc_embed_dim, D = c.dec_embed_dim;
+    P.fp = ws.act(fp_rows, E, split);
+    if (emb) P.emb = (float*)ws.take(fp_rows * D * 4);
+    P.a1 = ws.act(M, D, split);
+    P.ay = ws.act(M, D, split);
+    P.ao = ws.act(M, D, split);
+    P.f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
+    P.f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
+    P.qkv.npad = P.cqkv.npad = npad;          // cross attention (cqkv): its K / V^T are produced while the self-attention set is live
+    const int64_t hsz = (int64_t)nseq * c.dec_num_heads * npad * 64;
+    P.qkv.q = ws.planes(hsz, split); P.qkv.k = ws.planes(hsz, split);
+    P.cqkv.q = ws.planes(hsz, split); P.cqkv.k = ws.planes(hsz, split);
+    P.qkv.vt = ws.planes(hsz, split); P.cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    if (h->dry) return 0;
+    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
+    const Planes* z[2] = {&P.qkv.vt, &P.cqkv.vt};
+    return zero_planes(z, 2, hsz, split, st);
+}
+// Every decoder Block on the M rows of x (in a1 / ay: the LayerNorm pair of the layer input).  The route supplies
+//   self_step(b, i):   a1 -> self Q / K / V^T, ay -> the cross K / V^T, rotation, self attention of every sequence into ao
+//   cross_step(b, i):  a1 -> the cross Q, rotation, cross attention of every sequence into ao
+//   emit(idx, src):    the rows after layer idx (0: decoder input) to wherever the caller wants them
+//   final_dst(idx, x): where dec_norm of the last layer's rows goes before it is emitted (x: in place), nullptr if nobody wants them
+template <class Self, class Cross, class Emit, class FinalDst>
+static int decoder_layers(sta_handle* h, const DecPlanes& P, int M, float* x, hipStream_t st,
+                          Self&& self_step, Cross&& cross_step, Emit&& emit, FinalDst&& final_dst) {
+    const sta_config& c = h->cfg;
+    const int D = c.dec_embed_dim;
+    CHK(emit(0, x));
+    // norm1(x) and norm_y(x) from one read: y of one side == x of the other (sta_model.py:231-235); qkv and projk|projv:
+    // one class, one plane format.  Layer i+1's pair is issued with layer i's mlp.fc2 (gemm_resid_ln).
+    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, P.a1, &h->dec[0].ny, &P.ay, nullptr, st));
+    for (int i = 0; i < c.dec_depth; ++i) {
+        const DecBlk& b = h->dec[i];
+        CHK(self_step(b, i));
+        CHK(gemm_resid_ln(h, P.ao, b.proj, M, x, D, &b.n2, &P.a1, nullptr, nullptr, st));
+        CHK(cross_step(b, i));
+        CHK(gemm_resid_ln(h, P.ao, b.cproj, M, x, D, &b.n3, &P.a1, nullptr, nullptr, st));
+        CHK(gemm_f16(h, P.a1, b.fc1, M, P.f1, ACT_GELU, st, P.f1.mx));
+        if (i + 1 < c.dec_depth) {
+            const DecBlk& nb = h->dec[i + 1];
+            CHK(gemm_resid_ln(h, P.f1, b.fc2, M, x, D, &nb.n1, &P.a1, &nb.ny, &P.ay, st));
+            CHK(emit(i + 1, x));
+        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
+            CHK(gemm_resid_ln(h, P.f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
+            if (float* dst = final_dst(i + 1, x)) {
+                Planes none;
+                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, dst, st));
+                CHK(emit(i + 1, dst));
+            }
+        }
+    }
+    return 0;
+}
+// final_dst of the routes that emit through a kernel: x is dead after the last layer, normalise it in place
+static float* final_in_place(float* const* want1, float* const* want2, int idx, float* x) {
+    return (want1 && want1[idx]) || (want2 && want2[idx]) ? x : nullptr;
+}
+
 // Outputs through the `want` tables, after layer i (i = 0: decoder input):
 //   ref_layout:  want1[i] / want2[i] = [B, N+1, D] per side in the reference's token order (pose token first), or NULL
 //   otherwise:   want1[i] = the whole x in the row order above (internal consumers: sta_forward_pair, sta_regress_views)
@@ -173,33 +232,19 @@ struct TailHint { sta_handle* h; TailHint(sta_handle* h_, int t) : h(h_) { h->ta
 static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, int B, int hp, int wp,
                        float* x, float* const* want1, float* const* want2, bool ref_layout, hipStream_t st) {
     const sta_config& c = h->cfg;
-    const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, D = c.dec_embed_dim, Hh = c.dec_num_heads;
     const int N = hp * wp, Np = N + 1, S = 2 * B, M = S * Np, Mp = S * N, npad = rup(Np, 64);
-    Planes fp = ws.act((int64_t)S * N, E, split);
-    Planes a1 = ws.act(M, D, split);
-    Planes ay = ws.act(M, D, split);
-    Planes ao = ws.act(M, D, split);
-    Planes f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
-    f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
-    QKVOut qkv; qkv.npad = npad;
-    int64_t hsz = (int64_t)S * Hh * npad * 64;
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split);
-    QKVOut cqkv; cqkv.npad = npad;          // cross attention: its K / V^T are produced while the self-attention set is live
-    cqkv.q = ws.planes(hsz, split); cqkv.k = ws.planes(hsz, split);
-    qkv.vt = ws.planes(hsz, split); cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    DecPlanes P;
+    CHK(dec_planes(h, ws, (int64_t)S * N, M, S, npad, false, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
-    { const Planes* z[2] = {&qkv.vt, &cqkv.vt}; CHK(zero_planes(z, 2, hsz, split, st)); }
 
-    Planes fp2 = slice_rows(fp, (int64_t)B * N);
     if (feat2 == feat1 + (size_t)B * N * E) {          // both sides in one buffer (sta_forward_pair, the scheduler): one launch
-        CHK(run_rows_to_planes(h, feat1, (int64_t)N * E, 2 * B, N, E, fp, st));
+        CHK(run_rows_to_planes(h, feat1, (int64_t)N * E, 2 * B, N, E, P.fp, st));
     } else {
-        CHK(run_rows_to_planes(h, feat1, (int64_t)N * E, B, N, E, fp, st));
-        CHK(run_rows_to_planes(h, feat2, (int64_t)N * E, B, N, E, fp2, st));
+        CHK(run_rows_to_planes(h, feat1, (int64_t)N * E, B, N, E, P.fp, st));
+        CHK(run_rows_to_planes(h, feat2, (int64_t)N * E, B, N, E, slice_rows(P.fp, (int64_t)B * N), st));
     }
-    CHK(gemm_f32(h, fp, h->dec_embed, Mp, x, D, nullptr, st));
+    CHK(gemm_f32(h, P.fp, h->dec_embed, Mp, x, D, nullptr, st));
     float* xpose = x + (size_t)Mp * D;
     hipLaunchKernelGGL(fill_pose_token_kernel, dim3((S * D + 255) / 256), dim3(256), 0, st, xpose, S, 1, D, h->pose_tok);
     HIPCHK(hipGetLastError());
@@ -218,24 +263,20 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
         }
         return 0;
     };
-    CHK(emit(0, x));
     TailHint tail(h, S);                 // every dense GEMM below: the last S rows are the pose-token rows
-    // norm1(x) and norm_y(x) from one read: y of one side == x of the other (sta_model.py:231-235); qkv and projk|projv:
-    // one class, one plane format.  Layer i+1's pair is issued with layer i's mlp.fc2 (gemm_resid_ln).
-    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, a1, &h->dec[0].ny, &ay, nullptr, st));
     LaneJoin join_on_exit{h, st, false};          // armed by the first layer that forks
-    for (int i = 0; i < c.dec_depth; ++i) {
-        const DecBlk& b = h->dec[i];
-        // self-attention q,k,v and the cross-attention k,v of the OTHER side depend only on the layer input: one launch.
-        // (They write disjoint buffers: qkv / ckv_out.)
-        // Below the paired launch's scale (two launches + two split-K finishers) the cross-attention K / V run on the context's
-        // SIDE stream under the self-attention chain (qkv, attention, proj + norm2, cross q) and join before the cross attention.
-        bool forked = false;
-        {
+    bool forked = false;                 // this layer's cross K / V^T run on the side stream
+    return decoder_layers(h, P, M, x, st,
+        [&](const DecBlk& b, int i) -> int {
+            // self-attention q,k,v and the cross-attention k,v of the OTHER side depend only on the layer input: one launch.
+            // (They write disjoint buffers: qkv / cqkv.)
+            // Below the paired launch's scale (two launches + two split-K finishers) the cross-attention K / V run on the context's
+            // SIDE stream under the self-attention chain (qkv, attention, proj + norm2, cross q) and join before the cross attention.
             GemmParams pq, pkv;
-            CHK(gp_qkv(h, pq, a1, b.qkv, M, D, D, D, qkv, N, Hh, wp, 0, Mp));
-            CHK(gp_qkv(h, pkv, ay, b.ckv, M, 0, D, D, cqkv, N, Hh, wp, 0, Mp));
-            if (lanes_on(h) && !qkv_pair_one_launch(h, pq, pkv)) {
+            CHK(gp_qkv(h, pq, P.a1, b.qkv, M, D, D, D, P.qkv, N, Hh, wp, 0, Mp));
+            CHK(gp_qkv(h, pkv, P.ay, b.ckv, M, 0, D, D, P.cqkv, N, Hh, wp, 0, Mp));
+            forked = lanes_on(h) && !qkv_pair_one_launch(h, pq, pkv);
+            if (forked) {
                 CHK(ensure_side(h));
                 join_on_exit.armed = true;
                 hipEvent_t* ev = h->cur->side_ev + 2 * (i & 1);
@@ -247,38 +288,25 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
                 }
                 HIPCHK(hipEventRecord(ev[1], h->cur->side));
                 CHK((launch_gemm<A_DENSE, EPI_QKV>(h, pq, st)));
-                forked = true;
             } else {
                 CHK(gemm_qkv_pair(h, pq, pkv, st));
             }
-        }
-        if (h->rope_foreign) {        // sta_decode_pos: the epilogues above rotated by the identity; every sequence's q / k by its own positions now
-            CHK(rope_fix(h, qkv.q, S, Hh, npad, N, st)); CHK(rope_fix(h, qkv.k, S, Hh, npad, N, st)); CHK(rope_fix(h, cqkv.k, S, Hh, npad, N, st));
-        }
-        CHK(run_attn(h, qkv, ao, D, S, Hh, N, N, 0, st, true));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
-        CHK(gemm_qkv(h, a1, b.cq, M, D, 0, 0, cqkv, N, Hh, wp, 0, st, Mp));
-        CHK(rope_fix(h, cqkv.q, S, Hh, npad, N, st));
-        if (forked) HIPCHK(hipStreamWaitEvent(st, h->cur->side_ev[2 * (i & 1) + 1], 0));
-        CHK(run_attn(h, cqkv, ao, D, S, Hh, N, N, B, st, true));
-        CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
-        CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.dec_depth) {
-            const DecBlk& nb = h->dec[i + 1];
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, &nb.n1, &a1, &nb.ny, &ay, st));
-            CHK(emit(i + 1, x));
-        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
-            const bool wanted = (want1 && want1[i + 1]) || (ref_layout && want2 && want2[i + 1]);
-            if (wanted) {
-                Planes none;
-                float* dst = ref_layout ? x : want1[i + 1];          // x is dead after the last layer: normalise it in place
-                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, dst, st));
-                CHK(emit(i + 1, dst));
+            if (h->rope_foreign) {        // sta_decode_pos: the epilogues above rotated by the identity; every sequence's q / k by its own positions now
+                CHK(rope_fix(h, P.qkv.q, S, Hh, npad, N, st)); CHK(rope_fix(h, P.qkv.k, S, Hh, npad, N, st)); CHK(rope_fix(h, P.cqkv.k, S, Hh, npad, N, st));
             }
-        }
-    }
-    return 0;
+            return run_attn(h, P.qkv, P.ao, D, S, Hh, N, N, 0, st, true);
+        },
+        [&](const DecBlk& b, int i) -> int {
+            CHK(gemm_qkv(h, P.a1, b.cq, M, D, 0, 0, P.cqkv, N, Hh, wp, 0, st, Mp));
+            CHK(rope_fix(h, P.cqkv.q, S, Hh, npad, N, st));
+            if (forked) HIPCHK(hipStreamWaitEvent(st, h->cur->side_ev[2 * (i & 1) + 1], 0));
+            return run_attn(h, P.cqkv, P.ao, D, S, Hh, N, N, B, st, true);
+        },
+        emit,
+        [&](int idx, float* xin) -> float* {          // not ref_layout: straight into the caller's buffer, emit then has nothing to copy
+            const bool wanted = (want1 && want1[idx]) || (ref_layout && want2 && want2[idx]);
+            return !wanted ? nullptr : ref_layout ? xin : want1[idx];
+        });
 }
 
 // ------------------------------------------------------------------------------------------ decoder, two token counts
@@ -287,9 +315,8 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
 // Row order of x (fp32, [B*(N1+1) + B*(N2+1), D]) and of every plane buffer derived from it: each side is decode_impl's layout with
 // S = B, and the two sides are adjacent:
 //     [B*N1 patch rows of side 1 | B pose rows of side 1 | B*N2 patch rows of side 2 | B pose rows of side 2]
-// LayerNorm, proj, cproj, fc1, fc2 and the residual epilogues are row-wise: ONE launch over all rows, the calls of decode_impl
-// without the TailHint (the pose rows are not the last rows of the launch: gemm_plan drops the row tail, as for any caller without
-// a hint).  What knows the sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SIDE on that side's contiguous row
+// No TailHint (the pose rows are not the last rows of the launch: gemm_plan drops the row tail, as for any caller without a hint).
+// What knows the sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SIDE on that side's contiguous row
 // range (own ntok, wp, pose_base = B*Nx; Q / K / V^T planes advanced by B sequences of the shared npad) - the hot GEMMs' EPI_QKV is
 // untouched -, attention is the two-group launch (run_attn_mixed): kv_shift = 0 for the self attention of both sides, kv_shift = B
 // with (nq, nk) = (N1, N2) | (N2, N1) for the cross attention of both directions.  One lane (no side stream), outside
@@ -301,32 +328,18 @@ static int decode_impl(sta_handle* h, Bump& ws, const float* feat1, const float*
 static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, int B, int hp1, int wp1, int hp2, int wp2,
                              float* x, float* const* want1, float* const* want2, hipStream_t st) {
     const sta_config& c = h->cfg;
-    const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, D = c.dec_embed_dim, Hh = c.dec_num_heads;
     const int Nn[2] = {hp1 * wp1, hp2 * wp2}, wps[2] = {wp1, wp2};
     const int Mp[2] = {B * Nn[0], B * Nn[1]};                        // patch rows of a side = its pose_base
     const int R[2] = {Mp[0] + B, Mp[1] + B}, row0[2] = {0, R[0]};    // rows of a side, its first row
-    const int M = R[0] + R[1], S = 2 * B, npad = rup((Nn[0] > Nn[1] ? Nn[0] : Nn[1]) + 1, 64);
-    Planes fp = ws.act((int64_t)Mp[0] + Mp[1], E, split);
-    Planes a1 = ws.act(M, D, split);
-    Planes ay = ws.act(M, D, split);
-    Planes ao = ws.act(M, D, split);
-    Planes f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
-    f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
-    QKVOut qkv; qkv.npad = npad;
-    const int64_t ssz = (int64_t)B * Hh * npad * 64, hsz = 2 * ssz;   // B sequences = one side; all S sequences
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split);
-    QKVOut cqkv; cqkv.npad = npad;
-    cqkv.q = ws.planes(hsz, split); cqkv.k = ws.planes(hsz, split);
-    qkv.vt = ws.planes(hsz, split); cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    const int M = R[0] + R[1], npad = rup((Nn[0] > Nn[1] ? Nn[0] : Nn[1]) + 1, 64);
+    const int64_t ssz = (int64_t)B * Hh * npad * 64;                 // B sequences = one side
+    DecPlanes P;
+    CHK(dec_planes(h, ws, (int64_t)Mp[0] + Mp[1], M, 2 * B, npad, false, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
-    { const Planes* z[2] = {&qkv.vt, &cqkv.vt}; CHK(zero_planes(z, 2, hsz, split, st)); }
-    auto side_planes = [&](const Planes& p, int side) { Planes q = p; q.hi = p.hi + side * ssz; if (p.lo) q.lo = p.lo + side * ssz; return q; };
-    auto side_qkv = [&](const QKVOut& o, int side) { QKVOut q; q.npad = o.npad; q.q = side_planes(o.q, side); q.k = side_planes(o.k, side); q.vt = side_planes(o.vt, side); return q; };
 
     for (int side = 0; side < 2; ++side) {
-        const Planes fps = slice_rows(fp, side ? Mp[0] : 0);
+        const Planes fps = slice_rows(P.fp, side ? Mp[0] : 0);
         float* xs = x + (size_t)row0[side] * D;
         CHK(run_rows_to_planes(h, side ? feat2 : feat1, (int64_t)Nn[side] * E, B, Nn[side], E, fps, st));
         CHK(gemm_f32(h, fps, h->dec_embed, Mp[side], xs, D, nullptr, st));
@@ -347,40 +360,25 @@ static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const 
     // one QKV-epilogue GEMM per side: rows [row0, row0 + R) of A -> the side's B sequences of the Q / K / V^T buffers
     auto qkv_sides = [&](const Planes& A, const Lin& W, int nq, int nk, int nv, const QKVOut& o) -> int {
         for (int side = 0; side < 2; ++side)
-            CHK(gemm_qkv(h, slice_rows(A, row0[side]), W, R[side], nq, nk, nv, side_qkv(o, side), Nn[side], Hh, wps[side], 0, st, Mp[side]));
+            CHK(gemm_qkv(h, slice_rows(A, row0[side]), W, R[side], nq, nk, nv, qkv_at(o, side * ssz), Nn[side], Hh, wps[side], 0, st, Mp[side]));
         return 0;
     };
-    CHK(emit(0, x));
-    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, a1, &h->dec[0].ny, &ay, nullptr, st));
-    for (int i = 0; i < c.dec_depth; ++i) {
-        const DecBlk& b = h->dec[i];
-        CHK(qkv_sides(a1, b.qkv, D, D, D, qkv));
-        CHK(qkv_sides(ay, b.ckv, 0, D, D, cqkv));         // K / V of a side's OWN tokens: the other side's queries read them (kv_shift = B)
-        {   // sta_decode_tokens: the epilogues above rotated by the identity; both groups' q / k by their own positions now (one launch)
-            const Planes* rot[3] = {&qkv.q, &qkv.k, &cqkv.k};
+    return decoder_layers(h, P, M, x, st,
+        [&](const DecBlk& b, int) -> int {
+            CHK(qkv_sides(P.a1, b.qkv, D, D, D, P.qkv));
+            CHK(qkv_sides(P.ay, b.ckv, 0, D, D, P.cqkv));         // K / V of a side's OWN tokens: the other side's queries read them (kv_shift = B)
+            // sta_decode_tokens: the epilogues above rotated by the identity; both groups' q / k by their own positions now (one launch)
+            const Planes* rot[3] = {&P.qkv.q, &P.qkv.k, &P.cqkv.k};
             CHK(rope_tokens(h, rot, 3, B, B, Hh, npad, Nn[0], Nn[1], st));
-        }
-        CHK(run_attn_mixed(h, qkv, ao, D, B, B, Hh, Nn[0], Nn[0], Nn[1], Nn[1], 0, st));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
-        CHK(qkv_sides(a1, b.cq, D, 0, 0, cqkv));
-        { const Planes* rot[1] = {&cqkv.q}; CHK(rope_tokens(h, rot, 1, B, B, Hh, npad, Nn[0], Nn[1], st)); }
-        CHK(run_attn_mixed(h, cqkv, ao, D, B, B, Hh, Nn[0], Nn[1], Nn[1], Nn[0], B, st));
-        CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
-        CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.dec_depth) {
-            const DecBlk& nb = h->dec[i + 1];
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, &nb.n1, &a1, &nb.ny, &ay, st));
-            CHK(emit(i + 1, x));
-        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
-            if ((want1 && want1[i + 1]) || (want2 && want2[i + 1])) {
-                Planes none;
-                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, x, st));          // x is dead after the last layer: in place
-                CHK(emit(i + 1, x));
-            }
-        }
-    }
-    return 0;
+            return run_attn_mixed(h, P.qkv, P.ao, D, B, B, Hh, Nn[0], Nn[0], Nn[1], Nn[1], 0, st);
+        },
+        [&](const DecBlk& b, int) -> int {
+            CHK(qkv_sides(P.a1, b.cq, D, 0, 0, P.cqkv));
+            const Planes* rot[1] = {&P.cqkv.q};
+            CHK(rope_tokens(h, rot, 1, B, B, Hh, npad, Nn[0], Nn[1], st));
+            return run_attn_mixed(h, P.cqkv, P.ao, D, B, B, Hh, Nn[0], Nn[1], Nn[1], Nn[0], B, st);
+        },
+        emit, [&](int idx, float* xin) { return final_in_place(want1, want2, idx, xin); });
 }
 
 // ------------------------------------------------------------------------------------------ decoder, one token count per entry
@@ -390,46 +388,30 @@ static int decode_mixed_impl(sta_handle* h, Bump& ws, const float* feat1, const 
 // travels in the kernel arguments (the counts are host values: nothing is copied to the device, nothing is synchronised).
 // Row order of x and every plane buffer derived from it: packed, no padded rows,
 //     [n_0 patch rows | pose row] [n_1 patch rows | pose row] ... for s = 0 .. S - 1      (sequence s starts at row tok0[s] + s)
-// LayerNorm, proj, cproj, fc1, fc2 and the residual epilogues: ONE launch over all rows, as in decode_mixed_impl.  What knows the
-// sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SEQUENCE on its contiguous rows with the existing EPI_QKV
-// (one sequence of ntok = n_s, pose_base = n_s: exactly the launch of a B = 1 sta_decode_tokens call; Q / K / V^T planes advanced by s
-// sequences of the shared npad); the rotation is rope_varlen_kernel from the packed positions table; attention is the per-sequence
-// launch (run_attn_varlen: kv_shift = 0 self attention of all sequences, kv_shift = B both cross directions).  One lane, outside
-// sta_reserve's coverage.  want1[i] [sum(n1) + B, D] / want2[i] [sum(n2) + B, D]: entry by entry, pose token first, or NULL.
+// What knows the sequence structure: the QKV / cross-K|V / cross-Q GEMMs run once PER SEQUENCE on its contiguous rows with the
+// existing EPI_QKV (one sequence of ntok = n_s, pose_base = n_s: exactly the launch of a B = 1 sta_decode_tokens call; Q / K / V^T
+// planes advanced by s sequences of the shared npad); the rotation is rope_varlen_kernel from the packed positions table; attention is
+// the per-sequence launch (run_attn_varlen: kv_shift = 0 self attention of all sequences, kv_shift = B both cross directions).  One
+// lane, outside sta_reserve's coverage.  want1[i] [sum(n1) + B, D] / want2[i] [sum(n2) + B, D]: entry by entry, pose token first, or NULL.
 static int decode_varlen_impl(sta_handle* h, Bump& ws, const float* feat1, const float* feat2, const SeqTable& t, int B,
                               float* x, float* const* want1, float* const* want2, hipStream_t st) {
     const sta_config& c = h->cfg;
-    const bool split = h->prec != STA_PREC_F16;
     const int E = c.enc_embed_dim, D = c.dec_embed_dim, Hh = c.dec_num_heads, S = 2 * B;
     int n[SEQ_MAX], nmax = 0;
     for (int s = 0; s < S; ++s) { n[s] = t.tok0[s + 1] - t.tok0[s]; nmax = std::max(nmax, n[s]); }
     const int Mp = t.tok0[S], Mp1 = t.tok0[B], M = Mp + S, npad = rup(nmax + 1, 64);
+    const int64_t ssz = (int64_t)Hh * npad * 64;       // one sequence
     auto row0 = [&](int s) { return (int64_t)t.tok0[s] + s; };
-    Planes fp = ws.act(Mp, E, split);
-    float* emb = (float*)ws.take((int64_t)Mp * D * 4);
-    Planes a1 = ws.act(M, D, split);
-    Planes ay = ws.act(M, D, split);
-    Planes ao = ws.act(M, D, split);
-    Planes f1 = ws.act(M, (int64_t)D * c.mlp_ratio, split);
-    f1.mx = c.dec_depth > 0 && use_mx(h, h->dec[0].fc2);
-    QKVOut qkv; qkv.npad = npad;
-    const int64_t ssz = (int64_t)Hh * npad * 64, hsz = S * ssz;       // one sequence; all S
-    qkv.q = ws.planes(hsz, split); qkv.k = ws.planes(hsz, split);
-    QKVOut cqkv; cqkv.npad = npad;
-    cqkv.q = ws.planes(hsz, split); cqkv.k = ws.planes(hsz, split);
-    qkv.vt = ws.planes(hsz, split); cqkv.vt = ws.planes(hsz, split);      // back to back: one fill zeroes both paddings
+    DecPlanes P;
+    CHK(dec_planes(h, ws, Mp, M, S, npad, true, P, st));
     if (h->dry) return 0;
-    REQUIRE(!ws.overflow, "internal: decode workspace overflow");
-    { const Planes* z[2] = {&qkv.vt, &cqkv.vt}; CHK(zero_planes(z, 2, hsz, split, st)); }
-    auto seq_planes = [&](const Planes& p, int s) { Planes q = p; q.hi = p.hi + s * ssz; if (p.lo) q.lo = p.lo + s * ssz; return q; };
-    auto seq_qkv = [&](const QKVOut& o, int s) { QKVOut q; q.npad = o.npad; q.q = seq_planes(o.q, s); q.k = seq_planes(o.k, s); q.vt = seq_planes(o.vt, s); return q; };
 
     // patch embedding of all tokens in one GEMM on the packed rows, then into the row order above with the pose tokens
-    CHK(run_rows_to_planes(h, feat1, (int64_t)Mp1 * E, 1, Mp1, E, fp, st));
-    CHK(run_rows_to_planes(h, feat2, (int64_t)(Mp - Mp1) * E, 1, Mp - Mp1, E, slice_rows(fp, Mp1), st));
-    CHK(gemm_f32(h, fp, h->dec_embed, Mp, emb, D, nullptr, st));
+    CHK(run_rows_to_planes(h, feat1, (int64_t)Mp1 * E, 1, Mp1, E, P.fp, st));
+    CHK(run_rows_to_planes(h, feat2, (int64_t)(Mp - Mp1) * E, 1, Mp - Mp1, E, slice_rows(P.fp, Mp1), st));
+    CHK(gemm_f32(h, P.fp, h->dec_embed, Mp, P.emb, D, nullptr, st));
     auto blocks_for = [](int64_t total4) { int64_t b = (total4 + 255) / 256; return (int)(b > 8192 ? 8192 : b); };
-    hipLaunchKernelGGL(place_tokens_varlen_kernel, dim3(blocks_for((int64_t)M * D / 4)), dim3(256), 0, st, emb, t, D, h->pose_tok, x);
+    hipLaunchKernelGGL(place_tokens_varlen_kernel, dim3(blocks_for((int64_t)M * D / 4)), dim3(256), 0, st, P.emb, t, D, h->pose_tok, x);
     HIPCHK(hipGetLastError());
     auto emit = [&](int idx, const float* src) -> int {
         for (int side = 0; side < 2; ++side) {
@@ -444,40 +426,27 @@ static int decode_varlen_impl(sta_handle* h, Bump& ws, const float* feat1, const
     // one QKV-epilogue GEMM per sequence: its n_s + 1 rows of A -> its sequence of the Q / K / V^T buffers
     auto qkv_seqs = [&](const Planes& A, const Lin& W, int nq, int nk, int nv, const QKVOut& o) -> int {
         for (int s = 0; s < S; ++s)
-            CHK(gemm_qkv(h, slice_rows(A, row0(s)), W, n[s] + 1, nq, nk, nv, seq_qkv(o, s), n[s], Hh, n[s], 0, st, n[s]));
+            CHK(gemm_qkv(h, slice_rows(A, row0(s)), W, n[s] + 1, nq, nk, nv, qkv_at(o, s * ssz), n[s], Hh, n[s], 0, st, n[s]));
         return 0;
     };
     int nx[SEQ_MAX];                                    // cross attention: sequence s reads the keys of the other side's entry
     for (int s = 0; s < S; ++s) nx[s] = n[(s + B) % S];
     auto rope = [&](const Planes* const* bufs, int nbuf) -> int { return rope_varlen_launch(h, bufs, nbuf, t, Hh, npad, h->rope_pos, st); };
-    CHK(emit(0, x));
-    if (c.dec_depth > 0) CHK(run_ln(h, x, M, D, h->dec[0].n1, a1, &h->dec[0].ny, &ay, nullptr, st));
-    for (int i = 0; i < c.dec_depth; ++i) {
-        const DecBlk& b = h->dec[i];
-        CHK(qkv_seqs(a1, b.qkv, D, D, D, qkv));
-        CHK(qkv_seqs(ay, b.ckv, 0, D, D, cqkv));         // K / V of a sequence's OWN tokens: the other side's queries read them (kv_shift = B)
-        { const Planes* rot[3] = {&qkv.q, &qkv.k, &cqkv.k}; CHK(rope(rot, 3)); }      // the epilogues above rotated by the identity
-        CHK(run_attn_varlen(h, qkv, ao, D, S, Hh, n, n, 0, st));
-        CHK(gemm_resid_ln(h, ao, b.proj, M, x, D, &b.n2, &a1, nullptr, nullptr, st));
-        CHK(qkv_seqs(a1, b.cq, D, 0, 0, cqkv));
-        { const Planes* rot[1] = {&cqkv.q}; CHK(rope(rot, 1)); }
-        CHK(run_attn_varlen(h, cqkv, ao, D, S, Hh, n, nx, B, st));
-        CHK(gemm_resid_ln(h, ao, b.cproj, M, x, D, &b.n3, &a1, nullptr, nullptr, st));
-        CHK(gemm_f16(h, a1, b.fc1, M, f1, ACT_GELU, st, f1.mx));
-        if (i + 1 < c.dec_depth) {
-            const DecBlk& nb = h->dec[i + 1];
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, &nb.n1, &a1, &nb.ny, &ay, st));
-            CHK(emit(i + 1, x));
-        } else {   // final_x[-1] = dec_norm(final_x[-1])  (sta_model.py:241-242)
-            CHK(gemm_resid_ln(h, f1, b.fc2, M, x, D, nullptr, nullptr, nullptr, nullptr, st));
-            if ((want1 && want1[i + 1]) || (want2 && want2[i + 1])) {
-                Planes none;
-                CHK(run_ln(h, x, M, D, h->dec_norm, none, nullptr, nullptr, x, st));          // x is dead after the last layer: in place
-                CHK(emit(i + 1, x));
-            }
-        }
-    }
-    return 0;
+    return decoder_layers(h, P, M, x, st,
+        [&](const DecBlk& b, int) -> int {
+            CHK(qkv_seqs(P.a1, b.qkv, D, D, D, P.qkv));
+            CHK(qkv_seqs(P.ay, b.ckv, 0, D, D, P.cqkv));         // K / V of a sequence's OWN tokens: the other side's queries read them (kv_shift = B)
+            const Planes* rot[3] = {&P.qkv.q, &P.qkv.k, &P.cqkv.k};      // the epilogues above rotated by the identity
+            CHK(rope(rot, 3));
+            return run_attn_varlen(h, P.qkv, P.ao, D, S, Hh, n, n, 0, st);
+        },
+        [&](const DecBlk& b, int) -> int {
+            CHK(qkv_seqs(P.a1, b.cq, D, 0, 0, P.cqkv));
+            const Planes* rot[1] = {&P.cqkv.q};
+            CHK(rope(rot, 1));
+            return run_attn_varlen(h, P.cqkv, P.ao, D, S, Hh, n, nx, B, st);
+        },
+        emit, [&](int idx, float* xin) { return final_in_place(want1, want2, idx, xin); });
 }
 
 // ------------------------------------------------------------------------------------------ pose head

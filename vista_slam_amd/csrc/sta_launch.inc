@@ -816,34 +816,114 @@ static int rope_enc_tokens(sta_handle* h, const Planes& q, const Planes& k, int 
 
 static inline int rup(int x, int m) { return (x + m - 1) / m * m; }
 
-// ------------------------------------------------------------------------------------------ attention launch plan
-// Everything run_attn decides before it launches attn_kernel, as ONE pure host function of the shape and the switches (like
-// gemm_plan): run_attn runs exactly this plan and keeps it in the handle; sta_debug_attn_plan exposes it to the host-only sweep
-// (tests/test_attention_plan.py) and sta_debug_last_attn_plan reads back the plan a kernel test ran under.
+// ------------------------------------------------------------------------------------------ attention launch plans
+// Everything a run_attn* decides before it launches its kernel, as pure host functions of the shapes and the switches (like
+// gemm_plan): the launcher runs exactly its plan and keeps it in the handle; the sta_debug_attn_*plan hooks expose the plans to the
+// host-only sweeps (tests/test_attention*_plan.py) and the sta_debug_last_attn_*plan hooks read back the plan a kernel test ran under.
+// The rules of ONE sequence (nq queries over nk keys) live in attn_seq_rule and attn_seq_finish, the LDS of a launch in attn_lds;
+// the three builders below differ only in how sequences are laid out in the grid and in the output.
 //   pose query: 2 = one more row of the last query block when that block has spare rows (nq = 196: rows 196..255 of the second
 //   block are dead anyway - free, and no latency-bound side path at SLAM scale: 12.8 vs 26.1 us for 10 x 12 heads); 1 = one side
 //   workgroup per (sequence, head) when the patch queries fill their blocks exactly (nq = 768)
 //   prefetch: small grids with <= 4 key tiles run on 4 LDS stages, every K / V^T tile requested up front (attention.h; one
 //   workgroup per CU then, which a grid of <= 256 workgroups has anyway); no_prefetch = debug option 5
+// R: AttnPlan, AttnMixedPlan::Group or AttnVarlenPlan::Seq (the records the debug hooks serialise share these field names).
+// pose_form: the decoder's pose-token form (pose key at token index nk, pose query at token index nq).
+template <class R>
+static int attn_seq_rule(R& a, int nq, int nk, bool pose_form) {
+    a.pose = pose_form ? (nq % 128 != 0 ? 2 : 1) : 0;
+    a.qblocks = (nq + (a.pose == 2 ? 1 : 0) + 127) / 128;
+    a.ntiles = (nk + ATT_KV - 1) / ATT_KV; a.nfull = nk / ATT_KV;
+    // the pose-query blocks park npad scores + 8 + 256 partials (fp32) in the smallest LDS allocation of the kernel; npad >= nk + 1
+    // (attn_plan requires nq == nk in the pose form, so nk is also what the fixed launch would compute from nq)
+    a.pose_scratch = pose_form ? (rup(nk + 1, 64) + 8 + 256) * 4 : 0;
+    REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+    return 0;
+}
+// ... once the grid is known.  The prefetch decision uses the grid of the WHOLE launch: it is about how many workgroups share a CU.
+// Returns whether the sequence prefetches.
+template <class R>
+static bool attn_seq_finish(R& a, int nk, int grid, bool no_prefetch) {
+    a.prefetch = (nk <= ATT_PREFETCH_TILES * ATT_KV && grid <= 256 && !no_prefetch) ? 1 : 0;
+    a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
+    return a.prefetch != 0;
+}
+// A launch carries the LDS of its hungriest sequence: 4 stages as soon as one prefetches (a double-buffered sequence then simply
+// leaves stages 2 and 3 alone; the grid is <= 256 workgroups in that case, one per CU either way).
+template <class P>
+static void attn_lds(P& m, bool any_prefetch, bool split) {
+    m.stages = any_prefetch ? ATT_PREFETCH_TILES : 2;
+    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
+}
+
+// attn_kernel: S sequences of one shape
 static int attn_plan(int S, int heads, int nq, int nk, bool pose, bool split, bool no_prefetch, AttnPlan& out) {
     REQUIRE(S > 0 && heads > 0 && nq > 0 && nk > 0, "empty attention");
     REQUIRE(!pose || nq == nk, "internal: pose-token attention needs nq == nk < npad");
     AttnPlan a{};
-    a.pose = pose ? (nq % 128 != 0 ? 2 : 1) : 0;
+    CHK(attn_seq_rule(a, nq, nk, pose));
     a.pose_blocks = a.pose == 1 ? S * heads : 0;
-    a.qblocks = (nq + (a.pose == 2 ? 1 : 0) + 127) / 128;
     const int64_t grid = (int64_t)a.qblocks * heads * S + a.pose_blocks;
     REQUIRE(grid < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)grid);
     a.grid = (int)grid;
-    a.ntiles = (nk + ATT_KV - 1) / ATT_KV; a.nfull = nk / ATT_KV;
-    a.prefetch = (nk <= ATT_PREFETCH_TILES * ATT_KV && a.grid <= 256 && !no_prefetch) ? 1 : 0;
-    a.stages = a.prefetch ? ATT_PREFETCH_TILES : 2;
-    a.lds_bytes = split ? attn_smem_bytes<true>(a.stages) : attn_smem_bytes<false>(a.stages);
-    a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
-    // the pose-query blocks park npad scores + 8 + 256 partials (fp32) in the smallest LDS allocation of the kernel
-    a.pose_scratch = pose ? (rup(nq + 1, 64) + 8 + 256) * 4 : 0;
-    REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+    attn_lds(a, attn_seq_finish(a, nk, a.grid, no_prefetch), split);
     out = a;
+    return 0;
+}
+// attn_mixed_kernel (decode_mixed_impl): group a = S1 sequences of nq_a queries over nk_a keys, group b = S2 sequences of nq_b over
+// nk_b, both in the pose-token form
+static int attn_mixed_plan(int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, bool split, bool no_prefetch, AttnMixedPlan& out) {
+    REQUIRE(S1 > 0 && S2 >= 0 && heads > 0 && nq_a > 0 && nk_a > 0, "empty attention");
+    REQUIRE(S2 == 0 || (nq_b > 0 && nk_b > 0), "empty attention (second group)");
+    AttnMixedPlan m{};
+    const int Sg[2] = {S1, S2}, nq[2] = {nq_a, nq_b}, nk[2] = {nk_a, nk_b};
+    int64_t grid = 0;
+    for (int i = 0; i < 2; ++i) {
+        AttnMixedPlan::Group& a = m.g[i];
+        if (Sg[i] == 0) continue;
+        CHK(attn_seq_rule(a, nq[i], nk[i], true));
+        a.pose_blocks = a.pose == 1 ? Sg[i] * heads : 0;
+        grid += (int64_t)a.qblocks * heads * Sg[i] + a.pose_blocks;
+    }
+    REQUIRE(grid < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)grid);
+    m.grid = (int)grid;
+    m.nwg_a = m.g[0].qblocks * heads * S1;
+    bool any = false;
+    for (int i = 0; i < 2; ++i)
+        if (Sg[i] != 0 && attn_seq_finish(m.g[i], nk[i], m.grid, no_prefetch)) any = true;
+    attn_lds(m, any, split);
+    out = m;
+    return 0;
+}
+// attn_varlen_kernel: S <= ATT_MAX_SEQ sequences, sequence s with nq[s] queries over nk[s] keys (the caller resolves kv_shift: nk[s]
+// is the count of the sequence s reads).  Logical query-block ids and pose blocks are handed out in sequence order; output rows are
+// packed per sequence.  pose_form (decode_varlen_impl): [nq patch rows | pose row] per sequence.  !pose_form (encode_varlen_impl,
+// nq == nk == n): no pose token anywhere - no pose blocks, no pose scratch, orow0 = the prefix sum of n, and npad may EQUAL n[s]
+// (the pose form reads token index nk as the pose key: here that is row 0 of the next head, or the end of the buffer).
+static_assert(ATT_MAX_SEQ == SEQ_MAX, "the attention table (attention.h) and the row table (elementwise.h) hold the same sequences of one call");
+static int attn_varlen_plan(int S, int heads, const int* nq, const int* nk, bool pose_form, bool split, bool no_prefetch, AttnVarlenPlan& out) {
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && heads > 0 && nq && nk, "per-sequence attention takes 1 .. %d sequences", ATT_MAX_SEQ);
+    AttnVarlenPlan m{};
+    m.S = S;
+    const int pr = pose_form ? 1 : 0;
+    int64_t nwg = 0, npose = 0, orows = 0;
+    for (int i = 0; i < S; ++i) {
+        REQUIRE(nq[i] > 0 && nk[i] > 0, "empty attention (sequence %d)", i);
+        AttnVarlenPlan::Seq& a = m.s[i];
+        a.nq = nq[i]; a.nk = nk[i];
+        CHK(attn_seq_rule(a, nq[i], nk[i], pose_form));
+        a.pose_blocks = a.pose == 1 ? heads : 0;
+        REQUIRE(nwg + npose < ((int64_t)1 << 30) && orows < ((int64_t)1 << 31) - nq[i] - pr, "attention launch too large");
+        a.blk0 = (int)nwg; a.pose_blk0 = (int)npose; a.orow0 = (int)orows;
+        nwg += (int64_t)a.qblocks * heads; npose += a.pose_blocks; orows += (int64_t)nq[i] + pr;
+    }
+    REQUIRE(nwg + npose < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)(nwg + npose));
+    m.nwg = (int)nwg; m.pose_blocks = (int)npose; m.grid = (int)(nwg + npose); m.orows = (int)orows;
+    bool any = false;
+    for (int i = 0; i < S; ++i)
+        if (attn_seq_finish(m.s[i], nk[i], m.grid, no_prefetch)) any = true;
+    attn_lds(m, any, split);
+    out = m;
     return 0;
 }
 #ifdef STA_TEST_HOOKS
@@ -870,79 +950,6 @@ extern "C" int sta_debug_attn_block_map(int nwg, int* out) {
     for (int b = 0; b < nwg; ++b) out[b] = attn_block_map(b, nwg);
     return 0;
 }
-#endif
-
-static int run_attn(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads,
-                    int nq, int nk, int kv_shift, hipStream_t st, bool pose = false) {
-    if (h->dry) return 0;
-    REQUIRE(!pose || (nq == nk && nq + 1 <= qkv.npad), "internal: pose-token attention needs nq == nk < npad");
-    const bool split = h->prec != STA_PREC_F16;
-    AttnPlan a;
-    CHK(attn_plan(S, heads, nq, nk, pose, split, h->opt[5] == 1, a));
-    h->last_attn = a;
-    AttnParams p; memset(&p, 0, sizeof p);
-    p.range = h->range;
-    p.pose = a.pose;
-    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
-    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
-    p.S = S; p.heads = heads; p.nq = nq; p.nk = nk; p.npad = qkv.npad; p.kv_shift = kv_shift;
-    p.scale_log2e = 0.125f * 1.44269504088896340736f;
-    REQUIRE(!pose || (int64_t)(qkv.npad + 8 + 256) * 4 <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
-    REQUIRE(!pose || qkv.npad % 64 == 0, "internal: pose-query path needs npad % 64 == 0");
-    p.prefetch = a.prefetch;
-    const dim3 grid((unsigned)a.grid);
-    if (split) {
-        static unsigned attr_done = 0;      // one bit per device
-        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
-        hipLaunchKernelGGL(attn_kernel<true>, grid, dim3(256), a.lds_bytes, st, p);
-    } else {
-        STA_F16ONLY(hipLaunchKernelGGL(attn_kernel<false>, grid, dim3(256), a.lds_bytes, st, p));
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------ two-group attention (decode_mixed_impl)
-// The plan of attn_mixed_kernel, pure like attn_plan: group a = S1 sequences of nq_a queries over nk_a keys, group b = S2 sequences of
-// nq_b over nk_b, both in the decoder's pose-token form (pose key at token index nk, pose query at token index nq of the group).
-// Per group exactly attn_plan's rules on the group's own numbers - pose mode from its nq, tiles and tail from its nk, pose-query
-// scratch from its nk -; the prefetch decision uses the grid of the WHOLE launch (it is about how many workgroups share a CU), and
-// the launch carries the LDS of the hungrier group: 4 stages as soon as one group prefetches (a double-buffered group then simply
-// leaves stages 2 and 3 alone; the grid is <= 256 workgroups in that case, one per CU either way).  S2 == 0, or two groups of equal
-// (nq, nk) with nq == nk, reduce to attn_plan(S1 + S2, ..., pose) field by field (tests/test_attention_mixed_plan.py).
-static int attn_mixed_plan(int S1, int S2, int heads, int nq_a, int nk_a, int nq_b, int nk_b, bool split, bool no_prefetch, AttnMixedPlan& out) {
-    REQUIRE(S1 > 0 && S2 >= 0 && heads > 0 && nq_a > 0 && nk_a > 0, "empty attention");
-    REQUIRE(S2 == 0 || (nq_b > 0 && nk_b > 0), "empty attention (second group)");
-    AttnMixedPlan m{};
-    const int Sg[2] = {S1, S2}, nq[2] = {nq_a, nq_b}, nk[2] = {nk_a, nk_b};
-    int64_t grid = 0;
-    for (int i = 0; i < 2; ++i) {
-        AttnMixedPlan::Group& a = m.g[i];
-        if (Sg[i] == 0) continue;
-        a.pose = nq[i] % 128 != 0 ? 2 : 1;
-        a.pose_blocks = a.pose == 1 ? Sg[i] * heads : 0;
-        a.qblocks = (nq[i] + (a.pose == 2 ? 1 : 0) + 127) / 128;
-        grid += (int64_t)a.qblocks * heads * Sg[i] + a.pose_blocks;
-        a.ntiles = (nk[i] + ATT_KV - 1) / ATT_KV; a.nfull = nk[i] / ATT_KV;
-        a.pose_scratch = (rup(nk[i] + 1, 64) + 8 + 256) * 4;
-        REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
-    }
-    REQUIRE(grid < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)grid);
-    m.grid = (int)grid;
-    m.nwg_a = m.g[0].qblocks * heads * S1;
-    m.stages = 2;
-    for (int i = 0; i < 2; ++i) {
-        AttnMixedPlan::Group& a = m.g[i];
-        if (Sg[i] == 0) continue;
-        a.prefetch = (nk[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
-        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
-        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
-    }
-    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
-    out = m;
-    return 0;
-}
-#ifdef STA_TEST_HOOKS
 static void attn_mixed_plan_out(const AttnMixedPlan& m, int* out) {
     out[0] = m.stages; out[1] = m.lds_bytes; out[2] = m.grid; out[3] = m.nwg_a;
     for (int i = 0; i < 2; ++i) {
@@ -980,86 +987,6 @@ extern "C" int sta_debug_attn_mixed_block_map(int S1, int S2, int heads, int qbl
     }
     return 0;
 }
-#endif
-
-// out: [S1*nq_a patch rows | S1 pose rows | S2*nq_b patch rows | S2 pose rows] (decode_mixed_impl's row order), out.rp rows in all
-static int run_attn_mixed(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S1, int S2, int heads,
-                          int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift, hipStream_t st) {
-    if (h->dry) return 0;
-    const bool split = h->prec != STA_PREC_F16;
-    AttnMixedPlan m;
-    CHK(attn_mixed_plan(S1, S2, heads, nq_a, nk_a, nq_b, nk_b, split, h->opt[5] == 1, m));
-    h->last_attn_mixed = m;
-    const int nmax = std::max(std::max(nq_a, nk_a), S2 ? std::max(nq_b, nk_b) : 0);
-    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: two-group attention needs max(nq, nk) < npad, npad %% 64 == 0");
-    REQUIRE(kv_shift >= 0 && kv_shift < S1 + S2, "internal: kv_shift out of range");
-    const int64_t orows = (int64_t)S1 * (nq_a + 1) + (int64_t)S2 * (nq_b + 1);
-    REQUIRE(out.rp == orows && orows < ((int64_t)1 << 31), "internal: two-group attention output of %lld rows in planes of %lld", (long long)orows, (long long)out.rp);
-    AttnMixedParams mp; memset(&mp, 0, sizeof mp);
-    AttnParams& p = mp.a;
-    p.range = h->range;
-    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
-    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
-    p.S = S1 + S2; p.heads = heads; p.nq = nq_a; p.nk = nk_a; p.npad = qkv.npad; p.kv_shift = kv_shift;
-    p.scale_log2e = 0.125f * 1.44269504088896340736f;
-    p.pose = m.g[0].pose; p.prefetch = m.g[0].prefetch;
-    mp.b.S1 = S1;
-    mp.b.nq = S2 ? nq_b : nq_a; mp.b.nk = S2 ? nk_b : nk_a; mp.b.pose = S2 ? m.g[1].pose : m.g[0].pose; mp.b.prefetch = m.g[1].prefetch;
-    mp.b.orow0 = S1 * (nq_a + 1); mp.b.orows = (int)orows;
-    const dim3 grid((unsigned)m.grid);
-    if (split) {
-        static unsigned attr_done = 0;      // one bit per device
-        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_mixed_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
-        hipLaunchKernelGGL(attn_mixed_kernel<true>, grid, dim3(256), m.lds_bytes, st, mp);
-    } else {
-        STA_F16ONLY(hipLaunchKernelGGL(attn_mixed_kernel<false>, grid, dim3(256), m.lds_bytes, st, mp));
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------ per-sequence attention (decode_varlen_impl)
-// The plan of attn_varlen_kernel, pure like attn_plan: S <= ATT_MAX_SEQ sequences in the decoder's pose-token form, sequence s with
-// nq[s] queries over nk[s] keys (the caller resolves kv_shift: nk[s] is the count of the sequence s reads).  Per sequence exactly
-// attn_plan's rules on its own numbers - pose mode from its nq, tiles and tail from its nk, pose-query scratch from its nk -; the
-// prefetch decision uses the grid of the WHOLE launch and the launch carries the LDS of the hungriest sequence (attn_mixed_plan's
-// reasoning: 4 stages as soon as one sequence prefetches, the grid is <= 256 workgroups then).  Logical query-block ids and pose
-// blocks are handed out in sequence order; output rows are packed [nq patch rows | pose row] per sequence.  Sequences [0, S1) equal
-// and [S1, S) equal reduce to attn_mixed_plan field by field (tests/test_attention_varlen_plan.py).
-static_assert(ATT_MAX_SEQ == SEQ_MAX, "the attention table (attention.h) and the row table (elementwise.h) hold the same sequences of one call");
-static int attn_varlen_plan(int S, int heads, const int* nq, const int* nk, bool split, bool no_prefetch, AttnVarlenPlan& out) {
-    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && heads > 0 && nq && nk, "per-sequence attention takes 1 .. %d sequences", ATT_MAX_SEQ);
-    AttnVarlenPlan m{};
-    m.S = S;
-    int64_t nwg = 0, npose = 0, orows = 0;
-    for (int i = 0; i < S; ++i) {
-        REQUIRE(nq[i] > 0 && nk[i] > 0, "empty attention (sequence %d)", i);
-        AttnVarlenPlan::Seq& a = m.s[i];
-        a.nq = nq[i]; a.nk = nk[i];
-        a.pose = nq[i] % 128 != 0 ? 2 : 1;
-        a.pose_blocks = a.pose == 1 ? heads : 0;
-        a.qblocks = (nq[i] + (a.pose == 2 ? 1 : 0) + 127) / 128;
-        a.ntiles = (nk[i] + ATT_KV - 1) / ATT_KV; a.nfull = nk[i] / ATT_KV;
-        a.pose_scratch = (rup(nk[i] + 1, 64) + 8 + 256) * 4;
-        REQUIRE(a.pose_scratch <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
-        REQUIRE(nwg + npose < ((int64_t)1 << 30) && orows < ((int64_t)1 << 31) - nq[i] - 1, "attention launch too large");
-        a.blk0 = (int)nwg; a.pose_blk0 = (int)npose; a.orow0 = (int)orows;
-        nwg += (int64_t)a.qblocks * heads; npose += a.pose_blocks; orows += (int64_t)nq[i] + 1;
-    }
-    REQUIRE(nwg + npose < ((int64_t)1 << 31), "attention grid of %lld workgroups", (long long)(nwg + npose));
-    m.nwg = (int)nwg; m.pose_blocks = (int)npose; m.grid = (int)(nwg + npose); m.orows = (int)orows;
-    m.stages = 2;
-    for (int i = 0; i < S; ++i) {
-        AttnVarlenPlan::Seq& a = m.s[i];
-        a.prefetch = (nk[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
-        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
-        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
-    }
-    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
-    out = m;
-    return 0;
-}
-#ifdef STA_TEST_HOOKS
 static void attn_varlen_plan_out(const AttnVarlenPlan& m, int* out) {
     const int hd[7] = {m.S, m.stages, m.lds_bytes, m.grid, m.nwg, m.pose_blocks, m.orows};
     for (int j = 0; j < 7; ++j) out[j] = hd[j];
@@ -1069,12 +996,22 @@ static void attn_varlen_plan_out(const AttnVarlenPlan& m, int* out) {
         for (int j = 0; j < 11; ++j) out[7 + 11 * i + j] = v[j];
     }
 }
+// The workgroup -> (sequence, head, query block) map of attn_varlen_kernel's query-block workgroups under a plan, by the kernel's
+// arithmetic (attn_block_map, then the scan over the plan's first logical ids): out[3 * b + {0, 1, 2}] for workgroup b of the plan's nwg.
+static void attn_varlen_block_map_out(const AttnVarlenPlan& m, int heads, int* out) {
+    for (int b = 0; b < m.nwg; ++b) {
+        int logical = attn_block_map(b, m.nwg), s = 0;
+        for (int i = 1; i < m.S; ++i) if (m.s[i].blk0 <= logical) s = i;
+        logical -= m.s[s].blk0;
+        out[3 * b] = s; out[3 * b + 1] = (logical / m.s[s].qblocks) % heads; out[3 * b + 2] = logical % m.s[s].qblocks;
+    }
+}
 // out[7 + 11 * S] = {S, LDS stages, LDS bytes, grid, query-block workgroups, pose blocks, output rows, then per sequence {pose mode,
 // prefetch, pose blocks, query blocks, ntiles, nfull, tail stage, pose scratch bytes, first logical id, first pose block, first output row}}
 extern "C" int sta_debug_attn_varlen_plan(int S, int heads, const int* nq, const int* nk, int split, int no_prefetch, int* out) {
     REQUIRE(out, "bad argument");
     AttnVarlenPlan m;
-    CHK(attn_varlen_plan(S, heads, nq, nk, split != 0, no_prefetch != 0, m));
+    CHK(attn_varlen_plan(S, heads, nq, nk, true, split != 0, no_prefetch != 0, m));
     attn_varlen_plan_out(m, out);
     return 0;
 }
@@ -1083,108 +1020,18 @@ extern "C" int sta_debug_last_attn_varlen_plan(sta_handle* h, int* out) {
     attn_varlen_plan_out(h->last_attn_varlen, out);
     return 0;
 }
-// The workgroup -> (sequence, head, query block) map of attn_varlen_kernel's query-block workgroups by the kernel's arithmetic
-// (attn_block_map, then the scan over the plan's first logical ids): out[3 * b + {0, 1, 2}] for workgroup b of the plan's nwg.
 extern "C" int sta_debug_attn_varlen_block_map(int S, int heads, const int* nq, const int* nk, int* out) {
     REQUIRE(out, "bad argument");
     AttnVarlenPlan m;
-    CHK(attn_varlen_plan(S, heads, nq, nk, true, false, m));
-    for (int b = 0; b < m.nwg; ++b) {
-        int logical = attn_block_map(b, m.nwg), s = 0;
-        for (int i = 1; i < S; ++i) if (m.s[i].blk0 <= logical) s = i;
-        logical -= m.s[s].blk0;
-        out[3 * b] = s; out[3 * b + 1] = (logical / m.s[s].qblocks) % heads; out[3 * b + 2] = logical % m.s[s].qblocks;
-    }
+    CHK(attn_varlen_plan(S, heads, nq, nk, true, true, false, m));
+    attn_varlen_block_map_out(m, heads, out);
     return 0;
 }
-#endif
-
-static int launch_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int heads, const AttnVarlenPlan& m, int kv_shift, hipStream_t st);
-// out: [nq[s] patch rows | pose row] per sequence (decode_varlen_impl's row order), out.rp rows in all.  nq[s]: queries of sequence s;
-// nk[s]: the keys it reads, which are those of buffer sequence (s + kv_shift) % S.
-static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* nq, const int* nk, int kv_shift, hipStream_t st) {
-    if (h->dry) return 0;
-    const bool split = h->prec != STA_PREC_F16;
-    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && kv_shift >= 0 && kv_shift < S, "internal: per-sequence attention arguments");
-    int nmax = 0;
-    for (int s = 0; s < S; ++s) nmax = std::max(nmax, std::max(nq[s], nk[s]));
-    AttnVarlenPlan m;
-    CHK(attn_varlen_plan(S, heads, nq, nk, split, h->opt[5] == 1, m));
-    h->last_attn_varlen = m;
-    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: per-sequence attention needs max(n) < npad, npad %% 64 == 0");
-    return launch_attn_varlen(h, qkv, out, ldo, heads, m, kv_shift, st);
-}
-// attn_varlen_kernel under a plan: attn_varlen_plan's (the decoder's pose-token form) or attn_encv_plan's (the encoder's, pose = 0)
-static int launch_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int heads, const AttnVarlenPlan& m, int kv_shift, hipStream_t st) {
-    const bool split = h->prec != STA_PREC_F16;
-    const int S = m.S;
-    {
-    REQUIRE(out.rp == m.orows, "internal: per-sequence attention output of %d rows in planes of %lld", m.orows, (long long)out.rp);
-    AttnVarlenParams vp; memset(&vp, 0, sizeof vp);
-    AttnParams& p = vp.a;
-    p.range = h->range;
-    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
-    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
-    p.S = S; p.heads = heads; p.npad = qkv.npad; p.kv_shift = kv_shift;
-    p.scale_log2e = 0.125f * 1.44269504088896340736f;
-    vp.nwg = m.nwg; vp.npose_blocks = m.pose_blocks; vp.orows = m.orows;
-    for (int s = 0; s < S; ++s) {
-        const AttnVarlenPlan::Seq& a = m.s[s];
-        vp.seq[s] = AttnSeq{a.nq, a.nk, a.pose, a.prefetch, a.blk0, a.pose_blk0, a.orow0, 0};
-    }
-    const dim3 grid((unsigned)m.grid);
-    if (split) {
-        static unsigned attr_done = 0;      // one bit per device
-        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)attn_varlen_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
-        hipLaunchKernelGGL(attn_varlen_kernel<true>, grid, dim3(256), m.lds_bytes, st, vp);
-    } else {
-        STA_F16ONLY(hipLaunchKernelGGL(attn_varlen_kernel<false>, grid, dim3(256), m.lds_bytes, st, vp));
-    }
-    HIPCHK(hipGetLastError());
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------ per-sequence attention, encoder form (encode_varlen_impl)
-// attn_varlen_kernel on the ENCODER's buffers: sequence s is n[s] queries over its own n[s] keys, no pose token anywhere - pose = 0
-// for every sequence, no pose blocks, no pose scratch, and npad may EQUAL n[s] (the decoder's form reads token index nk as the pose
-// key: here that is row 0 of the next head, or the end of the buffer).  Per sequence attn_plan(pose = false)'s rules on its own count;
-// the prefetch decision uses the grid of the whole launch and the launch carries the LDS of the hungriest sequence, as in
-// attn_varlen_plan.  Output rows packed [n[s]] per sequence: orow0 = the prefix sum of n.  All sequences equal reduces to
-// attn_plan(S, heads, n, n, pose = false) field by field (tests/test_encode_varlen_cpu.py).
-static int attn_encv_plan(int S, int heads, const int* n, bool split, bool no_prefetch, AttnVarlenPlan& out) {
-    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && heads > 0 && n, "per-sequence attention takes 1 .. %d sequences", ATT_MAX_SEQ);
-    AttnVarlenPlan m{};
-    m.S = S;
-    int64_t nwg = 0, orows = 0;
-    for (int i = 0; i < S; ++i) {
-        REQUIRE(n[i] > 0, "empty attention (sequence %d)", i);
-        AttnVarlenPlan::Seq& a = m.s[i];
-        a.nq = a.nk = n[i];
-        a.qblocks = (n[i] + 127) / 128;
-        a.ntiles = (n[i] + ATT_KV - 1) / ATT_KV; a.nfull = n[i] / ATT_KV;
-        REQUIRE(nwg < ((int64_t)1 << 30) && orows < ((int64_t)1 << 31) - n[i], "attention launch too large");
-        a.blk0 = (int)nwg; a.orow0 = (int)orows;
-        nwg += (int64_t)a.qblocks * heads; orows += n[i];
-    }
-    m.nwg = m.grid = (int)nwg; m.orows = (int)orows;
-    m.stages = 2;
-    for (int i = 0; i < S; ++i) {
-        AttnVarlenPlan::Seq& a = m.s[i];
-        a.prefetch = (n[i] <= ATT_PREFETCH_TILES * ATT_KV && m.grid <= 256 && !no_prefetch) ? 1 : 0;
-        if (a.prefetch) m.stages = ATT_PREFETCH_TILES;
-        a.tail_stage = a.nfull == a.ntiles ? -1 : (a.prefetch ? a.nfull : (a.nfull & 1));
-    }
-    m.lds_bytes = split ? attn_smem_bytes<true>(m.stages) : attn_smem_bytes<false>(m.stages);
-    out = m;
-    return 0;
-}
-#ifdef STA_TEST_HOOKS
-// out[7 + 11 * S]: the record of sta_debug_attn_varlen_plan (pose mode, pose blocks, pose scratch and first pose block are 0 here)
+// the encoder form (pose mode, pose blocks, pose scratch and first pose block are 0 in the record)
 extern "C" int sta_debug_attn_encv_plan(int S, int heads, const int* n, int split, int no_prefetch, int* out) {
     REQUIRE(out, "bad argument");
     AttnVarlenPlan m;
-    CHK(attn_encv_plan(S, heads, n, split != 0, no_prefetch != 0, m));
+    CHK(attn_varlen_plan(S, heads, n, n, false, split != 0, no_prefetch != 0, m));
     attn_varlen_plan_out(m, out);
     return 0;
 }
@@ -1193,20 +1040,103 @@ extern "C" int sta_debug_last_attn_encv_plan(sta_handle* h, int* out) {
     attn_varlen_plan_out(h->last_attn_encv, out);
     return 0;
 }
-// The workgroup -> (sequence, head, query block) map under attn_encv_plan, by the kernel's arithmetic: out[3 * b + {0, 1, 2}]
 extern "C" int sta_debug_attn_encv_block_map(int S, int heads, const int* n, int* out) {
     REQUIRE(out, "bad argument");
     AttnVarlenPlan m;
-    CHK(attn_encv_plan(S, heads, n, true, false, m));
-    for (int b = 0; b < m.nwg; ++b) {
-        int logical = attn_block_map(b, m.nwg), s = 0;
-        for (int i = 1; i < S; ++i) if (m.s[i].blk0 <= logical) s = i;
-        logical -= m.s[s].blk0;
-        out[3 * b] = s; out[3 * b + 1] = (logical / m.s[s].qblocks) % heads; out[3 * b + 2] = logical % m.s[s].qblocks;
-    }
+    CHK(attn_varlen_plan(S, heads, n, n, false, true, false, m));
+    attn_varlen_block_map_out(m, heads, out);
     return 0;
 }
 #endif
+
+// ------------------------------------------------------------------------------------------ attention launch
+// the fields of AttnParams every launch fills the same way (the caller memsets the whole params struct first)
+static void attn_params(sta_handle* h, AttnParams& p, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, int kv_shift) {
+    p.range = h->range;
+    p.Q_hi = qkv.q.hi; p.Q_lo = qkv.q.lo; p.K_hi = qkv.k.hi; p.K_lo = qkv.k.lo; p.Vt_hi = qkv.vt.hi; p.Vt_lo = qkv.vt.lo;
+    p.O_hi = out.hi; p.O_lo = out.lo; p.ldo = ldo;
+    p.S = S; p.heads = heads; p.npad = qkv.npad; p.kv_shift = kv_shift;
+    p.scale_log2e = 0.125f * 1.44269504088896340736f;
+}
+// K names one attention kernel: K::fn<SPLIT>() is its instantiation (so that a -DSTA_DEV_FAST build never names the f16 one)
+struct AttnK { template <bool SPLIT> static auto fn() { return &attn_kernel<SPLIT>; } };
+struct AttnMixedK { template <bool SPLIT> static auto fn() { return &attn_mixed_kernel<SPLIT>; } };
+struct AttnVarlenK { template <bool SPLIT> static auto fn() { return &attn_varlen_kernel<SPLIT>; } };
+template <class K, class P>
+static int launch_attn(sta_handle* h, int grid, int lds_bytes, const P& p, hipStream_t st) {
+    if (h->prec != STA_PREC_F16) {
+        const auto kernel = K::template fn<true>();
+        static unsigned attr_done = 0;      // one bit per device (one set per kernel: the static belongs to this instantiation)
+        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds_bytes, st, p);
+    } else {
+        STA_F16ONLY(hipLaunchKernelGGL(K::template fn<false>(), dim3((unsigned)grid), dim3(256), lds_bytes, st, p));
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static int run_attn(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads,
+                    int nq, int nk, int kv_shift, hipStream_t st, bool pose = false) {
+    if (h->dry) return 0;
+    REQUIRE(!pose || (nq == nk && nq + 1 <= qkv.npad), "internal: pose-token attention needs nq == nk < npad");
+    AttnPlan a;
+    CHK(attn_plan(S, heads, nq, nk, pose, h->prec != STA_PREC_F16, h->opt[5] == 1, a));
+    h->last_attn = a;
+    REQUIRE(!pose || (int64_t)(qkv.npad + 8 + 256) * 4 <= attn_smem_bytes<false>(), "internal: pose-query scratch exceeds the LDS allocation");
+    REQUIRE(!pose || qkv.npad % 64 == 0, "internal: pose-query path needs npad % 64 == 0");
+    AttnParams p; memset(&p, 0, sizeof p);
+    attn_params(h, p, qkv, out, ldo, S, heads, kv_shift);
+    p.nq = nq; p.nk = nk; p.pose = a.pose; p.prefetch = a.prefetch;
+    return launch_attn<AttnK>(h, a.grid, a.lds_bytes, p, st);
+}
+
+// out: [S1*nq_a patch rows | S1 pose rows | S2*nq_b patch rows | S2 pose rows] (decode_mixed_impl's row order), out.rp rows in all
+static int run_attn_mixed(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S1, int S2, int heads,
+                          int nq_a, int nk_a, int nq_b, int nk_b, int kv_shift, hipStream_t st) {
+    if (h->dry) return 0;
+    AttnMixedPlan m;
+    CHK(attn_mixed_plan(S1, S2, heads, nq_a, nk_a, nq_b, nk_b, h->prec != STA_PREC_F16, h->opt[5] == 1, m));
+    h->last_attn_mixed = m;
+    const int nmax = std::max(std::max(nq_a, nk_a), S2 ? std::max(nq_b, nk_b) : 0);
+    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: two-group attention needs max(nq, nk) < npad, npad %% 64 == 0");
+    REQUIRE(kv_shift >= 0 && kv_shift < S1 + S2, "internal: kv_shift out of range");
+    const int64_t orows = (int64_t)S1 * (nq_a + 1) + (int64_t)S2 * (nq_b + 1);
+    REQUIRE(out.rp == orows && orows < ((int64_t)1 << 31), "internal: two-group attention output of %lld rows in planes of %lld", (long long)orows, (long long)out.rp);
+    AttnMixedParams mp; memset(&mp, 0, sizeof mp);
+    attn_params(h, mp.a, qkv, out, ldo, S1 + S2, heads, kv_shift);
+    mp.a.nq = nq_a; mp.a.nk = nk_a; mp.a.pose = m.g[0].pose; mp.a.prefetch = m.g[0].prefetch;
+    mp.b.S1 = S1;
+    mp.b.nq = S2 ? nq_b : nq_a; mp.b.nk = S2 ? nk_b : nk_a; mp.b.pose = S2 ? m.g[1].pose : m.g[0].pose; mp.b.prefetch = m.g[1].prefetch;
+    mp.b.orow0 = S1 * (nq_a + 1); mp.b.orows = (int)orows;
+    return launch_attn<AttnMixedK>(h, m.grid, m.lds_bytes, mp, st);
+}
+
+// attn_varlen_kernel under a plan of either form
+static int launch_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int heads, const AttnVarlenPlan& m, int kv_shift, hipStream_t st) {
+    REQUIRE(out.rp == m.orows, "internal: per-sequence attention output of %d rows in planes of %lld", m.orows, (long long)out.rp);
+    AttnVarlenParams vp; memset(&vp, 0, sizeof vp);
+    attn_params(h, vp.a, qkv, out, ldo, m.S, heads, kv_shift);
+    vp.nwg = m.nwg; vp.npose_blocks = m.pose_blocks; vp.orows = m.orows;
+    for (int s = 0; s < m.S; ++s) {
+        const AttnVarlenPlan::Seq& a = m.s[s];
+        vp.seq[s] = AttnSeq{a.nq, a.nk, a.pose, a.prefetch, a.blk0, a.pose_blk0, a.orow0, 0};
+    }
+    return launch_attn<AttnVarlenK>(h, m.grid, m.lds_bytes, vp, st);
+}
+// out: [nq[s] patch rows | pose row] per sequence (decode_varlen_impl's row order), out.rp rows in all.  nq[s]: queries of sequence s;
+// nk[s]: the keys it reads, which are those of buffer sequence (s + kv_shift) % S.
+static int run_attn_varlen(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* nq, const int* nk, int kv_shift, hipStream_t st) {
+    if (h->dry) return 0;
+    REQUIRE(S > 0 && S <= ATT_MAX_SEQ && kv_shift >= 0 && kv_shift < S, "internal: per-sequence attention arguments");
+    int nmax = 0;
+    for (int s = 0; s < S; ++s) nmax = std::max(nmax, std::max(nq[s], nk[s]));
+    AttnVarlenPlan m;
+    CHK(attn_varlen_plan(S, heads, nq, nk, true, h->prec != STA_PREC_F16, h->opt[5] == 1, m));
+    h->last_attn_varlen = m;
+    REQUIRE(nmax + 1 <= qkv.npad && qkv.npad % 64 == 0, "internal: per-sequence attention needs max(n) < npad, npad %% 64 == 0");
+    return launch_attn_varlen(h, qkv, out, ldo, heads, m, kv_shift, st);
+}
 // out: [n[s] rows] per sequence, packed (encode_varlen_impl's row order), out.rp = sum(n) rows
 static int run_attn_encv(sta_handle* h, const QKVOut& qkv, const Planes& out, int ldo, int S, int heads, const int* n, hipStream_t st) {
     if (h->dry) return 0;
@@ -1214,7 +1144,7 @@ static int run_attn_encv(sta_handle* h, const QKVOut& qkv, const Planes& out, in
     int nmax = 0;
     for (int s = 0; s < S; ++s) nmax = std::max(nmax, n[s]);
     AttnVarlenPlan m;
-    CHK(attn_encv_plan(S, heads, n, h->prec != STA_PREC_F16, h->opt[5] == 1, m));
+    CHK(attn_varlen_plan(S, heads, n, n, false, h->prec != STA_PREC_F16, h->opt[5] == 1, m));
     h->last_attn_encv = m;
     REQUIRE(nmax <= qkv.npad && qkv.npad % 64 == 0, "internal: encoder per-sequence attention needs max(n) <= npad, npad %% 64 == 0");
     return launch_attn_varlen(h, qkv, out, ldo, heads, m, 0, st);

@@ -1047,8 +1047,7 @@ extern "C" int sta_regress_views_tokens_begin(sta_handle* h, const float* feat_i
         HIPCHK(hipEventCreateWithFlags(&h->cur->rv_ev, hipEventDisableTiming));
         h->n_alloc += 2;
     }
-    struct Scope { sta_handle* h; ~Scope() { h->rope_foreign = false; h->rope_pos = nullptr; h->rope_ident = nullptr; } } scope{h};
-    h->rope_foreign = true;
+    RopeForeign scope(h);
     // one plan for both phases (phase B sized for k accepted edges), then phase A runs
     int r = plan_and_run(h, st, [&](Bump& ws) -> int {
         if (h->dry) {
