@@ -320,6 +320,19 @@ STA_API int sta_debug_up2_varlen(sta_handle* h, const float* x, int B, const int
  * (entry, y0, x0), tiles of 8 rows x 32 pixels of one entry, decoded by the function the kernel uses; -1 when cap is too small. */
 STA_API int sta_debug_dpt_varlen_plan(int B, const int* hp, const int* wp, long long* off, int* hw, int* ntiles, int* tiles, int cap);
 
+/* Workspace independence (tests/test_workspace_gpu.py).  The product entry points run on whatever the previous call on the stream left
+ * in its scratch context (workspace, the two split-K scratches, the side lane's scratch); their outputs must not depend on it.
+ * sta_debug_workspace_fill: enqueue `byte` (0 .. 255) over ALL of that scratch on `stream`; -1 when the stream has no context yet or a
+ * split-phase scheduler call (sta_regress_views[_tokens]_begin) is pending on it.
+ * sta_debug_workspace_info: out[0] workspace capacity, out[1] the planned peak of the last call on the context, out[2] / [3] / [4] bytes
+ * of the split-K scratch, the slab scratch and the side lane's scratch (0: not allocated), out[5] 1 while a split-phase call is
+ * pending, out[6], out[7] 0.
+ * sta_debug_workspace_tail: the bytes of workspace [planned peak + 4096, capacity) that differ from `byte`: their number and the
+ * offset of the first (-1: none).  Runs on `stream` and synchronises it; touches nothing inside the workspace. */
+STA_API int sta_debug_workspace_fill(sta_handle* h, void* stream, int byte);
+STA_API int sta_debug_workspace_info(sta_handle* h, void* stream, int64_t out[8]);
+STA_API int sta_debug_workspace_tail(sta_handle* h, void* stream, int byte, int64_t* n_bad, int64_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

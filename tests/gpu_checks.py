@@ -854,3 +854,27 @@ def range_rope(precision, entry, bufs, pos, pos_max, **kw):
         fn = lambda: _lib.check(lib.sta_debug_rope_varlen(h, ptrs, len(d), kw["S"], kw["heads"], n, table.data_ptr(), pos_max, st()))
     _, rng = with_range(m, fn)
     return [t.cpu().numpy() for t in d], rng
+
+
+# ---- tests/test_workspace_gpu.py: the scratch of the CURRENT stream's context of a frontend on the test-hooks library
+def workspace_fill_rc(m, byte):
+    """sta_debug_workspace_fill on the current stream -> the return code (0, or -1 with the message in sta_last_error)."""
+    return m.lib.sta_debug_workspace_fill(m._h, m._stream(), int(byte))
+
+
+def workspace_fill(m, byte):
+    _lib.check(workspace_fill_rc(m, byte))
+
+
+def workspace_info(m):
+    """-> {"ws_cap", "plan_peak", "skbuf", "slab", "side_skbuf" (bytes), "pending"} of the current stream's context."""
+    out = (C.c_int64 * 8)()
+    _lib.check(m.lib.sta_debug_workspace_info(m._h, m._stream(), out))
+    return dict(zip(("ws_cap", "plan_peak", "skbuf", "slab", "side_skbuf", "pending"), (int(v) for v in out)))
+
+
+def workspace_tail(m, byte):
+    """-> (bytes of workspace [planned peak + 4096, capacity) that differ from `byte`, offset of the first or -1).  Synchronises."""
+    n_bad, first = C.c_int64(0), C.c_int64(0)
+    _lib.check(m.lib.sta_debug_workspace_tail(m._h, m._stream(), int(byte), C.byref(n_bad), C.byref(first)))
+    return int(n_bad.value), int(first.value)

@@ -175,6 +175,9 @@ TEST_SIGNATURES = {
     "sta_debug_convt_varlen": (_i, [_vp, _fp, _fp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _fp, _vp, _vp]),
     "sta_debug_up2_varlen": (_i, [_vp, _fp, _i, C.POINTER(_i), C.POINTER(_i), _i, C.POINTER(_i), C.POINTER(_i), _fp, _vp, _vp]),
     "sta_debug_dpt_varlen_plan": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i]),
+    "sta_debug_workspace_fill": (_i, [_vp, _vp, _i]),
+    "sta_debug_workspace_info": (_i, [_vp, _vp, C.POINTER(_i64)]),
+    "sta_debug_workspace_tail": (_i, [_vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
 _lib = None

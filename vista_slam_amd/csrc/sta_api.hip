@@ -94,10 +94,17 @@ static const int64_t SKBUF_ELEMS = (int64_t)4 << 20;   // 16 MiB: M*N of the lar
 // stream it has been called on (stream_ctx), so calls enqueued on DIFFERENT streams never share scratch memory and may run
 // concurrently on the GPU - e.g. sta_encode of keyframe i+1 on a second stream under sta_regress_views of keyframe i
 // (independent in OnlineSLAM.step: slam.py:258 vs :263-277).  Weights, tables and the zero page are read-only and shared.
+//
+// THE WORKSPACE CONTRACT.  The bytes of ws, skbuf, slab and side_skbuf are whatever the previous call on this stream left there (or
+// what hipMalloc returned): no call may read a byte of them that it has not itself written earlier in the same call, unless its
+// outputs cannot depend on the value read - not as 0 * stale either, since stale bits may be NaN or Inf.  And no call writes behind
+// the peak its own dry pass planned (plus the 4096 bytes of slack plan_and_run adds).  tests/test_workspace_gpu.py fills all four
+// buffers with 0x00 / 0xFF / 0x3C / 0x7B in front of every product entry point and demands bit-identical outputs and an untouched tail.
 static const int MAX_STREAM_CTX = 8;
 struct StreamCtx {
     hipStream_t st = nullptr; uint64_t last_use = 0;      // last_use: the handle's use_clock at the latest call (recycling order)
     char* ws = nullptr; int64_t ws_cap = 0;   // bump-allocated workspace, sized by the dry planning pass of the call
+    int64_t plan_peak = 0;    // the planned peak of the last call on this context (plan_and_run; read by sta_debug_workspace_info / _tail)
     float* skbuf = nullptr;   // fp32 partial sums of split-K GEMMs with the plane / QKV epilogue (SKBUF_ELEMS floats)
     float* slab = nullptr;    // slab split-K of the small-M in-place residual GEMMs (GemmParams::slab), same size
     // split-phase keyframe scheduler (sta_regress_views_begin / _finish): the call pending on this stream
@@ -681,6 +688,7 @@ static int plan_and_run(sta_handle* h, hipStream_t st, F&& body) {
     h->dry = false;
     if (r != 0) return r;
     CHK(ensure_ws(h, plan.peak + 4096, st));
+    h->cur->plan_peak = plan.peak;
     if (h->reserve_only) return ensure_side(h);      // sta_reserve: the plan is allocated (and the side lane with it), nothing runs
     Bump ws = cur_bump(h);
     return body(ws);

@@ -981,3 +981,74 @@ extern "C" int sta_debug_dpt_varlen_plan(int B, const int* hp, const int* wp, lo
     }
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------ workspace independence (tests/test_workspace_gpu.py)
+// The product entry points run on whatever the previous call left in the stream's scratch (StreamCtx: the workspace contract).  These
+// hooks let a test put a known byte pattern there in front of a call, and look behind the call's planned peak afterwards.
+static StreamCtx* dbg_find_ctx(sta_handle* h, hipStream_t st) {
+    for (auto& c : h->ctx) if (c.st == st) return &c;
+    return nullptr;
+}
+// bytes of ws[lo, hi) that differ from `byte`: res[0] += their number, res[1] = min of their offsets
+__global__ void dbg_tail_scan_kernel(const unsigned char* ws, int64_t lo, int64_t hi, unsigned char byte, unsigned long long* res) {
+    for (int64_t i = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < hi; i += (int64_t)gridDim.x * blockDim.x)
+        if (ws[i] != byte) { atomicAdd(&res[0], 1ull); atomicMin(&res[1], (unsigned long long)i); }
+}
+
+// `byte` into every byte of the scratch of `stream`'s context: ws[0, ws_cap), skbuf, slab and (where allocated) side_skbuf, enqueued
+// on `stream`.  Fails when the stream has no context yet, or a split-phase scheduler call is pending on it (phase B reads phase A's
+// workspace: filling it there would break a call that keeps the contract).
+extern "C" int sta_debug_workspace_fill(sta_handle* h, void* stream, int byte) {
+    REQUIRE(h && byte >= 0 && byte <= 255, "sta_debug_workspace_fill: bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    StreamCtx* c = dbg_find_ctx(h, st);
+    REQUIRE(c, "sta_debug_workspace_fill: this stream has no scratch context (no call has run on it)");
+    REQUIRE(!c->rv_open, "sta_debug_workspace_fill: a split-phase scheduler call is pending on this stream (its workspace is live until _finish)");
+    if (c->ws && c->ws_cap > 0) HIPCHK(hipMemsetAsync(c->ws, byte, (size_t)c->ws_cap, st));
+    if (c->skbuf) HIPCHK(hipMemsetAsync(c->skbuf, byte, (size_t)SKBUF_ELEMS * 4, st));
+    if (c->slab) HIPCHK(hipMemsetAsync(c->slab, byte, (size_t)SKBUF_ELEMS * 4, st));
+    if (c->side_skbuf) HIPCHK(hipMemsetAsync(c->side_skbuf, byte, (size_t)SKBUF_ELEMS * 4, st));
+    return 0;
+}
+
+// out[0] ws_cap, out[1] the planned peak of the last plan_and_run call on the context, out[2] / [3] / [4] bytes of skbuf / slab /
+// side_skbuf (0: not allocated), out[5] 1 while a split-phase scheduler call is pending, out[6] / [7] 0.
+extern "C" int sta_debug_workspace_info(sta_handle* h, void* stream, int64_t out[8]) {
+    REQUIRE(h && out, "sta_debug_workspace_info: bad argument");
+    StreamCtx* c = dbg_find_ctx(h, (hipStream_t)stream);
+    REQUIRE(c, "sta_debug_workspace_info: this stream has no scratch context (no call has run on it)");
+    out[0] = c->ws_cap; out[1] = c->plan_peak;
+    out[2] = c->skbuf ? SKBUF_ELEMS * 4 : 0; out[3] = c->slab ? SKBUF_ELEMS * 4 : 0; out[4] = c->side_skbuf ? SKBUF_ELEMS * 4 : 0;
+    out[5] = c->rv_open ? 1 : 0; out[6] = out[7] = 0;
+    return 0;
+}
+
+// The bytes of ws[planned peak + 4096, ws_cap) that differ from `byte` (ensure_ws is asked for peak + 4096: that slack belongs to the
+// call): *n_bad their number, *first_bad the offset of the first one in ws (-1: none).  One scan kernel on `stream` with a 16-byte
+// result of its own (not from the workspace); synchronises the stream.
+extern "C" int sta_debug_workspace_tail(sta_handle* h, void* stream, int byte, int64_t* n_bad, int64_t* first_bad) {
+    REQUIRE(h && n_bad && first_bad && byte >= 0 && byte <= 255, "sta_debug_workspace_tail: bad argument");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    StreamCtx* c = dbg_find_ctx(h, st);
+    REQUIRE(c, "sta_debug_workspace_tail: this stream has no scratch context (no call has run on it)");
+    const int64_t lo = c->plan_peak + 4096, hi = c->ws_cap;
+    *n_bad = 0; *first_bad = -1;
+    if (!c->ws || lo >= hi) return 0;
+    unsigned long long* res = nullptr;
+    unsigned long long host[2] = {0ull, ~0ull};
+    HIPCHK(hipMalloc((void**)&res, 16));
+    hipError_t e = hipMemcpyAsync(res, host, 16, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        int64_t blocks = (hi - lo + 255) / 256; if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(dbg_tail_scan_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const unsigned char*)c->ws, lo, hi, (unsigned char)byte, res);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(host, res, 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(res);
+    if (e != hipSuccess) return set_err("sta_debug_workspace_tail failed: %s", hipGetErrorString(e));
+    *n_bad = (int64_t)host[0]; *first_bad = host[0] ? (int64_t)host[1] : -1;
+    return 0;
+}
