@@ -589,6 +589,76 @@ STA_API int sta_flow_track(sta_handle* h, const uint8_t* prev_pyramid, const uin
                            int max_level, const float* pts, const int32_t* n_dev, int n_cap, int max_iter, double eps, double min_eig,
                            float* next_pts, uint8_t* status, double* stats, void* stream);
 
+/* Loop candidates: ORB keypoints and descriptors, a bag-of-words vector from a vocabulary tree, L1 scores against the earlier
+ * keyframes (vista_slam/loop_detector.py:14-50, which calls cv2.ORB_create().detectAndCompute and DBoW3 on the CPU).  The contract
+ * RESTATES the documented algorithms in integer and float64 terms; the yardstick is the numpy restatement tests/loop_cases.py, it is
+ * NOT cv2 / DBoW3.  Stated differences from cv2: 1-degree angle bins (fastAtan2 there); the integer Harris order (float32 there);
+ * the blur kernel below (cv2's fixed-point Gaussian there); 11-bit bilinear resizing (INTER_LINEAR_EXACT there); no tie extension at
+ * the second cut (retainBest there); and the comparison table is the caller's (OpenCV's learned 256 pairs are not part of this library).
+ * Frame, uint8 conversion and reflect-101 are the keyframe gate's (above).  Limits: nlevels in [1, 8], nfeatures in [1, 4096], edge
+ * in [22, 64], fast_threshold in [1, 254], H and W > 2 edge, H * W <= 2^21.
+ * Scales and sizes (float64, every step one IEEE operation in the order written): s_0 = 1, s_(l+1) = s_l * 1.2; level l has size
+ * (rint(H / s_l), rint(W / s_l)); a level whose height or width is <= 2 edge holds no keypoints and is not built (nor is any level
+ * above it).  Features per level: f = 1 / 1.2, fp = f multiplied nlevels times into 1, nd = (nfeatures * (1 - f)) / (1 - fp); for
+ * l < nlevels - 1: n_l = rint(nd), then nd = nd * f; the last level gets max(nfeatures - sum, 0).  The outputs hold
+ * rows = max(nfeatures, sum of n_l) rows (the rounded counts can exceed nfeatures by a few).
+ * Level l from level l - 1, bilinear: fx = (x + 0.5) * (W_(l-1) / W_l) - 0.5, sx = floor(fx), a = fx - sx; sx < 0 -> (0, 0);
+ * sx >= W_(l-1) - 1 -> (W_(l-1) - 1, 0); c1 = rint(a * 2048), c0 = 2048 - c1, the same for y; pixel = (sum cy cx p + 2^21) >> 22.
+ * FAST-9 on the unblurred level, for pixels at least 3 from the border: ring = the 16 Bresenham offsets at radius 3 from (0, -3)
+ * clockwise; A = the maximum over the 16 contiguous arcs of 9 of the minimum over the arc of p - ring, Bm the same with ring - p;
+ * score = max(A, Bm) - 1; a pixel is a corner iff score >= fast_threshold, a non-corner has score 0.  A corner survives iff its
+ * score is STRICTLY greater than its 8 neighbours' scores (ties drop both); only survivors with edge <= x < W_l - edge and
+ * edge <= y < H_l - edge go on.  First cut: if more than 2 n_l survive, every survivor whose score is >= the score of the 2 n_l-th
+ * largest is kept (ties kept).  Harris on the 7x7 block of the unblurred level centred on the keypoint: Ix = 2 (I(x+1,y) - I(x-1,y))
+ * + (I(x+1,y-1) - I(x-1,y-1)) + (I(x+1,y+1) - I(x-1,y+1)), Iy its transpose, a = sum Ix^2, b = sum Iy^2, c = sum Ix Iy,
+ * R = 25 (a b - c^2) - (a + b)^2 in int64 (k = 0.04 exactly, OpenCV's positive scale dropped).  Order: R descending, then
+ * y * W_l + x ascending; the first n_l are kept, with no tie extension.  Output rows are level-major, in that order within a level;
+ * their number goes to *n_out (device), rows at or past it are not written.
+ * Orientation on the unblurred level: m10 = sum u I, m01 = sum v I over |v| <= 15, |u| <= umax[|v|], umax = {15,15,15,15,14,14,14,
+ * 13,13,12,11,10,9,8,6,3}.  The angle is one of 360 one-degree bins, found with integers from the caller's table
+ * trig int32 [720,2] = rint(2^30 (cos, sin)(j * 0.5 degrees)) - the library contains no trigonometry: with d_k = trig[(2k - 1) mod
+ * 720] and cross(d, m) = d.x m.y - d.y m.x (int64, m = (m10, m01)), the bin is the smallest k with cross(d_k, m) >= 0 and
+ * cross(d_(k+1), m) < 0; bin 0 for m = 0 (and if no k qualifies).
+ * Blur per level: B = (sum_ab k[a] k[b] ext(y + a - 3, x + b - 3) + 2^15) >> 16, k = {18,33,49,56,49,33,18}, reflect-101.
+ * Descriptor: pattern int8 [256,4] rows (x1, y1, x2, y2), every |value| <= 13 (the caller's to hold; a read is clamped into the
+ * level, so a table that breaks the rule cannot read outside it); with (C, S) = trig[2 bin]: rx = (x C - y S + 2^29) >> 30,
+ * ry = (x S + y C + 2^29) >> 30 (arithmetic shift = floor); bit i = B(kp + r(x1,y1)) < B(kp + r(x2,y2)), stored in byte i / 8 at
+ * bit i % 8.  With edge >= 22 no read leaves the level.
+ * sta_orb_plan (host only, no GPU): out = {nlevels, built levels, h[8], w[8], n_l[8], byte offset[8] of a built level in a plane (-1:
+ * not built), plane bytes, extraction workspace_bytes, rows, sta_bow_transform's workspace_bytes for `rows` descriptors, 0, 0}.
+ * Returns -1, with the numbers in sta_last_error(), for a parameter outside the limits above.
+ * sta_orb_extract: image uint8 [H,W] (dtype 0) or fp32 [H,W] (dtype 1); trig, pattern, workspace (8-byte aligned, contents free)
+ * on the device.  After the call the workspace begins with the plane of the levels and, plane bytes further, the plane of the blurred
+ * levels (each built level at its byte offset); the rest of it is scratch.  Outputs (device): kp int32 [rows,4] = (x, y, level, angle bin) in the level's own pixels, resp int64 [rows] = R,
+ * desc uint8 [rows,32], n_out int32.
+ *
+ * Vocabulary: a k-ary tree, k <= 64, depth <= 10: node_desc uint8 [n,32], child_first int32 [n], child_count int32 [n], word_of
+ * int32 [n] (-1 for an inner node), word_weight float64 [n_words]; node 0 is the root, siblings are contiguous, children follow
+ * their parent (child_first > the parent's index), a leaf may sit at any depth.
+ * sta_bow_transform(desc [n_cap,32], n_dev): n = min(*n_dev, n_cap) (n_cap when n_dev is null).  Per descriptor, from the root: at
+ * each node the child with the smallest Hamming distance, the first among equals; at a leaf its word w, dropped when
+ * word_weight[w] <= 0.  The vector = the distinct words in ascending order with count_w (int32) and val_w = count_w * weight_w (one
+ * float64 multiply), divided by its L1 norm (DBoW's mustNormalize path for L1 scoring); the norm is summed in an order that depends
+ * on the number of words alone.  Outputs (device): words, counts int32 [n_cap], vals float64 [n_cap], n_words int32; entries at or
+ * past n_words are not written; an empty vector is a result (n_words = 0).  workspace: 4 n_cap bytes.  n_cap in [1, 4104].
+ * sta_bow_score: sim[e] float64 = -0.5 * sum over the words common to the query and row rows[e] of the database of
+ * (|a - b| - |a|) - |b|  (DBoW's L1 score), e < m, one launch, a fixed summation order: two runs are bit-identical.  The query is
+ * (q_words, q_vals, q_n) as sta_bow_transform writes them, in arrays of q_cap entries: min(*q_n, q_cap) words are read, whatever the
+ * database's cap is (the two capacities are independent, both in [1, 4104]); the database is db_words int32 [max_views,cap], db_vals float64
+ * [max_views,cap], db_n int32 [max_views], rows int32 [m] - all on the device; a row index outside [0, max_views) scores 0.
+ * None of the three device calls allocates, copies to the host or synchronises. */
+STA_API int sta_orb_plan(int H, int W, int nfeatures, int nlevels, int fast_threshold, int edge, int64_t out[40]);
+STA_API int sta_orb_extract(sta_handle* h, const void* image, int dtype /*0 uint8, 1 float32*/, int H, int W, int nfeatures, int nlevels,
+                            int fast_threshold, int edge, const int32_t* trig, const int8_t* pattern, void* workspace, int64_t workspace_bytes,
+                            int32_t* kp, int64_t* resp, uint8_t* desc, int32_t* n_out, void* stream);
+STA_API int sta_bow_transform(sta_handle* h, const uint8_t* desc, const int32_t* n_dev, int n_cap, const uint8_t* node_desc,
+                              const int32_t* child_first, const int32_t* child_count, const int32_t* word_of, const double* word_weight,
+                              int n_nodes, int n_words, void* workspace, int64_t workspace_bytes, int32_t* words, int32_t* counts, double* vals,
+                              int32_t* n_words_out, void* stream);
+STA_API int sta_bow_score(sta_handle* h, const int32_t* q_words, const double* q_vals, const int32_t* q_n, int q_cap,
+                          const int32_t* db_words, const double* db_vals, const int32_t* db_n, int max_views, int cap, const int32_t* rows, int m,
+                          double* sim, void* stream);
+
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one
  * batched launch sequence instead of k sequential B=1 calls, with the reference's early reject kept:

@@ -20,7 +20,9 @@ def install_as_reference():
 
     Only the two module names of that import path are registered in `sys.modules` (a stub package `vista_slam.sta_model` whose
     one member is the stub module `vista_slam.sta_model.sta_model`); the reference's own `vista_slam` package, `slam.py`,
-    `pose_graph.py`, `loop_detector.py`, ... are imported from wherever they are installed and stay untouched.  The reference's
+    `pose_graph.py`, `loop_detector.py`, ... are imported from wherever they are installed and stay untouched (the keyframe gate and
+    the loop detector have device-side drop-ins of their own, `vista_slam_amd.flow.FlowTracker` and `vista_slam_amd.loop.LoopDetector`:
+    one assignment each on the constructed `OnlineSLAM`).  The reference's
     PyTorch model files are then never imported (nor xformers / curope, which they need).  Returns the stub module."""
     import sys
     import types

@@ -87,6 +87,10 @@ SIGNATURES = {
     "sta_flow_pyramid": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _fp, _vp]),
     "sta_flow_corners": (_i, [_vp, _fp, _i, _i, _i, C.c_double, _i, _i, _fp, _i64, _fp, _fp, _vp]),
     "sta_flow_track": (_i, [_vp, _fp, _fp, _i, _i, _i, _i, _i, _fp, _fp, _i, _i, C.c_double, C.c_double, _fp, _fp, _fp, _vp]),
+    "sta_orb_plan": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i64)]),
+    "sta_orb_extract": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
+    "sta_bow_transform": (_i, [_vp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
+    "sta_bow_score": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _fp, _i, _fp, _vp]),
     "sta_regress_views": (_i, [_vp, _fp, C.POINTER(_vp), _i, C.c_char_p, _f, _i, _i, _fp, C.POINTER(C.c_float),
                                C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),

@@ -14,6 +14,7 @@
 #include "select.h"
 #include "voxel.h"
 #include "flow.h"
+#include "loop.h"
 
 #include <algorithm>
 #include <cmath>

@@ -595,6 +595,171 @@ extern "C" int sta_flow_track(sta_handle* h, const uint8_t* prev_pyramid, const 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Loop candidates (kernels in loop.h; the contract is in include/sta_mi355.h).  sta_orb_plan holds every size and refusal and is host
+// only; the three device calls take the caller's buffers, launch on `stream` and return: no allocation, no copy to the host, no
+// synchronisation - the keypoint and word counts stay on the device.
+static int orb_levels(int H, int W, int nfeatures, int nlevels, int fast_threshold, int edge, OrbLevels* lv) {
+    REQUIRE(nlevels >= 1 && nlevels <= ORB_MAX_LEVELS, "orb: nlevels must lie in [1, %d] (got %d)", ORB_MAX_LEVELS, nlevels);
+    REQUIRE(nfeatures >= 1 && nfeatures <= ORB_MAX_FEATURES, "orb: nfeatures must lie in [1, %d] (got %d)", ORB_MAX_FEATURES, nfeatures);
+    REQUIRE(edge >= ORB_MIN_EDGE && edge <= ORB_MAX_EDGE, "orb: edge must lie in [%d, %d] (got %d)", ORB_MIN_EDGE, ORB_MAX_EDGE, edge);
+    REQUIRE(fast_threshold >= 1 && fast_threshold <= 254, "orb: fast_threshold must lie in [1, 254] (got %d)", fast_threshold);
+    REQUIRE(H > 2 * edge && W > 2 * edge, "orb: H and W must exceed 2 * edge = %d (got %d x %d)", 2 * edge, H, W);
+    REQUIRE((int64_t)H * W <= ORB_MAX_PIXELS, "orb: %d x %d is %lld pixels, above the limit of %d", H, W, (long long)H * W, ORB_MAX_PIXELS);
+    memset(lv, 0, sizeof(*lv));
+    lv->levels = nlevels; lv->edge = edge; lv->thr = fast_threshold;
+    // float64, one operation per step (volatile: no step is fused or reassociated)
+    volatile double s = 1.0;
+    for (int l = 0; l < nlevels; ++l) {
+        volatile double qh = (double)H / s, qw = (double)W / s;
+        lv->h[l] = (int)std::nearbyint(qh); lv->w[l] = (int)std::nearbyint(qw);
+        s = s * 1.2;
+    }
+    volatile double f = 1.0 / 1.2, fp = 1.0;
+    for (int l = 0; l < nlevels; ++l) fp = fp * f;
+    volatile double one_f = 1.0 - f, one_fp = 1.0 - fp;
+    volatile double nd = (double)nfeatures * one_f;
+    nd = nd / one_fp;
+    int sum = 0;
+    for (int l = 0; l < nlevels - 1; ++l) {
+        lv->nfeat[l] = (int)std::nearbyint(nd);
+        sum += lv->nfeat[l];
+        nd = nd * f;
+    }
+    lv->nfeat[nlevels - 1] = std::max(nfeatures - sum, 0);
+    sum += lv->nfeat[nlevels - 1];
+    lv->rows = std::max(nfeatures, sum);
+    int64_t end = 0;
+    for (int l = 0; l < nlevels; ++l) {
+        if (lv->h[l] <= 2 * edge || lv->w[l] <= 2 * edge) break;
+        lv->off[l] = end;
+        end += flow_align((int64_t)lv->h[l] * lv->w[l]);
+        // survivors are strict 3x3 maxima inside the edge: no two are neighbours
+        lv->cand_off[l] = lv->cand_total;
+        lv->cand_cap[l] = ((lv->h[l] - 2 * edge + 1) / 2) * ((lv->w[l] - 2 * edge + 1) / 2);
+        lv->cand_total += lv->cand_cap[l];
+        lv->sel_off[l] = lv->slots;
+        lv->slots += lv->nfeat[l];
+        lv->built = l + 1;
+    }
+    lv->bytes = end;
+    return 0;
+}
+// the extraction workspace: four level-shaped planes (levels and blurred levels first: the header promises them to the caller; scores,
+// survivors), the candidate lists, the slots, the histograms and 16 counters
+struct OrbWs { uint8_t *img, *blur, *score, *surv; long long *candR, *selR; int *candP, *selP, *hist, *counters; int64_t bytes; };
+static OrbWs orb_workspace(void* base, const OrbLevels& lv) {
+    OrbWs w;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { void* p = (void*)((uintptr_t)base + (uintptr_t)o); o += flow_align(b); return p; };
+    w.img = (uint8_t*)take(lv.bytes); w.blur = (uint8_t*)take(lv.bytes); w.score = (uint8_t*)take(lv.bytes); w.surv = (uint8_t*)take(lv.bytes);
+    w.candR = (long long*)take((int64_t)lv.cand_total * 8); w.selR = (long long*)take((int64_t)lv.slots * 8);
+    w.candP = (int*)take((int64_t)lv.cand_total * 4); w.selP = (int*)take((int64_t)lv.slots * 4);
+    w.hist = (int*)take(ORB_MAX_LEVELS * 256 * 4); w.counters = (int*)take(64);
+    w.bytes = o;
+    return w;
+}
+
+extern "C" int sta_orb_plan(int H, int W, int nfeatures, int nlevels, int fast_threshold, int edge, int64_t out[40]) {
+    REQUIRE(out, "null argument");
+    OrbLevels lv;
+    CHK(orb_levels(H, W, nfeatures, nlevels, fast_threshold, edge, &lv));
+    memset(out, 0, 40 * sizeof(int64_t));
+    out[0] = lv.levels; out[1] = lv.built;
+    for (int l = 0; l < lv.levels; ++l) { out[2 + l] = lv.h[l]; out[10 + l] = lv.w[l]; out[18 + l] = lv.nfeat[l]; out[26 + l] = l < lv.built ? lv.off[l] : -1; }
+    out[34] = lv.bytes;
+    out[35] = orb_workspace(nullptr, lv).bytes;
+    out[36] = lv.rows;
+    out[37] = flow_align((int64_t)lv.rows * 4);
+    return 0;
+}
+
+extern "C" int sta_orb_extract(sta_handle* h, const void* image, int dtype, int H, int W, int nfeatures, int nlevels, int fast_threshold, int edge,
+                               const int32_t* trig, const int8_t* pattern, void* workspace, int64_t workspace_bytes, int32_t* kp, int64_t* resp,
+                               uint8_t* desc, int32_t* n_out, void* stream) {
+    REQUIRE(h && image && trig && pattern && workspace && kp && resp && desc && n_out, "null argument");
+    REQUIRE(dtype == 0 || dtype == 1, "orb: dtype must be 0 (uint8) or 1 (float32) (got %d)", dtype);
+    OrbLevels lv;
+    CHK(orb_levels(H, W, nfeatures, nlevels, fast_threshold, edge, &lv));
+    REQUIRE(dtype == 0 || ((uintptr_t)image & 3) == 0, "orb: a float32 frame must be 4-byte aligned");
+    REQUIRE(((uintptr_t)trig & 3) == 0 && ((uintptr_t)kp & 3) == 0 && ((uintptr_t)n_out & 3) == 0 && ((uintptr_t)resp & 7) == 0,
+            "orb: trig, kp and n_out must be 4-byte aligned, resp 8-byte aligned");
+    REQUIRE(((uintptr_t)workspace & 7) == 0, "orb: the workspace must be 8-byte aligned");
+    const OrbWs w = orb_workspace(workspace, lv);
+    REQUIRE(workspace_bytes >= w.bytes, "orb: the workspace holds %lld bytes, %d x %d with %d features over %d levels needs %lld",
+            (long long)workspace_bytes, H, W, nfeatures, nlevels, (long long)w.bytes);
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int* ncand = w.counters; int* cut = w.counters + 8;
+    HIPCHK(hipMemsetAsync(w.hist, 0, ORB_MAX_LEVELS * 256 * 4, st));
+    HIPCHK(hipMemsetAsync(w.counters, 0, 64, st));
+    const int N = H * W;
+    if (dtype == 1) hipLaunchKernelGGL(orb_level0_kernel<true>, dim3((N + 255) / 256), dim3(256), 0, st, image, N, w.img);
+    else hipLaunchKernelGGL(orb_level0_kernel<false>, dim3((N + 255) / 256), dim3(256), 0, st, image, N, w.img);
+    for (int l = 1; l < lv.built; ++l) {
+        volatile double ry = (double)lv.h[l - 1] / (double)lv.h[l], rx = (double)lv.w[l - 1] / (double)lv.w[l];
+        hipLaunchKernelGGL(orb_resize_kernel, dim3((lv.w[l] + 15) / 16, (lv.h[l] + 15) / 16), dim3(256), 0, st,
+                           (const uint8_t*)(w.img + lv.off[l - 1]), lv.h[l - 1], lv.w[l - 1], w.img + lv.off[l], lv.h[l], lv.w[l], (double)ry, (double)rx);
+    }
+    const dim3 tiles((W + 15) / 16, (H + 15) / 16, lv.built);      // level 0 is the largest
+    hipLaunchKernelGGL(orb_fast_kernel, tiles, dim3(256), 0, st, (const uint8_t*)w.img, lv, w.score);
+    hipLaunchKernelGGL(orb_nms_kernel, tiles, dim3(256), 0, st, (const uint8_t*)w.score, lv, w.surv, w.hist);
+    hipLaunchKernelGGL(orb_cut_kernel, dim3(1), dim3(64), 0, st, (const int*)w.hist, lv, cut);
+    hipLaunchKernelGGL(orb_harris_kernel, tiles, dim3(256), 0, st, (const uint8_t*)w.img, (const uint8_t*)w.surv, lv, (const int*)cut, ncand, w.candR, w.candP);
+    int max_cap = 1;
+    for (int l = 0; l < lv.built; ++l) max_cap = std::max(max_cap, lv.cand_cap[l]);
+    hipLaunchKernelGGL(orb_rank_kernel, dim3((max_cap + 255) / 256, lv.built), dim3(256), 0, st, lv, (const int*)ncand, (const long long*)w.candR,
+                       (const int*)w.candP, w.selR, w.selP);
+    hipLaunchKernelGGL(orb_blur_kernel, tiles, dim3(256), 0, st, (const uint8_t*)w.img, lv, w.blur);
+    hipLaunchKernelGGL(orb_describe_kernel, dim3(std::max(lv.slots, 1)), dim3(64), 0, st, (const uint8_t*)w.img, (const uint8_t*)w.blur, lv,
+                       (const int*)ncand, (const long long*)w.selR, (const int*)w.selP, (const int*)trig, (const signed char*)pattern, (int*)kp,
+                       (long long*)resp, desc, (int*)n_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_bow_transform(sta_handle* h, const uint8_t* desc, const int32_t* n_dev, int n_cap, const uint8_t* node_desc,
+                                 const int32_t* child_first, const int32_t* child_count, const int32_t* word_of, const double* word_weight,
+                                 int n_nodes, int n_words, void* workspace, int64_t workspace_bytes, int32_t* words, int32_t* counts, double* vals,
+                                 int32_t* n_words_out, void* stream) {
+    REQUIRE(h && desc && node_desc && child_first && child_count && word_of && word_weight && workspace && words && counts && vals && n_words_out,
+            "null argument");
+    REQUIRE(n_cap >= 1 && n_cap <= ORB_MAX_ROWS, "bow: n_cap must lie in [1, %d] (got %d)", ORB_MAX_ROWS, n_cap);
+    REQUIRE(n_nodes >= 1 && n_words >= 0 && n_words <= n_nodes, "bow: a vocabulary has at least its root and at most one word per node (got %d nodes, %d words)",
+            n_nodes, n_words);
+    REQUIRE(((uintptr_t)desc & 3) == 0 && ((uintptr_t)node_desc & 3) == 0, "bow: descriptors must be 4-byte aligned");
+    REQUIRE(((uintptr_t)workspace & 3) == 0 && workspace_bytes >= (int64_t)n_cap * 4, "bow: the workspace holds %lld bytes, %d descriptors need %lld",
+            (long long)workspace_bytes, n_cap, (long long)n_cap * 4);
+    REQUIRE(((uintptr_t)vals & 7) == 0 && ((uintptr_t)word_weight & 7) == 0, "bow: vals and word_weight must be 8-byte aligned");
+    BowVocab v;
+    v.node_desc = node_desc; v.child_first = child_first; v.child_count = child_count; v.word_of = word_of; v.word_weight = word_weight;
+    v.n_nodes = n_nodes; v.n_words = n_words;
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    int* wid = (int*)workspace;
+    hipLaunchKernelGGL(bow_walk_kernel, dim3((n_cap + 3) / 4), dim3(256), 0, st, desc, (const int*)n_dev, n_cap, v, wid);
+    hipLaunchKernelGGL(bow_reduce_kernel, dim3(1), dim3(1024), 0, st, (const int*)wid, n_cap, word_weight, (int*)words, (int*)counts, vals, (int*)n_words_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_bow_score(sta_handle* h, const int32_t* q_words, const double* q_vals, const int32_t* q_n, int q_cap,
+                             const int32_t* db_words, const double* db_vals, const int32_t* db_n, int max_views, int cap, const int32_t* rows, int m,
+                             double* sim, void* stream) {
+    REQUIRE(h && q_words && q_vals && q_n && db_words && db_vals && db_n, "null argument");
+    REQUIRE(max_views >= 1 && cap >= 1 && cap <= ORB_MAX_ROWS, "bow: max_views must be positive and cap lie in [1, %d] (got %d, %d)", ORB_MAX_ROWS,
+            max_views, cap);
+    REQUIRE(q_cap >= 1 && q_cap <= ORB_MAX_ROWS, "bow: q_cap must lie in [1, %d] (got %d)", ORB_MAX_ROWS, q_cap);
+    REQUIRE(m >= 0 && m <= (1 << 20), "bow: m must lie in [0, 2^20] (got %d)", m);
+    REQUIRE(m == 0 || (rows && sim), "null argument");
+    REQUIRE(((uintptr_t)q_vals & 7) == 0 && ((uintptr_t)db_vals & 7) == 0 && ((uintptr_t)sim & 7) == 0, "bow: values and sim must be 8-byte aligned");
+    DEV_SCOPE(h->device);
+    if (m > 0) hipLaunchKernelGGL(bow_score_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, (const int*)q_words, q_vals, (const int*)q_n, q_cap,
+                                  (const int*)db_words, db_vals, (const int*)db_n, max_views, cap, (const int*)rows, sim);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
