@@ -659,6 +659,75 @@ STA_API int sta_bow_score(sta_handle* h, const int32_t* q_words, const double* q
                           const int32_t* db_words, const double* db_vals, const int32_t* db_n, int max_views, int cap, const int32_t* rows, int m,
                           double* sim, void* stream);
 
+/* The Sim(3) pose graph: OnlineSLAM.pose_graph_optimize (vista_slam/slam.py:108-140, pose_graph.py:70-154), there a pypose LM over
+ * Sim3 nodes with a dense autograd Jacobian and a dense Cholesky solve.  The contract RESTATES the problem in float64; the yardstick is
+ * the numpy restatement tests/pgo_cases.py, it is NOT pypose (which cannot be imported where this library is tested).  Stated
+ * differences from the reference: float64 inside (float32 there); inexact steps (PCG to rtol, dense Cholesky there); 7 tangent unknowns
+ * per node (pypose differentiates the 8 stored numbers).  The LM constants high / low / up / down / reject, and `decreasing` being
+ * relative to f, are restated from memory of pypose's TrustRegion and StopOnPlateau: every one is an argument.
+ * Limits: 1 <= n <= 8192 nodes, 1 <= E <= 16384 edges; a violation returns -1 with the numbers in sta_last_error().
+ * Group: an element is 8 float64 (tx,ty,tz, qx,qy,qz,qw, s), acting as x -> s R(q) x + t.  Product (s1 R1 t2 + t1, R1 R2, s1 s2),
+ * inverse (-(1/s) R^T t, R^T, 1/s); every quaternion written is normalised once and not sign-canonicalised.  A tangent is
+ * xi = (tau, phi, sigma) with generator [[sigma I + phi^, tau],[0,0]]; Exp: R = exp(phi^), s = e^sigma, t = W tau,
+ * W = C I + A phi^ + B phi^ phi^ with theta = |phi|, C = expm1(sigma) / sigma (1 at sigma = 0) and
+ *   theta >= 0.25:  A = Is / theta, B = (C - Ic) / theta^2, Is = (e^sigma (sigma sin - theta cos) + theta) / (sigma^2 + theta^2),
+ *                   Ic = (e^sigma (sigma cos + theta sin) - sigma) / (sigma^2 + theta^2);
+ *   theta <  0.25:  A = sum_j (-theta^2)^j m_(2j+1) / (2j+1)!, B = sum_j (-theta^2)^j m_(2j+2) / (2j+2)!, j < 6, with the moments
+ *                   m_k = int_0^1 u^k e^(u sigma) du from the backward recurrence m_(k-1) = (e^sigma - sigma m_k) / k started at
+ *                   m_48 = e^sigma / 49 (no division by sigma: the same branch serves small and large |sigma|).
+ * The quaternion of Exp is (k phi, cos(theta/2)), k = sin(theta/2) / theta, or 1/2 - theta^2 / 48 for theta < 1e-4.  Log: q normalised,
+ * negated if w < 0 (so |phi| <= pi); phi = f q.xyz, f = 2 atan2(n, w) / n with n = |q.xyz|, or (2/w)(1 - n^2 / (3 w^2)) for n < 1e-4;
+ * sigma = log s; tau = W^-1 t by the adjugate.  Ad and ad for the order (tau, phi, sigma):
+ *   Ad(T) = [[sR, t^ R, -t],[0, R, 0],[0, 0, 1]],   ad(xi) = [[sigma I + phi^, tau^, -tau],[0, phi^, 0],[0, 0, 0]].
+ * Jl(xi) = sum_(k<=32) ad^k / (k+1)! by Horner, column by column: y = e_j + ad y / (k + 1), k = 32 .. 1.
+ * sta_sim3_op(op): 0 mul(a, b), 1 inv(a), 2 inv(a) b, 3 Exp(a [count,7]), 4 Log(a) -> out [count,7], 5 retract: Exp(a [count,7]) b where
+ * mask (uint8 [count], null = everywhere) is set and a copy of b elsewhere; elements [count,8]; one thread per element.
+ * Graph: edge e = (a, b) = edges int32 [E,2] with measurement P_e (poses [E,8]) and weights w_e >= 0 (confs [E,7]) has the residual
+ * r_e = Log(P_e X_a^-1 X_b) (the reference's poses @ node1.Inv() @ node2).  An edge is ACTIVE iff a != b, both lie in [0, n) and
+ * opt[a] | opt[b] (opt uint8 [n]: the optimised nodes); an inactive edge contributes nothing; an index outside [0, n) sets status bit 1.
+ * Under X <- Exp(d) X, with A_e = P_e X_a^-1 and M_e = Jl(r_e)^-1 Ad(A_e) (7x7 elimination with partial pivoting, the first largest
+ * entry): dr/dd_b = M_e, dr/dd_a = -M_e.  S_e = M_e^T diag(w_e) M_e, v_e = M_e^T (w_e r_e), c_e = sum w r^2;
+ *   f = sum_e c_e,   g_k = sum over the half-edges at k of +-v_e,   (H x)_k = sum over the half-edges at k of +-S_e (x_b - x_a)
+ * (+ at k = b, - at k = a; x = 0 at a fixed node).  Nothing is assembled; there is no floating-point atomic.
+ * sta_pgo_index: off int32 [n+1], inc int32 [<= 2E] = edge * 2 + side (side 0: the node is a) for the active half-edges at optimised
+ * nodes, each node's list ASCENDING by edge; status int32.  One workgroup; workspace 16 E bytes.
+ * sta_pgo_linearize: c [E] always; full != 0 also r [E,7], S [E,7,7], v [E,7] (zeros on inactive edges), g [n,7] and the diagonal
+ * blocks [n,7,7] = sum of S_e in list order (zeros at fixed nodes); rec = {f, status}: f = the c_e summed as thread t of 1024 takes
+ * e = t, t + 1024, ... in order, a shuffle tree per wave, the 16 wave sums in order; status = bit 2 for a non-finite f, ored with
+ * *idx_status (sta_pgo_index's, may be null).  The cost-only form (full = 0: off, inc, r, S, v, g, blocks may be null) runs the
+ * same instructions: its f is bit-identical to the full form's.
+ * sta_pgo_solve: preconditioned CG for (H + D / radius) d = -g, D = diag(clamp(diag H, dmin, dmax)), block-Jacobi preconditioner (per
+ * optimised node the 7x7 Cholesky factor of its diagonal block + D_k / radius), x_0 = 0.  Stops at the first of |r_k|_2 <= rtol |g|_2,
+ * k = max_iter (bit 4), p^T A p <= 0 or a non-finite scalar (bit 8); a block that is not positive definite is bit 16 (no iteration).
+ * ONE workgroup of 1024 threads; node k belongs to thread k mod 1024; dot products sum each thread's rows in ascending order, then the
+ * fixed tree above: two runs are bit-identical.  d [n,7] (zeros at fixed nodes); stats float64 [4] = {iterations, |r| / |g| by
+ * recurrence, -2 d.g - d.H d (the model decrease), status}.  The products read the UPPER triangle of S_e (S_e is symmetric up to
+ * rounding).  Workspace: out[3] of sta_pgo_plan.
+ * sta_pgo_plan (host only): out = {off bytes, inc bytes, index workspace bytes, solve workspace bytes, sta_pgo_optimize workspace
+ * bytes, n, E, 0}.
+ * sta_pgo_optimize: the LM loop, host-driven, on nodes [n,8] in place.  Per outer step (at most `steps`): linearise at X (cost f); up to
+ * `reject` trials: solve at the current radius, X' = Exp(d) X on the optimised nodes, f' = f(X'), rho = (f - f') / model decrease
+ * (-inf if that is not positive), radius *= up if rho > high, *= down if rho < low, accept iff f' < f.  A step without an accepted
+ * trial, or whose accepted trial has f - f' < decreasing * f, raises a count that any other step resets; stop at `patience`.  A
+ * non-finite f leaves the nodes unchanged with status bits 2 | 32.  It reads ONE record of 64 bytes back per trial - that is its
+ * synchronisation - and allocates nothing; the workspace (256-byte aligned) is the caller's.  info (host, may be null): rows of 8
+ * float64 per trial {f, f', rho, radius, PCG iterations, PCG status, |r|/|g|, model decrease}, *n_info rows written.
+ * The other four device calls allocate nothing, copy nothing to the host and never synchronise; none takes the stream's scratch. */
+STA_API int sta_pgo_plan(int n, int E, int64_t out[8]);
+STA_API int sta_sim3_op(sta_handle* h, int op, const double* a, const double* b, const uint8_t* mask, double* out, int64_t count, void* stream);
+STA_API int sta_pgo_index(sta_handle* h, const int32_t* edges, const uint8_t* opt, int n, int E, void* workspace, int64_t workspace_bytes,
+                          int32_t* off, int32_t* inc, int32_t* status, void* stream);
+STA_API int sta_pgo_linearize(sta_handle* h, const double* nodes, const int32_t* edges, const double* poses, const double* confs, const uint8_t* opt,
+                              const int32_t* off, const int32_t* inc, const int32_t* idx_status, int n, int E, int full, double* r, double* S, double* v,
+                              double* c, double* g, double* blocks, double* rec, void* stream);
+STA_API int sta_pgo_solve(sta_handle* h, const int32_t* edges, const uint8_t* opt, const int32_t* off, const int32_t* inc, const double* S, const double* g,
+                          const double* blocks, int n, int E, double radius, double dmin, double dmax, double rtol, int max_iter, void* workspace,
+                          int64_t workspace_bytes, double* d, double* stats, void* stream);
+STA_API int sta_pgo_optimize(sta_handle* h, double* nodes, const int32_t* edges, const double* poses, const double* confs, const uint8_t* opt, int n, int E,
+                             double radius, double dmin, double dmax, int steps, int patience, double decreasing, int reject, double high, double low,
+                             double up, double down, double pcg_rtol, int pcg_max_iter, void* workspace, int64_t workspace_bytes, double* info,
+                             int info_rows, int* n_info, int* status_out, void* stream);
+
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one
  * batched launch sequence instead of k sequential B=1 calls, with the reference's early reject kept:

@@ -91,6 +91,13 @@ SIGNATURES = {
     "sta_orb_extract": (_i, [_vp, _fp, _i, _i, _i, _i, _i, _i, _i, _fp, _fp, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
     "sta_bow_transform": (_i, [_vp, _fp, _fp, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
     "sta_bow_score": (_i, [_vp, _fp, _fp, _fp, _i, _fp, _fp, _fp, _i, _i, _fp, _i, _fp, _vp]),
+    "sta_pgo_plan": (_i, [_i, _i, C.POINTER(_i64)]),
+    "sta_sim3_op": (_i, [_vp, _i, _fp, _fp, _fp, _fp, _i64, _vp]),
+    "sta_pgo_index": (_i, [_vp, _fp, _fp, _i, _i, _fp, _i64, _fp, _fp, _fp, _vp]),
+    "sta_pgo_linearize": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),
+    "sta_pgo_solve": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, _fp, _i64, _fp, _fp, _vp]),
+    "sta_pgo_optimize": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, C.c_double, C.c_double,
+                              C.c_double, C.c_double, C.c_double, _i, _fp, _i64, C.POINTER(C.c_double), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
     "sta_regress_views": (_i, [_vp, _fp, C.POINTER(_vp), _i, C.c_char_p, _f, _i, _i, _fp, C.POINTER(C.c_float),
                                C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),

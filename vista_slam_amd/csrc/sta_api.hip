@@ -15,6 +15,7 @@
 #include "voxel.h"
 #include "flow.h"
 #include "loop.h"
+#include "pgo.h"
 
 #include <algorithm>
 #include <cmath>

@@ -760,6 +760,157 @@ extern "C" int sta_bow_score(sta_handle* h, const int32_t* q_words, const double
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The Sim(3) pose graph (kernels in pgo.h; the contract is in include/sta_mi355.h).  sta_pgo_plan holds every size and refusal and is
+// host only.  sta_sim3_op, sta_pgo_index, sta_pgo_linearize and sta_pgo_solve take the caller's buffers, launch on `stream` and return:
+// no allocation, no copy to the host, no synchronisation.  sta_pgo_optimize is the host-driven LM loop: it reads ONE record of 64
+// bytes back per trial step (its synchronisation) and allocates nothing either.
+static int pgo_limits(int n, int E) {
+    REQUIRE(n >= 1 && n <= PGO_MAX_NODES, "pgo: n must lie in [1, %d] (got %d)", PGO_MAX_NODES, n);
+    REQUIRE(E >= 1 && E <= PGO_MAX_EDGES, "pgo: E must lie in [1, %d] (got %d)", PGO_MAX_EDGES, E);
+    return 0;
+}
+// the workspace of sta_pgo_optimize: every buffer of the four device calls, 256-byte aligned, and the record
+struct PgoWs { int *off, *inc, *tmp, *idx_status; double *r, *S, *v, *c, *g, *blocks, *d, *trial, *solve, *rec; int64_t bytes; };
+static PgoWs pgo_workspace(void* base, int n, int E) {
+    PgoWs w;
+    int64_t o = 0;
+    auto take = [&](int64_t b) { void* p = (void*)((uintptr_t)base + (uintptr_t)o); o += flow_align(b); return p; };
+    w.off = (int*)take((int64_t)(n + 1) * 4); w.inc = (int*)take((int64_t)E * 8); w.tmp = (int*)take((int64_t)E * 16); w.idx_status = (int*)take(4);
+    w.r = (double*)take((int64_t)E * 56); w.S = (double*)take((int64_t)E * 392); w.v = (double*)take((int64_t)E * 56); w.c = (double*)take((int64_t)E * 8);
+    w.g = (double*)take((int64_t)n * 56); w.blocks = (double*)take((int64_t)n * 392); w.d = (double*)take((int64_t)n * 56);
+    w.trial = (double*)take((int64_t)n * 64); w.solve = (double*)take((int64_t)pgo_solve_ws_doubles(n, E) * 8); w.rec = (double*)take(64);
+    w.bytes = o;
+    return w;
+}
+
+extern "C" int sta_pgo_plan(int n, int E, int64_t out[8]) {
+    REQUIRE(out, "null argument");
+    CHK(pgo_limits(n, E));
+    out[0] = (int64_t)(n + 1) * 4; out[1] = (int64_t)E * 8; out[2] = (int64_t)E * 16;
+    out[3] = (int64_t)pgo_solve_ws_doubles(n, E) * 8; out[4] = pgo_workspace(nullptr, n, E).bytes; out[5] = n; out[6] = E; out[7] = 0;
+    return 0;
+}
+
+extern "C" int sta_sim3_op(sta_handle* h, int op, const double* a, const double* b, const uint8_t* mask, double* out, int64_t count, void* stream) {
+    REQUIRE(h && a && out, "null argument");
+    REQUIRE(op >= SIM3_MUL && op <= SIM3_RETRACT, "sim3: op must lie in [0, 5] (got %d)", op);
+    REQUIRE(b || op == SIM3_INV || op == SIM3_EXP || op == SIM3_LOG, "sim3: op %d takes two operands", op);
+    REQUIRE(count >= 0 && count <= (1 << 24), "sim3: count must lie in [0, 2^24] (got %lld)", (long long)count);
+    REQUIRE((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 7) == 0, "sim3: operands must be 8-byte aligned");
+    DEV_SCOPE(h->device);
+    if (count > 0) hipLaunchKernelGGL(sim3_op_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream, op, a, b, mask, out, (long long)count);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_pgo_index(sta_handle* h, const int32_t* edges, const uint8_t* opt, int n, int E, void* workspace, int64_t workspace_bytes,
+                             int32_t* off, int32_t* inc, int32_t* status, void* stream) {
+    REQUIRE(h && edges && opt && workspace && off && inc && status, "null argument");
+    CHK(pgo_limits(n, E));
+    REQUIRE(((uintptr_t)workspace & 3) == 0 && workspace_bytes >= (int64_t)E * 16, "pgo: the index workspace holds %lld bytes, %d edges need %lld",
+            (long long)workspace_bytes, E, (long long)E * 16);
+    DEV_SCOPE(h->device);
+    hipLaunchKernelGGL(pgo_index_kernel, dim3(1), dim3(PGO_THREADS), 0, (hipStream_t)stream, (const int*)edges, opt, n, E, (int*)workspace, (int*)off, (int*)inc,
+                       (int*)status);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_pgo_linearize(sta_handle* h, const double* nodes, const int32_t* edges, const double* poses, const double* confs, const uint8_t* opt,
+                                 const int32_t* off, const int32_t* inc, const int32_t* idx_status, int n, int E, int full, double* r, double* S, double* v,
+                                 double* c, double* g, double* blocks, double* rec, void* stream) {
+    REQUIRE(h && nodes && edges && poses && confs && opt && c && rec, "null argument");
+    REQUIRE(!full || (off && inc && r && S && v && g && blocks), "pgo: the full form needs off, inc, r, S, v, g and blocks");
+    CHK(pgo_limits(n, E));
+    REQUIRE((((uintptr_t)nodes | (uintptr_t)poses | (uintptr_t)confs | (uintptr_t)r | (uintptr_t)S | (uintptr_t)v | (uintptr_t)c | (uintptr_t)g | (uintptr_t)blocks |
+              (uintptr_t)rec) & 7) == 0, "pgo: float64 buffers must be 8-byte aligned");
+    DEV_SCOPE(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pgo_linearize_kernel, dim3((E + 63) / 64), dim3(64), 0, st, nodes, (const int*)edges, poses, confs, opt, n, E, full ? 1 : 0, r, S, v, c);
+    hipLaunchKernelGGL(pgo_cost_kernel, dim3(1), dim3(PGO_THREADS), 0, st, (const double*)c, E, (const int*)idx_status, rec);
+    if (full) hipLaunchKernelGGL(pgo_node_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const int*)off, (const int*)inc, opt, n, (const double*)S,
+                                 (const double*)v, g, blocks);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_pgo_solve(sta_handle* h, const int32_t* edges, const uint8_t* opt, const int32_t* off, const int32_t* inc, const double* S, const double* g,
+                             const double* blocks, int n, int E, double radius, double dmin, double dmax, double rtol, int max_iter, void* workspace,
+                             int64_t workspace_bytes, double* d, double* stats, void* stream) {
+    REQUIRE(h && edges && opt && off && inc && S && g && blocks && workspace && d && stats, "null argument");
+    CHK(pgo_limits(n, E));
+    REQUIRE(radius > 0 && dmin > 0 && dmax >= dmin, "pgo: radius and dmin must be positive and dmax >= dmin (got %g, %g, %g)", radius, dmin, dmax);
+    REQUIRE(rtol >= 0 && max_iter >= 1 && max_iter <= (1 << 20), "pgo: rtol must be >= 0 and max_iter lie in [1, 2^20] (got %g, %d)", rtol, max_iter);
+    const int64_t need = (int64_t)pgo_solve_ws_doubles(n, E) * 8;
+    REQUIRE(((uintptr_t)workspace & 7) == 0 && workspace_bytes >= need, "pgo: the solve workspace holds %lld bytes, %d nodes and %d edges need %lld",
+            (long long)workspace_bytes, n, E, (long long)need);
+    REQUIRE((((uintptr_t)S | (uintptr_t)g | (uintptr_t)blocks | (uintptr_t)d | (uintptr_t)stats) & 7) == 0, "pgo: float64 buffers must be 8-byte aligned");
+    DEV_SCOPE(h->device);
+    hipLaunchKernelGGL(pgo_solve_kernel, dim3(1), dim3(PGO_THREADS), 0, (hipStream_t)stream, (const int*)edges, opt, (const int*)off, (const int*)inc, S, g, blocks,
+                       n, E, radius, dmin, dmax, rtol, max_iter, (double*)workspace, d, stats);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_pgo_optimize(sta_handle* h, double* nodes, const int32_t* edges, const double* poses, const double* confs, const uint8_t* opt, int n, int E,
+                                double radius, double dmin, double dmax, int steps, int patience, double decreasing, int reject, double high, double low,
+                                double up, double down, double pcg_rtol, int pcg_max_iter, void* workspace, int64_t workspace_bytes, double* info,
+                                int info_rows, int* n_info, int* status_out, void* stream) {
+    REQUIRE(h && nodes && edges && poses && confs && opt && workspace && status_out, "null argument");
+    CHK(pgo_limits(n, E));
+    REQUIRE(steps >= 1 && steps <= 1000 && patience >= 1 && reject >= 1 && reject <= 1000, "pgo: steps and reject must lie in [1, 1000], patience be positive (got %d, %d, %d)",
+            steps, reject, patience);
+    REQUIRE(up >= 1 && down > 0 && down <= 1 && high >= low, "pgo: up >= 1, 0 < down <= 1 and high >= low (got %g, %g, %g, %g)", up, down, high, low);
+    REQUIRE(!info || (info_rows >= 0 && n_info), "pgo: info needs info_rows >= 0 and n_info");
+    const PgoWs w = pgo_workspace(workspace, n, E);
+    REQUIRE(((uintptr_t)workspace & 255) == 0 && workspace_bytes >= w.bytes, "pgo: the workspace must be 256-byte aligned and holds %lld bytes, %d nodes and %d edges need %lld",
+            (long long)workspace_bytes, n, E, (long long)w.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t solve_bytes = (int64_t)pgo_solve_ws_doubles(n, E) * 8;
+    int status = 0, stall = 0, rows = 0;
+    if (n_info) *n_info = 0;
+    *status_out = 0;
+    CHK(sta_pgo_index(h, edges, opt, n, E, w.tmp, (int64_t)E * 16, w.off, w.inc, w.idx_status, stream));
+    for (int step = 0; step < steps; ++step) {
+        // rec = {solve stats [4], f', its status, f, its status}
+        CHK(sta_pgo_linearize(h, nodes, edges, poses, confs, opt, w.off, w.inc, w.idx_status, n, E, 1, w.r, w.S, w.v, w.c, w.g, w.blocks, w.rec + 6, stream));
+        bool accepted = false, good = false;
+        for (int t = 0; t < reject; ++t) {
+            CHK(sta_pgo_solve(h, edges, opt, w.off, w.inc, w.S, w.g, w.blocks, n, E, radius, dmin, dmax, pcg_rtol, pcg_max_iter, w.solve, solve_bytes, w.d, w.rec, stream));
+            CHK(sta_sim3_op(h, SIM3_RETRACT, w.d, nodes, opt, w.trial, n, stream));
+            CHK(sta_pgo_linearize(h, w.trial, edges, poses, confs, opt, nullptr, nullptr, nullptr, n, E, 0, nullptr, nullptr, nullptr, w.c, nullptr, nullptr, w.rec + 4, stream));
+            double rec[8];
+            {
+                DEV_SCOPE(h->device);
+                HIPCHK(hipMemcpyAsync(rec, w.rec, 64, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+            }
+            const double f = rec[6], fn = rec[4], mdec = rec[2];
+            status |= (int)rec[7] & PGO_ST_INDEX;
+            if (!std::isfinite(f)) { *status_out = status | PGO_ST_NONFINITE | PGO_ST_UNCHANGED; if (n_info) *n_info = rows; return 0; }
+            const double rho = (mdec > 0 && std::isfinite(fn)) ? (f - fn) / mdec : -INFINITY;
+            if (info && rows < info_rows) {
+                double* o = info + (size_t)rows * 8;
+                o[0] = f; o[1] = fn; o[2] = rho; o[3] = radius; o[4] = rec[0]; o[5] = rec[3]; o[6] = rec[1]; o[7] = mdec;
+                ++rows;
+            }
+            if (rho > high) radius *= up; else if (rho < low) radius *= down;
+            if (std::isfinite(fn) && fn < f) {
+                accepted = true; good = (f - fn) >= decreasing * f;
+                DEV_SCOPE(h->device);
+                HIPCHK(hipMemcpyAsync(nodes, w.trial, (size_t)n * 64, hipMemcpyDeviceToDevice, st));
+                break;
+            }
+        }
+        stall = (accepted && good) ? 0 : stall + 1;
+        if (stall >= patience) break;
+    }
+    if (n_info) *n_info = rows;
+    *status_out = status;
+    return 0;
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");
