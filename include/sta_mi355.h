@@ -728,6 +728,69 @@ STA_API int sta_pgo_optimize(sta_handle* h, double* nodes, const int32_t* edges,
                              double up, double down, double pcg_rtol, int pcg_max_iter, void* workspace, int64_t workspace_bytes, double* info,
                              int info_rows, int* n_info, int* status_out, void* stream);
 
+/* The device-resident pose graph: PoseGraphNodes / PoseGraphEdges (vista_slam/pose_graph.py:5-54) and OnlineSLAM.connect_view_i_j
+ * (slam.py:191-241), there host lists, a host copy of every node's maps, about a dozen small torch launches per node, .item() round
+ * trips and pypose products.  Here the state lives in the caller's device arrays (sta_graph_state; Python: vista_slam_amd/graph.py),
+ * allocated once.  The yardstick is the numpy restatement tests/graph_cases.py on the float64 group operations of tests/pgo_cases.py;
+ * it is NOT pypose (which cannot be imported where this library is tested).  Stated differences from the reference: float64 state
+ * (fp32 there); float64 sums in a fixed order (fp32 torch reductions there); one call per keyframe (one per edge there); the maps of
+ * every node stay on the device (host there).
+ * sta_graph_state: node poses float64 [max_nodes,8] in the (t, q, s) layout above; edges int64 [max_edges,2]; edge_poses float64
+ * [max_edges,8]; edge_confs float64 [max_edges,7]; the map pool depth, conf fp32 [max_nodes,H,W] and intri fp32 [max_nodes,3,3];
+ * mean_conf float64 [max_nodes]; per view first_node, best_node int32 [max_views] and best_conf float64 [max_views], max_views =
+ * max_view_num + 1 (run.py:209 looks at the view count after the step that exceeds it); partials
+ * float64 [32, chunks, 4], scratch of sta_graph_commit.  Every pointer is 16-byte aligned.  The host keeps the structure only: the
+ * counts and, per view, the first node (it knows every accept / reject decision from the scheduler's read-back).
+ * sta_graph_plan (host only): max_nodes = max_view_num (2 neighbor + loop), max_edges = max_view_num ((2 neighbor + loop - 1) +
+ * ((2 neighbor + loop) / 2 + 1)) (slam.py:33-36); refused beyond sta_pgo_plan's limits (8192 nodes, 16384 edges), for H or W that is
+ * not a positive multiple of 16, for max_view_num < 1, neighbor < 1 or loop < 0; the numbers are in sta_last_error().  out = {max_nodes,
+ * max_edges, chunk (2048 map elements, whatever H W is), chunks = ceil(H W / chunk), poses bytes, edges bytes, edge_poses bytes,
+ * edge_confs bytes, pool bytes (depth + conf + intri), mean_conf bytes, tables bytes, partials bytes, their total, max_views, 0, 0}.
+ * sta_graph_reset: one launch: poses and edge_poses identity, edges -1, edge_confs 1, first_node = best_node = -1, best_conf = -100.
+ * sta_graph_commit: connect_view_i_j for the k <= 16 candidate edges (view_i, view_j[e]) of one keyframe, in order.  Host arguments:
+ * the counts before the call, first_i / first_j[e] (the views' first nodes, -1 for none), accepted[e], conf[e]; device: pose[e] 4x4,
+ * and for an accepted edge depths[e], confs[e] fp32 [2,H,W] (side 0: view i) and intri[e] [3,3].  An accepted edge makes node n_i
+ * then n_j (slam.py:210-215).  Two launches, no allocation, no copy to the host, no synchronisation:
+ *   graph_reduce_kernel, grid (chunks, new nodes): one pass over the node's maps copies them to its pool slot and sums, per chunk,
+ *     c, and for a view with a first node f: w Dn Df, w Dn Dn with w = max(cn cf, 1e-6), and sqrt(cn cf) (slam.py:224-227,
+ *     pose_graph.py:41), every term in float64 from the fp32 inputs (w Dn first, then the second factor).  16-byte loads; a lane sums
+ *     its elements in ascending order, a wave by a shuffle tree, the 4 waves in order; the chunk's partial is stored.  When the first
+ *     node is made by an earlier edge of the SAME call its maps are read from the call's inputs, never from the slot being filled.
+ *   graph_link_kernel, one wave: lane l sums the chunk partials of new node l in ascending chunk order; lane 0 walks the accepted
+ *     edges in order: per node mean_conf = sum c / (H W), first_node, best node by strict > ; for a node with a first node f the
+ *     scale edge (n, f) with measurement (0, identity, sum w Dn Df / sum w Dn Dn) and weights (2,2,2,2,2,2, sum sqrt / (H W)), and
+ *     poses[n] = poses[f] * S; then sim3_ij = (t, q, 1) of pose[e] by sta_mat_to_se3's branch rule evaluated in float64;
+ *     poses[n_i] = poses[n_j] * sim3_ij iff view i had no node before this edge; the pose edge (n_i, n_j, sim3_ij, conf x 7).
+ *     Products are sta_sim3_op's multiplication, bit for bit.
+ * A rejected edge leaves no trace.  Refused (-1): k outside [1, 16], view_j[e] >= view_i or repeated, view_i >= max_views, a first
+ * node outside [-1, num_nodes), a missing or misaligned array of an accepted edge, a pool or edge store that would overflow.
+ * sta_graph_export: one launch, grid (chunks, n_views): the best node of every view < n_views gathered into poses fp32 [n,4,4]
+ * (rotation, translation), scales [n], depths, confs [n,H,W], intrinsics [n,3,3] - the arguments of sta_world_pointcloud; scaled:
+ * depth * (float)scale; filter: depth = 0 where conf < thres (get_view, slam.py:313-320).  A view without a node gives zeros. */
+typedef struct sta_graph_state {
+    int32_t max_nodes, max_edges, max_views, H, W, chunks;
+    double* poses;
+    int64_t* edges;
+    double* edge_poses;
+    double* edge_confs;
+    float* depth;
+    float* conf;
+    float* intri;
+    double* mean_conf;
+    int32_t* first_node;
+    int32_t* best_node;
+    double* best_conf;
+    double* partials;
+} sta_graph_state;
+STA_API int sta_graph_plan(int max_view_num, int neighbor_edge_num, int loop_edge_num, int H, int W, int64_t out[16]);
+STA_API int sta_graph_reset(sta_handle* h, const sta_graph_state* g, void* stream);
+STA_API int sta_graph_commit(sta_handle* h, const sta_graph_state* g, int num_nodes, int num_edges, int view_i, int first_i, int k,
+                             const int32_t* view_j, const int32_t* first_j, const uint8_t* accepted, const double* conf,
+                             const float* const* pose, const float* const* depths, const float* const* confs, const float* const* intri,
+                             int* num_nodes_out, int* num_edges_out, void* stream);
+STA_API int sta_graph_export(sta_handle* h, const sta_graph_state* g, int n_views, int scaled, int filter, float thres, float* poses,
+                             float* scales, float* depths, float* confs, float* intrinsics, void* stream);
+
 /* keyframe scheduler = OnlineSLAM.regress_two_views (vista_slam/slam.py:153-189) for ALL k candidate
  * edges (i, j_e) of a new keyframe i (the neighbour loop slam.py:263-265 and the loop-closure loop :273-277) in one
  * batched launch sequence instead of k sequential B=1 calls, with the reference's early reject kept:

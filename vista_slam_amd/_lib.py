@@ -29,6 +29,14 @@ class StaConfig(C.Structure):
                 ("ln_eps", C.c_float), ("precision", C.c_int32)]
 
 
+class StaGraphState(C.Structure):
+    """sta_graph_state of include/sta_mi355.h: the device arrays of one pose graph (vista_slam_amd/graph.py owns them)."""
+    _fields_ = [("max_nodes", C.c_int32), ("max_edges", C.c_int32), ("max_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("chunks", C.c_int32), ("poses", C.c_void_p), ("edges", C.c_void_p), ("edge_poses", C.c_void_p), ("edge_confs", C.c_void_p),
+                ("depth", C.c_void_p), ("conf", C.c_void_p), ("intri", C.c_void_p), ("mean_conf", C.c_void_p), ("first_node", C.c_void_p),
+                ("best_node", C.c_void_p), ("best_conf", C.c_void_p), ("partials", C.c_void_p)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _fp = C.c_void_p   # device float* passed as integer address
 
@@ -98,6 +106,11 @@ SIGNATURES = {
     "sta_pgo_solve": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, _fp, _i64, _fp, _fp, _vp]),
     "sta_pgo_optimize": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, C.c_double, _i, C.c_double, C.c_double,
                               C.c_double, C.c_double, C.c_double, _i, _fp, _i64, C.POINTER(C.c_double), _i, C.POINTER(_i), C.POINTER(_i), _vp]),
+    "sta_graph_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i64)]),
+    "sta_graph_reset": (_i, [_vp, C.POINTER(StaGraphState), _vp]),
+    "sta_graph_commit": (_i, [_vp, C.POINTER(StaGraphState), _i, _i, _i, _i, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p,
+                              C.POINTER(C.c_double), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i), _vp]),
+    "sta_graph_export": (_i, [_vp, C.POINTER(StaGraphState), _i, _i, _i, _f, _fp, _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views": (_i, [_vp, _fp, C.POINTER(_vp), _i, C.c_char_p, _f, _i, _i, _fp, C.POINTER(C.c_float),
                                C.POINTER(_i), C.POINTER(_i), _fp, _fp, _fp, _fp, _vp]),
     "sta_regress_views_begin": (_i, [_vp, _fp, C.POINTER(_vp), _i, _i, _i, _fp, _vp]),

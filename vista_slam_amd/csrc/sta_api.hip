@@ -16,6 +16,7 @@
 #include "flow.h"
 #include "loop.h"
 #include "pgo.h"
+#include "graph.h"
 
 #include <algorithm>
 #include <cmath>

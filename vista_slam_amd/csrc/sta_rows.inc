@@ -911,6 +911,124 @@ extern "C" int sta_pgo_optimize(sta_handle* h, double* nodes, const int32_t* edg
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The device-resident pose graph (kernels in graph.h; the contract is in include/sta_mi355.h).  sta_graph_plan holds every size and
+// refusal and is host only; the three device calls take the caller's arrays, launch on `stream` and return.
+static int graph_state_ok(const sta_graph_state* g) {
+    REQUIRE(g && g->poses && g->edges && g->edge_poses && g->edge_confs && g->depth && g->conf && g->intri && g->mean_conf && g->first_node && g->best_node &&
+            g->best_conf && g->partials, "graph: null array in the state");
+    REQUIRE(g->max_nodes >= 1 && g->max_nodes <= PGO_MAX_NODES && g->max_edges >= 1 && g->max_edges <= PGO_MAX_EDGES && g->max_views >= 1,
+            "graph: the state holds %d nodes, %d edges and %d views (at most %d nodes and %d edges)", g->max_nodes, g->max_edges, g->max_views, PGO_MAX_NODES, PGO_MAX_EDGES);
+    REQUIRE(g->H >= 16 && g->W >= 16 && g->H % 16 == 0 && g->W % 16 == 0, "graph: H and W must be positive multiples of 16 (got %d x %d)", g->H, g->W);
+    REQUIRE(g->chunks == (g->H * g->W + GRAPH_CHUNK - 1) / GRAPH_CHUNK, "graph: %d chunks for %d x %d maps (expected %d)", g->chunks, g->H, g->W,
+            (g->H * g->W + GRAPH_CHUNK - 1) / GRAPH_CHUNK);
+    REQUIRE((((uintptr_t)g->poses | (uintptr_t)g->edges | (uintptr_t)g->edge_poses | (uintptr_t)g->edge_confs | (uintptr_t)g->depth | (uintptr_t)g->conf |
+              (uintptr_t)g->intri | (uintptr_t)g->mean_conf | (uintptr_t)g->first_node | (uintptr_t)g->best_node | (uintptr_t)g->best_conf | (uintptr_t)g->partials) & 15) == 0,
+            "graph: every array of the state must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int sta_graph_plan(int max_view_num, int neighbor_edge_num, int loop_edge_num, int H, int W, int64_t out[16]) {
+    REQUIRE(out, "null argument");
+    REQUIRE(max_view_num >= 1 && neighbor_edge_num >= 1 && loop_edge_num >= 0, "graph: max_view_num and neighbor_edge_num must be positive, loop_edge_num >= 0 (got %d, %d, %d)",
+            max_view_num, neighbor_edge_num, loop_edge_num);
+    REQUIRE(H >= 16 && W >= 16 && H % 16 == 0 && W % 16 == 0 && (int64_t)H * W <= (1 << 24), "graph: H and W must be positive multiples of 16 with H W <= 2^24 (got %d x %d)", H, W);
+    const int64_t per = 2 * (int64_t)neighbor_edge_num + loop_edge_num;
+    const int64_t n = (int64_t)max_view_num * per, E = (int64_t)max_view_num * ((per - 1) + (per / 2 + 1));          // slam.py:33-36
+    REQUIRE(n <= PGO_MAX_NODES && E <= PGO_MAX_EDGES, "graph: %d views with %d neighbour and %d loop edges need %lld nodes and %lld edges, above the optimiser's limits of %d and %d",
+            max_view_num, neighbor_edge_num, loop_edge_num, (long long)n, (long long)E, PGO_MAX_NODES, PGO_MAX_EDGES);
+    const int64_t hw = (int64_t)H * W, chunks = (hw + GRAPH_CHUNK - 1) / GRAPH_CHUNK;
+    out[0] = n; out[1] = E; out[2] = GRAPH_CHUNK; out[3] = chunks;
+    out[4] = n * 64; out[5] = E * 16; out[6] = E * 64; out[7] = E * 56;
+    out[8] = n * (2 * hw + 9) * 4; out[9] = n * 8; out[10] = ((int64_t)max_view_num + 1) * 16; out[11] = GRAPH_MAX_CALL_NODES * chunks * 32;
+    out[12] = out[4] + out[5] + out[6] + out[7] + out[8] + out[9] + out[10] + out[11]; out[13] = (int64_t)max_view_num + 1; out[14] = out[15] = 0;
+    return 0;
+}
+
+extern "C" int sta_graph_reset(sta_handle* h, const sta_graph_state* g, void* stream) {
+    REQUIRE(h, "null argument");
+    CHK(graph_state_ok(g));
+    DEV_SCOPE(h->device);
+    GraphResetArgs a;
+    a.poses = g->poses; a.edge_poses = g->edge_poses; a.edge_confs = g->edge_confs; a.mean_conf = g->mean_conf; a.best_conf = g->best_conf;
+    a.edges = (long long*)g->edges; a.first_node = g->first_node; a.best_node = g->best_node;
+    a.max_nodes = g->max_nodes; a.max_edges = g->max_edges; a.max_views = g->max_views;
+    const int most = std::max(g->max_nodes, std::max(g->max_edges, g->max_views));
+    hipLaunchKernelGGL(graph_reset_kernel, dim3((most + 255) / 256), dim3(256), 0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_graph_commit(sta_handle* h, const sta_graph_state* g, int num_nodes, int num_edges, int view_i, int first_i, int k,
+                                const int32_t* view_j, const int32_t* first_j, const uint8_t* accepted, const double* conf,
+                                const float* const* pose, const float* const* depths, const float* const* confs, const float* const* intri,
+                                int* num_nodes_out, int* num_edges_out, void* stream) {
+    REQUIRE(h && view_j && first_j && accepted && conf && pose && depths && confs && intri && num_nodes_out && num_edges_out, "null argument");
+    CHK(graph_state_ok(g));
+    REQUIRE(k >= 1 && k <= GRAPH_MAX_CALL_EDGES, "graph: 1 .. %d candidate edges per call (got %d)", GRAPH_MAX_CALL_EDGES, k);
+    REQUIRE(num_nodes >= 0 && num_nodes <= g->max_nodes && num_edges >= 0 && num_edges <= g->max_edges, "graph: counts %d / %d outside the store of %d nodes and %d edges",
+            num_nodes, num_edges, g->max_nodes, g->max_edges);
+    REQUIRE(view_i >= 1 && view_i < g->max_views, "graph: view i must lie in [1, %d) (got %d)", g->max_views, view_i);
+    REQUIRE(first_i >= -1 && first_i < num_nodes, "graph: the first node of view %d must lie in [-1, %d) (got %d)", view_i, num_nodes, first_i);
+    const int hw = g->H * g->W;
+    GraphReduceArgs ra;
+    GraphLinkArgs la;
+    int nn = num_nodes, ne = num_edges, jobs = 0;
+    const float *i_depth = nullptr, *i_conf = nullptr;      // view i's first node, when an earlier edge of this call made it
+    for (int e = 0; e < k; ++e) {
+        REQUIRE(view_j[e] >= 0 && view_j[e] < view_i, "graph: edge %d connects view %d to view %d: j must lie in [0, i)", e, view_i, view_j[e]);
+        for (int f = 0; f < e; ++f) REQUIRE(view_j[f] != view_j[e], "graph: view %d is a candidate of view %d twice (edges %d and %d)", view_j[e], view_i, f, e);
+        REQUIRE(first_j[e] >= -1 && first_j[e] < num_nodes, "graph: the first node of view %d must lie in [-1, %d) (got %d)", view_j[e], num_nodes, first_j[e]);
+        if (!accepted[e]) continue;
+        REQUIRE(pose[e] && depths[e] && confs[e] && intri[e], "graph: accepted edge %d lacks its pose, maps or intrinsics", e);
+        REQUIRE((((uintptr_t)depths[e] | (uintptr_t)confs[e]) & 15) == 0 && (((uintptr_t)pose[e] | (uintptr_t)intri[e]) & 3) == 0, "graph: the maps of edge %d must be 16-byte aligned", e);
+        const int scale_edges = (first_i >= 0 ? 1 : 0) + (first_j[e] >= 0 ? 1 : 0);
+        REQUIRE(nn + 2 <= g->max_nodes, "graph: the pool of %d nodes is full (edge %d of view %d)", g->max_nodes, e, view_i);
+        REQUIRE(ne + scale_edges + 1 <= g->max_edges, "graph: the store of %d edges is full (edge %d of view %d)", g->max_edges, e, view_i);
+        const int n_i = nn, n_j = nn + 1;
+        GraphNodeJob& ji = ra.job[2 * jobs];
+        GraphNodeJob& jj = ra.job[2 * jobs + 1];
+        ji.depth = depths[e]; ji.conf = confs[e]; ji.intri = intri[e]; ji.node = n_i; ji.pad = 0;
+        jj.depth = depths[e] + hw; jj.conf = confs[e] + hw; jj.intri = intri[e]; jj.node = n_j; jj.pad = 0;
+        ji.ref_depth = ji.ref_conf = jj.ref_depth = jj.ref_conf = nullptr;
+        if (first_i >= 0) {
+            ji.ref_depth = i_depth ? i_depth : g->depth + (size_t)first_i * hw;
+            ji.ref_conf = i_conf ? i_conf : g->conf + (size_t)first_i * hw;
+        }
+        if (first_j[e] >= 0) { jj.ref_depth = g->depth + (size_t)first_j[e] * hw; jj.ref_conf = g->conf + (size_t)first_j[e] * hw; }
+        GraphEdgeJob& je = la.job[jobs];
+        je.pose = pose[e]; je.conf = conf[e]; je.n_i = n_i; je.n_j = n_j; je.first_i = first_i; je.first_j = first_j[e]; je.view_i = view_i; je.view_j = view_j[e];
+        if (first_i < 0) { first_i = n_i; i_depth = depths[e]; i_conf = confs[e]; }
+        nn += 2; ne += scale_edges + 1; ++jobs;
+    }
+    *num_nodes_out = nn; *num_edges_out = ne;
+    if (jobs == 0) return 0;
+    DEV_SCOPE(h->device);
+    ra.pool_depth = g->depth; ra.pool_conf = g->conf; ra.pool_intri = g->intri; ra.partials = g->partials; ra.hw = hw; ra.chunks = g->chunks;
+    la.partials = g->partials; la.poses = g->poses; la.edge_poses = g->edge_poses; la.edge_confs = g->edge_confs; la.mean_conf = g->mean_conf; la.best_conf = g->best_conf;
+    la.edges = (long long*)g->edges; la.first_node = g->first_node; la.best_node = g->best_node; la.n_jobs = jobs; la.num_edges = num_edges; la.hw = hw; la.chunks = g->chunks;
+    hipLaunchKernelGGL(graph_reduce_kernel, dim3(g->chunks, 2 * jobs), dim3(GRAPH_THREADS), 0, (hipStream_t)stream, ra);
+    hipLaunchKernelGGL(graph_link_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, la);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int sta_graph_export(sta_handle* h, const sta_graph_state* g, int n_views, int scaled, int filter, float thres, float* poses,
+                                float* scales, float* depths, float* confs, float* intrinsics, void* stream) {
+    REQUIRE(h && poses && scales && depths && confs && intrinsics, "null argument");
+    CHK(graph_state_ok(g));
+    REQUIRE(n_views >= 1 && n_views <= g->max_views, "graph: export of %d views from a graph of at most %d", n_views, g->max_views);
+    REQUIRE((((uintptr_t)depths | (uintptr_t)confs) & 15) == 0, "graph: the exported maps must be 16-byte aligned");
+    DEV_SCOPE(h->device);
+    GraphExportArgs a;
+    a.node_poses = g->poses; a.pool_depth = g->depth; a.pool_conf = g->conf; a.pool_intri = g->intri; a.best_node = g->best_node;
+    a.poses = poses; a.scales = scales; a.depths = depths; a.confs = confs; a.intrinsics = intrinsics;
+    a.hw = g->H * g->W; a.max_nodes = g->max_nodes; a.scaled = scaled ? 1 : 0; a.filter = filter ? 1 : 0; a.thres = thres;
+    hipLaunchKernelGGL(graph_export_kernel, dim3(g->chunks, n_views), dim3(GRAPH_THREADS), 0, (hipStream_t)stream, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // f4, continued: pp.mat2SE3
 extern "C" int sta_mat_to_se3(sta_handle* h, const float* poses, int B, float* se3_out, void* stream) {
     REQUIRE(h && poses && se3_out && B > 0, "bad argument");

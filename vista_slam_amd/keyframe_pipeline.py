@@ -16,7 +16,8 @@ reference's edge order - the same records whichever schedule produced them:
                has: add_view(i+1) needs no result of keyframe i (slam.py:258) and the edges of keyframe i need encoder
                features only (slam.py:153-162).
 
-What is NOT here is the reference's CPU side of the loop (the pypose Sim3 bookkeeping of connect_view_i_j; the pose-graph
+What is NOT here is the reference's CPU side of the loop (the pypose Sim3 bookkeeping of connect_view_i_j - that state lives in
+`vista_slam_amd.graph.PoseGraph`, under `vista_slam_amd.slam.OnlineSLAM`; the pose-graph
 optimisation itself is `vista_slam_amd.pgo.optimize`, on the device) nor the choice of the edges: the caller
 supplies `edge_list(i)` - from `vista_slam_amd.loop.LoopDetector.detect_loop`, which finds a keyframe's loop candidates on the device, or
 from anywhere else.  bench.py's `slam_replay` and tests/test_gpu_parity.py (the `seq_*` reference goldens) both run this.
