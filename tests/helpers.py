@@ -520,3 +520,36 @@ def conv_integer_inputs(n, H, W, Cin, Co, stride, nres, seed):
     b = rng.integers(-32, 33, size=Co).astype(np.float32)
     res = [rng.integers(-100, 101, size=(n, Ho, Wo, Co)).astype(np.float32) for _ in range(nres)]
     return x, w.reshape(Co, Cin, 3, 3).astype(np.float32), b, res
+
+
+# ---------------------------------------------------------------------------------------------------------
+# bit-level comparison of the outputs of two runs: tests/test_workspace_gpu.py and tests/test_stream_order_gpu.py
+def snapshot(outs):
+    """Outputs of a run, detached from the buffers the next run may reuse."""
+    import torch
+    torch.cuda.synchronize()
+    return [(name, t.detach().clone()) for name, t in outs]
+
+
+def bits(t):
+    import torch
+    t = t.contiguous().reshape(-1)
+    as_int = {torch.float32: torch.int32, torch.float64: torch.int64, torch.float16: torch.int16, torch.bfloat16: torch.int16}
+    return t.view(as_int[t.dtype]) if t.dtype in as_int else t
+
+
+def first_difference(got, ref):
+    """None when the two output lists are bit-identical, else text naming the first output that differs and where."""
+    import torch
+    if [n for n, _ in got] != [n for n, _ in ref]:
+        return f"the outputs themselves differ: {[n for n, _ in got]} against {[n for n, _ in ref]}"
+    for (name, a), (_n, b) in zip(got, ref):
+        if a.shape != b.shape or a.dtype != b.dtype:
+            return f"output {name}: {a.dtype} {tuple(a.shape)} against {b.dtype} {tuple(b.shape)}"
+        ne = bits(a) != bits(b)
+        if bool(ne.any()):
+            flat = int(torch.nonzero(ne)[0])
+            idx = tuple(int(v) for v in np.unravel_index(flat, tuple(a.shape))) if a.dim() else ()
+            return (f"output {name} {tuple(a.shape)}: {int(ne.sum())} of {ne.numel()} elements differ, first at index {idx}: "
+                    f"got {a.contiguous().reshape(-1)[flat].item()!r}, reference {b.contiguous().reshape(-1)[flat].item()!r}")
+    return None

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import workspace_cases as WC
+from helpers import first_difference, snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -61,36 +62,6 @@ def reset_switches(m):
     m.set_varlen_heads(False)
     _lib.check(m.lib.sta_debug_set_option(m._h, 8, 0))
     m.lib.sta_regress_views_abort(m._h, m._stream())
-
-
-def snapshot(outs):
-    """Outputs of a run, detached from the buffers the next run may reuse."""
-    import torch
-    torch.cuda.synchronize()
-    return [(name, t.detach().clone()) for name, t in outs]
-
-
-def bits(t):
-    import torch
-    t = t.contiguous().reshape(-1)
-    return t.view(torch.int32) if t.dtype == torch.float32 else (t.view(torch.int64) if t.dtype == torch.float64 else t)
-
-
-def first_difference(got, ref):
-    """None when the two output lists are bit-identical, else text naming the first output that differs and where."""
-    import torch
-    if [n for n, _ in got] != [n for n, _ in ref]:
-        return f"the outputs themselves differ: {[n for n, _ in got]} against {[n for n, _ in ref]}"
-    for (name, a), (_n, b) in zip(got, ref):
-        if a.shape != b.shape or a.dtype != b.dtype:
-            return f"output {name}: {a.dtype} {tuple(a.shape)} against {b.dtype} {tuple(b.shape)}"
-        ne = bits(a) != bits(b)
-        if bool(ne.any()):
-            flat = int(torch.nonzero(ne)[0])
-            idx = tuple(int(v) for v in np.unravel_index(flat, tuple(a.shape))) if a.dim() else ()
-            return (f"output {name} {tuple(a.shape)}: {int(ne.sum())} of {ne.numel()} elements differ, first at index {idx}: "
-                    f"got {a.contiguous().reshape(-1)[flat].item()!r}, reference {b.contiguous().reshape(-1)[flat].item()!r}")
-    return None
 
 
 def tail_bytes(G, m):

@@ -628,7 +628,9 @@ class STAFrontend:
 
     # ------------------------------------------------------------------ the encoder on token subsets
     def _subset_positions(self, B: int, hp: int, wp: int, pos, index) -> torch.Tensor:
-        """The one of `pos` [B, N, 2] / `index` [B, N] that was given -> device int64 [B, N, 2] (y, x) positions, checked on the host."""
+        """The one of `pos` [B, N, 2] / `index` [B, N] that was given -> device int64 [B, N, 2] (y, x) positions, checked on the host:
+        a selection in host memory is uploaded with a synchronous copy and one on the device is read back: either way the call waits
+        for its stream before the entry point is called (the entry points themselves never do)."""
         if (pos is None) == (index is None):
             raise ValueError("give exactly one of pos ([B, N, 2] (y, x) patch positions) and index ([B, N] into the row-major patch grid)")
         if index is not None:
