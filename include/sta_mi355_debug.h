@@ -29,6 +29,12 @@ STA_API int sta_set_gemm_variant(sta_handle* h, int variant);
  * (sta_launch.inc: pick_family). */
 STA_API int sta_debug_pick_family(int amode, int epi, long long M, int N, int K, int split, int cstride, int Ho, int Wo);
 
+/* Is there a kernel for this loader / epilogue / tile family / arithmetic (pure host function; sta_launch.inc: gemm_has_kernel -
+ * what gemm_plan asks before it returns a plan and what launch_gemm's dispatch instantiates by)?  amode, epi as above; family
+ * 1 .. 8 (7, the paired launch, is no launch_gemm kernel: 0); mx: f16mx rows and weights; split: 1 for the split precisions;
+ * N = Cout and cstride decide for the halo-tiled family 8 and the fused head only.  Returns 1 or 0. */
+STA_API int sta_debug_gemm_has_kernel(int amode, int epi, int family, int mx, int split, int N, int cstride);
+
 /* The launch plan of a dense GEMM / convolution (pure host function, no handle, no GPU; sta_launch.inc: gemm_plan, what
  * launch_gemm runs): tile family after the forced-family mapping and the f16mx remaps, its tile, the pose-token row tail the
  * skinny tail blocks compute, and the K slices.  M_all: every row, tail rows included; precision: STA_PREC_*; mx: f16mx rows and
@@ -36,7 +42,9 @@ STA_API int sta_debug_pick_family(int amode, int epi, long long M, int N, int K,
  * (0..4, 8, 9).  out[8] = {family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks}; the main tiles cover rows
  * [0, M_all - m_tail).  Fails when the plan would name a kernel that does not exist.  epi 5 below the small-grid predicate (where the
  * product never launches that epilogue): the plan of gemm_resid_ln's launch there - the fp32 epilogue in place with the handle's
- * slab, slab_ks > 1 when its K slices are left to resid_ln_kernel (N % 64 == 0, N <= 1024, forced_variant 0 or 9). */
+ * slab, slab_ks > 1 when its K slices are left to resid_ln_kernel (N % 64 == 0, N <= 1024, forced_variant 0 or 9).
+ * Refused as well: a (loader, epilogue) pair launch_gemm is not built for - amode 1 with an epilogue other than 1 / 6, amode 0 with
+ * epilogue 6 (sta_debug_gemm_has_kernel says 0 for every family). */
 STA_API int sta_debug_gemm_plan(int amode, int epi, int M_all, int N, int K, int precision, int mx, int tail_hint, int forced_variant, int* out);
 
 /* The launch plan of a 3x3 convolution (pure host function: gemm_plan with the implicit-GEMM loader and the image geometry, so

@@ -85,6 +85,10 @@ CASES = [
     _c("s6_s2_odd_even", 2, 7, 10, 32, 64, 2, PLAIN, 0, 6, 64),
     _c("s6_r2", 2, 9, 11, 64, 128, 1, R2, 0, 6, 64),
     _c("s6_forced2", 2, 19, 23, 96, 256, 1, R1, 2, 6, 64),            # a forced family never displaces the small-grid one
+    # the 4-WAVE form of family 6 (every case above runs at most 256 workgroups, i.e. the 8-wave form in the split arithmetics):
+    # 2 x 130 x 130 = 33800 pixels at Cout = 64 are 177 tiles of 192x128 - a small grid - and 265 workgroups of 128x64, too many
+    # for K slices (tests/test_conv_plan.py asserts the count)
+    _c("s6_four_waves", 2, 130, 130, 32, 64, 1, R1, 0, 6, 64),
     # ---- halo-tiled kernel (family 8, forced): W % 32 in {0, 1, 16, 31}, H % 8 != 0, every tap count parity
     # 256 columns: one tap per K step
     _c("h256_plain_w32", 2, 9, 32, 32, 256, 1, PLAIN, 8, 8, 256),

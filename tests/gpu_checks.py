@@ -116,8 +116,8 @@ def check_qkv_rope(precision, S=2, hp=3, wp=4, pose_tok=1, K=128, Cdim=128, seed
     b = torch.randn(3 * Cdim, generator=g) * 0.1
     heads = Cdim // 64
     npad = (ntok + 63) // 64 * 64
-    q = torch.empty(S, heads, ntok, 64, device=DEV)
-    k = torch.empty_like(q)
+    q = torch.full((S, heads, ntok, 64), float("nan"), device=DEV)      # (an element no block writes stays NaN and fails every bar)
+    k = torch.full_like(q, float("nan"))
     vt = torch.empty(S * heads * 64, npad, device=DEV)
     xd, Wd, bd = x.to(DEV), Wt.to(DEV), b.to(DEV)      # keep device inputs alive across the call
     _lib.check(lib.sta_debug_qkv_rope(h, xd.data_ptr(), Wd.data_ptr(), bd.data_ptr(), S, ntok, K, Cdim,
@@ -129,7 +129,8 @@ def check_qkv_rope(precision, S=2, hp=3, wp=4, pose_tok=1, K=128, Cdim=128, seed
     v = vt.cpu().numpy().reshape(S, heads, 64, npad)[..., :ntok].transpose(0, 1, 3, 2)
     pad = vt.cpu().numpy().reshape(S, heads, 64, npad)[..., ntok:]
     return {"q": max_rel(q.cpu().numpy(), qr), "k": max_rel(k.cpu().numpy(), kr), "v": max_rel(v, vr),
-            "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0}
+            "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0, "plan": last_plan(lib, h),
+            "nan": int(np.isnan(q.cpu().numpy()).sum() + np.isnan(k.cpu().numpy()).sum() + np.isnan(v).sum())}
 
 
 def check_attention(precision, S=2, heads=2, nq=197, nk=197, kv_shift=0, sharp=1.0, seed=2):

@@ -61,6 +61,23 @@ def test_forced_families_need_a_shape_above_the_small_grid_predicate(lib):
     assert plan(lib, EPI_F16, 2 * 19 * 23, 256, 9 * 96, 3, 0, 8, 1, 19, 23)["family"] == 8     # only the halo form is really forced
 
 
+def test_table_reaches_both_wave_forms_of_the_small_grid_family(lib):
+    """Family 6 runs on 8 waves up to 256 workgroups (K slices included) and on 4 waves beyond (sta_launch.inc: gemm_plan, FAM6 /
+    FAM6_LONE; plain f16 has the 4-wave form only): the table holds unsplit cases on both sides of that count."""
+    wgs = {}
+    for cid, n, H, W, Cin, Co, stride, relu_in, act, nres, variant, cls in CC.CASES:
+        if cls[0] != 6:
+            continue
+        Ho, Wo = CC.out_size(H, W, stride)
+        for arith, (prec, mx) in CC.PLAN_ARGS.items():
+            p = plan(lib, EPI_F16, n * Ho * Wo, Co, 9 * Cin, prec, mx, variant, stride, Ho, Wo)
+            wgs[(cid, arith)] = p["tiles_m"] * p["tiles_n"] * p["ksplit"]
+    for arith in CC.PLAN_ARGS:
+        assert wgs[("s6_four_waves", arith)] == 265, wgs
+        assert any(w <= 256 for (cid, a), w in wgs.items() if a == arith and cid != "s6_four_waves"), wgs
+    assert all(w <= 256 for (cid, a), w in wgs.items() if cid != "s6_four_waves"), wgs
+
+
 def test_conv_plan_sweep_invariants(lib):
     """gemm_plan on the convolution loader over host-only shapes (the dense sweep is tests/test_gemm_plan.py): every plan names a
     kernel that exists (the call fails otherwise), tiles the output exactly, keeps the small-grid family under forced 2 / 3 / 4,

@@ -21,10 +21,11 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 A_DENSE, EPI_F32 = 0, 0
 
 
-def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0, tail=0, plan=None):
+def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0, tail=0, plan=None, wg_over=None):
     """tail: the last `tail` rows are pose-token rows (tail hint).  The output starts as NaN - an element no block writes fails -
     or, with resid, as the residual itself (the in-place form x += A W^T: a row that two blocks add shows up as a wrong integer).
-    plan: the (family, m_tail) the launch must have run under.  Long K: operands in {-1, 0, 1} keep every sum exact."""
+    plan: the (family, m_tail) the launch must have run under; wg_over: its grid must have MORE main workgroups than this.
+    Long K: operands in {-1, 0, 1} keep every sum exact."""
     import torch
     import gpu_checks as G
     from vista_slam_amd import _lib
@@ -52,6 +53,8 @@ def _int_gemm(precision, M, N, K, variant, resid=False, via_f16=0, seed=0, tail=
         _lib.check(lib.sta_set_gemm_variant(h, 0))
     if plan is not None:
         assert (got_plan["family"], got_plan["m_tail"]) == plan, got_plan
+    if wg_over is not None:
+        assert got_plan["tiles_m"] * got_plan["tiles_n"] * got_plan["ksplit"] > wg_over, got_plan
     got = out.cpu().numpy().astype(np.float64)
     bad = np.argwhere(got != ref)
     assert bad.size == 0, f"{len(bad)} wrong elements, first (row, col) {bad[:4].tolist()}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}"
@@ -97,6 +100,25 @@ MX_TAIL_CASES = [dict(M=36 * 192 + 16, N=768, K=1024, variant=3, tail=16, resid=
 @pytest.mark.gpu
 @pytest.mark.parametrize("prec,kw", [(p, kw) for p in ("f16x3", "f16") for kw in TAIL_CASES] + [("mlp_mx", kw) for kw in MX_TAIL_CASES])
 def test_gemm_tail_integer_exact(prec, kw):
+    _int_gemm(prec, **kw)
+
+
+# Rows of the launch layer's dispatch table (sta_launch.inc: TileFamily x has_kernel) that no other case of the kernel tests launches,
+# at the smallest shapes that reach them, K = 2 GEMM_BK:
+#   * the fp32 epilogue in the f16mx arithmetic on 192x256 (forced 3; 6145 = 32 x 192 + 1 rows: above the small-grid predicate);
+#   * the plane epilogue on the 4-WAVE form of the small-grid family, split and f16mx operands: 513 rows x 3328 columns = 5 x 52 = 260
+#     workgroups, more than the 256 up to which the 8-wave form runs (and too many tiles for K slices);
+#   * the in-place residual epilogue on the register-staged 128x128 kernel (forced 1).
+DISPATCH_CASES = [("mlp_mx", dict(M=6145, N=768, K=64, variant=3, plan=(3, 0))),
+                  ("f16x3", dict(M=513, N=3328, K=64, variant=0, via_f16=1, plan=(6, 0), wg_over=256)),
+                  ("head_mx", dict(M=513, N=3328, K=64, variant=0, via_f16=1, plan=(6, 0), wg_over=256)),
+                  ("f16x3", dict(M=6145, N=768, K=64, variant=1, resid=True, plan=(1, 0))),
+                  ("f16", dict(M=6145, N=768, K=64, variant=1, resid=True, plan=(1, 0)))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec,kw", DISPATCH_CASES)
+def test_gemm_dispatch_rows_integer_exact(prec, kw):
     _int_gemm(prec, **kw)
 
 

@@ -295,3 +295,65 @@ def test_reference_op_goldens(G, prec):
     assert r["svd_orth"] < 1e-5, r
     assert r["bilinear"] < TOL[prec], r
     assert r["post_pts"] < TOL[prec] * 5 and r["post_conf"] < TOL[prec] * 5, r
+
+
+# Rows of the launch layer's dispatch table (sta_launch.inc: TileFamily x has_kernel) that no other kernel test launches, at the
+# smallest shapes that reach them, each with the plan of the launch asserted.
+# GELU and RoPE are no integer functions, so these rows keep the file's bars:
+#   * GELU on 192x256 (forced 3) and on the register-staged kernel (forced 1) above the small-grid predicate, and on the 4-WAVE form
+#     of the small-grid family: 641 rows x 5632 columns = 4 x 44 = 176 tiles of 192x128 (small grid), 6 x 88 = 528 workgroups of
+#     128x64 (more than the 256 up to which the 8-wave form runs);
+#   * the RoPE epilogue on the register-staged kernel (forced 1, the throughput shape of test_qkv_rope).
+@pytest.mark.parametrize("prec,kw,fam", [(p, kw, fam) for p in PRECS for kw, fam in (
+    (dict(M=6200, N=768, K=64, variant=3, act=1, via_f16=1), 3), (dict(M=6200, N=768, K=64, variant=1, act=1, via_f16=1), 1))] +
+    [("f16x3", dict(M=641, N=5632, K=64, act=1, via_f16=1), 6)])
+def test_gemm_dispatch_rows_gelu(G, prec, kw, fam):
+    r = G.check_gemm(prec, **kw)
+    assert (r["plan"]["family"], r["plan"]["ksplit"]) == (fam, 1), r
+    assert fam != 6 or r["plan"]["tiles_m"] * r["plan"]["tiles_n"] > 256, r
+    assert r["nan"] == 0, r
+    assert r["rel_l2"] < TOL[prec], r
+
+
+@pytest.mark.parametrize("prec", PRECS)
+def test_qkv_rope_dispatch_row_register_staged(G, prec):
+    r = G.check_qkv_rope(prec, hp=24, wp=32, pose_tok=0, S=4, K=64, Cdim=512, variant=1)
+    assert (r["plan"]["family"], r["plan"]["ksplit"], r["plan"]["m_tail"]) == (1, 1, 0), r
+    assert r["nan"] == 0, r
+    assert r["q"] < TOL[prec] and r["k"] < TOL[prec] and r["v"] < TOL[prec], r
+    assert r["vpad_abs"] == 0.0, r
+
+
+# The transposed-convolution scatter is an integer function: exact, on integers as in test_dpt_varlen_kernels.py (inputs in [-3, 3],
+# weights +-1, bias in [-32, 32]: |sum| <= 3 C + 32 <= 704, exact in every arithmetic), the output NaN before the launch.
+#   * the register-staged kernel (forced 1) above the small-grid predicate: 2 x 55 x 56 = 6160 pixels x 4 x 192 columns;
+#   * the 4-wave form of the small-grid family, split and f16mx operands: 2 x 16 x 20 = 640 pixels x 16 x 224 columns = 5 x 56 = 280
+#     workgroups of 128x64, too many for K slices.
+@pytest.mark.parametrize("prec,kw,fam", [("f16x3", dict(H=55, W_=56, Cdim=192, k=2, variant=1), 1), ("f16", dict(H=55, W_=56, Cdim=192, k=2, variant=1), 1),
+                                         ("f16x3", dict(H=16, W_=20, Cdim=224, k=4), 6), ("head_mx", dict(H=16, W_=20, Cdim=224, k=4), 6)])
+def test_convt_dispatch_rows_integer_exact(G, prec, kw, fam):
+    import numpy as np
+    import torch
+    from vista_slam_amd import _lib
+    n, H, W_, Cd, k, variant = 2, kw["H"], kw["W_"], kw["Cdim"], kw["k"], kw.get("variant", 0)
+    rng = np.random.default_rng(11 + k)
+    w = (rng.integers(0, 2, size=(Cd, Cd, k, k)) * 2 - 1).astype(np.float32)            # ConvTranspose2d layout [Cin, Cout, k, k]
+    b = rng.integers(-32, 33, size=Cd).astype(np.float32)
+    x = rng.integers(-3, 4, size=(n, H, W_, Cd)).astype(np.float32)
+    want = torch.nn.functional.conv_transpose2d(torch.from_numpy(x).double().permute(0, 3, 1, 2), torch.from_numpy(w).double(),
+                                                torch.from_numpy(b).double(), stride=k).permute(0, 2, 3, 1).numpy()
+    assert np.abs(want).max() <= 3 * Cd + 32 < 2048
+    m, lib, h = G.kernel_handle(prec, variant)
+    out = torch.full((n, H * k, W_ * k, Cd), float("nan"), device=G.DEV)
+    xd, wd, bd = G.dev(x), G.dev(w), G.dev(b)
+    try:
+        _lib.check(lib.sta_debug_convt(h, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), n, H, W_, Cd, k, out.data_ptr(), G.st()))
+        torch.cuda.synchronize()
+        plan = G.last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    assert (plan["family"], plan["ksplit"], plan["m_tail"]) == (fam, 1, 0), plan
+    assert fam != 6 or plan["tiles_m"] * plan["tiles_n"] > 256, plan
+    got = out.cpu().numpy().astype(np.float64)
+    bad = np.argwhere(~(got == want))
+    assert len(bad) == 0, f"{len(bad)} wrong elements ({int(np.isnan(got).sum())} NaN), first (image, y, x, channel) {bad[:4].tolist()}"

@@ -180,6 +180,7 @@ TEST_SIGNATURES = {
     "sta_debug_set_tail_hint": (_i, [_vp, _i]),
     "sta_debug_set_option": (_i, [_vp, _i, _i]),
     "sta_debug_pick_family": (_i, [_i, _i, C.c_longlong, _i, _i, _i, _i, _i, _i]),
+    "sta_debug_gemm_has_kernel": (_i, [_i, _i, _i, _i, _i, _i, _i]),
     "sta_debug_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sta_debug_last_gemm_plan": (_i, [_vp, C.POINTER(_i)]),
     "sta_debug_qkv_pair_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_i)]),

@@ -127,7 +127,8 @@ struct StreamCtx {
 // family: pick_family's ids (1 128x128 register-staged, 2 256x256, 3 192x256, 5 192x128, 6 128x64 small grid, 7 the paired
 // 192x128 launch, 8 halo-tiled 3x3 convolution); bm x bn = its tile; tiles_m x tiles_n main tiles cover rows [0, M - m_tail),
 // the m_tail rows after them run on the skinny tail blocks; ksplit K slices (slab_ks of them to the caller's slab).
-struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks; };
+// Internal (not among the 8 integers the debug hooks report): lone = family 6 on its 8-wave layout (sta_launch.inc: FAM6_LONE).
+struct GemmPlan { int family, bm, bn, m_tail, tiles_m, tiles_n, ksplit, slab_ks; bool lone = false; };
 // What run_attn decides before it launches attn_kernel (attn_plan, sta_launch.inc).  pose: AttnParams::pose (0 none, 1 side
 // blocks, 2 spare row of the last query block); prefetch: the 4-stage request-everything schedule instead of the double-buffered
 // loop; grid = qblocks x heads x S + pose_blocks workgroups; ntiles key tiles of 64, nfull of them whole; tail_stage: where the

@@ -41,22 +41,20 @@ __global__ void fill_rand_f16_kernel(f16* p, int64_t n, uint32_t seed, float sca
     }
 }
 
+template <bool SPLIT, int BM, int BN, int WMS, int WNS, int ABL>
+static int bench_launch2s(const GemmParams& p, hipStream_t st) {
+    constexpr int smem = gemm2_smem_bytes<SPLIT, BM, BN>();
+    constexpr auto kern = gemm2_kernel<SPLIT, A_DENSE, EPI_F32, BM, BN, WMS, WNS, ABL>;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    CHK(set_smem_once<kern>(dev, smem));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN))), dim3(WMS * WNS * 64), smem, st, p);
+    return 0;
+}
 template <int BM, int BN, int WMS, int WNS, int ABL>
 static int bench_launch2(bool split, const GemmParams& p, hipStream_t st) {
-    if (split) {
-        constexpr int smem = gemm2_smem_bytes<true, BM, BN>();
-        HIPCHK(hipFuncSetAttribute((const void*)gemm2_kernel<true, A_DENSE, EPI_F32, BM, BN, WMS, WNS, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        hipLaunchKernelGGL((gemm2_kernel<true, A_DENSE, EPI_F32, BM, BN, WMS, WNS, ABL>), dim3((unsigned)(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN))), dim3(WMS * WNS * 64), smem, st, p);
-    } else {
-#ifndef STA_DEV_FAST
-        constexpr int smem = gemm2_smem_bytes<false, BM, BN>();
-        HIPCHK(hipFuncSetAttribute((const void*)gemm2_kernel<false, A_DENSE, EPI_F32, BM, BN, WMS, WNS, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        hipLaunchKernelGGL((gemm2_kernel<false, A_DENSE, EPI_F32, BM, BN, WMS, WNS, ABL>), dim3((unsigned)(((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN))), dim3(WMS * WNS * 64), smem, st, p);
-#else
-        return set_err("development build: precision f16 kernels are not compiled in");
-#endif
-    }
-    return 0;
+    if (split) return bench_launch2s<true, BM, BN, WMS, WNS, ABL>(p, st);
+    STA_F16ONLY(return (bench_launch2s<false, BM, BN, WMS, WNS, ABL>(p, st)));
 }
 
 // tile: 0 = automatic product selection, 1 = 128x128, 2 = 256x256, 3 = 256x128; abl: gemm2 ablation (tile 2/3 only)

@@ -1,63 +1,128 @@
 // Launch layer of the STA path: tile-family cost model (pick_family), launch_gemm and the GEMM / convolution / LayerNorm / attention
 // wrappers the orchestration code calls.  Included by sta_api.hip (one translation unit; needs its types and macros).
+// ------------------------------------------------------------------------------------------ tile families
+// THE table of tile families: block tile BM x BN, WMS x WNS waves, NSTG stages of the LDS-DMA ring.  plan_tiles, the dispatch of
+// launch_gemm, the row-tail rule and the paired launch all read it, so a family's shape is stated here and nowhere else (the
+// cost model above pick_family keeps its own measured constants).  The kernels' template arguments are these numbers in this
+// order: bench.py and the tools match kernel symbols by them.  Not part of the table, because no family owns them: the 32-pixel
+// width of a halo tile (conv3h.h tiles an image in BM / 32 rows x 32 pixels for every Cout), the 32 rows a row tail may have, and
+// the chip's 256 CUs (the grid up to which family 6 runs on 8 waves, gemm_plan; the K-slice targets of sg_slices).
+struct TileFamily { int id, bm, bn, wms, wns, nstg; };
+constexpr TileFamily FAM1{1, GEMM_BM, GEMM_BN, 2, 2, 1};      // gemm.h: 128x128 register-staged, 256 threads (N % 128 != 0)
+constexpr TileFamily FAM2{2, 256, 256, 4, 4, 2};
+constexpr TileFamily FAM3{3, 192, 256, 3, 4, 2};
+constexpr TileFamily FAM5{5, 192, 128, 2, 4, 2};
+constexpr TileFamily FAM6{6, 128, 64, 2, 2, 3};               // small grids: 4 waves ...
+constexpr TileFamily FAM6_LONE{6, 128, 64, 4, 2, 3};          // ... or 8 where every workgroup is alone on its CU (GemmPlan::lone)
+constexpr TileFamily FAM7{7, FAM5.bm, FAM5.bn, FAM5.wms, FAM5.wns, FAM5.nstg};      // two 192x128 GEMMs in one grid (gemm_qkv_pair)
+constexpr TileFamily FAM8{8, 256, 256, 4, 4, 0};              // conv3h.h: BM / 32 rows x 32 pixels of one image, Cout = 256 ...
+constexpr TileFamily FAM8_N128{8, 256, 128, 4, 4, 0};         // ... and Cout = 128
+constexpr TileFamily NO_FAMILY{0, 0, 0, 0, 0, 0};
+constexpr int TAIL_BN = 32;                                   // columns of one skinny row-tail block (gemm2.h: gemm2_tail)
+constexpr const TileFamily* FAMILIES[] = {&FAM1, &FAM2, &FAM3, &FAM5, &FAM6, &FAM7, &FAM8};
+constexpr const TileFamily& tile_family(int id, int N = 0) {      // (the planner's view: family 6 by its 4-wave row, family 8 by Cout)
+    if (id == FAM8.id && N == FAM8_N128.bn) return FAM8_N128;
+    for (const TileFamily* f : FAMILIES) if (f->id == id) return *f;
+    return NO_FAMILY;
+}
+// THE existence predicate: is there a kernel for this loader / epilogue / tile family / arithmetic?  gemm_plan asks it at run
+// time; the dispatch of launch_gemm asks it in `if constexpr`, so what it denies is never instantiated and what it admits
+// must compile (tests/test_gemm_dispatch_table.py holds the library's kernel symbols to it).
+//   * launch_gemm exists for the six dense epilogues and for the plane and fused-head epilogues of the 3x3 convolution;
+//   * f16mx kernels exist for the DPT head's epilogues and (precision f16x3m) for the fp32 / in-place-residual epilogues of dense
+//     GEMMs: mlp.fc2.  The latter not on 256x256 (compile time), none on the register-staged family;
+//   * the RoPE epilogue exists on the 192x128 / 128x64 / 128x128 tiles only, the fused head on 192x128 and the Cout = 128 halo form;
+//   * the 8-wave small-grid form exists in the split arithmetics only;
+//   * family 7 is not a launch_gemm kernel (gemm_qkv_pair launches it under qkv_pair_plan).
+// Dead rows: (dense, EPI_F32R, family 6), both wave forms, all three arithmetics - five kernels - are admitted and instantiated but
+// no caller plans them: gemm_f32 (and sta_bench.inc) launch EPI_F32R only above the small-grid predicate, and family 6 is planned only
+// below it.  They stay because this table must describe the kernel list as it is; dropping them is a change of that list.
+constexpr bool has_kernel(int amode, int epi, const TileFamily& f, bool mx, bool split) {
+    const bool f32 = epi == EPI_F32 || epi == EPI_F32R;
+    if (amode == A_CONV3 ? !(epi == EPI_F16 || epi == EPI_HEAD) : !(amode == A_DENSE && epi >= EPI_F32 && epi <= EPI_F32R)) return false;
+    if (mx && !(epi == EPI_F16 || epi == EPI_CONVT || epi == EPI_HEAD || f32)) return false;
+    switch (f.id) {
+        case 1: return !mx && epi != EPI_HEAD;
+        case 2: return epi != EPI_QKV && epi != EPI_HEAD && !(mx && f32);
+        case 3: return epi != EPI_QKV && epi != EPI_HEAD;
+        case 5: return true;
+        case 6: return epi != EPI_HEAD && (f.wms == FAM6.wms || split || mx);
+        case 8: return amode == A_CONV3 && (epi == EPI_F16 || f.bn == FAM8_N128.bn);
+        default: return false;
+    }
+}
+// ... with the shape: the halo form runs stride 1 at Cout = its tile width, the fused head needs all 128 channels in one tile
+constexpr bool gemm_has_kernel(int amode, int epi, int family, bool mx, bool split, int N, int cstride) {
+    const TileFamily& f = tile_family(family, N);
+    return has_kernel(amode, epi, f, mx, split) && (f.id == 8 ? cstride == 1 && N == f.bn : epi != EPI_HEAD || N == f.bn);
+}
+#ifdef STA_TEST_HOOKS
+extern "C" int sta_debug_gemm_has_kernel(int amode, int epi, int family, int mx, int split, int N, int cstride) {
+    return gemm_has_kernel(amode, epi, family, mx != 0, split != 0, N, cstride) ? 1 : 0;
+}
+#endif
+
 // ------------------------------------------------------------------------------------------ launch helpers
+// Raises a kernel's dynamic-LDS limit once per device (one bit each: the attribute is set on the current device's copy of the
+// function).  The static belongs to the instantiation, i.e. to the kernel.
+template <auto Kernel>
+static int set_smem_once(int dev, int bytes) {
+    static unsigned done = 0;
+    if (!(done >> (dev & 31) & 1u)) {
+        HIPCHK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        done |= 1u << (dev & 31);
+    }
+    return 0;
+}
 template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WMS, int WNS, int NSTG = 2, bool MX = false>
 static int launch_gemm2(const GemmParams& p, hipStream_t st, int dev = 0, const VlGeo* geo = nullptr) {
-    static unsigned attr_done = 0;        // one bit per device: the attribute is set on the current device's copy of the function
     constexpr int smem = gemm2_smem_bytes<SPLIT, BM, BN>(NSTG);
+    const int tm = (p.M - p.m_tail + BM - 1) / BM, tn = (p.N + BN - 1) / BN, ks = p.ksplit > 1 ? p.ksplit : 1;
+    const int ntail = p.m_tail > 0 ? (p.N + TAIL_BN - 1) / TAIL_BN : 0;     // skinny tail blocks (gemm2_tail), first in the grid
+    const dim3 grid((unsigned)(tm * tn * ks + ntail)), block(WMS * WNS * 64);
     if (geo) {      // the varlen form of the same tile family (sta_head_pts_varlen): same grid, the geometry table next to the parameters
         if constexpr (SPLIT && (AMODE == A_CONV3 || EPI == EPI_CONVT)) {
-            static unsigned attr_done_v = 0;
-            auto kern = gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX, VlGeo>;
-            if (!(attr_done_v >> (dev & 31) & 1u)) {
-                HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-                attr_done_v |= 1u << (dev & 31);
-            }
+            constexpr auto kern = gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX, VlGeo>;
+            CHK(set_smem_once<kern>(dev, smem));
             REQUIRE(p.m_tail == 0, "internal: a varlen launch has no row tail");
-            const int tm = (p.M + BM - 1) / BM, tn = (p.N + BN - 1) / BN, ks = p.ksplit > 1 ? p.ksplit : 1;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(tm * tn * ks)), dim3(WMS * WNS * 64), smem, st, p, *geo);
+            hipLaunchKernelGGL(kern, grid, block, smem, st, p, *geo);
             return 0;
         } else REQUIRE(false, "internal: no varlen form of this GEMM (precision f16, or an epilogue that decodes no geometry)");
     }
-    if (!(attr_done >> (dev & 31) & 1u)) {
-        HIPCHK(hipFuncSetAttribute((const void*)gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done |= 1u << (dev & 31);
-    }
-    int tm = (p.M - p.m_tail + BM - 1) / BM, tn = (p.N + BN - 1) / BN;
-    const int ks = p.ksplit > 1 ? p.ksplit : 1;
-    const int ntail = p.m_tail > 0 ? (p.N + 31) / 32 : 0;     // skinny tail blocks (gemm2_tail), first in the grid
-    hipLaunchKernelGGL((gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX>), dim3((unsigned)(tm * tn * ks + ntail)), dim3(WMS * WNS * 64), smem, st, p);
+    constexpr auto kern = gemm2_kernel<SPLIT, AMODE, EPI, BM, BN, WMS, WNS, 0, NSTG, MX>;
+    CHK(set_smem_once<kern>(dev, smem));
+    hipLaunchKernelGGL(kern, grid, block, smem, st, p);
     return 0;
 }
 
 template <bool SPLIT, int EPI, int BM, int BN, bool MX, int WMS = 4, int WNS = 4>
 static int launch_conv3h(const GemmParams& p, hipStream_t st, int dev, const VlGeo* geo = nullptr) {
-    static unsigned attr_done = 0;        // one bit per device
     constexpr int smem = conv3h_smem_bytes<SPLIT, BM, BN>();
     static_assert(smem <= 160 * 1024, "conv3h: LDS budget");
     if (geo) {      // the varlen form: tiles = the sum of every entry's own tiles
         if constexpr (SPLIT) {
-            static unsigned attr_done_v = 0;
-            auto kv = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX, VlGeo>;
-            if (!(attr_done_v >> (dev & 31) & 1u)) {
-                HIPCHK(hipFuncSetAttribute((const void*)kv, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-                attr_done_v |= 1u << (dev & 31);
-            }
+            constexpr auto kv = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX, VlGeo>;
+            CHK(set_smem_once<kv>(dev, smem));
             const int64_t tiles = (int64_t)vl_tiles(*geo, BM / 32) * ((p.N + BN - 1) / BN);
             REQUIRE(tiles > 0 && tiles < ((int64_t)1 << 31), "internal: conv3h varlen grid");
             hipLaunchKernelGGL(kv, dim3((unsigned)tiles), dim3(WMS * WNS * 64), smem, st, p, *geo);
             return 0;
         } else REQUIRE(false, "internal: the varlen halo-tiled convolution has no precision-f16 form");
     }
-    auto kern = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX>;
-    if (!(attr_done >> (dev & 31) & 1u)) {
-        HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_done |= 1u << (dev & 31);
-    }
+    constexpr auto kern = conv3h_kernel<SPLIT, EPI, BM, BN, WMS, WNS, MX>;
+    CHK(set_smem_once<kern>(dev, smem));
     const int n_img = p.M / (p.Ho * p.Wo);
     const int tiles = n_img * ((p.Ho + BM / 32 - 1) / (BM / 32)) * ((p.Wo + 31) / 32) * ((p.N + BN - 1) / BN);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(WMS * WNS * 64), smem, st, p);
+    return 0;
+}
+// family 1: the register-staged kernel of gemm.h
+template <bool SPLIT, int AMODE, int EPI>
+static int launch_gemm1(const GemmParams& p, hipStream_t st, int dev) {
+    constexpr auto kern = gemm_kernel<SPLIT, AMODE, EPI>;
+    if constexpr (SPLIT) CHK(set_smem_once<kern>(dev, gemm_smem_bytes<SPLIT>()));      // (the f16 form fits the default limit)
+    const int tm = (p.M + FAM1.bm - 1) / FAM1.bm, tn = (p.N + FAM1.bn - 1) / FAM1.bn;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(tm * tn)), dim3(FAM1.wms * FAM1.wns * 64), gemm_smem_bytes<SPLIT>(), st, p);
     return 0;
 }
 
@@ -181,48 +246,32 @@ struct PlanQuery {
     bool deterministic;
     int inplace;                                // EPI_F32 added in place to its residual: 0 no, 1 with a caller slab, 2 without
     int cstride, Ho, Wo;                        // convolutions only
+    int lone_opt = 0;                           // h->opt[2]: 1 = never the 8-wave small-grid form, > 1 = its grid limit (A/B)
+    int geo_tiles = -1;                         // varlen launch under forced family 8: halo tiles of the entry table (else -1)
 };
-static GemmPlan plan_tiles(int family, int M, int m_tail, int N, int Ho, int Wo) {
-    GemmPlan g{family, 0, 0, m_tail, 0, 0, 1, 0};
-    switch (family) {
-        case 1: g.bm = GEMM_BM; g.bn = GEMM_BN; break;
-        case 2: g.bm = 256; g.bn = 256; break;
-        case 3: g.bm = 192; g.bn = 256; break;
-        case 5: case 7: g.bm = 192; g.bn = 128; break;
-        case 6: g.bm = 128; g.bn = 64; break;
-        case 8: g.bm = 256; g.bn = N == 128 ? 128 : 256; break;      // 8 rows x 32 pixels of one image
-    }
+// geo_tiles >= 0: the row tiles of a varlen halo launch (every entry's own tiles) instead of those of whole images
+static GemmPlan plan_tiles(int family, int M, int m_tail, int N, int Ho, int Wo, int geo_tiles = -1) {
+    const TileFamily& f = tile_family(family, N);
+    GemmPlan g{family, f.bm, f.bn, m_tail, 0, 0, 1, 0};
     if (g.bm == 0) return g;
-    if (family == 8) g.tiles_m = (int)((int64_t)M / ((int64_t)Ho * Wo) * ((Ho + 7) / 8) * ((Wo + 31) / 32));
+    const int rows = f.bm / 32;      // family 8: rows x 32 pixels of one image
+    if (family == 8) g.tiles_m = geo_tiles >= 0 ? geo_tiles : (int)((int64_t)M / ((int64_t)Ho * Wo) * ((Ho + rows - 1) / rows) * ((Wo + 31) / 32));
     else g.tiles_m = (M - m_tail + g.bm - 1) / g.bm;
     g.tiles_n = (N + g.bn - 1) / g.bn;
     return g;
 }
-// f16mx kernels exist for the DPT head's epilogues and (round 6, precision f16x3m) for the fp32 / in-place-residual epilogues of
-// dense GEMMs: mlp.fc2.  The latter only on the 192-row and small-grid families (no 256x256 instantiation: compile time).
-static bool mx_epi(int amode, int epi) {
-    return epi == EPI_F16 || epi == EPI_CONVT || epi == EPI_HEAD || (amode == A_DENSE && (epi == EPI_F32R || epi == EPI_F32));
-}
-// Is there a kernel for this family / epilogue / arithmetic?  Mirrors the launch branches of launch_gemm (each of which REQUIREs
-// it again instead of launching nothing).
-static bool plan_has_kernel(int amode, int epi, int family, bool mx, int N, int cstride) {
-    if (mx && !mx_epi(amode, epi)) return false;
-    if (family == 8) return amode == A_CONV3 && (epi == EPI_F16 || epi == EPI_HEAD) && cstride == 1 && (N == 128 || (N == 256 && epi == EPI_F16));
-    if (epi == EPI_HEAD) return family == 5 && N == 128;
-    switch (family) {
-        case 1: return !mx;
-        case 2: return epi != EPI_QKV && (!mx || epi == EPI_F16 || epi == EPI_CONVT);
-        case 3: return epi != EPI_QKV;
-        case 5: case 6: return true;
-        default: return false;
-    }
-}
 static int gemm_plan(const PlanQuery& q, GemmPlan& out) {
+    if (q.geo_tiles >= 0 && q.forced == 8 && gemm_has_kernel(q.amode, q.epi, 8, q.mx, q.split, q.N, q.cstride)) {
+        // the halo-tiled family on a varlen launch (forced: the cost model, which counts the tiles of ONE image size, never proposes it
+        // there): rows x 32 pixels of one ENTRY per tile, the tiles of all entries in one grid
+        out = plan_tiles(8, q.M, 0, q.N, q.Ho, q.Wo, q.geo_tiles);
+        return 0;
+    }
     // Row tail hint (decode_impl: the 2B pose-token rows after the 2B x N patch rows).  Tile rules below look at the patch
     // rows; the tail is kept only where the FINAL family tiles them exactly and has tail blocks (checked last).
     const bool mx_f32 = q.epi == EPI_F32R || q.epi == EPI_F32;       // mlp.fc2 in the f16mx arithmetic (precision f16x3m)
     int m_tail = 0;
-    if (q.amode == A_DENSE && q.tail_hint > 0 && q.tail_hint <= 32 && q.M > q.tail_hint && (!q.mx || mx_f32) && q.N % 128 == 0 && q.forced != 1) {
+    if (q.amode == A_DENSE && q.tail_hint > 0 && q.tail_hint <= 32 && q.M > q.tail_hint && (!q.mx || mx_f32) && q.N % FAM5.bn == 0 && q.forced != 1) {
         if (!small_grid_m(q.sg_mode, q.M - q.tail_hint, q.N)) m_tail = q.tail_hint;   // throughput scale only (the small-grid family splits K instead)
     }
     const int M = q.M - m_tail;
@@ -238,7 +287,7 @@ static int gemm_plan(const PlanQuery& q, GemmPlan& out) {
     // splitk_finish_kernel: fixed order, bit-reproducible) - the product path.  Only an in-place residual GEMM whose caller
     // passed no slab (forced tile families, N > 1024) still adds its slices with fp32 atomics, and not in deterministic mode.
     if (variant == 6) {
-        const int tiles_r = ((M + 127) / 128) * (q.N / 64);
+        const int tiles_r = ((M + FAM6.bm - 1) / FAM6.bm) * (q.N / FAM6.bn);
         const int tiles = q.deterministic ? (1 << 30) : tiles_r;    // deterministic: no ATOMIC split-K (the slab forms below have a fixed order)
         if (q.amode == A_DENSE && q.epi == EPI_F32 && q.inplace == 1) {
             // the caller finishes the GEMM in the LayerNorm kernel that follows (gemm_resid_ln): slices store partial tiles
@@ -281,30 +330,40 @@ static int gemm_plan(const PlanQuery& q, GemmPlan& out) {
     }
     // forced families (tests / tools): 1 = 128x128 register-staged, 2 = 256x256, 3 = 192x256 (both wherever N % 256 == 0 and
     // the epilogue is not the RoPE one), 4 = 192x128 everywhere
-    if ((q.forced == 2 || q.forced == 3) && variant != 6 && q.N % 128 == 0)
-        variant = (q.N % 256 == 0 && q.epi != EPI_QKV) ? q.forced : 5;
-    if (q.forced == 4 && variant != 6 && q.N % 128 == 0) variant = 5;
+    if ((q.forced == 2 || q.forced == 3) && variant != 6 && q.N % FAM5.bn == 0)
+        variant = (q.N % FAM2.bn == 0 && q.epi != EPI_QKV) ? q.forced : 5;
+    if (q.forced == 4 && variant != 6 && q.N % FAM5.bn == 0) variant = 5;
     if (q.forced == 1) variant = 1;
     // 8 forced (tests): the halo-tiled 3x3 convolution wherever it is legal (stride 1, Cout 128 / 256)
-    if (q.amode == A_CONV3 && (q.epi == EPI_F16 || q.epi == EPI_HEAD) && q.cstride == 1 && (q.N == 128 || q.N == 256) && q.forced == 8) variant = 8;
+    if (q.amode == A_CONV3 && (q.epi == EPI_F16 || q.epi == EPI_HEAD) && q.cstride == 1 && (q.N == FAM8_N128.bn || q.N == FAM8.bn) && q.forced == 8) variant = 8;
     if (variant != 6) { ksplit = 1; slab_ks = 0; }
     // f16mx arithmetic: no form of the register-staged kernel (use_mx() already requires N % 64 == 0), and the fp32 epilogues
     // have no 256x256 one.  Remapped BEFORE the row tail is checked: the tail must fit the tile the launch really uses.
     if (q.mx && variant == 1) variant = 5;
-    if (q.mx && mx_f32 && variant == 2) variant = q.N % 256 == 0 ? 3 : 5;
+    if (q.mx && mx_f32 && variant == 2) variant = q.N % FAM3.bn == 0 ? 3 : 5;
     GemmPlan g = plan_tiles(variant, q.M, 0, q.N, q.Ho, q.Wo);
-    if (m_tail && g.bm && (q.M - m_tail) % g.bm == 0 && gemm2_has_tail(q.amode, q.epi, g.bm, variant == 6 ? 3 : 2, q.mx))
+    if (m_tail && g.bm && (q.M - m_tail) % g.bm == 0 && gemm2_has_tail(q.amode, q.epi, g.bm, tile_family(variant, q.N).nstg, q.mx))
         g = plan_tiles(variant, q.M, m_tail, q.N, q.Ho, q.Wo);
     g.ksplit = ksplit; g.slab_ks = slab_ks;
-    REQUIRE(plan_has_kernel(q.amode, q.epi, variant, q.mx, q.N, q.cstride),
+    REQUIRE(gemm_has_kernel(q.amode, q.epi, variant, q.mx, q.split, q.N, q.cstride),
             "internal: no kernel for tile family %d, epilogue %d, f16mx %d, N = %d", variant, q.epi, (int)q.mx, q.N);
+    if (variant == 6 && (q.split || q.mx)) {
+        // A grid of <= 256 workgroups leaves every workgroup alone on its CU: with 4 waves (one per SIMD) the barrier, the DMA
+        // issue, the fragment reads and the MFMAs of a K tile simply add up (ablations, tools/ring_ablate.py: 0.12 + 0.14 + 0.09 +
+        // 0.19 = 0.54 us per K tile) - the same tile on 8 waves (two per SIMD, wave tile 32x32) lets one wave's MFMAs run under
+        // the other's issue and waits: encode -3.8 %, one pair @224 +4.1 %.  Larger grids (two workgroups per CU already) keep
+        // the 4-wave form, whose 64x32 wave tile reads 25 % fewer fragments (8 waves there: -1.2 ... -1.4 %).
+        const int sg_grid = g.tiles_m * (q.N / g.bn) * ksplit;
+        g.lone = sg_grid <= (q.lone_opt > 1 ? q.lone_opt : 256) && q.lone_opt != 1;
+    }
     out = g;
     return 0;
 }
-static PlanQuery plan_query(const sta_handle* h, int amode, int epi, const GemmParams& p) {
+static PlanQuery plan_query(const sta_handle* h, int amode, int epi, const GemmParams& p, const VlGeo* geo) {
     PlanQuery q{amode, epi, p.M, p.N, p.K, h->prec != STA_PREC_F16, p.mx != 0, h->tail_hint, h->gemm_variant,
                 h->small_grid_mode, h->opt[0] == 1 ? 1 : 0, h->opt[1] == 1 ? 1 : 0, h->deterministic,
-                (epi == EPI_F32 && p.resid == p.C32) ? (p.slab ? 1 : 2) : 0, p.cstride, p.Ho, p.Wo};
+                (epi == EPI_F32 && p.resid == p.C32) ? (p.slab ? 1 : 2) : 0, p.cstride, p.Ho, p.Wo, h->opt[2],
+                geo && h->gemm_variant == 8 ? vl_tiles(*geo, FAM8.bm / 32) : -1};      // (fewer than 2^31 / 8 tiles: every level has fewer than 2^31 pixels)
     return q;
 }
 #ifdef STA_TEST_HOOKS
@@ -342,7 +401,88 @@ extern "C" int sta_debug_conv_plan(int epi, int M, int N, int K, int precision, 
 }
 #endif
 
-static int no_mx_kernel(int family, int epi) { return set_err("internal: tile family %d has no f16mx form for epilogue %d", family, epi); }
+// Per-launch HIP-event timing (bench / tools): every launch (mode 2), or only the launches of ONE kernel symbol (mode 3,
+// sta_kernel_timing_filter: the event pairs break back-to-back dispatch, ~3.5 us each, so the timed region of bench.py carries
+// them on the dominant kernel only).  begin() before the launch opens the record (shape, flops, algorithmic bytes, start event),
+// end() after it closes it (end event, tile family).
+struct KTimer {
+    sta_handle* h; hipStream_t st;
+    bool timed = false; int family = 0;
+    int begin(int epi, int amode, int fam, int mx, int M, int N, int K, double flops, double bytes) {
+        family = fam;
+        timed = h->ktime && (h->ktime_all || (h->kfilter[0] == epi && h->kfilter[1] == amode && h->kfilter[2] == fam && h->kfilter[3] == mx));
+        if (timed && !h->ktime_all && !ksample(h)) timed = false;      // mode 3: a 1-in-kevery sample of the symbol's launches
+        if (!timed) return 0;
+        if ((int)h->kev.size() < 2 * (h->kn + 1)) {
+            hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
+            h->kev.push_back(a); h->kev.push_back(b);
+        }
+        if ((int)h->kflops.size() <= h->kn) h->kflops.resize(h->kn + 1);
+        h->kflops[h->kn] = flops;
+        if ((int)h->kshape.size() < 6 * (h->kn + 1)) h->kshape.resize(6 * (h->kn + 1));
+        { int* q = &h->kshape[6 * h->kn]; q[0] = M; q[1] = N; q[2] = K; q[3] = epi; q[4] = amode; q[5] = mx; }
+        if ((int)h->kbytes.size() <= h->kn) h->kbytes.resize(h->kn + 1);
+        h->kbytes[h->kn] = bytes;
+        HIPCHK(hipEventRecord(h->kev[2 * h->kn], st));
+        h->kn++;
+        return 0;
+    }
+    // the record's in-kernel stamp rows (sta_kernel_timing mode 4), or nullptr
+    unsigned long long* stamps() const {
+        return timed && h->kstamp_on && h->kn <= KSTAMP_LAUNCHES ? h->kstamp + (size_t)(h->kn - 1) * KSTAMP_WG * 4 : nullptr;
+    }
+    int end() {
+        if (!timed) return 0;
+        HIPCHK(hipEventRecord(h->kev[2 * (h->kn - 1) + 1], st));
+        if ((int)h->kvar.size() < h->kn) h->kvar.resize(h->kn);
+        h->kvar[h->kn - 1] = family;
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------------------------ dispatch
+// One kernel of the table: the predicate decides at compile time whether it exists, the family which launcher it takes.
+template <bool SPLIT, bool MX, int AMODE, int EPI, const TileFamily& F>
+static int launch_tile(const GemmParams& p, hipStream_t st, int dev, const VlGeo* geo) {
+    if constexpr (!has_kernel(AMODE, EPI, F, MX, SPLIT)) {
+        // unreachable after gemm_plan succeeded; fails instead of returning 0 with the output unwritten
+        return set_err("internal: no kernel for tile family %d (%dx%d, %d waves), epilogue %d, f16mx %d", F.id, F.bm, F.bn, F.wms * F.wns, EPI, (int)MX);
+    } else if constexpr (F.id == 8) {
+        REQUIRE(geo || ((int64_t)p.Ho * p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0), "internal: conv3h needs whole images");
+        REQUIRE(p.N == F.bn && p.cstride == 1, "internal: no halo-tiled convolution for epilogue %d at N = %d", EPI, p.N);
+        return launch_conv3h<SPLIT, EPI, F.bm, F.bn, MX, F.wms, F.wns>(p, st, dev, geo);
+    } else if constexpr (F.id == 1) {
+        REQUIRE(!geo, "internal: tile family %d planned for a varlen launch", F.id);
+        return launch_gemm1<SPLIT, AMODE, EPI>(p, st, dev);
+    } else {
+        REQUIRE(EPI != EPI_HEAD || p.N == F.bn, "internal: fused head epilogue on a tile family without it");
+        return launch_gemm2<SPLIT, AMODE, EPI, F.bm, F.bn, F.wms, F.wns, F.nstg, MX>(p, st, dev, geo);
+    }
+}
+// THE arithmetic choice: f16mx rows and weights, the split precisions, plain f16
+template <int AMODE, int EPI, const TileFamily& F>
+static int launch_family(const GemmParams& p, bool split, hipStream_t st, int dev, const VlGeo* geo) {
+    if (p.mx) return launch_tile<true, true, AMODE, EPI, F>(p, st, dev, geo);
+    if (split) return launch_tile<true, false, AMODE, EPI, F>(p, st, dev, geo);
+    STA_F16ONLY(return (launch_tile<false, false, AMODE, EPI, F>(p, st, dev, geo)));
+}
+// The finisher of a small-grid GEMM whose K slices went to fp32 partial sums (gemm_plan: ksplit > 1 without slab_ks): bias, RoPE /
+// activation and residuals, in a fixed summation order
+template <int EPI>
+static void finish_split_k(const GemmParams& p, bool split, hipStream_t st) {      // (the caller checks the launch)
+    if (EPI == EPI_QKV) {
+        const int64_t nthr = (int64_t)p.M * (p.nq + p.nk) + (int64_t)((p.M + 3) / 4) * p.nv;
+        const int blocks = (int)((nthr + 255) / 256);
+        if (split) hipLaunchKernelGGL(qkv_finish_kernel<true>, dim3(blocks), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(qkv_finish_kernel<false>, dim3(blocks), dim3(256), 0, st, p);
+    }
+    if (EPI == EPI_F16) {
+        const int64_t n4 = (int64_t)p.M * (p.N / 4);
+        const int blocks = (int)((n4 + 255) / 256);
+        if (split) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3(blocks), dim3(256), 0, st, p.skbuf, p.ksplit, p.bias, p.M, p.N, p.act, p.R1_hi, p.R2_hi, p.C_hi, p.c_rp, p.r_mx, p.c_mx, p.range);
+        else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3(blocks), dim3(256), 0, st, p.skbuf, p.ksplit, p.bias, p.M, p.N, p.act, p.R1_hi, p.R2_hi, p.C_hi, p.c_rp, 0, 0, p.range);
+    }
+}
 // slab_ks_out: K slices a slab GEMM wrote (0: it did not take the slab path) - the caller's finisher sums exactly those
 template <int AMODE, int EPI>
 static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, int* slab_ks_out = nullptr, const VlGeo* geo = nullptr) {
@@ -362,136 +502,32 @@ static int launch_gemm(sta_handle* h, const GemmParams& p_in, hipStream_t st, in
     // varlen launches (geo): every family but the register-staged family 1 has the form; forcing that one is refused here
     REQUIRE(!geo || h->gemm_variant != 1, "tile family %d has no varlen form (sta_head_pts_varlen runs on families 2 / 3 / 5 / 6 / 8)", h->gemm_variant);
     GemmPlan g;
-    if (geo && h->gemm_variant == 8 && AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD) && p.cstride == 1 && (p.N == 128 || (p.N == 256 && EPI == EPI_F16))) {
-        // the halo-tiled family on a varlen launch (forced: the cost model, which counts the tiles of ONE image size, never proposes it
-        // there): 8 rows x 32 pixels of one ENTRY per tile, the tiles of all entries in one grid
-        const int tm = vl_tiles(*geo, 8);          // (fewer than 2^31 / 8 tiles: every level has fewer than 2^31 pixels)
-        const int bn = p.N == 128 ? 128 : 256;
-        g = GemmPlan{8, 256, bn, 0, tm, (p.N + bn - 1) / bn, 1, 0};
-    } else CHK(gemm_plan(plan_query(h, AMODE, EPI, p), g));
+    CHK(gemm_plan(plan_query(h, AMODE, EPI, p, geo), g));
     h->last_plan = g;
-    const int variant = g.family;
     p.m_tail = g.m_tail;
     p.ksplit = g.ksplit;
     if (g.ksplit > 1 && (EPI == EPI_QKV || EPI == EPI_F16)) p.skbuf = lane_skbuf(h);
     if (g.slab_ks == 0) p.slab = nullptr;
     if (slab_ks_out) *slab_ks_out = g.slab_ks;
-    constexpr bool MX_EPI = EPI == EPI_F16 || EPI == EPI_CONVT || EPI == EPI_HEAD || (AMODE == A_DENSE && (EPI == EPI_F32R || EPI == EPI_F32));
-    constexpr bool MX_256 = MX_EPI && EPI != EPI_F32R && EPI != EPI_F32;
-    // per-launch HIP-event timing (bench / tools): every launch (mode 2), or only the launches of ONE kernel symbol
-    // (mode 3, sta_kernel_timing_filter: the event pairs break back-to-back dispatch, ~3.5 us each, so the timed region of
-    // bench.py carries them on the dominant kernel only)
-    bool timed = h->ktime && (h->ktime_all || (h->kfilter[0] == EPI && h->kfilter[1] == AMODE && h->kfilter[2] == variant && h->kfilter[3] == p.mx));
-    if (timed && !h->ktime_all && !ksample(h)) timed = false;      // mode 3: a 1-in-kevery sample of the symbol's launches
-    if (timed) {
-        if ((int)h->kev.size() < 2 * (h->kn + 1)) {
-            hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-            h->kev.push_back(a); h->kev.push_back(b);
-        }
-        if ((int)h->kflops.size() <= h->kn) h->kflops.resize(h->kn + 1);
-        h->kflops[h->kn] = 2.0 * p.M * p.N * p.K;
-        if ((int)h->kshape.size() < 6 * (h->kn + 1)) h->kshape.resize(6 * (h->kn + 1));
-        { int* q = &h->kshape[6 * h->kn]; q[0] = p.M; q[1] = p.N; q[2] = p.K; q[3] = EPI; q[4] = AMODE; q[5] = p.mx; }
-        if ((int)h->kbytes.size() <= h->kn) h->kbytes.resize(h->kn + 1);
-        // algorithmic bytes: A and W planes (2 B x planes) read once, C written once (+ residual read)
-        h->kbytes[h->kn] = (split ? 4.0 : 2.0) * ((double)p.M * p.K + (double)p.N * p.K) + 4.0 * p.M * p.N * (p.resid ? 2.0 : 1.0);
-        HIPCHK(hipEventRecord(h->kev[2 * h->kn], st));
-        h->kn++;
+    KTimer kt{h, st};
+    // algorithmic bytes: A and W planes (2 B x planes) read once, C written once (+ residual read)
+    CHK(kt.begin(EPI, AMODE, g.family, p.mx, p.M, p.N, p.K, 2.0 * p.M * p.N * p.K,
+                 (split ? 4.0 : 2.0) * ((double)p.M * p.K + (double)p.N * p.K) + 4.0 * p.M * p.N * (p.resid ? 2.0 : 1.0)));
+    if (kt.timed && g.family == 5) p.clk_dbg = h->clk_buf;   // effective-clock probe (bench only)
+    if (unsigned long long* s = kt.stamps()) p.stamps = s;
+    // the planned family -> its row of the table
+    switch (g.family) {
+        case 1: CHK((launch_family<AMODE, EPI, FAM1>(p, split, st, h->device, geo))); break;
+        case 2: CHK((launch_family<AMODE, EPI, FAM2>(p, split, st, h->device, geo))); break;
+        case 3: CHK((launch_family<AMODE, EPI, FAM3>(p, split, st, h->device, geo))); break;
+        case 5: CHK((launch_family<AMODE, EPI, FAM5>(p, split, st, h->device, geo))); break;
+        case 6: CHK(g.lone ? (launch_family<AMODE, EPI, FAM6_LONE>(p, split, st, h->device, geo)) : (launch_family<AMODE, EPI, FAM6>(p, split, st, h->device, geo))); break;
+        case 8: CHK(g.bn == FAM8_N128.bn ? (launch_family<AMODE, EPI, FAM8_N128>(p, split, st, h->device, geo)) : (launch_family<AMODE, EPI, FAM8>(p, split, st, h->device, geo))); break;
+        default: REQUIRE(false, "internal: tile family %d (f16mx %d) has no launch", g.family, p.mx);
     }
-    if (timed && variant == 5) p.clk_dbg = h->clk_buf;   // effective-clock probe (bench only)
-    if (timed && h->kstamp_on && h->kn <= KSTAMP_LAUNCHES) p.stamps = h->kstamp + (size_t)(h->kn - 1) * KSTAMP_WG * 4;
-    REQUIRE(!geo || variant != 1, "internal: tile family %d planned for a varlen launch", variant);
-    if constexpr (AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD)) {
-        if (variant == 8) {
-            REQUIRE(geo || ((int64_t)p.Ho * p.Wo > 0 && p.M % (p.Ho * p.Wo) == 0), "internal: conv3h needs whole images");
-            if (p.N == 128) {
-                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 128, true>(p, st, h->device, geo)));
-                else if (split) CHK((launch_conv3h<true, EPI, 256, 128, false>(p, st, h->device, geo)));
-                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 128, false>(p, st, h->device, geo))));
-            } else if constexpr (EPI == EPI_F16) {
-                if (p.mx) CHK((launch_conv3h<true, EPI, 256, 256, true>(p, st, h->device, geo)));
-                else if (split) CHK((launch_conv3h<true, EPI, 256, 256, false>(p, st, h->device, geo)));
-                else STA_F16ONLY(CHK((launch_conv3h<false, EPI, 256, 256, false>(p, st, h->device, geo))));
-            } else REQUIRE(false, "internal: no halo-tiled convolution for epilogue %d at N = %d", EPI, p.N);
-        }
-    }
-    // gemm_plan admitted only instantiated kernels; every branch below that has none for this plan fails instead of returning 0
-    // with the output unwritten
-    if (variant == 2 || variant == 3) REQUIRE(EPI != EPI_QKV, "internal: the RoPE epilogue exists on the 192x128 / 128x64 / 128x128 tiles only");
-    if (variant == 8) {
-        REQUIRE(AMODE == A_CONV3 && (EPI == EPI_F16 || EPI == EPI_HEAD), "internal: halo-tiled family for a GEMM without it");
-    } else
-    if constexpr (EPI == EPI_HEAD) {      // exists for the 192x128 family only (conv3_head checks the shape)
-        REQUIRE(variant == 5 && p.N == 128, "internal: fused head epilogue on a tile family without it");
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo))));
-    } else
-    if (variant == 2) {
-      if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_256) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device, geo)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 256, 256, 4, 4>(p, st, h->device, geo))));
-      } else REQUIRE(false, "internal: no 256x256 RoPE epilogue");
-    } else if (variant == 3) {
-      if constexpr (EPI != EPI_QKV) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device, geo)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 256, 3, 4>(p, st, h->device, geo))));
-      } else REQUIRE(false, "internal: no 192x256 RoPE epilogue");
-    } else if (variant == 5) {
-        if (p.mx) { if constexpr (MX_EPI) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4, 2, true>(p, st, h->device, geo))); else return no_mx_kernel(variant, EPI); }
-        else if (split) CHK((launch_gemm2<true, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo)));
-        else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 192, 128, 2, 4>(p, st, h->device, geo))));
-    } else if (variant == 6) {
-        // A grid of <= 256 workgroups leaves every workgroup alone on its CU: with 4 waves (one per SIMD) the barrier, the DMA
-        // issue, the fragment reads and the MFMAs of a K tile simply add up (ablations, tools/ring_ablate.py: 0.12 + 0.14 + 0.09 +
-        // 0.19 = 0.54 us per K tile) - the same tile on 8 waves (two per SIMD, wave tile 32x32) lets one wave's MFMAs run under
-        // the other's issue and waits: encode -3.8 %, one pair @224 +4.1 %.  Larger grids (two workgroups per CU already) keep
-        // the 4-wave form, whose 64x32 wave tile reads 25 % fewer fragments (8 waves there: -1.2 ... -1.4 %).
-        const int sg_grid = ((p.M + 127) / 128) * (p.N / 64) * (p.ksplit > 1 ? p.ksplit : 1);
-        const bool lone = sg_grid <= (h->opt[2] > 1 ? h->opt[2] : 256) && h->opt[2] != 1;
-        if (p.mx) {
-            if constexpr (MX_EPI) {
-                if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3, true>(p, st, h->device, geo)));
-                else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3, true>(p, st, h->device, geo)));
-            } else return no_mx_kernel(variant, EPI);
-        } else if (split) {
-            if (lone) CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 4, 2, 3>(p, st, h->device, geo)));
-            else CHK((launch_gemm2<true, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device, geo)));
-        } else STA_F16ONLY(CHK((launch_gemm2<false, AMODE, EPI, 128, 64, 2, 2, 3>(p, st, h->device, geo))));
-        if (EPI == EPI_QKV && p.ksplit > 1) {
-            const int64_t nthr = (int64_t)p.M * (p.nq + p.nk) + (int64_t)((p.M + 3) / 4) * p.nv;
-            const int blocks = (int)((nthr + 255) / 256);
-            if (split) hipLaunchKernelGGL(qkv_finish_kernel<true>, dim3(blocks), dim3(256), 0, st, p);
-            else hipLaunchKernelGGL(qkv_finish_kernel<false>, dim3(blocks), dim3(256), 0, st, p);
-            HIPCHK(hipGetLastError());
-        }
-        if (EPI == EPI_F16 && p.ksplit > 1) {
-            const int64_t n4 = (int64_t)p.M * (p.N / 4);
-            const int blocks = (int)((n4 + 255) / 256);
-            if (split) hipLaunchKernelGGL(splitk_finish_kernel<true>, dim3(blocks), dim3(256), 0, st, p.skbuf, p.ksplit, p.bias, p.M, p.N, p.act, p.R1_hi, p.R2_hi, p.C_hi, p.c_rp, p.r_mx, p.c_mx, p.range);
-            else hipLaunchKernelGGL(splitk_finish_kernel<false>, dim3(blocks), dim3(256), 0, st, p.skbuf, p.ksplit, p.bias, p.M, p.N, p.act, p.R1_hi, p.R2_hi, p.C_hi, p.c_rp, 0, 0, p.range);
-            HIPCHK(hipGetLastError());
-        }
-    } else {
-        REQUIRE(variant == 1 && !p.mx, "internal: tile family %d (f16mx %d) has no launch", variant, p.mx);
-        int tm = (p.M + GEMM_BM - 1) / GEMM_BM, tn = (p.N + GEMM_BN - 1) / GEMM_BN;
-        dim3 grid((unsigned)(tm * tn));
-        if (split) {
-            static unsigned attr_done = 0;
-            if (!(attr_done >> (h->device & 31) & 1u)) {
-                HIPCHK(hipFuncSetAttribute((const void*)gemm_kernel<true, AMODE, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, gemm_smem_bytes<true>()));
-                attr_done |= 1u << (h->device & 31);
-            }
-            hipLaunchKernelGGL((gemm_kernel<true, AMODE, EPI>), grid, dim3(256), gemm_smem_bytes<true>(), st, p);
-        } else {
-            STA_F16ONLY(hipLaunchKernelGGL((gemm_kernel<false, AMODE, EPI>), grid, dim3(256), gemm_smem_bytes<false>(), st, p));
-        }
-    }
+    if (g.ksplit > 1) finish_split_k<EPI>(p, split, st);      // (family 6 only)
     HIPCHK(hipGetLastError());
-    if (timed) { HIPCHK(hipEventRecord(h->kev[2 * (h->kn - 1) + 1], st)); if ((int)h->kvar.size() < h->kn) h->kvar.resize(h->kn); h->kvar[h->kn - 1] = variant; }
-    return 0;
+    return kt.end();
 }
 
 // mx: A is in the f16mx row format and the f16mx copy of the weight is used (transformer linears in precision f16mx)
@@ -579,12 +615,12 @@ static int gemm_qkv(sta_handle* h, const Planes& A, const Lin& W, int M, int nq,
 // of both halves as tail blocks (*m_tail) where the patch rows are whole 192-row tiles.
 static bool qkv_pair_plan(bool split, bool auto_fam, int sg_mode, int tail_hint, int M_a, int N_a, int K_a, bool mx_a,
                           int M_b, int N_b, int K_b, bool mx_b, int* m_tail) {
-    auto big = [sg_mode](int M, int N) { return N % 128 == 0 && !small_grid_m(sg_mode, M, N); };
+    auto big = [sg_mode](int M, int N) { return N % FAM7.bn == 0 && !small_grid_m(sg_mode, M, N); };
     *m_tail = 0;
     if (!(split && !mx_a && !mx_b && big(M_a, N_a) && big(M_b, N_b) && K_a == K_b && M_a == M_b && auto_fam)) return false;
     const int t = tail_hint;
-    if (t > 0 && t <= 32 && M_a > t && (M_a - t) % 192 == 0 && !small_grid_m(sg_mode, M_a - t, N_a) && !small_grid_m(sg_mode, M_b - t, N_b) &&
-        gemm2_has_tail(A_DENSE, EPI_QKV, 192, 2, false))
+    if (t > 0 && t <= 32 && M_a > t && (M_a - t) % FAM7.bm == 0 && !small_grid_m(sg_mode, M_a - t, N_a) && !small_grid_m(sg_mode, M_b - t, N_b) &&
+        gemm2_has_tail(A_DENSE, EPI_QKV, FAM7.bm, FAM7.nstg, false))
         *m_tail = t;
     return true;
 }
@@ -643,36 +679,21 @@ static int gemm_qkv_pair(sta_handle* h, const GemmParams& pa_in, const GemmParam
     pa.zero_page = pb.zero_page = h->zero_page;
     pa.ksplit = pb.ksplit = 1;
     pa.m_tail = pb.m_tail = m_tail;       // pose-token rows as skinny tail blocks (GemmParams::m_tail)
-    h->last_plan = GemmPlan{7, 192, 128, m_tail, (pa.M - m_tail + 191) / 192, pa.N / 128 + pb.N / 128, 1, 0};
-    const int ta = ((pa.M - pa.m_tail + 191) / 192) * (pa.N / 128) + (pa.m_tail ? pa.N / 32 : 0);
-    const int tb = ((pb.M - pb.m_tail + 191) / 192) * (pb.N / 128) + (pb.m_tail ? pb.N / 32 : 0);
-    bool timed = h->ktime && (h->ktime_all || (h->kfilter[0] == EPI_QKV && h->kfilter[1] == A_DENSE && h->kfilter[2] == 7 && h->kfilter[3] == 0));
-    if (timed && !h->ktime_all && !ksample(h)) timed = false;
-    if (timed) {      // one record: M x (Na + Nb) x K, tile family id 7 = gemm2_pair_kernel
-        if ((int)h->kev.size() < 2 * (h->kn + 1)) {
-            hipEvent_t a, b; HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-            h->kev.push_back(a); h->kev.push_back(b);
-        }
-        if ((int)h->kflops.size() <= h->kn) h->kflops.resize(h->kn + 1);
-        h->kflops[h->kn] = 2.0 * pa.M * (pa.N + pb.N) * pa.K;
-        if ((int)h->kshape.size() < 6 * (h->kn + 1)) h->kshape.resize(6 * (h->kn + 1));
-        { int* q = &h->kshape[6 * h->kn]; q[0] = pa.M; q[1] = pa.N + pb.N; q[2] = pa.K; q[3] = EPI_QKV; q[4] = A_DENSE; q[5] = 0; }
-        if ((int)h->kbytes.size() <= h->kn) h->kbytes.resize(h->kn + 1);
-        h->kbytes[h->kn] = 4.0 * (2.0 * pa.M * pa.K + (double)(pa.N + pb.N) * pa.K) + 4.0 * pa.M * (pa.N + pb.N);
-        HIPCHK(hipEventRecord(h->kev[2 * h->kn], st));
-        h->kn++;
-        if (h->kstamp_on && h->kn <= KSTAMP_LAUNCHES && ta + tb <= KSTAMP_WG) {
-            pa.stamps = h->kstamp + (size_t)(h->kn - 1) * KSTAMP_WG * 4; pb.stamps = pa.stamps + (size_t)ta * 4;
-        }
-    }
-    static unsigned attr_done = 0;      // one bit per device
-    constexpr int smem = gemm2_smem_bytes<true, 192, 128>(2);
-    auto kern = gemm2_pair_kernel<true, A_DENSE, EPI_QKV, 192, 128, 2, 4>;
-    if (!(attr_done >> (h->device & 31) & 1u)) { HIPCHK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); attr_done |= 1u << (h->device & 31); }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(ta + tb)), dim3(512), smem, st, pa, pb, ta);
+    constexpr const TileFamily& F = FAM7;
+    const GemmPlan g = plan_tiles(F.id, pa.M, m_tail, pa.N + pb.N, 0, 0);      // (both N are whole tiles, both M equal: qkv_pair_plan)
+    h->last_plan = g;
+    const int ta = g.tiles_m * (pa.N / F.bn) + (m_tail ? pa.N / TAIL_BN : 0);
+    const int tb = g.tiles_m * (pb.N / F.bn) + (m_tail ? pb.N / TAIL_BN : 0);
+    KTimer kt{h, st};      // one record: M x (Na + Nb) x K, tile family id 7 = gemm2_pair_kernel
+    CHK(kt.begin(EPI_QKV, A_DENSE, F.id, 0, pa.M, pa.N + pb.N, pa.K, 2.0 * pa.M * (pa.N + pb.N) * pa.K,
+                 4.0 * (2.0 * pa.M * pa.K + (double)(pa.N + pb.N) * pa.K) + 4.0 * pa.M * (pa.N + pb.N)));
+    if (unsigned long long* s = kt.stamps(); s && ta + tb <= KSTAMP_WG) { pa.stamps = s; pb.stamps = s + (size_t)ta * 4; }
+    constexpr int smem = gemm2_smem_bytes<true, F.bm, F.bn>(F.nstg);
+    constexpr auto kern = gemm2_pair_kernel<true, A_DENSE, EPI_QKV, F.bm, F.bn, F.wms, F.wns>;
+    CHK(set_smem_once<kern>(h->device, smem));
+    hipLaunchKernelGGL(kern, dim3((unsigned)(ta + tb)), dim3(F.wms * F.wns * 64), smem, st, pa, pb, ta);
     HIPCHK(hipGetLastError());
-    if (timed) { HIPCHK(hipEventRecord(h->kev[2 * (h->kn - 1) + 1], st)); if ((int)h->kvar.size() < h->kn) h->kvar.resize(h->kn); h->kvar[h->kn - 1] = 7; }
-    return 0;
+    return kt.end();
 }
 static int gemm_convt(sta_handle* h, const Planes& A, const Lin& W, int nimg, int hh, int ww, int k, int cout,
                       const Planes& out, hipStream_t st) {
@@ -1059,15 +1080,14 @@ static void attn_params(sta_handle* h, AttnParams& p, const QKVOut& qkv, const P
     p.scale_log2e = 0.125f * 1.44269504088896340736f;
 }
 // K names one attention kernel: K::fn<SPLIT>() is its instantiation (so that a -DSTA_DEV_FAST build never names the f16 one)
-struct AttnK { template <bool SPLIT> static auto fn() { return &attn_kernel<SPLIT>; } };
-struct AttnMixedK { template <bool SPLIT> static auto fn() { return &attn_mixed_kernel<SPLIT>; } };
-struct AttnVarlenK { template <bool SPLIT> static auto fn() { return &attn_varlen_kernel<SPLIT>; } };
+struct AttnK { template <bool SPLIT> static constexpr auto fn() { return &attn_kernel<SPLIT>; } };
+struct AttnMixedK { template <bool SPLIT> static constexpr auto fn() { return &attn_mixed_kernel<SPLIT>; } };
+struct AttnVarlenK { template <bool SPLIT> static constexpr auto fn() { return &attn_varlen_kernel<SPLIT>; } };
 template <class K, class P>
 static int launch_attn(sta_handle* h, int grid, int lds_bytes, const P& p, hipStream_t st) {
     if (h->prec != STA_PREC_F16) {
-        const auto kernel = K::template fn<true>();
-        static unsigned attr_done = 0;      // one bit per device (one set per kernel: the static belongs to this instantiation)
-        if (!(attr_done >> (h->device & 31) & 1u)) { hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, attn_smem_bytes<true>(ATT_PREFETCH_TILES)); attr_done |= 1u << (h->device & 31); }
+        constexpr auto kernel = K::template fn<true>();
+        CHK(set_smem_once<kernel>(h->device, attn_smem_bytes<true>(ATT_PREFETCH_TILES)));
         hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), lds_bytes, st, p);
     } else {
         STA_F16ONLY(hipLaunchKernelGGL(K::template fn<false>(), dim3((unsigned)grid), dim3(256), lds_bytes, st, p));
