@@ -14,6 +14,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libsta_mi355.so")
 TEST_LIB_PATH = os.path.join(PKG, "libsta_mi355_test.so")
+CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library with its own ABI (include/sta_cloud.h): `load_cloud()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -35,6 +36,12 @@ class StaGraphState(C.Structure):
                 ("chunks", C.c_int32), ("poses", C.c_void_p), ("edges", C.c_void_p), ("edge_poses", C.c_void_p), ("edge_confs", C.c_void_p),
                 ("depth", C.c_void_p), ("conf", C.c_void_p), ("intri", C.c_void_p), ("mean_conf", C.c_void_p), ("first_node", C.c_void_p),
                 ("best_node", C.c_void_p), ("best_conf", C.c_void_p), ("partials", C.c_void_p)]
+
+
+class StaNNIndex(C.Structure):
+    """sta_nn_index of include/sta_cloud.h: a host struct whose pointers point into the caller's device index buffer."""
+    _fields_ = [("cell_key", C.c_void_p), ("cell_start", C.c_void_p), ("sorted_pts", C.c_void_p), ("sorted_idx", C.c_void_p),
+                ("lo", C.c_int64 * 3), ("ext", C.c_int64 * 3), ("cell", C.c_double), ("M", C.c_int64), ("n_finite", C.c_int64), ("C", C.c_int64)]
 
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -205,8 +212,18 @@ TEST_SIGNATURES = {
     "sta_debug_workspace_tail": (_i, [_vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
+# include/sta_cloud.h: libsta_cloud.so, handle-free; NOT part of SIGNATURES (which stays equal to include/sta_mi355.h)
+CLOUD_SIGNATURES = {
+    "sta_nn_plan": (_i, [_i64, _i64, C.POINTER(_i64)]),
+    "sta_nn_build": (_i, [_fp, _i64, C.c_double, _vp, _i64, _vp, _i64, C.POINTER(StaNNIndex), _vp]),
+    "sta_nn_query": (_i, [C.POINTER(StaNNIndex), _fp, _i64, C.POINTER(C.c_double), C.c_double, _fp, _fp, _fp, _vp, _i64, _vp]),
+    "sta_cloud_transform": (_i, [_fp, _i64, C.POINTER(C.c_double), _fp, _vp]),
+    "sta_cloud_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _test_lib = None
+_cloud_lib = None
 
 
 class StaError(RuntimeError):
@@ -276,6 +293,29 @@ def load_test():
     _bind(lib, TEST_SIGNATURES, strict=True)
     _test_lib = lib
     return lib
+
+
+def load_cloud():
+    """Load libsta_cloud.so and bind every symbol of include/sta_cloud.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_cloud(rc)`."""
+    global _cloud_lib
+    if _cloud_lib is not None:
+        return _cloud_lib
+    if not os.path.exists(CLOUD_LIB_PATH):
+        raise _missing(CLOUD_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(CLOUD_LIB_PATH)
+    for name, (res, args) in CLOUD_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _cloud_lib = lib
+    return lib
+
+
+def check_cloud(rc):
+    if rc != 0:
+        raise StaError((load_cloud().sta_cloud_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

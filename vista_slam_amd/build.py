@@ -4,6 +4,8 @@
                                             #    vista_slam_amd/libsta_mi355_test.so   the same translation unit + -DSTA_TEST_HOOKS:
                                             #    additionally the kernel-level test / micro-benchmark entry points of
                                             #    include/sta_mi355_debug.h (loaded by tests/ and tools/ only)
+                                            #    vista_slam_amd/libsta_cloud.so        a second, handle-free library: exports include/sta_cloud.h
+                                            #    (nearest neighbours between clouds for the offline metrics; its own translation unit)
 """
 import os
 import shutil
@@ -17,6 +19,11 @@ TEST_LIB = os.path.join(PKG, "libsta_mi355_test.so")
 SOURCES = ["sta_api.hip"]
 DEPS = ["sta_exports.map", "sta_api.hip", "sta_launch.inc", "sta_forward.inc", "sta_debug.inc", "sta_rows.inc", "sta_bench.inc", "gemm.h", "gemm2.h", "conv3h.h", "attention.h", "elementwise.h", "geo.h", "select.h", "voxel.h", "flow.h", "loop.h", "pgo.h", "graph.h", "sta_common.h",
         os.path.join("..", "..", "include", "sta_mi355.h"), os.path.join("..", "..", "include", "sta_mi355_debug.h")]
+# libsta_cloud.so: nothing of it is in DEPS, so the product library's source_hash() does not move when it changes
+CLOUD_LIB = os.path.join(PKG, "libsta_cloud.so")
+CLOUD_SOURCES = ["sta_cloud.hip"]
+CLOUD_DEPS = ["sta_exports.map", "sta_cloud.hip", "cloud.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
+              os.path.join("..", "..", "include", "sta_cloud.h")]
 
 
 def hipcc_path():
@@ -34,6 +41,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", 
               "-Wl,--version-script=" + os.path.join(CSRC, "sta_exports.map")]
 HASH_FILE = LIB + ".srchash"
 TEST_HASH_FILE = TEST_LIB + ".srchash"
+CLOUD_HASH_FILE = CLOUD_LIB + ".srchash"
 
 
 def extra_flags():
@@ -47,51 +55,54 @@ def extra_flags():
     return f
 
 
-def source_hash():
+def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
-    snapshot copy, so staleness is decided by content) and of the build flags."""
+    snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
+    libraries) unless given (CLOUD_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
-    for d in DEPS:
+    for d in (DEPS if deps is None else deps):
         with open(os.path.join(CSRC, d), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
 
 
-def is_stale(lib=LIB, hash_file=HASH_FILE):
+def is_stale(lib=LIB, hash_file=HASH_FILE, deps=None):
     if not os.path.exists(lib) or not os.path.exists(hash_file):
         return True
     with open(hash_file) as f:
-        return f.read().strip() != source_hash()
+        return f.read().strip() != source_hash(deps)
 
 
-def _cmd(hipcc, out, hooks):
+def _cmd(hipcc, out, hooks, sources=None):
     return ([hipcc] + BASE_FLAGS + ["-o", out] + extra_flags() +
-            (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in SOURCES])
+            (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True):
-    """Build the product library and (test_hooks) the test-hooks library; both compile concurrently (one hipcc process each,
-    ~100 s).  Returns the product library's path."""
-    jobs = []
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True):
+    """Build the product library, (test_hooks) the test-hooks library and (cloud) libsta_cloud.so; all compile concurrently (one
+    hipcc process each, ~100 s).  Returns the product library's path."""
+    jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
-        jobs.append((LIB, HASH_FILE, False))
+        jobs.append((LIB, HASH_FILE, False, None, None))
     if test_hooks and (force or is_stale(TEST_LIB, TEST_HASH_FILE)):
-        jobs.append((TEST_LIB, TEST_HASH_FILE, True))
+        jobs.append((TEST_LIB, TEST_HASH_FILE, True, None, None))
+    if cloud and (force or is_stale(CLOUD_LIB, CLOUD_HASH_FILE, CLOUD_DEPS)):
+        jobs.append((CLOUD_LIB, CLOUD_HASH_FILE, False, CLOUD_SOURCES, CLOUD_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()
     if hipcc is None:
         raise RuntimeError("hipcc not found: cannot build libsta_mi355.so (ROCm toolchain required)")
     procs = []
-    for out, _hf, hooks in jobs:
-        cmd = _cmd(hipcc, out, hooks)
+    for out, _hf, hooks, sources, _deps in jobs:
+        cmd = _cmd(hipcc, out, hooks, sources)
         if verbose:
             print("[build]", " ".join(cmd), flush=True)
         procs.append((subprocess.Popen(cmd, cwd=CSRC), cmd))
     failed = None
-    for (p, cmd), (out, hf, _hooks) in zip(procs, jobs):
+    for (p, cmd), (out, hf, _hooks, _sources, deps) in zip(procs, jobs):
         if failed is not None:             # a sibling compile already failed: do not leave this one running un-waited
             p.kill()
             p.wait()
@@ -100,7 +111,7 @@ def build_lib(force=False, verbose=True, test_hooks=True):
             failed = subprocess.CalledProcessError(p.returncode, cmd)
             continue
         with open(hf, "w") as f:
-            f.write(source_hash())
+            f.write(source_hash(deps))
     if failed is not None:
         raise failed
     return LIB

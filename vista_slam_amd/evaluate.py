@@ -1,0 +1,182 @@
+"""Score a run: the surface of the reference's `vista_slam/eval/` (eval_traj.py, eval_recon.py) without evo, Open3D or pykdtree.
+
+Trajectory half (`align_traj`, `ape_translation`, `full_traj_eval`): Umeyama's Sim(3) alignment of the camera positions and the
+translation APE.  A trajectory is at most a few thousand poses: this half has no hot path and runs on the host in numpy float64.
+
+Reconstruction half (`eval_recon`, `eval_recon_from_saved_data`): world clouds, voxel down-sampling, point-to-point ICP and the clipped
+chamfer distance, all on the device (formats.world_pointcloud, formats.voxel_downsample, vista_slam_amd.cloud).
+
+What this is not: a comparison against evo, Open3D or pykdtree (none is available; ICP's loop and the alignment are restated from
+their published definitions, tests/cloud_cases.py holds the numpy restatement they are tested against); no plots.
+"""
+from __future__ import annotations
+
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from . import cloud, formats
+
+
+def _host(a):
+    if isinstance(a, torch.Tensor):
+        return a.detach().cpu().numpy()
+    if isinstance(a, (list, tuple)):
+        return np.stack([_host(v) for v in a], axis=0)
+    return np.asarray(a)
+
+
+def umeyama(x, y):
+    """Sim(3) (R, t, c) minimising sum |y_i - (c R x_i + t)|^2 (Umeyama 1991, evo's `umeyama_alignment` with scale):
+    cov = sum (y - mu_y)(x - mu_x)^T / n = U D V^T, S = diag(1, 1, sign(det U det V)), R = U S V^T, c = trace(D S) / var_x,
+    t = mu_y - c R mu_x."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    n = x.shape[0]
+    mx, my = x.mean(axis=0), y.mean(axis=0)
+    xc, yc = x - mx, y - my
+    var_x = (xc * xc).sum() / n
+    U, D, Vt = np.linalg.svd(yc.T @ xc / n)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0.0:
+        S[2, 2] = -1.0
+    R = U @ S @ Vt
+    c = np.trace(np.diag(D) @ S) / var_x
+    return R, my - c * (R @ mx), c
+
+
+def align_traj(traj_est_all, traj_ref_all):
+    """eval_traj.py:4-28.  Poses whose reference entry sums to NaN or Inf are dropped; the estimate is aligned to the reference with
+    scale: aligned pose i = (R R_i, c R t_i + t).  -> r_a [3,3], t_a [3], s, est_aligned [n,4,4], ref [n,4,4] (float64 numpy)."""
+    est_all, ref_all = _host(traj_est_all).astype(np.float64), _host(traj_ref_all).astype(np.float64)
+    keep = [i for i in range(len(ref_all)) if np.isfinite(ref_all[i].sum())]
+    if len(keep) < 3:
+        raise ValueError(f"align_traj needs at least 3 poses with a finite reference (got {len(keep)})")
+    est, ref = est_all[keep], ref_all[keep]
+    r_a, t_a, s = umeyama(est[:, :3, 3], ref[:, :3, 3])
+    aligned = est.copy()
+    aligned[:, :3, :3] = r_a @ est[:, :3, :3]
+    aligned[:, :3, 3] = s * (est[:, :3, 3] @ r_a.T) + t_a
+    return r_a, t_a, float(s), aligned, ref
+
+
+def ape_translation(est_aligned, ref):
+    """evo's APE on PoseRelation.translation_part: the statistics of e_i = ||t_est_i - t_ref_i||."""
+    e = np.linalg.norm(_host(est_aligned)[:, :3, 3].astype(np.float64) - _host(ref)[:, :3, 3].astype(np.float64), axis=1)
+    return {"rmse": float(np.sqrt(np.mean(e * e))), "mean": float(np.mean(e)), "median": float(np.median(e)), "std": float(np.std(e)),
+            "min": float(np.min(e)), "max": float(np.max(e)), "sse": float(np.sum(e * e))}
+
+
+def full_traj_eval(traj_est, traj_ref, plot_parent_dir=None, plot_name=None):
+    """eval_traj.py:62-75 without the plot (matplotlib and evo are absent; the two plot arguments are accepted and ignored).
+    -> traj_est (aligned), traj_ref, r_a, t_a, s, ape_statistics."""
+    r_a, t_a, s, est, ref = align_traj(traj_est, traj_ref)
+    return est, ref, r_a, t_a, s, ape_translation(est, ref)
+
+
+def eval_recon(frontend, gt_depths, gt_poses, gt_intri, est_depths, est_poses, est_intris, est_masks, rel_R, rel_t, rel_s, *,
+               voxel_size: float = 0.05, max_corr: float = 0.1, max_error: float = 0.5, return_stages: bool = False):
+    """eval_recon.py:108-178 on the device.
+      1. world clouds through formats.world_pointcloud: gt keeps pixels with gt_depth > 0, est keeps est_mask & gt_mask (the masks
+         go in as the confidence plane with threshold 0.5, scales of 1)
+      2. est <- s R est + t
+      3. both through formats.voxel_downsample(voxel_size)
+      4. cloud.icp of the down-sampled est onto an index of the down-sampled gt (cell = max_corr, init = I)
+      5. est <- T est, written as fp32 first, so that both chamfer directions see the same points (a stated difference: the
+         reference keeps float64 points)
+      6. cloud.chamfer(gt, est, max_error)
+    -> rmse_acc, rmse_comp, chamfer_dist, gt_points, est_points (device tensors) [, the stages as a dict]."""
+    dev = frontend.device
+    gt_depths = torch.as_tensor(gt_depths).to(dev, torch.float32)
+    N, H, W = gt_depths.shape
+    est_depths = torch.as_tensor(est_depths).to(dev, torch.float32)
+    est_masks = torch.as_tensor(est_masks).to(dev)
+    gt_poses, est_poses = torch.as_tensor(gt_poses).to(dev, torch.float32), torch.as_tensor(est_poses).to(dev, torch.float32)
+    if not (len(est_depths) == len(est_masks) == len(est_poses) == len(gt_poses) == N):
+        raise ValueError("eval_recon: the view counts differ")
+    gt_K = torch.as_tensor(gt_intri).to(dev, torch.float32)
+    if gt_K.dim() == 2:
+        gt_K = gt_K[None].expand(N, 3, 3)
+    est_K = torch.as_tensor(est_intris).to(dev, torch.float32)
+    if est_K.dim() == 2:
+        est_K = est_K[None].expand(N, 3, 3)
+    ones = torch.ones(N, device=dev)
+    gt_mask = gt_depths > 0
+    both = (est_masks.reshape(N, H, W) > 0) & gt_mask
+    gt_pts, _ = formats.world_pointcloud(frontend, gt_depths, ones, gt_K, gt_poses, gt_mask.float(), None, 0.5)
+    est_raw, _ = formats.world_pointcloud(frontend, est_depths, ones, est_K, est_poses, both.float(), None, 0.5)
+    if gt_pts.shape[0] == 0 or est_raw.shape[0] == 0:
+        raise ValueError("eval_recon: an empty cloud")
+    sR = float(rel_s) * np.asarray(_host(rel_R), dtype=np.float64).reshape(3, 3)
+    rel = np.concatenate([sR, np.asarray(_host(rel_t), dtype=np.float64).reshape(3, 1)], axis=1)
+    est_pts = cloud.transform(est_raw, rel)
+    est_down, _ = formats.voxel_downsample(frontend, est_pts, voxel_size=voxel_size)
+    gt_down, _ = formats.voxel_downsample(frontend, gt_pts, voxel_size=voxel_size)
+    reg = cloud.icp(est_down, cloud.NNIndex.build(gt_down, max_corr), max_corr)
+    est_final = cloud.transform(est_pts, reg.T)
+    ch = cloud.chamfer(gt_pts, est_final, max_error)
+    out = (ch.rmse_1, ch.rmse_2, ch.chamfer, gt_pts, est_final)
+    if return_stages:
+        out += (dict(est_raw=est_raw, rel=rel, est_pts=est_pts, est_down=est_down, gt_down=gt_down, icp=reg),)
+    return out
+
+
+def load_data(output_folder, load_view_graph=True, load_gt_depths=True, load_gt_poses=True, load_gt_intrinsic=True, load_unscaled_depths=True,
+              load_scales=True, load_intrinsics=True, load_confs=True, load_poses=True):
+    """eval_recon.py:7-35: what formats.save_data_all wrote, as a plain namespace (no munch)."""
+    data = {}
+    j = lambda name: os.path.join(output_folder, name)
+    if load_view_graph:
+        z = np.load(j("view_graph.npz"), allow_pickle=True)
+        data["view_graph"] = z["view_graph"].item()
+        data["loop_min_dist"] = z["loop_min_dist"].item()
+        data["view_names"] = z["view_names"].tolist()
+    if load_gt_depths:
+        data["gt_depths"] = np.load(j("gt_depths.npy"))
+    if load_gt_poses:
+        data["gt_poses"] = np.load(j("gt_poses.npy"))
+    if load_gt_intrinsic:
+        data["gt_intrinsic"] = np.load(j("gt_intrinsics.npy"))
+    if load_unscaled_depths:
+        data["unscaled_depths"] = np.load(j("depths.npy"))
+    if load_scales:
+        data["scales"] = np.load(j("scales.npy"))[..., None]          # [N, 1, 1]
+    if load_intrinsics:
+        data["intrinsics"] = np.load(j("intrinsics.npy"))
+    if load_confs:
+        z = np.load(j("confs.npz"))
+        data["confs"] = z["confs"]
+        data["conf_thres"] = z["thres"].item()
+    if load_poses:
+        data["poses"] = np.load(j("trajectory.npy"))
+    return SimpleNamespace(**data)
+
+
+def eval_recon_from_saved_data(frontend, output_folder, rel_est_gt=None, **kwargs):
+    """eval_recon.py:181-206.  rel_est_gt: None (align_traj of the saved poses) or [R, t, s]."""
+    d = load_data(output_folder, load_view_graph=False)
+    est_depths = (d.unscaled_depths * d.scales).astype(np.float32)
+    est_masks = (d.confs > d.conf_thres).astype(np.float32)
+    if rel_est_gt is not None:
+        rel_R, rel_t, rel_s = rel_est_gt
+    else:
+        rel_R, rel_t, rel_s, _, _ = align_traj(d.poses, d.gt_poses)
+    return eval_recon(frontend, d.gt_depths.astype(np.float32), d.gt_poses.astype(np.float32), d.gt_intrinsic, est_depths,
+                      d.poses.astype(np.float32), d.intrinsics.astype(np.float32), est_masks, rel_R, rel_t, rel_s, **kwargs)
+
+
+def eval_slam(slam, gt_poses, gt_depths=None, gt_intrinsic=None):
+    """The metrics of a run held by an `OnlineSLAM`: -> dict(ape = the APE statistics, r_a, t_a, s) and, with the ground-truth
+    depth maps and intrinsics, rmse_acc, rmse_comp and chamfer."""
+    ex = slam.pose_graph.export(view_num=slam.view_num)
+    est, ref, r_a, t_a, s, stats = full_traj_eval(ex.poses, gt_poses)
+    out = {"ape": stats, "r_a": r_a, "t_a": t_a, "s": s}
+    if gt_depths is not None:
+        if gt_intrinsic is None:
+            raise ValueError("eval_slam: gt_depths needs gt_intrinsic")
+        N = ex.depths.shape[0]
+        acc, comp, ch, _, _ = eval_recon(slam.frontend, gt_depths, gt_poses, gt_intrinsic, ex.depths * ex.scales.reshape(N, 1, 1), ex.poses,
+                                         ex.intrinsics, ex.confs > slam.conf_thres, r_a, t_a, s)
+        out.update(rmse_acc=acc, rmse_comp=comp, chamfer=ch)
+    return out
