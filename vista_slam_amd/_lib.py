@@ -15,6 +15,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libsta_mi355.so")
 TEST_LIB_PATH = os.path.join(PKG, "libsta_mi355_test.so")
 CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library with its own ABI (include/sta_cloud.h): `load_cloud()`
+RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (include/sta_raster.h): `load_raster()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -221,9 +222,21 @@ CLOUD_SIGNATURES = {
     "sta_cloud_last_error": (C.c_char_p, []),
 }
 
+# include/sta_raster.h: libsta_raster.so, handle-free; a table of its own like CLOUD_SIGNATURES
+_dp = C.POINTER(C.c_double)
+RASTER_SIGNATURES = {
+    "sta_raster_plan": (_i, [_i, _i, _i, C.POINTER(_i64)]),
+    "sta_raster_clear": (_i, [_vp, _i, _i, _i, _vp]),
+    "sta_raster_points": (_i, [_vp, _i, _i, _i, _fp, _vp, _i, _i64, _i64, _dp, _dp, C.c_double, C.c_double, _i, _vp, _vp]),
+    "sta_raster_lines": (_i, [_vp, _i, _i, _i, _fp, _vp, _i64, _dp, _dp, C.c_double, C.c_double, _i, _vp]),
+    "sta_raster_resolve": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_uint8), _vp, _vp, _vp, _vp]),
+    "sta_raster_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _test_lib = None
 _cloud_lib = None
+_raster_lib = None
 
 
 class StaError(RuntimeError):
@@ -316,6 +329,29 @@ def load_cloud():
 def check_cloud(rc):
     if rc != 0:
         raise StaError((load_cloud().sta_cloud_last_error() or b"unknown error").decode())
+
+
+def load_raster():
+    """Load libsta_raster.so and bind every symbol of include/sta_raster.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_raster(rc)`."""
+    global _raster_lib
+    if _raster_lib is not None:
+        return _raster_lib
+    if not os.path.exists(RASTER_LIB_PATH):
+        raise _missing(RASTER_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(RASTER_LIB_PATH)
+    for name, (res, args) in RASTER_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _raster_lib = lib
+    return lib
+
+
+def check_raster(rc):
+    if rc != 0:
+        raise StaError((load_raster().sta_raster_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

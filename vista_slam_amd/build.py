@@ -6,6 +6,8 @@
                                             #    include/sta_mi355_debug.h (loaded by tests/ and tools/ only)
                                             #    vista_slam_amd/libsta_cloud.so        a second, handle-free library: exports include/sta_cloud.h
                                             #    (nearest neighbours between clouds for the offline metrics; its own translation unit)
+                                            #    vista_slam_amd/libsta_raster.so       a third, handle-free library: exports include/sta_raster.h
+                                            #    (the headless z-buffer rasteriser of vista_slam_amd/render.py; its own translation unit)
 """
 import os
 import shutil
@@ -24,6 +26,10 @@ CLOUD_LIB = os.path.join(PKG, "libsta_cloud.so")
 CLOUD_SOURCES = ["sta_cloud.hip"]
 CLOUD_DEPS = ["sta_exports.map", "sta_cloud.hip", "cloud.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
               os.path.join("..", "..", "include", "sta_cloud.h")]
+# libsta_raster.so: likewise a library of its own; neither of the hashes above covers it
+RASTER_LIB = os.path.join(PKG, "libsta_raster.so")
+RASTER_SOURCES = ["sta_raster.hip"]
+RASTER_DEPS = ["sta_exports.map", "sta_raster.hip", "raster.h", "sta_common.h", os.path.join("..", "..", "include", "sta_raster.h")]
 
 
 def hipcc_path():
@@ -42,6 +48,7 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", 
 HASH_FILE = LIB + ".srchash"
 TEST_HASH_FILE = TEST_LIB + ".srchash"
 CLOUD_HASH_FILE = CLOUD_LIB + ".srchash"
+RASTER_HASH_FILE = RASTER_LIB + ".srchash"
 
 
 def extra_flags():
@@ -58,7 +65,7 @@ def extra_flags():
 def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (CLOUD_DEPS)."""
+    libraries) unless given (CLOUD_DEPS, RASTER_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
@@ -80,9 +87,9 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True):
-    """Build the product library, (test_hooks) the test-hooks library and (cloud) libsta_cloud.so; all compile concurrently (one
-    hipcc process each, ~100 s).  Returns the product library's path."""
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True):
+    """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so and (raster) libsta_raster.so; all
+    compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
@@ -90,6 +97,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True):
         jobs.append((TEST_LIB, TEST_HASH_FILE, True, None, None))
     if cloud and (force or is_stale(CLOUD_LIB, CLOUD_HASH_FILE, CLOUD_DEPS)):
         jobs.append((CLOUD_LIB, CLOUD_HASH_FILE, False, CLOUD_SOURCES, CLOUD_DEPS))
+    if raster and (force or is_stale(RASTER_LIB, RASTER_HASH_FILE, RASTER_DEPS)):
+        jobs.append((RASTER_LIB, RASTER_HASH_FILE, False, RASTER_SOURCES, RASTER_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()
