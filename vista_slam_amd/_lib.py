@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(PKG, "libsta_mi355.so")
 TEST_LIB_PATH = os.path.join(PKG, "libsta_mi355_test.so")
 CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library with its own ABI (include/sta_cloud.h): `load_cloud()`
 RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (include/sta_raster.h): `load_raster()`
+TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (include/sta_tsdf.h): `load_tsdf()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -233,10 +234,24 @@ RASTER_SIGNATURES = {
     "sta_raster_last_error": (C.c_char_p, []),
 }
 
+# include/sta_tsdf.h: libsta_tsdf.so, handle-free; a table of its own like the two above
+_i64p = C.POINTER(_i64)
+TSDF_SIGNATURES = {
+    "sta_tsdf_plan": (_i, [_i64, _i, _i, C.c_double, C.c_double, _i64, _i64, _i64, _i64p]),
+    "sta_tsdf_table": (_i, [C.POINTER(C.c_int8)]),
+    "sta_tsdf_blocks": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, C.c_double, C.c_double, _dp, C.c_double, _vp, _i64, _vp, _i64, _i64p, _vp]),
+    "sta_tsdf_clear": (_i, [_vp, _vp, _vp, _i64, _vp]),
+    "sta_tsdf_integrate": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i64, _i64, C.c_double, C.c_double, _dp, C.c_double,
+                                C.c_double, _vp]),
+    "sta_tsdf_mesh": (_i, [_vp, _i64, _vp, _vp, _vp, C.c_double, _dp, C.c_double, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64p, _vp]),
+    "sta_tsdf_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _test_lib = None
 _cloud_lib = None
 _raster_lib = None
+_tsdf_lib = None
 
 
 class StaError(RuntimeError):
@@ -352,6 +367,29 @@ def load_raster():
 def check_raster(rc):
     if rc != 0:
         raise StaError((load_raster().sta_raster_last_error() or b"unknown error").decode())
+
+
+def load_tsdf():
+    """Load libsta_tsdf.so and bind every symbol of include/sta_tsdf.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_tsdf(rc)`."""
+    global _tsdf_lib
+    if _tsdf_lib is not None:
+        return _tsdf_lib
+    if not os.path.exists(TSDF_LIB_PATH):
+        raise _missing(TSDF_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(TSDF_LIB_PATH)
+    for name, (res, args) in TSDF_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _tsdf_lib = lib
+    return lib
+
+
+def check_tsdf(rc):
+    if rc != 0:
+        raise StaError((load_tsdf().sta_tsdf_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():
