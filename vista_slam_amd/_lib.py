@@ -17,6 +17,7 @@ TEST_LIB_PATH = os.path.join(PKG, "libsta_mi355_test.so")
 CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library with its own ABI (include/sta_cloud.h): `load_cloud()`
 RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (include/sta_raster.h): `load_raster()`
 TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (include/sta_tsdf.h): `load_tsdf()`
+MESH_LIB_PATH = os.path.join(PKG, "libsta_mesh.so")        # a fifth one (include/sta_mesh.h): `load_mesh()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -247,11 +248,20 @@ TSDF_SIGNATURES = {
     "sta_tsdf_last_error": (C.c_char_p, []),
 }
 
+# include/sta_mesh.h: libsta_mesh.so, handle-free; a table of its own like the three above
+MESH_SIGNATURES = {
+    "sta_mesh_plan": (_i, [_i64, _i64, _i64p]),
+    "sta_mesh_triangles": (_i, [_vp, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _dp, _dp, _i, _i, _i64, _dp, _dp, C.c_double, C.c_double, _vp, _vp, _i64, _vp]),
+    "sta_mesh_vertex_normals": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "sta_mesh_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _test_lib = None
 _cloud_lib = None
 _raster_lib = None
 _tsdf_lib = None
+_mesh_lib = None
 
 
 class StaError(RuntimeError):
@@ -390,6 +400,29 @@ def load_tsdf():
 def check_tsdf(rc):
     if rc != 0:
         raise StaError((load_tsdf().sta_tsdf_last_error() or b"unknown error").decode())
+
+
+def load_mesh():
+    """Load libsta_mesh.so and bind every symbol of include/sta_mesh.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_mesh(rc)`."""
+    global _mesh_lib
+    if _mesh_lib is not None:
+        return _mesh_lib
+    if not os.path.exists(MESH_LIB_PATH):
+        raise _missing(MESH_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(MESH_LIB_PATH)
+    for name, (res, args) in MESH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _mesh_lib = lib
+    return lib
+
+
+def check_mesh(rc):
+    if rc != 0:
+        raise StaError((load_mesh().sta_mesh_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

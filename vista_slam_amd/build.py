@@ -10,6 +10,8 @@
                                             #    (the headless z-buffer rasteriser of vista_slam_amd/render.py; its own translation unit)
                                             #    vista_slam_amd/libsta_tsdf.so         a fourth, handle-free library: exports include/sta_tsdf.h
                                             #    (sparse TSDF fusion and marching tetrahedra of vista_slam_amd/tsdf.py; its own translation unit)
+                                            #    vista_slam_amd/libsta_mesh.so         a fifth, handle-free library: exports include/sta_mesh.h
+                                            #    (triangles for the rasteriser's key buffer and vertex normals; its own translation unit)
 """
 import os
 import shutil
@@ -37,6 +39,11 @@ TSDF_LIB = os.path.join(PKG, "libsta_tsdf.so")
 TSDF_SOURCES = ["sta_tsdf.hip"]
 TSDF_DEPS = ["sta_exports.map", "sta_tsdf.hip", "tsdf.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
              os.path.join("..", "..", "include", "sta_tsdf.h")]
+# libsta_mesh.so: likewise; it includes raster.h, voxel.h, select.h and elementwise.h unchanged (and include/sta_raster.h for its limits)
+MESH_LIB = os.path.join(PKG, "libsta_mesh.so")
+MESH_SOURCES = ["sta_mesh.hip"]
+MESH_DEPS = ["sta_exports.map", "sta_mesh.hip", "mesh.h", "raster.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
+             os.path.join("..", "..", "include", "sta_mesh.h"), os.path.join("..", "..", "include", "sta_raster.h")]
 
 
 def hipcc_path():
@@ -57,6 +64,7 @@ TEST_HASH_FILE = TEST_LIB + ".srchash"
 CLOUD_HASH_FILE = CLOUD_LIB + ".srchash"
 RASTER_HASH_FILE = RASTER_LIB + ".srchash"
 TSDF_HASH_FILE = TSDF_LIB + ".srchash"
+MESH_HASH_FILE = MESH_LIB + ".srchash"
 
 
 def extra_flags():
@@ -73,7 +81,7 @@ def extra_flags():
 def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS)."""
+    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
@@ -95,9 +103,9 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True):
-    """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so, (raster) libsta_raster.so and (tsdf)
-    libsta_tsdf.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True):
+    """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so, (raster) libsta_raster.so, (tsdf)
+    libsta_tsdf.so and (mesh) libsta_mesh.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
@@ -109,6 +117,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
         jobs.append((RASTER_LIB, RASTER_HASH_FILE, False, RASTER_SOURCES, RASTER_DEPS))
     if tsdf and (force or is_stale(TSDF_LIB, TSDF_HASH_FILE, TSDF_DEPS)):
         jobs.append((TSDF_LIB, TSDF_HASH_FILE, False, TSDF_SOURCES, TSDF_DEPS))
+    if mesh and (force or is_stale(MESH_LIB, MESH_HASH_FILE, MESH_DEPS)):
+        jobs.append((MESH_LIB, MESH_HASH_FILE, False, MESH_SOURCES, MESH_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()

@@ -6,8 +6,14 @@ is a 64-bit key (depth bits, then colour or id) merged with an integer atomic mi
 order the hardware runs the points in.  The same key buffer gives the colour image, a depth map of the fused map from any pose, and an
 id image (which point is visible at each pixel).  Cameras and the line geometry are host float64 numpy: they have no hot path.
 
-Not here: Open3D, rerun, a live window; meshes, lighting, text; round or anti-aliased points (footprints are squares, smoothing is box
-supersampling); GL's diamond-exit line rule (the DDA of the header instead).  DESIGN.md section 9.
+Triangles come from a library of their own, libsta_mesh.so (include/sta_mesh.h, restated in tests/mesh_cases.py): `Canvas.mesh` draws an
+indexed mesh - a `tsdf.Mesh` - into the same key buffer with exact integer coverage on a 1/256-pixel grid, a near-plane clip and
+perspective-correct depth and colour, so the mesh, the cloud and the lines occlude each other in any issue order; `render_mesh`,
+`mesh_depth` and `render_folder(mesh=)` sit on it.
+
+Not here: Open3D, rerun, a live window; text; round or anti-aliased points (footprints are squares, smoothing is box supersampling); GL's
+diamond-exit line rule (the DDA of the header instead); for triangles: far-plane and 2-D polygon clipping (a per-fragment far test and a
+drop beyond 2^28 sub-pixels instead), smooth shading (one two-sided light factor per face), textures, transparency.  DESIGN.md section 9.
 """
 from __future__ import annotations
 
@@ -32,6 +38,10 @@ CUR_CAMERA_COLOR = (19, 80, 27)
 NEIGHBOR_EDGE_COLOR = (0, 0, 255)
 LOOP_EDGE_COLOR = (255, 128, 0)
 TRAJECTORY_COLOR = (220, 30, 30)
+MESH_COLOR = (200, 200, 200)
+MESH_MODES = {"shaded": 1, "color": 1, "normal": 2, "id": 0}          # -> STA_MESH_PAYLOAD_*
+MESH_CULL = {"none": 0, "back": 1, "front": 2}
+MESH_COUNTERS = ("seen", "bad", "behind", "clipped", "too_large", "degenerate", "culled", "off_canvas")
 FRUSTUM_LINES = ((0, 1), (0, 2), (0, 3), (0, 4), (1, 2), (2, 3), (3, 4), (4, 1))
 
 
@@ -54,7 +64,7 @@ def plan(H: int, W: int, ssaa: int = 1) -> Plan:
 
 
 def _value_error(e: _lib.StaError):
-    return ValueError(str(e)) if str(e).startswith("raster_") else e
+    return ValueError(str(e)) if str(e).startswith(("raster_", "mesh_")) else e
 
 
 def _host(a, dtype=np.float64):
@@ -183,6 +193,8 @@ class Canvas:
         self.lib = _lib.load_raster()
         self.keys = torch.empty(self.plan.Hs, self.plan.Ws, dtype=torch.int64, device=self.device)      # uint64 bit patterns
         self._counters = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._mesh_counters = torch.zeros(len(MESH_COUNTERS), dtype=torch.int64, device=self.device)
+        self._mesh_work = None                     # the triangle pass's list of large pieces: grown on demand, kept
         self.clear()
 
     def _stream(self):
@@ -203,6 +215,7 @@ class Canvas:
 
     def clear(self):
         self._counters.zero_()
+        self._mesh_counters.zero_()
         self._check(self.lib.sta_raster_clear(self.keys.data_ptr(), self.H, self.W, self.ssaa, self._stream()))
         return self
 
@@ -233,6 +246,56 @@ class Canvas:
         self._check(self.lib.sta_raster_lines(self.keys.data_ptr(), self.H, self.W, self.ssaa, segs.data_ptr(), col.data_ptr(), len(segs), T, K, near, far,
                                               int(line_width), self._stream()))
         return self
+
+    def mesh(self, camera: Camera, mesh_or_verts, triangles=None, colors=None, mode: str = "shaded", cull: str = "none", ambient: float = 0.3,
+             color=MESH_COLOR, id_base: int = 0):
+        """A `tsdf.Mesh` (its colours are used unless `colors` is given), or vertices [nv,3] with triangles [nt,3] int32 and optional
+        colours [nv,3] floating point in [0, 1].  mode "color": the vertex colours, perspective-correct (without colours: `color`, three
+        bytes, everywhere); "shaded": the same times a two-sided light factor per face, ambient + (1 - ambient) |cos|, with the light at
+        the camera's centre; "normal": the face normal as a colour; "id": id_base + the triangle's index (`ids()`).  cull "back" does not
+        draw the faces seen from behind (a top-down camera then looks into a room through its ceiling), "front" the others."""
+        if mode not in MESH_MODES:
+            raise ValueError(f"mode must be one of {sorted(MESH_MODES)} (got {mode!r})")
+        if cull not in MESH_CULL:
+            raise ValueError(f"cull must be one of {sorted(MESH_CULL)} (got {cull!r})")
+        if triangles is None:
+            verts, triangles, colors = mesh_or_verts.vertices, mesh_or_verts.triangles, (mesh_or_verts.colors if colors is None else colors)
+        else:
+            verts = mesh_or_verts
+        verts, tris = self._dev(verts, torch.float32, (3,)), self._dev(triangles, torch.int32, (3,))
+        kind = MESH_MODES[mode]
+        col = uni = light = None
+        if kind == 1:
+            if colors is not None:
+                col = self._dev(colors, torch.float32, (3,))
+                if len(col) != len(verts):
+                    raise ValueError(f"{len(verts)} vertices but {len(col)} colours")
+            else:
+                uni = (C.c_double * 3)(*[int(v) / 255.0 for v in color])
+            if mode == "shaded":
+                R, t = camera.w2c[:, :3], camera.w2c[:, 3]
+                eye = -np.linalg.solve(R, t)                                   # the camera's centre, host float64
+                light = (C.c_double * 4)(*eye.tolist(), float(ambient))
+        lib = _lib.load_mesh()
+        sizes = (C.c_int64 * 2)()
+        self._check_mesh(lib.sta_mesh_plan(len(tris), len(verts), sizes))
+        if self._mesh_work is None or self._mesh_work.numel() < sizes[0]:
+            self._mesh_work = torch.empty(int(sizes[0]), dtype=torch.uint8, device=self.device)
+        T, K, near, far = camera._args()
+        self._check_mesh(lib.sta_mesh_triangles(self.keys.data_ptr(), self.H, self.W, self.ssaa, verts.data_ptr(), len(verts), tris.data_ptr(), len(tris),
+                                                col.data_ptr() if col is not None else None, uni, light, kind, MESH_CULL[cull], int(id_base), T, K, near, far,
+                                                self._mesh_counters.data_ptr(), self._mesh_work.data_ptr(), self._mesh_work.numel(), self._stream()))
+        return self
+
+    def _check_mesh(self, rc):
+        try:
+            _lib.check_mesh(rc)
+        except _lib.StaError as e:
+            raise _value_error(e) from None
+
+    def mesh_counters(self) -> Dict[str, int]:
+        """Of the triangles drawn since the last clear, the eight of include/sta_mesh.h (one readback, which waits for the stream)."""
+        return dict(zip(MESH_COUNTERS, self._mesh_counters.cpu().tolist()))
 
     def cameras(self, camera: Camera, poses, intrinsics, size, scale: float = 0.1, color=CAMERA_COLOR, line_width: int = 1):
         """A frustum per camera-to-world pose: `camera_segments`."""
@@ -294,6 +357,33 @@ def render_map(frontend, camera: Camera, *, depths, scales, intrinsics, poses, c
     return cv.points(camera, pts, col, point_size)
 
 
+def render_mesh(frontend, camera: Camera, mesh, *, H: int = 480, W: int = 720, ssaa: int = 1, mode: str = "shaded", cull: str = "none",
+                background=(255, 255, 255, 255), poses=None, intrinsics=None, size=None, view_graph=None, loop_min_dist: int = 0, camera_scale: float = 0.1,
+                ambient: float = 0.3, color=MESH_COLOR, line_width: int = 1, canvas: Optional[Canvas] = None) -> torch.Tensor:
+    """A `tsdf.Mesh` as an image uint8 [H,W,4].  poses [N,4,4] camera-to-world: the trajectory is drawn over the mesh; with intrinsics and
+    size = (width_px, height_px) a frustum per pose as well; with view_graph (and loop_min_dist) its edges - all with the line calls, so
+    the mesh occludes them.  frontend: anything with a `.device`, or a device."""
+    dev = getattr(frontend, "device", frontend)
+    cv = canvas.clear() if canvas is not None else Canvas(dev, H, W, ssaa)
+    cv.mesh(camera, mesh, mode=mode, cull=cull, ambient=ambient, color=color)
+    if poses is not None:
+        poses = _host(poses).reshape(-1, 4, 4)
+        if intrinsics is not None and size is not None:
+            cv.cameras(camera, poses, _host(intrinsics), size, camera_scale, CAMERA_COLOR, line_width)
+        if len(poses) > 1:
+            cv.trajectory(camera, poses, TRAJECTORY_COLOR, line_width)
+        if view_graph is not None:
+            cv.view_graph(camera, view_graph, poses, loop_min_dist, line_width=line_width)
+    return cv.image(background)
+
+
+def mesh_depth(frontend, mesh, camera: Camera, H: int, W: int) -> torch.Tensor:
+    """The depth map of a `tsdf.Mesh` from a pose: float32 [H,W], the z of the nearest surface through each pixel's centre, +inf where
+    there is none."""
+    dev = getattr(frontend, "device", frontend)
+    return Canvas(dev, H, W, 1).mesh(camera, mesh, mode="id").depth()
+
+
 def render_slam(slam, camera: Optional[Camera] = None, H: int = 480, W: int = 720, ssaa: int = 1, point_size: int = 1, direction: str = "topdown",
                 draw_cameras: bool = True, draw_graph: bool = True, camera_scale: float = 0.1, background=(255, 255, 255, 255)) -> torch.Tensor:
     """The map of a live OnlineSLAM as an image uint8 [H,W,4]: the cloud, a frustum per keyframe, the view-graph edges.  camera None:
@@ -342,12 +432,14 @@ def folder_frames(folder: str):
 
 
 def render_folder(frontend, folder: str, out_folder: str, mode: str = "topdown", H: int = 480, W: int = 720, ssaa: int = 1, point_size: int = 1,
-                  camera: Optional[Camera] = None, camera_scale: float = 0.1, background=(255, 255, 255, 255)) -> List[str]:
+                  camera: Optional[Camera] = None, camera_scale: float = 0.1, background=(255, 255, 255, 255), mesh=None, mesh_mode: str = "shaded",
+                  mesh_cull: str = "none") -> List[str]:
     """What scripts/video.py does with a save_data_all folder: one PNG per view v, {v:04d}.png, of the views 0 .. v under the poses and
     scales of the snapshot current at v - the cloud (colours divided by 1.5), a small frustum per earlier view, the current view's frustum
     ten times larger in dark green, the view-graph edges.  mode "topdown": one fixed camera (`camera`, or Camera.fit on the final
     trajectory); "follow": behind the current view (`follow_offset`).  Not drawn: the extra {v:04d}_pgo.png frames and the previous-view
-    frustum of the reference.  -> the paths written."""
+    frustum of the reference.  mesh: a `tsdf.Mesh`, or the path of a mesh.ply of `tsdf.write_mesh_ply` - every frame then draws the
+    whole mesh (mesh_mode, mesh_cull of `Canvas.mesh`) in place of the cloud.  -> the paths written."""
     if mode not in ("topdown", "follow"):
         raise ValueError(f'mode must be "topdown" or "follow" (got {mode!r})')
     N, at = folder_frames(folder)
@@ -367,13 +459,19 @@ def render_folder(frontend, folder: str, out_folder: str, mode: str = "topdown",
         camera = Camera.fit(np.load(os.path.join(folder, "trajectory.npy")), H, W, "topdown")
     os.makedirs(out_folder, exist_ok=True)
     cv = Canvas(dev, H, W, ssaa)
+    if isinstance(mesh, (str, os.PathLike)):
+        from . import tsdf
+        mesh = tsdf.mesh_from_ply(mesh, dev)
     paths = []
     for v in range(N):
         traj, scales = at(v)
         cam = camera if mode == "topdown" else Camera.from_pose(traj[v], K_out, follow_offset())
-        render_map(frontend, cam, depths=depths_d[:v + 1], scales=torch.from_numpy(scales[:v + 1]).to(dev), intrinsics=K_d[:v + 1],
-                   poses=torch.from_numpy(traj[:v + 1]).to(dev), confs=confs_d[:v + 1], imgs=imgs_d[:v + 1], conf_thres=thres,
-                   point_size=point_size, color_divisor=1.5, canvas=cv)
+        if mesh is not None:
+            cv.clear().mesh(cam, mesh, mode=mesh_mode, cull=mesh_cull)
+        else:
+            render_map(frontend, cam, depths=depths_d[:v + 1], scales=torch.from_numpy(scales[:v + 1]).to(dev), intrinsics=K_d[:v + 1],
+                       poses=torch.from_numpy(traj[:v + 1]).to(dev), confs=confs_d[:v + 1], imgs=imgs_d[:v + 1], conf_thres=thres,
+                       point_size=point_size, color_divisor=1.5, canvas=cv)
         if v > 0:
             cv.cameras(cam, traj[:v], intrinsics[:v], size, camera_scale, CAMERA_COLOR)
         cv.cameras(cam, traj[v:v + 1], intrinsics[v:v + 1], size, 10.0 * camera_scale, CUR_CAMERA_COLOR)

@@ -10,8 +10,12 @@ point, no floating-point atomics - a volume and a mesh are defined bit for bit b
     tsdf.write_mesh_ply("mesh.ply", mesh)
 
 Not here: growing a volume's block set after `allocate` (poses move under the optimiser, so fusion is a pass over an export, as
-`world_pointcloud` is); trilinear depth lookup (the nearest pixel is used); ray casting; normals; mesh simplification; marching cubes;
+`world_pointcloud` is); trilinear depth lookup (the nearest pixel is used); ray casting; mesh simplification; marching cubes;
 Open3D's ScalableTSDFVolume bit for bit - this is a contract of its own.  DESIGN.md section 9.
+
+On top of a mesh, through libsta_mesh.so (include/sta_mesh.h): `vertex_normals` (area-weighted, summed in ascending triangle order, no
+floating-point atomics), `write_mesh_ply(normals=)`, `visible_triangles` (the triangles whose id survives in a camera's id image) and
+`cull_mesh`.  `render.Canvas.mesh` draws a Mesh.
 """
 from __future__ import annotations
 
@@ -268,24 +272,35 @@ def mesh_from_folder(folder: str, voxel_size: float, device="cuda:0", **kw) -> M
 
 
 # ------------------------------------------------------------------------------------------ files
-def _ply_header(nv: int, nt: int) -> bytes:
+def _ply_header(nv: int, nt: int, normals: bool = False) -> bytes:
     return ("ply\nformat binary_little_endian 1.0\ncomment Created by vista_slam_amd (Open3D layout)\n"
             f"element vertex {nv}\nproperty double x\nproperty double y\nproperty double z\n"
+            + ("property double nx\nproperty double ny\nproperty double nz\n" if normals else "") +
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
             f"element face {nt}\nproperty list uchar int vertex_indices\nend_header\n").encode("ascii")
 
 
 FACE_RECORD = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
 assert FACE_RECORD.itemsize == 13
+# a vertex with normals, in Open3D's order: coordinates, normals, colours
+PLY_NORMAL_RECORD = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8"), ("red", "u1"), ("green", "u1"),
+                              ("blue", "u1")])
+assert PLY_NORMAL_RECORD.itemsize == 51
 
 
-def write_mesh_ply(path: str, mesh: Mesh):
+def write_mesh_ply(path: str, mesh: Mesh, normals=None):
     """Binary little-endian PLY: `formats.PLY_RECORD` vertices (double coordinates, uchar colours = rint(clamp(c, 0, 1) * 255); white
-    without colours), then `property list uchar int vertex_indices` faces."""
+    without colours), then `property list uchar int vertex_indices` faces.  normals [nv,3] (`vertex_normals`): `property double nx, ny,
+    nz` between the coordinates and the colours (PLY_NORMAL_RECORD); without them the file is what it always was."""
     from .formats import PLY_RECORD
     v = mesh.vertices.detach().cpu().numpy()
-    rec = np.zeros(len(v), dtype=PLY_RECORD)
+    rec = np.zeros(len(v), dtype=PLY_RECORD if normals is None else PLY_NORMAL_RECORD)
     rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = normals.detach().cpu().numpy() if isinstance(normals, torch.Tensor) else np.asarray(normals)
+        if n.shape != v.shape:
+            raise ValueError(f"{len(v)} vertices but normals of shape {n.shape}")
+        rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
     if mesh.colors is not None:
         c = np.rint(np.clip(np.nan_to_num(mesh.colors.detach().cpu().numpy(), nan=0.0), 0.0, 1.0) * np.float32(255.0)).astype(np.uint8)
     else:
@@ -295,25 +310,88 @@ def write_mesh_ply(path: str, mesh: Mesh):
     faces = np.zeros(len(t), dtype=FACE_RECORD)
     faces["n"], faces["v"] = 3, t
     with open(path, "wb") as f:
-        f.write(_ply_header(len(v), len(t)))
+        f.write(_ply_header(len(v), len(t), normals is not None))
         f.write(rec.tobytes())
         f.write(faces.tobytes())
 
 
 def read_mesh_ply(path: str):
-    """-> (vertex records [nv] formats.PLY_RECORD, triangles [nt,3] int32) of a file of `write_mesh_ply`"""
+    """-> (vertex records [nv] formats.PLY_RECORD - PLY_NORMAL_RECORD, with nx, ny, nz, when the file has normals -, triangles [nt,3]
+    int32) of a file of `write_mesh_ply`"""
     from .formats import PLY_RECORD
+    dtype = PLY_RECORD
     with open(path, "rb") as f:
         nv = nt = None
         while True:
             line = f.readline().decode("ascii").strip()
+            if line == "property double nx":
+                dtype = PLY_NORMAL_RECORD
             if line.startswith("element vertex"):
                 nv = int(line.split()[-1])
             if line.startswith("element face"):
                 nt = int(line.split()[-1])
             if line == "end_header":
                 break
-        rec = np.frombuffer(f.read(nv * PLY_RECORD.itemsize), dtype=PLY_RECORD)
+        rec = np.frombuffer(f.read(nv * dtype.itemsize), dtype=dtype)
         faces = np.frombuffer(f.read(nt * FACE_RECORD.itemsize), dtype=FACE_RECORD)
     assert (faces["n"] == 3).all()
     return rec, faces["v"].astype(np.int32)
+
+
+def mesh_from_ply(path: str, device="cuda:0") -> Mesh:
+    """A file of `write_mesh_ply` as a Mesh on the device (coordinates rounded to float32, colours byte / 255)."""
+    rec, tris = read_mesh_ply(path)
+    v = np.stack([rec["x"], rec["y"], rec["z"]], axis=1).astype(np.float32)
+    c = np.stack([rec["red"], rec["green"], rec["blue"]], axis=1).astype(np.float32) / np.float32(255.0)
+    return Mesh(torch.from_numpy(v).to(device), torch.from_numpy(c).to(device), torch.from_numpy(np.ascontiguousarray(tris)).to(device))
+
+
+# ------------------------------------------------------------------------------------------ on top of a mesh: libsta_mesh.so
+def _check_mesh(rc):
+    try:
+        _lib.check_mesh(rc)
+    except _lib.StaError as e:
+        raise (ValueError(str(e)) if str(e).startswith("mesh_") else e) from None
+
+
+def vertex_normals(mesh: Mesh) -> torch.Tensor:
+    """[nv,3] float32: per vertex the sum of the un-normalised face normals of its triangles (so each face weighs by its area), in
+    ascending triangle index in float64, normalised; (0, 0, 0) for a vertex of no triangle or of a zero sum (sta_mesh_vertex_normals).
+    The call does not wait for the stream; its workspace is allocated here."""
+    lib = _lib.load_mesh()
+    verts, tris = mesh.vertices.to(torch.float32).contiguous(), mesh.triangles.to(torch.int32).contiguous()
+    dev = verts.device
+    nv, nt = len(verts), len(tris)
+    sizes = (C.c_int64 * 2)()
+    _check_mesh(lib.sta_mesh_plan(nt, nv, sizes))
+    if sizes[1] < 0:
+        raise ValueError(f"mesh_vertex_normals: 3 * nt must be below 2^31 (got nt = {nt})")
+    work = torch.empty(int(sizes[1]), dtype=torch.uint8, device=dev)
+    out = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    _check_mesh(lib.sta_mesh_vertex_normals(verts.data_ptr(), nv, tris.data_ptr(), nt, out.data_ptr(), work.data_ptr(), work.numel(), _stream(dev)))
+    return out
+
+
+def visible_triangles(frontend, mesh: Mesh, cameras, H: int, W: int, ssaa: int = 1) -> torch.Tensor:
+    """bool [nt]: the triangles whose id survives in the id image (`Canvas.ids`) of at least one of `cameras` (render.Camera) - the
+    nearest surface at some pixel.  The triangle pass does the work; the union is torch plumbing."""
+    from . import render
+    dev = getattr(frontend, "device", frontend)
+    nt = len(mesh.triangles)
+    seen = torch.zeros(nt + 1, dtype=torch.bool, device=dev)          # the last slot takes the empty pixels
+    cv = render.Canvas(dev, H, W, ssaa)
+    for cam in cameras:
+        cv.clear().mesh(cam, mesh, mode="id")
+        ids = (cv.ids().reshape(-1).to(torch.int64) & 0xFFFFFFFF).clamp_(max=nt)      # an empty pixel's id is 2^32 - 1
+        seen[ids] = True
+    return seen[:nt]
+
+
+def cull_mesh(mesh: Mesh, keep) -> Mesh:
+    """The triangles of `keep` (bool [nt]) and the vertices they name, re-indexed in ascending order; the other vertices are dropped."""
+    keep = torch.as_tensor(keep, dtype=torch.bool, device=mesh.triangles.device)
+    tris = mesh.triangles[keep].to(torch.int64)
+    used = torch.zeros(len(mesh.vertices), dtype=torch.bool, device=tris.device)
+    used[tris.reshape(-1)] = True
+    new = torch.cumsum(used.to(torch.int64), 0) - 1
+    return Mesh(mesh.vertices[used], mesh.colors[used] if mesh.colors is not None else None, new[tris].to(torch.int32))
