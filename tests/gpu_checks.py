@@ -167,16 +167,28 @@ def check_gemm_tail(precision, tiles_m=12, tail=16, N=2304, K=256, act=0, via_f1
     return r
 
 
-def check_qkv_rope_decoder_rows(precision, S=2, hp=3, wp=4, K=128, Cdim=128, seed=12, variant=0):
+def split_linear(seed, rows, N, K, precision, v_cols):
+    """split_cases.linear_operands as float32 torch tensors: x [*rows, K], W [N, K], b [N], and the ONE right value of the columns
+    v_cols [prod(rows), len(v_cols)] float64."""
+    import split_cases as SC
+    x, w, b, want = SC.linear_operands(seed, rows, N, K, precision, v_cols, HP.mm64)
+    return torch.from_numpy(x), torch.from_numpy(w), torch.from_numpy(b), want
+
+
+def check_qkv_rope_decoder_rows(precision, S=2, hp=3, wp=4, K=128, Cdim=128, seed=12, variant=0, ints=False):
     """QKV + RoPE epilogue on the decoder's row order: x = [S*N patch rows | S pose rows]; the buffers hold N + 1 tokens per
-    sequence with the pose token (position -1) last."""
+    sequence with the pose token (position -1) last.  ints: split operands with ONE right answer (split_linear) - the un-rotated V
+    columns must come out EXACT, both parts ("v_exact_bad")."""
     m, lib, h = kernel_handle(precision, variant)
     g = torch.Generator().manual_seed(seed)
     N = hp * wp
     ntok = N + 1
-    xs = torch.randn(S, ntok, K, generator=g)                 # reference order: pose token first
-    Wt = torch.randn(3 * Cdim, K, generator=g) * 0.1
-    b = torch.randn(3 * Cdim, generator=g) * 0.1
+    if ints:
+        xs, Wt, b, v_want = split_linear(seed, (S, ntok), 3 * Cdim, K, precision, slice(2 * Cdim, 3 * Cdim))
+    else:
+        xs = torch.randn(S, ntok, K, generator=g)                 # reference order: pose token first
+        Wt = torch.randn(3 * Cdim, K, generator=g) * 0.1
+        b = torch.randn(3 * Cdim, generator=g) * 0.1
     heads = Cdim // 64
     npad = (ntok + 63) // 64 * 64
     x_dec = torch.cat([xs[:, 1:].reshape(S * N, K), xs[:, 0]], 0).contiguous()
@@ -196,17 +208,22 @@ def check_qkv_rope_decoder_rows(precision, S=2, hp=3, wp=4, K=128, Cdim=128, see
     plan = last_plan(lib, h)
     _lib.check(lib.sta_set_gemm_variant(h, 0))
     qd_, kd_ = q.cpu().numpy(), k.cpu().numpy()
-    return {"q": max_rel(qd_, qr[:, :, order]), "k": max_rel(kd_, kr[:, :, order]), "v": max_rel(v, vr[:, :, order]),
-            "q_pose": max_rel(qd_[:, :, -1:], qr[:, :, :1]), "k_pose": max_rel(kd_[:, :, -1:], kr[:, :, :1]),
-            "v_pose": max_rel(v[:, :, -1:], vr[:, :, :1]),
-            "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0, "plan": plan}
+    res = {"q": max_rel(qd_, qr[:, :, order]), "k": max_rel(kd_, kr[:, :, order]), "v": max_rel(v, vr[:, :, order]),
+           "q_pose": max_rel(qd_[:, :, -1:], qr[:, :, :1]), "k_pose": max_rel(kd_[:, :, -1:], kr[:, :, :1]),
+           "v_pose": max_rel(v[:, :, -1:], vr[:, :, :1]),
+           "vpad_abs": float(np.abs(pad).max()) if pad.size else 0.0, "plan": plan}
+    if ints:
+        want = v_want.reshape(S, ntok, heads, 64).transpose(0, 2, 1, 3)[:, :, order]
+        res["v_exact_bad"], res["v_first"] = HP.first_wrong(v, want, np.rint(want), ("sequence", "head", "token", "column"))
+    return res
 
 
 def check_qkv_pair(precision, S=4, hp=24, wp=32, Cdim=768, K=768, ints=False, seed=14):
     """The decoder's paired launch (gemm_qkv_pair): a = attn.qkv (q | k | v) and b = cross_attn.projk|projv (k | v, nq = 0) on
     two inputs in the decoder's row order [S*N patch rows | S pose rows], pose-token tail hint S.  Against an fp64 reference +
-    RoPE (pose token at position -1).  ints: small-integer operands, so that V (not rotated) must come out EXACT for both halves -
-    any column offset of the second GEMM in the one-grid launch shows up as a wrong integer."""
+    RoPE (pose token at position -1).  ints: operands hi + q 2^-12 with ONE right answer (split_linear), so that V (not rotated) must
+    come out EXACT for both halves, hi and lo plane - any column offset of the second GEMM in the one-grid launch, and any dropped or
+    misplaced correction product, shows up as a wrong value."""
     m, lib, h = kernel_handle(precision)
     g = torch.Generator().manual_seed(seed)
     N = hp * wp
@@ -215,12 +232,14 @@ def check_qkv_pair(precision, S=4, hp=24, wp=32, Cdim=768, K=768, ints=False, se
     npad = (nt + 63) // 64 * 64
 
     def operand(*shape, scale):
-        if ints:
-            return torch.randint(-2, 3, shape, generator=g).float()
         return torch.randn(*shape, generator=g) * scale
-    xa, xb = operand(S, nt, K, scale=1.0), operand(S, nt, K, scale=1.0)        # reference order: pose token first
-    Wa, Wb = operand(3 * Cdim, K, scale=0.05), operand(2 * Cdim, K, scale=0.05)
-    ba, bb = operand(3 * Cdim, scale=0.1), operand(2 * Cdim, scale=0.1)
+    if ints:      # split operands (hi + q 2^-12, both parts non-zero) with ONE right answer: split_linear
+        xa, Wa, ba, va_want = split_linear(seed, (S, nt), 3 * Cdim, K, precision, slice(2 * Cdim, 3 * Cdim))
+        xb, Wb, bb, vb_want = split_linear(seed + 1, (S, nt), 2 * Cdim, K, precision, slice(Cdim, 2 * Cdim))
+    else:
+        xa, xb = operand(S, nt, K, scale=1.0), operand(S, nt, K, scale=1.0)        # reference order: pose token first
+        Wa, Wb = operand(3 * Cdim, K, scale=0.05), operand(2 * Cdim, K, scale=0.05)
+        ba, bb = operand(3 * Cdim, scale=0.1), operand(2 * Cdim, scale=0.1)
 
     def dec(x):
         return torch.cat([x[:, 1:].reshape(S * N, K), x[:, 0]], 0).contiguous()
@@ -250,7 +269,12 @@ def check_qkv_pair(precision, S=4, hp=24, wp=32, Cdim=768, K=768, ints=False, se
         res[name] = max_rel(got[name], ref[name])
         res[name + "_pose"] = max_rel(got[name][:, :, -1:], ref[name][:, :, -1:])
     if ints:
-        res["v_exact_bad"] = int(sum((got[n].astype(np.float64) != ref[n]).sum() for n in ("v_a", "v_b")))
+        res["v_exact_bad"], res["v_first"] = 0, ""
+        for n, w_ in (("v_a", va_want), ("v_b", vb_want)):
+            want = w_.reshape(S, nt, heads, 64).transpose(0, 2, 1, 3)[:, :, order]
+            bad, first = HP.first_wrong(got[n], want, np.rint(want), ("sequence", "head", "token", "column"))
+            res["v_exact_bad"] += bad
+            res["v_first"] += f"{n}: {first} " if bad else ""
     return res
 
 
@@ -308,16 +332,23 @@ def attn_launch(precision, case, q, k, v):
     return HP.attn_rows_to_tokens(out.cpu().numpy(), form, S, heads, nq), AC.schedule_class(plan, nq)
 
 
-def check_attention_selection(precision, case, pose_sel="self", seed=21):
+def check_attention_selection(precision, case, pose_sel="self", seed=21, v_lo=False):
     """Every query selects one key with probability exactly 1 (helpers.attn_selection_inputs): the output must EQUAL V[pi(query)].
+    v_lo: V = integer + lo (split_cases.attn_v_with_lo) - the output planes must hold BOTH parts of the selected row (f16: its hi).
     -> {"class", "margin", "nan", "wrong": number of wrong (sequence, head, query) rows, "first": text naming the first ones}."""
     cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
     q, k, v, pi, margin = HP.attn_selection_inputs(form, S, heads, nq, nk, pose_sel, seed)
     assert margin > 160, (cid, margin)          # every other probability is exp2(-margin): exactly 0 in fp32
+    vw = v
+    if v_lo:
+        import split_cases as SC
+        v = SC.attn_v_with_lo(v, seed)
+        assert SC.split_holds(v)
+        vw = v.astype(np.float16).astype(np.float32) if precision == "f16" else v
     # q was built against its own sequence's keys: hand the kernel K / V rotated so that sequence (s + kv_shift) % S holds them
     idx = [(s - kv_shift) % S for s in range(S)]
     got, ran = attn_launch(precision, case, q, k[idx], v[idx])
-    want = np.take_along_axis(v, pi[..., None], 2)
+    want = np.take_along_axis(vw, pi[..., None], 2)
     bad = np.argwhere((got != want).any(-1))
     first = []
     for s, h, t in bad[:6]:
@@ -328,14 +359,43 @@ def check_attention_selection(precision, case, pose_sel="self", seed=21):
     return {"class": ran, "margin": margin, "nan": int(np.isnan(got).sum()), "wrong": len(bad), "first": "; ".join(first)}
 
 
-def check_attention_uniform(precision, case, seed=22):
+def check_attention_decided(precision, case, seed=23):
+    """Q K^T decided by the correction products alone (split_cases.attn_decided_inputs): every query has a selected key and a decoy
+    that tie at exactly 0 in hi hi; f16x3 must return the selected V row (both parts), f16 - where the decoy ties - the mean of the
+    hi parts of the two rows.  -> as check_attention_selection, with the family and the tiles of the first wrong rows."""
+    import split_cases as SC
+    cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
+    d = SC.attn_decided_inputs(form, S, heads, nq, nk, seed)
+    m_dec, m_rest = SC.attn_decided_assert(d)
+    idx = [(s - kv_shift) % S for s in range(S)]          # (q was built against its own sequence's keys)
+    got, ran = attn_launch(precision, case, d["q"], d["k"][idx], d["v"][idx])
+    want = SC.attn_decided_expected(d, precision)
+    bad = np.argwhere((got != want).any(-1))
+    first = []
+    for s, h, t in bad[:6]:
+        g, b, dk = got[s, h, t], d["pi"][s, h, t], d["dec"][s, h, t]
+        first.append(f"(sequence {s}, head {h}, query {t}): selected key {b} (tile {b // 64}), decoy {dk} (tile {dk // 64}), separated by "
+                     f"{'q_lo k_hi' if d['family'][s, h, t] else 'q_hi k_lo'}; got columns 0..2 = ({g[0]:g}, {g[1]:g}, {g[2]:g}), "
+                     f"{int((g != want[s, h, t]).sum())} of 64 columns differ")
+    return {"class": ran, "margin": (m_dec, m_rest), "nan": int(np.isnan(got).sum()), "wrong": len(bad), "first": "; ".join(first)}
+
+
+def check_attention_uniform(precision, case, seed=22, v_lo=False):
     """q = 0: the output is the column mean of V over exactly nk (+ 1) keys.  -> max |error|, max |V|, the fp16 half-ulp of the
-    largest mean (what the f16 form's single output rounding adds)."""
+    largest mean (what the f16 form's single output rounding adds).  v_lo: V + lo of one sign per column
+    (split_cases.attn_uniform_lo); the f16 form must return the mean of the hi parts."""
     cid, form, S, heads, nq, nk, kv_shift, opt5, cls = case
     q, k, v = HP.attn_uniform_inputs(form, S, heads, nq, nk, seed)
+    vw = v
+    if v_lo:
+        import split_cases as SC
+        vw, v = v, SC.attn_uniform_lo(v, seed)[0]
+        assert SC.split_is(v, (vw, np.rint((v.astype(np.float64) - vw) * 4096)))
+        if precision != "f16":
+            vw = v
     got, ran = attn_launch(precision, case, q, k, v)
     idx = [(s + kv_shift) % S for s in range(S)]
-    ref = np.broadcast_to(v[idx].astype(np.float64).mean(2, keepdims=True), got.shape)
+    ref = np.broadcast_to(vw[idx].astype(np.float64).mean(2, keepdims=True), got.shape)
     err = np.abs(got - ref)
     w = np.unravel_index(np.nanargmax(err), err.shape) if not np.isnan(err).all() else (0, 0, 0, 0)
     return {"class": ran, "nan": int(np.isnan(got).sum()), "max_abs": float(np.nanmax(err)) if not np.isnan(err).all() else float("nan"),
@@ -658,6 +718,89 @@ def check_conv_classes(precision, case, seed=32):
     bm = {2: 256, 3: 192, 5: 192, 6: 128, 8: 256}[ran[0]]
     errs = HP.class_errors(got, ref, HP.conv_pixel_classes(n, Ho, Wo, ran[0], bm))
     return {"class": ran, "nan": int(np.isnan(got).sum()), "rel_l2": rel_l2(got, ref), "errs": errs, "worst": HP.worst_class(errs)}
+
+
+# ---- tests/test_split_exact_gpu.py: operands with a lo part that have ONE right answer (tests/split_cases.py)
+def check_gemm_split(precision, M, N, K, variant, resid=False, via_f16=0, seed=0, tail=0, plan=None, wg_over=None):
+    """sta_debug_gemm on split operands; arguments as _int_gemm of tests/test_gemm_mfma16.py (tail hint, plan and workgroup
+    assertions, NaN / residual start of the output).  -> {"wrong", "first", "nan", "plan"}."""
+    import split_cases as SC
+
+    def make():
+        ops = SC.gemm_operands(M, N, K, resid, seed)
+        for name in ("A", "W"):
+            SC.assert_split(SC.value(ops[name]), ops[name], name)
+        return ops, SC.gemm_terms(ops, HP.mm64)
+    ops, t = _cached(("gemm_split", M, N, K, resid, seed), make)
+    want = SC.gemm_expected(ops, t, precision, bool(via_f16))
+    hi_only = SC.gemm_expected(ops, t, "f16", False)
+    m, lib, h = kernel_handle(precision, variant)
+    Ad, Wd, bd = dev(SC.value(ops["A"])), dev(SC.value(ops["W"])), dev(ops["b"].astype(np.float32))
+    out = dev(SC.value(ops["R"])) if resid else torch.full((M, N), float("nan"), device=DEV)
+    _lib.check(lib.sta_debug_set_tail_hint(h, tail))
+    try:
+        _lib.check(lib.sta_debug_gemm(h, Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, 0, via_f16,
+                                      out.data_ptr() if resid else None, out.data_ptr(), st()))
+        torch.cuda.synchronize()
+        got_plan = last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_debug_set_tail_hint(h, 0))
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    if plan is not None:
+        assert (got_plan["family"], got_plan["m_tail"]) == tuple(plan), got_plan
+    if wg_over is not None:
+        assert got_plan["tiles_m"] * got_plan["tiles_n"] * got_plan["ksplit"] > wg_over, got_plan
+    got = out.cpu().numpy()
+    wrong, first = HP.first_wrong(got, want, hi_only, ("row", "col"))
+    return {"wrong": wrong, "first": first, "nan": int(np.isnan(got).sum()), "plan": got_plan}
+
+
+def check_conv_split(precision, case, seed=33):
+    """A case of tests/conv_cases.py on split inputs, weights and residuals (split_cases.conv_operands).  -> as check_conv_integers."""
+    import split_cases as SC
+    cid, n, H, W_, Cin, Co, stride, relu_in, act, nres, variant, cls = case
+
+    def make():
+        ops = SC.conv_operands(case, seed)
+        t = HP.split_conv_terms(ops, stride)
+        b = SC.conv_bias(ops, t)
+        SC.conv_window(ops, b)
+        for name, p in [("x", ops["x"]), ("w", ops["w"])] + [(f"residual {i}", r) for i, r in enumerate(ops["res"])]:
+            SC.assert_split(SC.value(p), p, f"{cid} {name}")
+        return ops, t, b
+    ops, t, b = _cached(("conv_split", cid), make)
+    want = SC.conv_expected(ops, t, b, precision)
+    hi_only = SC.conv_expected(ops, t, b, "f16x3", wrong="hi_only")
+    got, ran = conv_launch(precision, case, SC.value(ops["x"]), SC.value(ops["w"]), b.astype(np.float32), [SC.value(r) for r in ops["res"]])
+    wrong, first = HP.first_wrong(got, want, hi_only, ("image", "y", "x", "channel"))
+    return {"class": ran, "nan": int(np.isnan(got).sum()), "wrong": wrong, "first": first, "max_abs": float(np.abs(want).max())}
+
+
+def check_convt_split(precision, H, W_, Cdim, k, variant=0):
+    """sta_debug_convt on split operands (the rows of test_convt_dispatch_rows_integer_exact).  -> {"wrong", "first", "nan", "plan"}."""
+    import split_cases as SC
+
+    def make():
+        ops = SC.convt_operands(H, W_, Cdim, k)
+        for name in ("x", "w"):
+            SC.assert_split(SC.value(ops[name]), ops[name], name)
+        return ops, SC.convt_terms(ops, HP.mm64)
+    ops, t = _cached(("convt_split", H, W_, Cdim, k), make)
+    want = SC.convt_expected(ops, t, precision)
+    hi_only = SC.convt_expected(ops, t, "f16x3", wrong="hi_only")
+    n = ops["x"][0].shape[0]
+    m, lib, h = kernel_handle(precision, variant)
+    out = torch.full((n, H * k, W_ * k, Cdim), float("nan"), device=DEV)
+    xd, wd, bd = dev(SC.value(ops["x"])), dev(SC.value(ops["w"])), dev(ops["b"].astype(np.float32))
+    try:
+        _lib.check(lib.sta_debug_convt(h, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), n, H, W_, Cdim, k, out.data_ptr(), st()))
+        torch.cuda.synchronize()
+        plan = last_plan(lib, h)
+    finally:
+        _lib.check(lib.sta_set_gemm_variant(h, 0))
+    got = out.cpu().numpy()
+    wrong, first = HP.first_wrong(got, want, hi_only, ("image", "y", "x", "channel"))
+    return {"wrong": wrong, "first": first, "nan": int(np.isnan(got).sum()), "plan": plan}
 
 
 def tail_launch(precision, hcase, nA, x, w2, b2, w4, b4, expect_range=(0, 0)):

@@ -11,6 +11,7 @@ import torch
 import attention_mixed_cases as AM
 import gpu_checks as G
 import helpers as HP
+import split_cases as SC
 from vista_slam_amd import _lib
 
 
@@ -50,7 +51,7 @@ def claimed(case):
     return [case[10], case[11]][:len(groups_of(case))]
 
 
-def check_selection(precision, case, pose_sel="self", seed=21):
+def check_selection(precision, case, pose_sel="self", seed=21, v_lo=False):
     """Every query selects one key with probability exactly 1: the output must EQUAL V[pi(query)].  V columns 0..2 = (sequence of the
     whole launch, head, key): a failure names what was expected and what came back."""
     heads, S1 = case[3], case[1]
@@ -58,12 +59,16 @@ def check_selection(precision, case, pose_sel="self", seed=21):
     for g, (S, nq, nk) in enumerate(groups_of(case)):
         q, k, v, pi, mg = HP.attn_selection_inputs("pose", S, heads, nq, nk, pose_sel, seed + g)
         v[..., 0] += g * S1
+        if v_lo:        # V = integer + lo (split_cases.attn_v_with_lo): both parts of the selected row must come back (f16: its hi)
+            v = SC.attn_v_with_lo(v, seed + g)
+            assert SC.split_holds(v)
         inputs.append((q, k, v)); pis.append(pi); margin = min(margin, mg)
     assert margin > 160, (case[0], margin)
     got, ran = mixed_launch(precision, case, inputs)
     wrong, nan, first = 0, 0, []
     for g, (S, nq, nk) in enumerate(groups_of(case)):
-        want = np.take_along_axis(inputs[g][2], pis[g][..., None], 2)
+        vw = inputs[g][2].astype(np.float16).astype(np.float32) if v_lo and precision == "f16" else inputs[g][2]
+        want = np.take_along_axis(vw, pis[g][..., None], 2)
         bad = np.argwhere((got[g] != want).any(-1))
         wrong += len(bad); nan += int(np.isnan(got[g]).sum())
         for s, h, t in bad[:4]:

@@ -12,6 +12,7 @@ import torch
 import attention_varlen_cases as AV
 import gpu_checks as G
 import helpers as HP
+import split_cases as SC
 from vista_slam_amd import _lib
 
 
@@ -53,7 +54,7 @@ def claimed(case):
     return list(case[4])
 
 
-def check_selection(precision, case, shift, pose_sel="self", seed=21):
+def check_selection(precision, case, shift, pose_sel="self", seed=21, v_lo=False):
     """Every query selects one key with probability exactly 1: the output must EQUAL V[pi(query)].  V columns 0..2 = (sequence of the
     launch, head, key): a failure names what was expected and what came back."""
     heads, seqs = case[1], case[3]
@@ -61,12 +62,16 @@ def check_selection(precision, case, shift, pose_sel="self", seed=21):
     for s, (nq, nk) in enumerate(seqs):
         q, k, v, pi, mg = HP.attn_selection_inputs("pose", 1, heads, nq, nk, pose_sel, seed + s)
         v[..., 0] += s
+        if v_lo:        # V = integer + lo (split_cases.attn_v_with_lo): both parts of the selected row must come back (f16: its hi)
+            v = SC.attn_v_with_lo(v, seed + s)
+            assert SC.split_holds(v)
         inputs.append((q, k, v)); pis.append(pi); margin = min(margin, mg)
     assert margin > 160, (case[0], margin)
     got, ran = varlen_launch(precision, case, shift, inputs)
     wrong, nan, first = 0, 0, []
     for s, (nq, nk) in enumerate(seqs):
-        want = np.take_along_axis(inputs[s][2], pis[s][..., None], 2)
+        vw = inputs[s][2].astype(np.float16).astype(np.float32) if v_lo and precision == "f16" else inputs[s][2]
+        want = np.take_along_axis(vw, pis[s][..., None], 2)
         bad = np.argwhere((got[s] != want).any(-1))
         wrong += len(bad); nan += int(np.isnan(got[s]).sum())
         for _z, h, t in bad[:4]:

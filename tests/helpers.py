@@ -523,6 +523,45 @@ def conv_integer_inputs(n, H, W, Cin, Co, stride, nres, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# tests/test_split_exact_*.py: the integer sums of tests/split_cases.py on the float64 backends of this file (integer-valued arrays,
+# every partial sum below 2^53: exact whatever the order)
+def mm64(a, b):
+    """a [M, K], b [N, K] integer-valued -> a b^T in float64, on the GPU where there is one."""
+    import torch
+    d = _ref_device()
+    at = torch.from_numpy(np.ascontiguousarray(a)).to(d).double()
+    bt = torch.from_numpy(np.ascontiguousarray(b)).to(d).double()
+    return (at @ bt.T).cpu().numpy()
+
+
+def split_conv_terms(ops, stride, lolo=False):
+    """The sums of split_cases.conv_expected for the operands of split_cases.conv_operands: I, T1 = x_hi * w_q, T2 = x_q * w_hi
+    (, L = x_q * w_q), NHWC float64, of the input after its ReLU."""
+    import torch
+    import split_cases as SC
+    (xh, xq), (wh, wq) = (SC.conv_relu_in(ops["x"]) if ops["relu_in"] else ops["x"]), ops["w"]
+
+    def f(a, w):
+        return _conv2d(a.astype(np.float64), w.astype(np.float64), stride, torch.float64, _ref_device())
+    t = {"I": f(xh, wh), "T1": f(xh, wq), "T2": f(xq, wh)}
+    if lolo:
+        t["L"] = f(xq, wq)
+    return t
+
+
+def first_wrong(got, want, hi_only, names, limit=4):
+    """-> (count of wrong elements, text naming the first ones: index, got, want, the hi-only value - got == hi-only: a correction
+    was dropped; neither: it was misplaced or applied twice)."""
+    bad = np.argwhere(~(np.asarray(got, np.float64) == want))
+    lines = []
+    for ix in bad[:limit]:
+        ix = tuple(ix)
+        where = ", ".join(f"{n} {i}" for n, i in zip(names, ix))
+        lines.append(f"({where}): got {float(got[ix])!r} want {float(want[ix])!r} hi-only {float(hi_only[ix])!r}")
+    return len(bad), "; ".join(lines)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # bit-level comparison of the outputs of two runs: tests/test_workspace_gpu.py and tests/test_stream_order_gpu.py
 def snapshot(outs):
     """Outputs of a run, detached from the buffers the next run may reuse."""
