@@ -18,6 +18,7 @@ CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library wi
 RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (include/sta_raster.h): `load_raster()`
 TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (include/sta_tsdf.h): `load_tsdf()`
 MESH_LIB_PATH = os.path.join(PKG, "libsta_mesh.so")        # a fifth one (include/sta_mesh.h): `load_mesh()`
+SURF_LIB_PATH = os.path.join(PKG, "libsta_surf.so")        # a sixth one (include/sta_surf.h): `load_surf()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -256,12 +257,22 @@ MESH_SIGNATURES = {
     "sta_mesh_last_error": (C.c_char_p, []),
 }
 
+# include/sta_surf.h: libsta_surf.so, handle-free; a table of its own like the four above
+SURF_SIGNATURES = {
+    "sta_surf_plan": (_i, [_i64, _i64, _i64, _i64p]),
+    "sta_surf_components": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sta_surf_weights": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sta_surf_sample": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "sta_surf_last_error": (C.c_char_p, []),
+}
+
 _lib = None
 _test_lib = None
 _cloud_lib = None
 _raster_lib = None
 _tsdf_lib = None
 _mesh_lib = None
+_surf_lib = None
 
 
 class StaError(RuntimeError):
@@ -423,6 +434,29 @@ def load_mesh():
 def check_mesh(rc):
     if rc != 0:
         raise StaError((load_mesh().sta_mesh_last_error() or b"unknown error").decode())
+
+
+def load_surf():
+    """Load libsta_surf.so and bind every symbol of include/sta_surf.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_surf(rc)`."""
+    global _surf_lib
+    if _surf_lib is not None:
+        return _surf_lib
+    if not os.path.exists(SURF_LIB_PATH):
+        raise _missing(SURF_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(SURF_LIB_PATH)
+    for name, (res, args) in SURF_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _surf_lib = lib
+    return lib
+
+
+def check_surf(rc):
+    if rc != 0:
+        raise StaError((load_surf().sta_surf_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

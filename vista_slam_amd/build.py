@@ -12,6 +12,8 @@
                                             #    (sparse TSDF fusion and marching tetrahedra of vista_slam_amd/tsdf.py; its own translation unit)
                                             #    vista_slam_amd/libsta_mesh.so         a fifth, handle-free library: exports include/sta_mesh.h
                                             #    (triangles for the rasteriser's key buffer and vertex normals; its own translation unit)
+                                            #    vista_slam_amd/libsta_surf.so         a sixth, handle-free library: exports include/sta_surf.h
+                                            #    (connected components and area-uniform surface samples of a mesh; its own translation unit)
 """
 import os
 import shutil
@@ -44,6 +46,10 @@ MESH_LIB = os.path.join(PKG, "libsta_mesh.so")
 MESH_SOURCES = ["sta_mesh.hip"]
 MESH_DEPS = ["sta_exports.map", "sta_mesh.hip", "mesh.h", "raster.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
              os.path.join("..", "..", "include", "sta_mesh.h"), os.path.join("..", "..", "include", "sta_raster.h")]
+# libsta_surf.so: likewise; of the shared kernel headers it includes sta_common.h alone, unchanged
+SURF_LIB = os.path.join(PKG, "libsta_surf.so")
+SURF_SOURCES = ["sta_surf.hip"]
+SURF_DEPS = ["sta_exports.map", "sta_surf.hip", "surf.h", "sta_common.h", os.path.join("..", "..", "include", "sta_surf.h")]
 
 
 def hipcc_path():
@@ -65,6 +71,7 @@ CLOUD_HASH_FILE = CLOUD_LIB + ".srchash"
 RASTER_HASH_FILE = RASTER_LIB + ".srchash"
 TSDF_HASH_FILE = TSDF_LIB + ".srchash"
 MESH_HASH_FILE = MESH_LIB + ".srchash"
+SURF_HASH_FILE = SURF_LIB + ".srchash"
 
 
 def extra_flags():
@@ -81,7 +88,7 @@ def extra_flags():
 def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS)."""
+    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS, SURF_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
@@ -103,9 +110,9 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True):
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True):
     """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so, (raster) libsta_raster.so, (tsdf)
-    libsta_tsdf.so and (mesh) libsta_mesh.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    libsta_tsdf.so, (mesh) libsta_mesh.so and (surf) libsta_surf.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
@@ -119,6 +126,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
         jobs.append((TSDF_LIB, TSDF_HASH_FILE, False, TSDF_SOURCES, TSDF_DEPS))
     if mesh and (force or is_stale(MESH_LIB, MESH_HASH_FILE, MESH_DEPS)):
         jobs.append((MESH_LIB, MESH_HASH_FILE, False, MESH_SOURCES, MESH_DEPS))
+    if surf and (force or is_stale(SURF_LIB, SURF_HASH_FILE, SURF_DEPS)):
+        jobs.append((SURF_LIB, SURF_HASH_FILE, False, SURF_SOURCES, SURF_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()

@@ -6,6 +6,11 @@ translation APE.  A trajectory is at most a few thousand poses: this half has no
 Reconstruction half (`eval_recon`, `eval_recon_from_saved_data`): world clouds, voxel down-sampling, point-to-point ICP and the clipped
 chamfer distance, all on the device (formats.world_pointcloud, formats.voxel_downsample, vista_slam_amd.cloud).
 
+Mesh half (`eval_mesh`, `mesh_depth_l1`): the protocol of the 7-Scenes and Replica evaluations of dense SLAM systems - points drawn
+uniformly by area from the estimated and the ground-truth surface (vista_slam_amd.surface), nearest neighbours both ways
+(vista_slam_amd.cloud), accuracy, completion, completion ratio and F-score; and the L1 difference of the two meshes' depth maps
+(render.mesh_depth).  Samples are scored against samples: there are no point-to-triangle distances.
+
 What this is not: a comparison against evo, Open3D or pykdtree (none is available; ICP's loop and the alignment are restated from
 their published definitions, tests/cloud_cases.py holds the numpy restatement they are tested against); no plots.
 """
@@ -13,6 +18,7 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -120,6 +126,70 @@ def eval_recon(frontend, gt_depths, gt_poses, gt_intri, est_depths, est_poses, e
     if return_stages:
         out += (dict(est_raw=est_raw, rel=rel, est_pts=est_pts, est_down=est_down, gt_down=gt_down, icp=reg),)
     return out
+
+
+class MeshScore(NamedTuple):
+    accuracy: float                # mean of min(d, max_error), estimate -> ground truth
+    completion: float              # the same mean, ground truth -> estimate
+    completion_ratio: float        # share of the ground-truth samples with d <= threshold
+    precision: float               # share of the estimate's samples with d <= threshold
+    fscore: float                  # 2 precision completion_ratio / (precision + completion_ratio), 0 when both are 0
+    chamfer: float                 # (accuracy + completion) / 2
+    est_points: torch.Tensor       # [n,3] f32, after T
+    gt_points: torch.Tensor        # [n,3] f32 (the cloud itself when gt is a cloud)
+    n_precise: int                 # the integer counts behind the two ratios
+    n_complete: int
+
+
+def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: float = 0.05, max_error: float = 0.5, T=None, seed: int = 0) -> MeshScore:
+    """Score a mesh against a ground truth, samples against samples.  gt: a `tsdf.Mesh`, the path of a PLY of `tsdf.write_mesh_ply`, or an
+    [M,3] cloud (taken as it is, not sampled).
+      1. n_samples points by area from the estimate with `seed`, from the ground-truth mesh with seed + 1 (surface.sample_surface)
+      2. the estimate's samples moved by T ([3,4] or [4,4]; None = identity, not applied) through cloud.transform
+      3. both directions of clipped nearest-neighbour distances from cloud.chamfer(gt, est, max_error, return_distances=True)
+      4. means, counts of d <= threshold and the F-score, summed on the device in float64
+    The clipped distance is cloud.chamfer's: sqrt(min(d^2, max_error^2)), and max_error for a sample without a neighbour within max_error
+    or that is not finite (a mesh without area gives NaN samples: every one of them scores max_error).
+    threshold > max_error is refused (every distance is clipped at max_error, so no sample could pass)."""
+    from . import surface, tsdf
+    if not float(threshold) <= float(max_error):
+        raise ValueError(f"eval_mesh: threshold must be <= max_error (got {threshold}, {max_error})")
+    dev = getattr(frontend, "device", frontend)
+    est = surface.sample_surface(tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in est_mesh]), n_samples, seed=seed).points
+    if T is not None:
+        est = cloud.transform(est, np.asarray(_host(T), dtype=np.float64)[:3])
+    if isinstance(gt, (str, os.PathLike)):
+        gt = tsdf.mesh_from_ply(gt, dev)
+    if isinstance(gt, tsdf.Mesh):
+        gt_pts = surface.sample_surface(tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in gt]), n_samples, seed=int(seed) + 1).points
+    else:
+        gt_pts = torch.as_tensor(gt).to(dev, torch.float32).reshape(-1, 3).contiguous()
+    ch = cloud.chamfer(gt_pts, est, max_error, return_distances=True)
+    d_est, d_gt = ch.dist_1, ch.dist_2              # est -> gt, gt -> est
+    thr = float(threshold)
+
+    def score(d):
+        n = len(d)
+        return (float(d.sum().item()) / n if n else float("nan")), int((d <= thr).sum().item()), n
+    acc, n_precise, n_est = score(d_est)
+    comp, n_complete, n_gt = score(d_gt)
+    precision = n_precise / n_est if n_est else float("nan")
+    ratio = n_complete / n_gt if n_gt else float("nan")
+    f = 2.0 * precision * ratio / (precision + ratio) if precision + ratio > 0 else (0.0 if precision + ratio == 0 else float("nan"))
+    return MeshScore(acc, comp, ratio, precision, f, (acc + comp) / 2.0, est, gt_pts, n_precise, n_complete)
+
+
+def mesh_depth_l1(frontend, est_mesh, gt_mesh, cameras, H: int, W: int):
+    """(mean |depth_est - depth_gt| over the pixels of `cameras` (render.Camera) that both meshes cover, the number of those pixels),
+    through render.mesh_depth; NaN when there is no such pixel.  Plumbing: the triangle pass does the work."""
+    from . import render
+    total, count = 0.0, 0
+    for cam in cameras:
+        de, dg = render.mesh_depth(frontend, est_mesh, cam, H, W), render.mesh_depth(frontend, gt_mesh, cam, H, W)
+        both = torch.isfinite(de) & torch.isfinite(dg)
+        total += float((de.to(torch.float64) - dg.to(torch.float64)).abs()[both].sum().item())
+        count += int(both.sum().item())
+    return (total / count if count else float("nan")), count
 
 
 def load_data(output_folder, load_view_graph=True, load_gt_depths=True, load_gt_poses=True, load_gt_intrinsic=True, load_unscaled_depths=True,

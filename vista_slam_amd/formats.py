@@ -213,13 +213,15 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
                   view_names: Optional[Sequence[str]] = None, save_view_graph=True, traj_name_postfix=None,
                   save_poses=True, save_images=True, save_scales=True, save_depths=True, save_intrinsics=True,
                   save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None,
-                  counts=None, min_views: int = 0, ply_voxel_size=None, mesh_voxel_size=None):
+                  counts=None, min_views: int = 0, ply_voxel_size=None, mesh_min_triangles=None, mesh_voxel_size=None):
     """Same switches and files as OnlineSLAM.save_data_all (slam.py:338-421).  poses [N,4,4] (rotation + translation
     of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1].
     counts / min_views: pointcloud.ply keeps only pixels that at least min_views neighbouring views agree with
     (world_pointcloud); ply_voxel_size: pointcloud.ply holds the cloud fused on a voxel grid of that size, one vertex per occupied
     voxel (voxel_downsample); every other file is unaffected.  mesh_voxel_size: additionally mesh.ply, the TSDF fusion of the same views at
-    that voxel size (vista_slam_amd.tsdf.fuse, read back with tsdf.read_mesh_ply); without it every file is byte for byte what it was."""
+    that voxel size (vista_slam_amd.tsdf.fuse, read back with tsdf.read_mesh_ply); without it every file is byte for byte what it was.
+    mesh_min_triangles: that mesh without its connected components of fewer triangles (vista_slam_amd.surface.clean_mesh) - the floaters;
+    without it mesh.ply is byte for byte what it was."""
     os.makedirs(output_folder, exist_ok=True)
 
     def host(t):
@@ -247,9 +249,12 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
         write_ply(f"{output_folder}/pointcloud.ply", records)
     if mesh_voxel_size is not None:
         from . import tsdf
-        tsdf.write_mesh_ply(f"{output_folder}/mesh.ply", tsdf.fuse(frontend, depths=depths, scales=scales, intrinsics=intrinsics, poses=poses, confs=confs,
-                                                                   imgs=imgs, conf_thres=conf_thres, counts=counts, min_views=min_views,
-                                                                   voxel_size=mesh_voxel_size))
+        mesh = tsdf.fuse(frontend, depths=depths, scales=scales, intrinsics=intrinsics, poses=poses, confs=confs, imgs=imgs, conf_thres=conf_thres,
+                         counts=counts, min_views=min_views, voxel_size=mesh_voxel_size)
+        if mesh_min_triangles is not None:
+            from . import surface
+            mesh = surface.clean_mesh(mesh, min_triangles=mesh_min_triangles)
+        tsdf.write_mesh_ply(f"{output_folder}/mesh.ply", mesh)
     if gt_poses is not None:
         np.save(f"{output_folder}/gt_poses.npy", np.array(gt_poses).astype(np.float32))
     if gt_depths is not None:
