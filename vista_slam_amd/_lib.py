@@ -19,6 +19,7 @@ RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (includ
 TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (include/sta_tsdf.h): `load_tsdf()`
 MESH_LIB_PATH = os.path.join(PKG, "libsta_mesh.so")        # a fifth one (include/sta_mesh.h): `load_mesh()`
 SURF_LIB_PATH = os.path.join(PKG, "libsta_surf.so")        # a sixth one (include/sta_surf.h): `load_surf()`
+SIMP_LIB_PATH = os.path.join(PKG, "libsta_simp.so")        # a seventh one (include/sta_simp.h): `load_simp()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -265,6 +266,15 @@ SURF_SIGNATURES = {
     "sta_surf_sample": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "sta_surf_last_error": (C.c_char_p, []),
 }
+# include/sta_simp.h: libsta_simp.so, handle-free; a table of its own like the five above
+_d = C.c_double
+SIMP_SIGNATURES = {
+    "sta_simp_plan": (_i, [_i64, _i64, _i64p]),
+    "sta_simp_cells": (_i, [_vp, _i64, _d, _d, _d, _d, _vp, _vp, _vp, _i64, _vp]),
+    "sta_simp_triangles": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sta_simp_place": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _d, _d, _d, _d, _i, _d, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sta_simp_last_error": (C.c_char_p, []),
+}
 
 _lib = None
 _test_lib = None
@@ -273,6 +283,7 @@ _raster_lib = None
 _tsdf_lib = None
 _mesh_lib = None
 _surf_lib = None
+_simp_lib = None
 
 
 class StaError(RuntimeError):
@@ -457,6 +468,29 @@ def load_surf():
 def check_surf(rc):
     if rc != 0:
         raise StaError((load_surf().sta_surf_last_error() or b"unknown error").decode())
+
+
+def load_simp():
+    """Load libsta_simp.so and bind every symbol of include/sta_simp.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_simp(rc)`."""
+    global _simp_lib
+    if _simp_lib is not None:
+        return _simp_lib
+    if not os.path.exists(SIMP_LIB_PATH):
+        raise _missing(SIMP_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(SIMP_LIB_PATH)
+    for name, (res, args) in SIMP_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _simp_lib = lib
+    return lib
+
+
+def check_simp(rc):
+    if rc != 0:
+        raise StaError((load_simp().sta_simp_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

@@ -14,6 +14,8 @@
                                             #    (triangles for the rasteriser's key buffer and vertex normals; its own translation unit)
                                             #    vista_slam_amd/libsta_surf.so         a sixth, handle-free library: exports include/sta_surf.h
                                             #    (connected components and area-uniform surface samples of a mesh; its own translation unit)
+                                            #    vista_slam_amd/libsta_simp.so         a seventh, handle-free library: exports include/sta_simp.h
+                                            #    (mesh simplification by vertex clustering with quadrics; its own translation unit)
 """
 import os
 import shutil
@@ -50,6 +52,11 @@ MESH_DEPS = ["sta_exports.map", "sta_mesh.hip", "mesh.h", "raster.h", "voxel.h",
 SURF_LIB = os.path.join(PKG, "libsta_surf.so")
 SURF_SOURCES = ["sta_surf.hip"]
 SURF_DEPS = ["sta_exports.map", "sta_surf.hip", "surf.h", "sta_common.h", os.path.join("..", "..", "include", "sta_surf.h")]
+# libsta_simp.so: likewise; it includes voxel.h, select.h, elementwise.h and sta_common.h unchanged
+SIMP_LIB = os.path.join(PKG, "libsta_simp.so")
+SIMP_SOURCES = ["sta_simp.hip"]
+SIMP_DEPS = ["sta_exports.map", "sta_simp.hip", "simp.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
+             os.path.join("..", "..", "include", "sta_simp.h")]
 
 
 def hipcc_path():
@@ -72,6 +79,7 @@ RASTER_HASH_FILE = RASTER_LIB + ".srchash"
 TSDF_HASH_FILE = TSDF_LIB + ".srchash"
 MESH_HASH_FILE = MESH_LIB + ".srchash"
 SURF_HASH_FILE = SURF_LIB + ".srchash"
+SIMP_HASH_FILE = SIMP_LIB + ".srchash"
 
 
 def extra_flags():
@@ -88,7 +96,7 @@ def extra_flags():
 def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS, SURF_DEPS)."""
+    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS, SURF_DEPS, SIMP_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
@@ -110,9 +118,9 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True):
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True):
     """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so, (raster) libsta_raster.so, (tsdf)
-    libsta_tsdf.so, (mesh) libsta_mesh.so and (surf) libsta_surf.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    libsta_tsdf.so, (mesh) libsta_mesh.so, (surf) libsta_surf.so and (simp) libsta_simp.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
@@ -128,6 +136,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
         jobs.append((MESH_LIB, MESH_HASH_FILE, False, MESH_SOURCES, MESH_DEPS))
     if surf and (force or is_stale(SURF_LIB, SURF_HASH_FILE, SURF_DEPS)):
         jobs.append((SURF_LIB, SURF_HASH_FILE, False, SURF_SOURCES, SURF_DEPS))
+    if simp and (force or is_stale(SIMP_LIB, SIMP_HASH_FILE, SIMP_DEPS)):
+        jobs.append((SIMP_LIB, SIMP_HASH_FILE, False, SIMP_SOURCES, SIMP_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()

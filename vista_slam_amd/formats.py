@@ -213,7 +213,7 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
                   view_names: Optional[Sequence[str]] = None, save_view_graph=True, traj_name_postfix=None,
                   save_poses=True, save_images=True, save_scales=True, save_depths=True, save_intrinsics=True,
                   save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None,
-                  counts=None, min_views: int = 0, ply_voxel_size=None, mesh_min_triangles=None, mesh_voxel_size=None):
+                  counts=None, min_views: int = 0, ply_voxel_size=None, mesh_min_triangles=None, mesh_simplify_cell=None, mesh_voxel_size=None):
     """Same switches and files as OnlineSLAM.save_data_all (slam.py:338-421).  poses [N,4,4] (rotation + translation
     of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1].
     counts / min_views: pointcloud.ply keeps only pixels that at least min_views neighbouring views agree with
@@ -221,7 +221,8 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
     voxel (voxel_downsample); every other file is unaffected.  mesh_voxel_size: additionally mesh.ply, the TSDF fusion of the same views at
     that voxel size (vista_slam_amd.tsdf.fuse, read back with tsdf.read_mesh_ply); without it every file is byte for byte what it was.
     mesh_min_triangles: that mesh without its connected components of fewer triangles (vista_slam_amd.surface.clean_mesh) - the floaters;
-    without it mesh.ply is byte for byte what it was."""
+    without it mesh.ply is byte for byte what it was.  mesh_simplify_cell: that mesh, after the cleaning, simplified by vertex clustering on
+    cells of that size (vista_slam_amd.simplify.simplify_mesh, quadric placement); without it mesh.ply is byte for byte what it was."""
     os.makedirs(output_folder, exist_ok=True)
 
     def host(t):
@@ -254,6 +255,9 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
         if mesh_min_triangles is not None:
             from . import surface
             mesh = surface.clean_mesh(mesh, min_triangles=mesh_min_triangles)
+        if mesh_simplify_cell is not None:
+            from . import simplify
+            mesh = simplify.simplify_mesh(mesh, mesh_simplify_cell)
         tsdf.write_mesh_ply(f"{output_folder}/mesh.ply", mesh)
     if gt_poses is not None:
         np.save(f"{output_folder}/gt_poses.npy", np.array(gt_poses).astype(np.float32))

@@ -9,8 +9,8 @@ generator (splitmix64) and float64 operations in a written order - labels, count
     mesh = surface.clean_mesh(mesh, min_triangles=100)
     s = surface.sample_surface(mesh, 200000, seed=0)
 
-Not here: components by shared EDGE (Open3D's cluster_connected_triangles; here a shared vertex connects), component areas, mesh
-simplification, point-to-triangle distances.  DESIGN.md section 9.
+Not here: components by shared EDGE (Open3D's cluster_connected_triangles; here a shared vertex connects), component areas, point-to-triangle
+distances (mesh simplification: vista_slam_amd/simplify.py).  DESIGN.md section 9.
 """
 from __future__ import annotations
 

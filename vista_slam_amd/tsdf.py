@@ -10,7 +10,7 @@ point, no floating-point atomics - a volume and a mesh are defined bit for bit b
     tsdf.write_mesh_ply("mesh.ply", mesh)
 
 Not here: growing a volume's block set after `allocate` (poses move under the optimiser, so fusion is a pass over an export, as
-`world_pointcloud` is); trilinear depth lookup (the nearest pixel is used); ray casting; mesh simplification; marching cubes;
+`world_pointcloud` is); trilinear depth lookup (the nearest pixel is used); ray casting; marching cubes;
 Open3D's ScalableTSDFVolume bit for bit - this is a contract of its own.  DESIGN.md section 9.
 
 On top of a mesh, through libsta_mesh.so (include/sta_mesh.h): `vertex_normals` (area-weighted, summed in ascending triangle order, no
