@@ -20,6 +20,7 @@ TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (inclu
 MESH_LIB_PATH = os.path.join(PKG, "libsta_mesh.so")        # a fifth one (include/sta_mesh.h): `load_mesh()`
 SURF_LIB_PATH = os.path.join(PKG, "libsta_surf.so")        # a sixth one (include/sta_surf.h): `load_surf()`
 SIMP_LIB_PATH = os.path.join(PKG, "libsta_simp.so")        # a seventh one (include/sta_simp.h): `load_simp()`
+DIST_LIB_PATH = os.path.join(PKG, "libsta_dist.so")        # an eighth one (include/sta_dist.h): `load_dist()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -275,6 +276,20 @@ SIMP_SIGNATURES = {
     "sta_simp_place": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _d, _d, _d, _d, _i, _d, _vp, _vp, _vp, _vp, _i64, _vp]),
     "sta_simp_last_error": (C.c_char_p, []),
 }
+# include/sta_dist.h: libsta_dist.so, handle-free; a table of its own like the six above (the host struct sta_tri_index goes as void*)
+DIST_SIGNATURES = {
+    "sta_tri_plan": (_i, [_i64, _i64, _i64p]),
+    "sta_tri_build": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "sta_tri_query": (_i, [_vp, _vp, _i64, _d, _vp, _vp, _vp, _vp]),
+    "sta_tri_last_error": (C.c_char_p, []),
+}
+
+
+class StaTriIndex(C.Structure):
+    """sta_tri_index of include/sta_dist.h: pointers into the caller's index buffer and the shape of the implicit tree."""
+    _fields_ = [("tri", C.c_void_p), ("src", C.c_void_p), ("boxes", C.c_void_p), ("counters", C.c_void_p), ("nt", C.c_int64),
+                ("levels", C.c_int32), ("reserved", C.c_int32), ("level_offset", C.c_int64 * 10)]
+
 
 _lib = None
 _test_lib = None
@@ -284,6 +299,7 @@ _tsdf_lib = None
 _mesh_lib = None
 _surf_lib = None
 _simp_lib = None
+_dist_lib = None
 
 
 class StaError(RuntimeError):
@@ -491,6 +507,29 @@ def load_simp():
 def check_simp(rc):
     if rc != 0:
         raise StaError((load_simp().sta_simp_last_error() or b"unknown error").decode())
+
+
+def load_dist():
+    """Load libsta_dist.so and bind every symbol of include/sta_dist.h; raises if it is absent (no fallback here either).
+    Its errors are its own: `check_dist(rc)`."""
+    global _dist_lib
+    if _dist_lib is not None:
+        return _dist_lib
+    if not os.path.exists(DIST_LIB_PATH):
+        raise _missing(DIST_LIB_PATH)
+    import torch  # noqa: F401      (one HIP runtime per process: see load())
+    lib = C.CDLL(DIST_LIB_PATH)
+    for name, (res, args) in DIST_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _dist_lib = lib
+    return lib
+
+
+def check_dist(rc):
+    if rc != 0:
+        raise StaError((load_dist().sta_tri_last_error() or b"unknown error").decode())
 
 
 def use_test_hooks():

@@ -16,6 +16,8 @@
                                             #    (connected components and area-uniform surface samples of a mesh; its own translation unit)
                                             #    vista_slam_amd/libsta_simp.so         a seventh, handle-free library: exports include/sta_simp.h
                                             #    (mesh simplification by vertex clustering with quadrics; its own translation unit)
+                                            #    vista_slam_amd/libsta_dist.so         an eighth, handle-free library: exports include/sta_dist.h
+                                            #    (exact point-to-triangle distances over an implicit BVH; its own translation unit)
 """
 import os
 import shutil
@@ -57,6 +59,11 @@ SIMP_LIB = os.path.join(PKG, "libsta_simp.so")
 SIMP_SOURCES = ["sta_simp.hip"]
 SIMP_DEPS = ["sta_exports.map", "sta_simp.hip", "simp.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
              os.path.join("..", "..", "include", "sta_simp.h")]
+# libsta_dist.so: likewise; it includes voxel.h, select.h, elementwise.h and sta_common.h unchanged
+DIST_LIB = os.path.join(PKG, "libsta_dist.so")
+DIST_SOURCES = ["sta_dist.hip"]
+DIST_DEPS = ["sta_exports.map", "sta_dist.hip", "dist.h", "voxel.h", "select.h", "elementwise.h", "sta_common.h",
+             os.path.join("..", "..", "include", "sta_dist.h")]
 
 
 def hipcc_path():
@@ -80,6 +87,7 @@ TSDF_HASH_FILE = TSDF_LIB + ".srchash"
 MESH_HASH_FILE = MESH_LIB + ".srchash"
 SURF_HASH_FILE = SURF_LIB + ".srchash"
 SIMP_HASH_FILE = SIMP_LIB + ".srchash"
+DIST_HASH_FILE = DIST_LIB + ".srchash"
 
 
 def extra_flags():
@@ -96,7 +104,7 @@ def extra_flags():
 def source_hash(deps=None):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS, SURF_DEPS, SIMP_DEPS)."""
+    libraries) unless given (CLOUD_DEPS, RASTER_DEPS, TSDF_DEPS, MESH_DEPS, SURF_DEPS, SIMP_DEPS, DIST_DEPS)."""
     import hashlib
     h = hashlib.sha256()
     h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
@@ -118,9 +126,9 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True):
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True):
     """Build the product library, (test_hooks) the test-hooks library, (cloud) libsta_cloud.so, (raster) libsta_raster.so, (tsdf)
-    libsta_tsdf.so, (mesh) libsta_mesh.so, (surf) libsta_surf.so and (simp) libsta_simp.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    libsta_tsdf.so, (mesh) libsta_mesh.so, (surf) libsta_surf.so, (simp) libsta_simp.so and (dist) libsta_dist.so; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
@@ -138,6 +146,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
         jobs.append((SURF_LIB, SURF_HASH_FILE, False, SURF_SOURCES, SURF_DEPS))
     if simp and (force or is_stale(SIMP_LIB, SIMP_HASH_FILE, SIMP_DEPS)):
         jobs.append((SIMP_LIB, SIMP_HASH_FILE, False, SIMP_SOURCES, SIMP_DEPS))
+    if dist and (force or is_stale(DIST_LIB, DIST_HASH_FILE, DIST_DEPS)):
+        jobs.append((DIST_LIB, DIST_HASH_FILE, False, DIST_SOURCES, DIST_DEPS))
     if not jobs:
         return LIB
     hipcc = hipcc_path()

@@ -9,7 +9,8 @@ chamfer distance, all on the device (formats.world_pointcloud, formats.voxel_dow
 Mesh half (`eval_mesh`, `mesh_depth_l1`): the protocol of the 7-Scenes and Replica evaluations of dense SLAM systems - points drawn
 uniformly by area from the estimated and the ground-truth surface (vista_slam_amd.surface), nearest neighbours both ways
 (vista_slam_amd.cloud), accuracy, completion, completion ratio and F-score; and the L1 difference of the two meshes' depth maps
-(render.mesh_depth).  Samples are scored against samples: there are no point-to-triangle distances.
+(render.mesh_depth).  By default samples are scored against samples; `eval_mesh(mode="surface")` scores them against the other mesh
+itself, with the exact point-to-triangle distances of vista_slam_amd.meshdist.
 
 What this is not: a comparison against evo, Open3D or pykdtree (none is available; ICP's loop and the alignment are restated from
 their published definitions, tests/cloud_cases.py holds the numpy restatement they are tested against); no plots.
@@ -141,8 +142,9 @@ class MeshScore(NamedTuple):
     n_complete: int
 
 
-def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: float = 0.05, max_error: float = 0.5, T=None, seed: int = 0) -> MeshScore:
-    """Score a mesh against a ground truth, samples against samples.  gt: a `tsdf.Mesh`, the path of a PLY of `tsdf.write_mesh_ply`, or an
+def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: float = 0.05, max_error: float = 0.5, T=None, seed: int = 0,
+              mode: str = "samples") -> MeshScore:
+    """Score a mesh against a ground truth, samples against samples (mode="samples", the default).  gt: a `tsdf.Mesh`, the path of a PLY of `tsdf.write_mesh_ply`, or an
     [M,3] cloud (taken as it is, not sampled).
       1. n_samples points by area from the estimate with `seed`, from the ground-truth mesh with seed + 1 (surface.sample_surface)
       2. the estimate's samples moved by T ([3,4] or [4,4]; None = identity, not applied) through cloud.transform
@@ -150,22 +152,49 @@ def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: flo
       4. means, counts of d <= threshold and the F-score, summed on the device in float64
     The clipped distance is cloud.chamfer's: sqrt(min(d^2, max_error^2)), and max_error for a sample without a neighbour within max_error
     or that is not finite (a mesh without area gives NaN samples: every one of them scores max_error).
-    threshold > max_error is refused (every distance is clipped at max_error, so no sample could pass)."""
+    threshold > max_error is refused (every distance is clipped at max_error, so no sample could pass).
+    mode="surface": the same samples with the same seeds (est_points and gt_points are those of the default mode), scored against the
+    SURFACE: the estimate's samples against the ground-truth mesh, the ground truth's samples against the estimate's mesh (its vertices
+    moved by T through cloud.transform, once), both as sqrt(min(d2, max_error^2)) of meshdist's exact point-to-triangle query with
+    radius = max_error.  Scoring samples against samples has a floor of about one sample spacing even for identical surfaces; this has
+    none.  When gt is a cloud there is no ground-truth surface: completion is the cloud against the estimate's mesh, accuracy stays the
+    nearest-neighbour distance from the estimate's samples to the cloud, as in the default mode."""
     from . import surface, tsdf
     if not float(threshold) <= float(max_error):
         raise ValueError(f"eval_mesh: threshold must be <= max_error (got {threshold}, {max_error})")
+    if mode not in ("samples", "surface"):
+        raise ValueError(f"eval_mesh: mode must be 'samples' or 'surface' (got {mode!r})")
     dev = getattr(frontend, "device", frontend)
-    est = surface.sample_surface(tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in est_mesh]), n_samples, seed=seed).points
+    est_m = tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in est_mesh])
+    est = surface.sample_surface(est_m, n_samples, seed=seed).points
     if T is not None:
         est = cloud.transform(est, np.asarray(_host(T), dtype=np.float64)[:3])
     if isinstance(gt, (str, os.PathLike)):
         gt = tsdf.mesh_from_ply(gt, dev)
+    gt_m = None
     if isinstance(gt, tsdf.Mesh):
-        gt_pts = surface.sample_surface(tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in gt]), n_samples, seed=int(seed) + 1).points
+        gt_m = tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in gt])
+        gt_pts = surface.sample_surface(gt_m, n_samples, seed=int(seed) + 1).points
     else:
         gt_pts = torch.as_tensor(gt).to(dev, torch.float32).reshape(-1, 3).contiguous()
-    ch = cloud.chamfer(gt_pts, est, max_error, return_distances=True)
-    d_est, d_gt = ch.dist_1, ch.dist_2              # est -> gt, gt -> est
+    if mode == "samples":
+        ch = cloud.chamfer(gt_pts, est, max_error, return_distances=True)
+        d_est, d_gt = ch.dist_1, ch.dist_2              # est -> gt, gt -> est
+    else:
+        from . import meshdist
+        r2 = float(max_error) * float(max_error)
+
+        def to_surface(points, verts, tris):
+            d2, = meshdist.TriIndex.build(SimpleNamespace(vertices=verts, triangles=tris)).query(points, float(max_error), want=("d2",))
+            return torch.sqrt(torch.clamp(d2, max=r2))
+        est_v = est_m.vertices.to(torch.float32).contiguous()
+        if T is not None:
+            est_v = cloud.transform(est_v, np.asarray(_host(T), dtype=np.float64)[:3])
+        d_gt = to_surface(gt_pts, est_v, est_m.triangles)
+        if gt_m is not None:
+            d_est = to_surface(est, gt_m.vertices, gt_m.triangles)
+        else:
+            d_est = cloud.chamfer(gt_pts, est, max_error, return_distances=True).dist_1
     thr = float(threshold)
 
     def score(d):
