@@ -1,7 +1,7 @@
 """Host only: libsta_mesh.so exports exactly include/sta_mesh.h, the ctypes table mirrors it, no name collides with the other five tables,
 every declaration that takes a stream has a row in tests/mesh_stream_cases.py (and the other way round) and none of them may wait, the
-header's constants are those of vista_slam_amd/render.py and tests/mesh_cases.py, and none of the other four libraries' sources moved:
-their content hashes are the ones computed on the commit before this library."""
+header's constants are those of vista_slam_amd/render.py and tests/mesh_cases.py.  That no
+library is built from another's own files is tests/test_library_table.py's to check."""
 import ctypes as C
 import inspect
 import os
@@ -14,10 +14,6 @@ from test_stream_inventory import stream_entry_points
 
 HEADER = pathlib.Path(__file__).resolve().parents[1] / "include" / "sta_mesh.h"
 LINKER = {"_init", "_fini", "_edata", "_end", "__bss_start"}
-PRODUCT_HASH = "4d785dbc25cf4c3ce89a79d6ef484b12d215e827b6f16294b017cdcb7a8b38e4"
-CLOUD_HASH = "a02cd9e31729b56d655e0d7689abd56ed576625caeaedc18fe086a7bb2b6927e"
-RASTER_HASH = "52ff4fc399cbdfd434423a134a95220541ec0d631113bd4e7a93c38a1db7635e"
-TSDF_HASH = "62fba8772684c0584b6ab7343330bab3b2ddc0886d12ef3f80f3e3394f64dbb1"
 
 
 def test_the_library_exports_exactly_its_header():
@@ -112,22 +108,3 @@ def test_every_stream_entry_point_has_a_row_and_none_may_wait():
     header = " ".join(HEADER.read_text().split())
     assert "NO CALL ALLOCATES, COPIES TO THE HOST OR SYNCHRONISES" in header.replace(" * ", " ")
 
-
-def test_the_other_libraries_are_what_they_were():
-    """The triangles are a library of their own: nothing of it is among the sources the other four hashes cover, those hashes are the parent
-    commit's, and a fifth, distinct one exists."""
-    from vista_slam_amd import _lib, build
-    assert build.source_hash() == PRODUCT_HASH
-    assert build.source_hash(build.CLOUD_DEPS) == CLOUD_HASH
-    assert build.source_hash(build.RASTER_DEPS) == RASTER_HASH
-    assert build.source_hash(build.TSDF_DEPS) == TSDF_HASH
-    mine = {"sta_mesh.hip", "mesh.h", os.path.join("..", "..", "include", "sta_mesh.h")}
-    for deps in (build.DEPS, build.CLOUD_DEPS, build.RASTER_DEPS, build.TSDF_DEPS):
-        assert not mine & set(deps)
-    assert mine <= set(build.MESH_DEPS)
-    assert len({build.source_hash(), build.source_hash(build.CLOUD_DEPS), build.source_hash(build.RASTER_DEPS), build.source_hash(build.TSDF_DEPS),
-                build.source_hash(build.MESH_DEPS)}) == 5
-    prod = declared_symbols("sta_mi355.h")
-    assert exported_symbols(_lib.LIB_PATH) == prod == set(_lib.SIGNATURES)
-    others = all_exported(_lib.LIB_PATH) | all_exported(_lib.CLOUD_LIB_PATH) | all_exported(_lib.RASTER_LIB_PATH) | all_exported(_lib.TSDF_LIB_PATH)
-    assert not {s for s in others if "mesh" in s and s.startswith("sta_mesh")}

@@ -1,8 +1,7 @@
 """Host only: libsta_raster.so exports exactly include/sta_raster.h, the ctypes table mirrors it, no name collides with the other
-tables, every declaration that takes a stream has a row in tests/render_stream_cases.py (and the other way round), and neither the
-product library's nor libsta_cloud.so's sources moved: their content hashes are the ones computed on the commit before the rasteriser."""
+tables, every declaration that takes a stream has a row in tests/render_stream_cases.py (and the other way round).  That no
+library is built from another's own files is tests/test_library_table.py's to check."""
 import ctypes as C
-import os
 import pathlib
 import re
 
@@ -12,8 +11,6 @@ from test_stream_inventory import stream_entry_points
 
 HEADER = pathlib.Path(__file__).resolve().parents[1] / "include" / "sta_raster.h"
 LINKER = {"_init", "_fini", "_edata", "_end", "__bss_start"}
-PRODUCT_HASH = "4d785dbc25cf4c3ce89a79d6ef484b12d215e827b6f16294b017cdcb7a8b38e4"
-CLOUD_HASH = "a02cd9e31729b56d655e0d7689abd56ed576625caeaedc18fe086a7bb2b6927e"
 
 
 def test_the_library_exports_exactly_its_header():
@@ -81,16 +78,3 @@ def test_every_stream_entry_point_has_a_row():
     header = HEADER.read_text()
     assert "no call allocates, copies to the host or synchronises" in header
 
-
-def test_the_other_libraries_are_what_they_were():
-    """The rasteriser is a library of its own: nothing of it is among the sources the product's or the cloud library's hash covers, those
-    hashes are the parent commit's, and the product's export table is include/sta_mi355.h."""
-    from vista_slam_amd import _lib, build
-    assert build.source_hash() == PRODUCT_HASH
-    assert build.source_hash(build.CLOUD_DEPS) == CLOUD_HASH
-    mine = {"sta_raster.hip", "raster.h", os.path.join("..", "..", "include", "sta_raster.h")}
-    assert not mine & set(build.DEPS) and not mine & set(build.CLOUD_DEPS) and mine <= set(build.RASTER_DEPS)
-    assert len({build.source_hash(), build.source_hash(build.CLOUD_DEPS), build.source_hash(build.RASTER_DEPS)}) == 3
-    prod = declared_symbols("sta_mi355.h")
-    assert exported_symbols(_lib.LIB_PATH) == prod == set(_lib.SIGNATURES)
-    assert not {s for s in all_exported(_lib.LIB_PATH) | all_exported(_lib.CLOUD_LIB_PATH) if "raster" in s}

@@ -1,7 +1,7 @@
 """Host only: libsta_simp.so exports exactly include/sta_simp.h, the ctypes table mirrors it, no name collides with the other seven
 tables, every declaration that takes a stream has a row in tests/simp_stream_cases.py (and the other way round) and none of them may wait,
-the header's constants are those of vista_slam_amd/simplify.py and tests/simp_cases.py, and none of the other six libraries' sources
-moved: their content hashes are the ones computed on the commit before this library."""
+the header's constants are those of vista_slam_amd/simplify.py and tests/simp_cases.py.  That no
+library is built from another's own files is tests/test_library_table.py's to check."""
 import ctypes as C
 import inspect
 import os
@@ -11,13 +11,10 @@ import re
 import simp_cases as SP
 import simp_stream_cases as SS
 from test_cabi_symbols import all_exported, declared_symbols, exported_symbols
-from test_mesh_abi import CLOUD_HASH, PRODUCT_HASH, RASTER_HASH, TSDF_HASH
 from test_stream_inventory import stream_entry_points
-from test_surf_abi import MESH_HASH
 
 HEADER = pathlib.Path(__file__).resolve().parents[1] / "include" / "sta_simp.h"
 LINKER = {"_init", "_fini", "_edata", "_end", "__bss_start"}
-SURF_HASH = "625d16b55e02db850be48bb0405313b28f4a020efcc84a56b1da150b448ce68d"
 
 
 def test_the_library_exports_exactly_its_header():
@@ -103,25 +100,3 @@ def test_every_stream_entry_point_has_a_row_and_none_may_wait():
     header = " ".join(HEADER.read_text().split())
     assert "NO CALL ALLOCATES, COPIES TO THE HOST OR SYNCHRONISES" in header.replace(" * ", " ")
 
-
-def test_the_other_libraries_are_what_they_were():
-    """The simplification library is a library of its own: nothing of it is among the sources the other six hashes cover, those hashes are
-    the parent commit's, and a seventh, distinct one exists."""
-    from vista_slam_amd import _lib, build
-    assert build.source_hash() == PRODUCT_HASH
-    assert build.source_hash(build.CLOUD_DEPS) == CLOUD_HASH
-    assert build.source_hash(build.RASTER_DEPS) == RASTER_HASH
-    assert build.source_hash(build.TSDF_DEPS) == TSDF_HASH
-    assert build.source_hash(build.MESH_DEPS) == MESH_HASH
-    assert build.source_hash(build.SURF_DEPS) == SURF_HASH
-    mine = {"sta_simp.hip", "simp.h", os.path.join("..", "..", "include", "sta_simp.h")}
-    others = (build.DEPS, build.CLOUD_DEPS, build.RASTER_DEPS, build.TSDF_DEPS, build.MESH_DEPS, build.SURF_DEPS)
-    for deps in others:
-        assert not mine & set(deps)
-    assert mine <= set(build.SIMP_DEPS)
-    assert len({build.source_hash(d) for d in others + (build.SIMP_DEPS,)}) == 7
-    assert exported_symbols(_lib.LIB_PATH) == declared_symbols("sta_mi355.h") == set(_lib.SIGNATURES)
-    exported = set()
-    for path in (_lib.LIB_PATH, _lib.CLOUD_LIB_PATH, _lib.RASTER_LIB_PATH, _lib.TSDF_LIB_PATH, _lib.MESH_LIB_PATH, _lib.SURF_LIB_PATH):
-        exported |= all_exported(path)
-    assert not {s for s in exported if s.startswith("sta_simp")}

@@ -1,9 +1,8 @@
 """Host only: libsta_tsdf.so exports exactly include/sta_tsdf.h, the ctypes table mirrors it, no name collides with the other tables,
 every declaration that takes a stream has a row in tests/tsdf_stream_cases.py (and the other way round), the header's constants are those
-of vista_slam_amd/tsdf.py and tests/tsdf_cases.py, and none of the other three libraries' sources moved: their content hashes are the
-ones computed on the commit before this library."""
+of vista_slam_amd/tsdf.py and tests/tsdf_cases.py.  That no
+library is built from another's own files is tests/test_library_table.py's to check."""
 import ctypes as C
-import os
 import pathlib
 import re
 
@@ -13,9 +12,6 @@ from test_stream_inventory import stream_entry_points
 
 HEADER = pathlib.Path(__file__).resolve().parents[1] / "include" / "sta_tsdf.h"
 LINKER = {"_init", "_fini", "_edata", "_end", "__bss_start"}
-PRODUCT_HASH = "4d785dbc25cf4c3ce89a79d6ef484b12d215e827b6f16294b017cdcb7a8b38e4"
-CLOUD_HASH = "a02cd9e31729b56d655e0d7689abd56ed576625caeaedc18fe086a7bb2b6927e"
-RASTER_HASH = "52ff4fc399cbdfd434423a134a95220541ec0d631113bd4e7a93c38a1db7635e"
 
 
 def test_the_library_exports_exactly_its_header():
@@ -91,17 +87,3 @@ def test_every_stream_entry_point_has_a_row():
     from vista_slam_amd import tsdf
     assert "allocate and mesh wait for the stream once each (their counts come back); integrate does not" in " ".join(tsdf.TSDFVolume.__doc__.split())
 
-
-def test_the_other_libraries_are_what_they_were():
-    """The fusion is a library of its own: nothing of it is among the sources the other three hashes cover, those hashes are the parent
-    commit's, and the product's export table is include/sta_mi355.h."""
-    from vista_slam_amd import _lib, build
-    assert build.source_hash() == PRODUCT_HASH
-    assert build.source_hash(build.CLOUD_DEPS) == CLOUD_HASH
-    assert build.source_hash(build.RASTER_DEPS) == RASTER_HASH
-    mine = {"sta_tsdf.hip", "tsdf.h", os.path.join("..", "..", "include", "sta_tsdf.h")}
-    assert not mine & set(build.DEPS) and not mine & set(build.CLOUD_DEPS) and not mine & set(build.RASTER_DEPS) and mine <= set(build.TSDF_DEPS)
-    assert len({build.source_hash(), build.source_hash(build.CLOUD_DEPS), build.source_hash(build.RASTER_DEPS), build.source_hash(build.TSDF_DEPS)}) == 4
-    prod = declared_symbols("sta_mi355.h")
-    assert exported_symbols(_lib.LIB_PATH) == prod == set(_lib.SIGNATURES)
-    assert not {s for s in all_exported(_lib.LIB_PATH) | all_exported(_lib.CLOUD_LIB_PATH) | all_exported(_lib.RASTER_LIB_PATH) if "tsdf" in s}

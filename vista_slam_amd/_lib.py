@@ -293,14 +293,7 @@ class StaTriIndex(C.Structure):
 
 _lib = None
 _test_lib = None
-_cloud_lib = None
-_raster_lib = None
-_tsdf_lib = None
-_mesh_lib = None
-_surf_lib = None
-_simp_lib = None
-_dist_lib = None
-
+_satellites = {}      # path -> the loaded handle-free library
 
 class StaError(RuntimeError):
     pass
@@ -371,165 +364,42 @@ def load_test():
     return lib
 
 
-def load_cloud():
-    """Load libsta_cloud.so and bind every symbol of include/sta_cloud.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_cloud(rc)`."""
-    global _cloud_lib
-    if _cloud_lib is not None:
-        return _cloud_lib
-    if not os.path.exists(CLOUD_LIB_PATH):
-        raise _missing(CLOUD_LIB_PATH)
+def _load_satellite(path, table):
+    """Load one handle-free library (once per path) and bind every symbol of its signature table; raises if it is absent (no fallback
+    here either)."""
+    lib = _satellites.get(path)
+    if lib is not None:
+        return lib
+    if not os.path.exists(path):
+        raise _missing(path)
     import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(CLOUD_LIB_PATH)
-    for name, (res, args) in CLOUD_SIGNATURES.items():
+    lib = C.CDLL(path)
+    for name, (res, args) in table.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
-    _cloud_lib = lib
+    _satellites[path] = lib
     return lib
 
 
-def check_cloud(rc):
-    if rc != 0:
-        raise StaError((load_cloud().sta_cloud_last_error() or b"unknown error").decode())
+def _satellite(path, table, last_error):
+    """(load_x, check_x) of one handle-free library.  Its errors are its own: check_x(rc) raises what its `last_error` function says."""
+    def load_x():
+        return _load_satellite(path, table)
+
+    def check_x(rc):
+        if rc != 0:
+            raise StaError((getattr(load_x(), last_error)() or b"unknown error").decode())
+    return load_x, check_x
 
 
-def load_raster():
-    """Load libsta_raster.so and bind every symbol of include/sta_raster.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_raster(rc)`."""
-    global _raster_lib
-    if _raster_lib is not None:
-        return _raster_lib
-    if not os.path.exists(RASTER_LIB_PATH):
-        raise _missing(RASTER_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(RASTER_LIB_PATH)
-    for name, (res, args) in RASTER_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _raster_lib = lib
-    return lib
-
-
-def check_raster(rc):
-    if rc != 0:
-        raise StaError((load_raster().sta_raster_last_error() or b"unknown error").decode())
-
-
-def load_tsdf():
-    """Load libsta_tsdf.so and bind every symbol of include/sta_tsdf.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_tsdf(rc)`."""
-    global _tsdf_lib
-    if _tsdf_lib is not None:
-        return _tsdf_lib
-    if not os.path.exists(TSDF_LIB_PATH):
-        raise _missing(TSDF_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(TSDF_LIB_PATH)
-    for name, (res, args) in TSDF_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _tsdf_lib = lib
-    return lib
-
-
-def check_tsdf(rc):
-    if rc != 0:
-        raise StaError((load_tsdf().sta_tsdf_last_error() or b"unknown error").decode())
-
-
-def load_mesh():
-    """Load libsta_mesh.so and bind every symbol of include/sta_mesh.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_mesh(rc)`."""
-    global _mesh_lib
-    if _mesh_lib is not None:
-        return _mesh_lib
-    if not os.path.exists(MESH_LIB_PATH):
-        raise _missing(MESH_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(MESH_LIB_PATH)
-    for name, (res, args) in MESH_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _mesh_lib = lib
-    return lib
-
-
-def check_mesh(rc):
-    if rc != 0:
-        raise StaError((load_mesh().sta_mesh_last_error() or b"unknown error").decode())
-
-
-def load_surf():
-    """Load libsta_surf.so and bind every symbol of include/sta_surf.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_surf(rc)`."""
-    global _surf_lib
-    if _surf_lib is not None:
-        return _surf_lib
-    if not os.path.exists(SURF_LIB_PATH):
-        raise _missing(SURF_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(SURF_LIB_PATH)
-    for name, (res, args) in SURF_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _surf_lib = lib
-    return lib
-
-
-def check_surf(rc):
-    if rc != 0:
-        raise StaError((load_surf().sta_surf_last_error() or b"unknown error").decode())
-
-
-def load_simp():
-    """Load libsta_simp.so and bind every symbol of include/sta_simp.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_simp(rc)`."""
-    global _simp_lib
-    if _simp_lib is not None:
-        return _simp_lib
-    if not os.path.exists(SIMP_LIB_PATH):
-        raise _missing(SIMP_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(SIMP_LIB_PATH)
-    for name, (res, args) in SIMP_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _simp_lib = lib
-    return lib
-
-
-def check_simp(rc):
-    if rc != 0:
-        raise StaError((load_simp().sta_simp_last_error() or b"unknown error").decode())
-
-
-def load_dist():
-    """Load libsta_dist.so and bind every symbol of include/sta_dist.h; raises if it is absent (no fallback here either).
-    Its errors are its own: `check_dist(rc)`."""
-    global _dist_lib
-    if _dist_lib is not None:
-        return _dist_lib
-    if not os.path.exists(DIST_LIB_PATH):
-        raise _missing(DIST_LIB_PATH)
-    import torch  # noqa: F401      (one HIP runtime per process: see load())
-    lib = C.CDLL(DIST_LIB_PATH)
-    for name, (res, args) in DIST_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _dist_lib = lib
-    return lib
-
-
-def check_dist(rc):
-    if rc != 0:
-        raise StaError((load_dist().sta_tri_last_error() or b"unknown error").decode())
+load_cloud, check_cloud = _satellite(CLOUD_LIB_PATH, CLOUD_SIGNATURES, "sta_cloud_last_error")        # include/sta_cloud.h
+load_raster, check_raster = _satellite(RASTER_LIB_PATH, RASTER_SIGNATURES, "sta_raster_last_error")    # include/sta_raster.h
+load_tsdf, check_tsdf = _satellite(TSDF_LIB_PATH, TSDF_SIGNATURES, "sta_tsdf_last_error")              # include/sta_tsdf.h
+load_mesh, check_mesh = _satellite(MESH_LIB_PATH, MESH_SIGNATURES, "sta_mesh_last_error")              # include/sta_mesh.h
+load_surf, check_surf = _satellite(SURF_LIB_PATH, SURF_SIGNATURES, "sta_surf_last_error")              # include/sta_surf.h
+load_simp, check_simp = _satellite(SIMP_LIB_PATH, SIMP_SIGNATURES, "sta_simp_last_error")              # include/sta_simp.h
+load_dist, check_dist = _satellite(DIST_LIB_PATH, DIST_SIGNATURES, "sta_tri_last_error")               # include/sta_dist.h: its names are sta_tri_*
 
 
 def use_test_hooks():

@@ -152,7 +152,7 @@ extern "C" int sta_world_pointcloud(sta_handle* h, const float* depths, const fl
         p.N = N; p.H = H; p.W = W; p.thres = conf_thres; p.counts = counts; p.offs = offs; p.nblk = nblk;
         p.pts = pts_out; p.col = col_out; p.rec = ply_records_out;
         hipLaunchKernelGGL(cloud_count_kernel, dim3(nblk), dim3(256), 0, st, p);
-        hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, p);
+        vox_scan(st, counts, offs, nblk);
         hipLaunchKernelGGL(cloud_emit_kernel, dim3(nblk), dim3(256), 0, st, p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(count_host, offs + nblk, 8, hipMemcpyDeviceToHost, st));
@@ -185,19 +185,17 @@ extern "C" int sta_voxel_downsample(sta_handle* h, const float* pts, const float
     DEV_SCOPE(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int m = (int)M;
-    const int nb256 = (m + 255) / 256, nbs = (m + VOX_TILE - 1) / VOX_TILE, nbb = nb256 < 1024 ? nb256 : 1024;
+    const int nb256 = (m + 255) / 256, nbb = nb256 < 1024 ? nb256 : 1024;
     const int long_cap = m / VOX_LONG + 1;
     return plan_and_run(h, st, [&](Bump& ws) -> int {
         float* bpart = (float*)ws.take((int64_t)nbb * 32);
         float* bout = (float*)ws.take(32);
-        unsigned long long* key[2] = {(unsigned long long*)ws.take((int64_t)m * 8), (unsigned long long*)ws.take((int64_t)m * 8)};
-        int* idx[2] = {(int*)ws.take((int64_t)m * 4), (int*)ws.take((int64_t)m * 4)};
-        int* hist = (int*)ws.take((int64_t)256 * nbs * 4);
-        int* dtot = (int*)ws.take(256 * 4);
-        int* cnt_h = (int*)ws.take((int64_t)nb256 * 4);
-        int64_t* off_h = (int64_t*)ws.take((int64_t)(nb256 + 1) * 8);
-        int* cnt_r = (int*)ws.take((int64_t)nb256 * 4);
-        int64_t* off_r = (int64_t*)ws.take((int64_t)(nb256 + 1) * 8);
+        VoxSort sort; VoxScan hscan, rscan;
+        vox_take_sort(ws, m, &sort);
+        vox_take_scan(ws, nb256, &hscan);
+        vox_take_scan(ws, nb256, &rscan);
+        int* const cnt_h = hscan.counts; int64_t* const off_h = hscan.offs;
+        int* const cnt_r = rscan.counts; int64_t* const off_r = rscan.offs;
         int* seg = (int*)ws.take((int64_t)(m + 1) * 4);
         int2* rows = (int2*)ws.take((int64_t)m * 8);
         int* n_long = (int*)ws.take(4);
@@ -239,27 +237,18 @@ extern "C" int sta_voxel_downsample(sta_handle* h, const float* pts, const float
         // digit does it, a key width that fills its digits takes one more pass
         const int passes = (bits + 7) / 8 + (dropped > 0 && bits % 8 == 0 ? 1 : 0);
         // 2. keys  3. sort
-        hipLaunchKernelGGL(vox_key_kernel, dim3(nb256), dim3(256), 0, st, pts, m, g, key[0], idx[0]);
-        for (int p = 0; p < passes; ++p) {
-            const int a = p & 1, b = a ^ 1;
-            hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)key[a], m, 8 * p, nbs, hist);
-            hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, hist, nbs, dtot);
-            hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)key[a], (const int*)idx[a], m, 8 * p, nbs,
-                               (const int*)hist, (const int*)dtot, key[b], idx[b]);
-        }
-        const unsigned long long* skey = key[passes & 1];
-        const int* sidx = idx[passes & 1];
+        hipLaunchKernelGGL(vox_key_kernel, dim3(nb256), dim3(256), 0, st, pts, m, g, sort.key[0], sort.idx[0]);
+        const int r = vox_sort(st, sort, m, passes);
+        const unsigned long long* skey = sort.key[r];
+        const int* sidx = sort.idx[r];
         // 4. heads, then rows
         const int nbn = (n + 255) / 256;
-        CloudParams sc{};
-        sc.counts = cnt_h; sc.offs = off_h; sc.nblk = nbn;
         hipLaunchKernelGGL(vox_head_count_kernel, dim3(nbn), dim3(256), 0, st, skey, n, cnt_h);
-        hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
+        vox_scan(st, cnt_h, off_h, nbn);
         hipLaunchKernelGGL(vox_head_emit_kernel, dim3(nbn), dim3(256), 0, st, skey, n, (const int64_t*)off_h, nbn, seg);
         HIPCHK(hipMemsetAsync(n_long, 0, 4, st));
-        sc.counts = cnt_r; sc.offs = off_r;
         hipLaunchKernelGGL(vox_row_count_kernel, dim3(nbn), dim3(256), 0, st, (const int*)seg, (const int64_t*)(off_h + nbn), min_points, cnt_r);
-        hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
+        vox_scan(st, cnt_r, off_r, nbn);
         hipLaunchKernelGGL(vox_row_emit_kernel, dim3(nbn), dim3(256), 0, st, (const int*)seg, (const int64_t*)(off_h + nbn), min_points,
                            (const int64_t*)off_r, rows, n_long, long_rows);
         HIPCHK(hipGetLastError());
@@ -552,7 +541,7 @@ extern "C" int sta_flow_corners(sta_handle* h, const uint8_t* image, int H, int 
     REQUIRE(workspace_bytes >= w.bytes, "flow: the workspace holds %lld bytes, %d x %d needs %lld", (long long)workspace_bytes, H, W, (long long)w.bytes);
     DEV_SCOPE(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const int N = H * W, nb256 = (N + 255) / 256, nbs = (N + VOX_TILE - 1) / VOX_TILE;
+    const int N = H * W, nb256 = (N + 255) / 256;
     int* rmax = w.counters; int* n_cand = w.counters + 1;
     HIPCHK(hipMemsetAsync(w.counters, 0, 16, st));
     hipLaunchKernelGGL(flow_response_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, st, image, H, W, block_size / 2, w.R, rmax);
@@ -560,14 +549,8 @@ extern "C" int sta_flow_corners(sta_handle* h, const uint8_t* image, int H, int 
     hipLaunchKernelGGL(flow_key_kernel, dim3(nb256), dim3(256), 0, st, (const int*)w.R, H, W, (const int*)rmax, quality, idx_bits, w.key[0], w.idx[0], n_cand);
     // the all-ones key of a pixel that is no candidate must sort behind every candidate: a spare bit in the top digit does it
     const int passes = (bits + 7) / 8 + (bits % 8 == 0 ? 1 : 0);
-    for (int p = 0; p < passes; ++p) {
-        const int a = p & 1, b = a ^ 1;
-        hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)w.key[a], N, 8 * p, nbs, w.hist);
-        hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, w.hist, nbs, w.dtot);
-        hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)w.key[a], (const int*)w.idx[a], N, 8 * p, nbs,
-                           (const int*)w.hist, (const int*)w.dtot, w.key[b], w.idx[b]);
-    }
-    const int* sidx = w.idx[passes & 1];
+    const VoxSort sort{{w.key[0], w.key[1]}, {w.idx[0], w.idx[1]}, w.hist, w.dtot};
+    const int* sidx = sort.idx[vox_sort(st, sort, N, passes)];
     hipLaunchKernelGGL(flow_rank_kernel, dim3(nb256), dim3(256), 0, st, sidx, N, (const int*)n_cand, w.cell);
     hipLaunchKernelGGL(flow_suppress_kernel, dim3(1), dim3(1024), 0, st, w.cell, sidx, (const int*)n_cand, H, W, min_distance, max_corners, corners, n_out);
     HIPCHK(hipGetLastError());

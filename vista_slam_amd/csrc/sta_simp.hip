@@ -1,107 +1,64 @@
 // libsta_simp.so: the C ABI of include/sta_simp.h.  A translation unit of its own - no handle, no allocation, no copy to the host, no
 // synchronisation: none of the other six libraries includes or links any of this.  Static helpers carry the prefix sp_.
+// The error buffer, REQUIRE, HIPCHK, the bump and blocks() are sta_hostkit.h's: one copy per library, none exported.
 #include "../../include/sta_simp.h"
 #include "sta_common.h"
+#include "sta_hostkit.h"
 #include "elementwise.h"      // cloud_scan_kernel (voxel.h)
 #include "select.h"           // sel_block_scan (voxel.h)
 #include "voxel.h"            // the stable LSD radix sort, vox_block_count / vox_block_rank
 #include "simp.h"
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
 static_assert(SP_SWEEPS == STA_SIMP_SWEEPS && SP_BIAS == (1ll << (STA_SIMP_INDEX_BITS - 1)), "simp.h repeats the header's constants");
 static_assert(STA_SIMP_N_CELLS == 0 && STA_SIMP_N_VERTS == 1 && STA_SIMP_N_TRIS == 2 && STA_SIMP_N_DROPPED == 3 && STA_SIMP_N_INVALID == 4 &&
               STA_SIMP_N_COLLAPSED == 5 && STA_SIMP_N_DUPLICATE == 6 && STA_SIMP_N_FALLBACK == 7 && STA_SIMP_COUNTERS == 8, "simp.h uses the counter layout by number");
 
-static thread_local char sp_err[1024] = "";
-static int sp_set_err(const char* fmt, ...) {
-    va_list ap; va_start(ap, fmt); vsnprintf(sp_err, sizeof(sp_err), fmt, ap); va_end(ap);
-    return -1;
-}
-#define SP_HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return sp_set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
-#define SP_REQUIRE(c, ...) do { if (!(c)) return sp_set_err(__VA_ARGS__); } while (0)
-
-extern "C" const char* sta_simp_last_error(void) { return sp_err; }
+extern "C" const char* sta_simp_last_error(void) { return g_err; }
 
 // One bump layout per workspace serves the plan and the call: what the plan reports is what the call takes.
-struct SpBump {
-    char* base; int64_t used;
-    void* take(int64_t bytes) { void* p = base ? base + used : nullptr; used += (bytes + 255) & ~(int64_t)255; return p; }
-};
-struct SpSort { unsigned long long* key[2]; int* idx[2]; int* hist; int* dtot; };
-struct SpScan { int* counts; int64_t* offs; };
-static void sp_take_sort(SpBump& b, int64_t m, SpSort* L) {
-    const int64_t nbs = (m + VOX_TILE - 1) / VOX_TILE;
-    L->key[0] = (unsigned long long*)b.take(m * 8);
-    L->key[1] = (unsigned long long*)b.take(m * 8);
-    L->idx[0] = (int*)b.take(m * 4);
-    L->idx[1] = (int*)b.take(m * 4);
-    L->hist = (int*)b.take(256 * nbs * 4);
-    L->dtot = (int*)b.take(256 * 4);
-}
 static int64_t sp_nblk(int64_t n) { return (n + 255) / 256; }
-static void sp_take_scan(SpBump& b, int64_t n, SpScan* S) {
-    S->counts = (int*)b.take(sp_nblk(n) * 4);
-    S->offs = (int64_t*)b.take((sp_nblk(n) + 1) * 8);
-}
-struct SpCellsLayout { SpSort sort; SpScan scan; };
-struct SpTrisLayout { SpSort sort; SpScan tscan, cscan; int* flag; int* used; };
-struct SpPlaceLayout { SpSort vsort, psort; };
+struct SpCellsLayout { VoxSort sort; VoxScan scan; };
+struct SpTrisLayout { VoxSort sort; VoxScan tscan, cscan; int* flag; int* used; };
+struct SpPlaceLayout { VoxSort vsort, psort; };
 static int64_t sp_cells_layout(void* buf, int64_t nv, SpCellsLayout* L) {
-    SpBump b{(char*)buf, 0};
-    sp_take_sort(b, nv, &L->sort); sp_take_scan(b, nv, &L->scan);
+    PlanBump b{(char*)buf, 0};
+    vox_take_sort(b, nv, &L->sort); vox_take_scan(b, sp_nblk(nv), &L->scan);
     return b.used;
 }
 static int64_t sp_tris_layout(void* buf, int64_t nt, int64_t nv, SpTrisLayout* L) {
-    SpBump b{(char*)buf, 0};
-    sp_take_sort(b, nt, &L->sort); sp_take_scan(b, nt, &L->tscan); sp_take_scan(b, nv, &L->cscan);
+    PlanBump b{(char*)buf, 0};
+    vox_take_sort(b, nt, &L->sort); vox_take_scan(b, sp_nblk(nt), &L->tscan); vox_take_scan(b, sp_nblk(nv), &L->cscan);
     L->flag = (int*)b.take(nt * 4);
     L->used = (int*)b.take(nv * 4);
     return b.used;
 }
 static int64_t sp_place_layout(void* buf, int64_t nt, int64_t nv, SpPlaceLayout* L) {
-    SpBump b{(char*)buf, 0};
-    sp_take_sort(b, nv, &L->vsort); sp_take_sort(b, 3 * nt, &L->psort);
+    PlanBump b{(char*)buf, 0};
+    vox_take_sort(b, nv, &L->vsort); vox_take_sort(b, 3 * nt, &L->psort);
     return b.used;
 }
 
 static int sp_check_counts(const char* who, int64_t nt, int64_t nv) {
-    SP_REQUIRE(nv >= 0 && nv < (int64_t)1 << 31, "%s: nv must be in [0, 2^31) (got %lld)", who, (long long)nv);
-    SP_REQUIRE(nt >= 0 && nt < ((int64_t)1 << 31) && 3 * nt < (int64_t)1 << 31, "%s: nt must be >= 0 and 3 * nt below 2^31 (got nt = %lld)", who, (long long)nt);
+    REQUIRE(nv >= 0 && nv < (int64_t)1 << 31, "%s: nv must be in [0, 2^31) (got %lld)", who, (long long)nv);
+    REQUIRE(nt >= 0 && nt < ((int64_t)1 << 31) && 3 * nt < (int64_t)1 << 31, "%s: nt must be >= 0 and 3 * nt below 2^31 (got nt = %lld)", who, (long long)nt);
     return 0;
 }
 static int sp_check_grid(const char* who, double cell, double ox, double oy, double oz) {
-    SP_REQUIRE(std::isfinite(cell) && cell > 0.0, "%s: cell must be finite and > 0 (got %g)", who, cell);
-    SP_REQUIRE(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), "%s: the origin must be finite (got %g, %g, %g)", who, ox, oy, oz);
+    REQUIRE(std::isfinite(cell) && cell > 0.0, "%s: cell must be finite and > 0 (got %g)", who, cell);
+    REQUIRE(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), "%s: the origin must be finite (got %g, %g, %g)", who, ox, oy, oz);
     return 0;
 }
-static unsigned sp_blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
 static int sp_bits(int64_t n) { int b = 1; while (b < 63 && (n >> b) != 0) ++b; return b; }      // the bits that hold the value n
 
-// The stable LSD sort of voxel.h over the low `bits` bits of key[0] / idx[0]; returns the buffer (0 or 1) that holds the result.
-static int sp_sort(hipStream_t st, const SpSort& L, int64_t m64, int bits, int cur = 0) {
-    const int m = (int)m64, nbs = (int)((m64 + VOX_TILE - 1) / VOX_TILE), passes = (bits + 7) / 8;
-    for (int p = 0; p < passes; ++p) {
-        const int a = cur, b = cur ^ 1;
-        hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)L.key[a], m, 8 * p, nbs, L.hist);
-        hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, L.hist, nbs, L.dtot);
-        hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)L.key[a], (const int*)L.idx[a], m, 8 * p, nbs,
-                           (const int*)L.hist, (const int*)L.dtot, L.key[b], L.idx[b]);
-        cur = b;
-    }
-    return cur;
-}
-static void sp_scan(hipStream_t st, const SpScan& S, int64_t n) {
-    CloudParams sc = {};
-    sc.counts = S.counts; sc.offs = S.offs; sc.nblk = (int)sp_nblk(n);
-    hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
-}
+// The stable LSD sort of voxel.h over the low `bits` bits of key[cur] / idx[cur]; returns the buffer (0 or 1) that holds the result.
+static int sp_sort(hipStream_t st, const VoxSort& L, int64_t m, int bits, int cur = 0) { return vox_sort(st, L, (int)m, (bits + 7) / 8, cur); }
+static void sp_scan(hipStream_t st, const VoxScan& S, int64_t n) { vox_scan(st, S.counts, S.offs, (int)sp_nblk(n)); }
 
 extern "C" int sta_simp_plan(int64_t nt, int64_t nv, int64_t* sizes_out) {
     const char* who = "simp_plan";
-    SP_REQUIRE(sizes_out, "%s: null argument", who);
+    REQUIRE(sizes_out, "%s: null argument", who);
     if (sp_check_counts(who, nt, nv)) return -1;
     SpCellsLayout cl; SpTrisLayout tl; SpPlaceLayout pl;
     sizes_out[0] = sp_cells_layout(nullptr, nv, &cl);
@@ -116,21 +73,21 @@ extern "C" int sta_simp_cells(const float* verts, int64_t nv, double cell, doubl
     if (sp_check_counts(who, 0, nv) || sp_check_grid(who, cell, ox, oy, oz)) return -1;
     SpCellsLayout L;
     const int64_t need = sp_cells_layout(work, nv, &L);
-    SP_REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld vertices", who, (long long)work_bytes, (long long)need, (long long)nv);
-    SP_REQUIRE(counters && (nv == 0 || (verts && vcell && work)), "%s: null argument", who);
+    REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld vertices", who, (long long)work_bytes, (long long)need, (long long)nv);
+    REQUIRE(counters && (nv == 0 || (verts && vcell && work)), "%s: null argument", who);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sp_zero_kernel, dim3(1), dim3(64), 0, st, (long long*)counters, (1u << STA_SIMP_N_CELLS) | (1u << STA_SIMP_N_DROPPED));
     if (nv > 0) {
         SpGrid g; g.o[0] = ox; g.o[1] = oy; g.o[2] = oz; g.cell = cell;
         const int n = (int)nv;
-        hipLaunchKernelGGL(sp_key_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, verts, n, g, L.sort.key[0], L.sort.idx[0]);
+        hipLaunchKernelGGL(sp_key_kernel, dim3(blocks(nv)), dim3(256), 0, st, verts, n, g, L.sort.key[0], L.sort.idx[0]);
         const int r = sp_sort(st, L.sort, nv, 64);         // all 64 bits: the dropped key, all ones, sorts behind the largest cell key, 2^63 - 1
-        hipLaunchKernelGGL(sp_head_count_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, (const unsigned long long*)L.sort.key[r], n, L.scan.counts);
+        hipLaunchKernelGGL(sp_head_count_kernel, dim3(blocks(nv)), dim3(256), 0, st, (const unsigned long long*)L.sort.key[r], n, L.scan.counts);
         sp_scan(st, L.scan, nv);
-        hipLaunchKernelGGL(sp_rank_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, (const unsigned long long*)L.sort.key[r], (const int*)L.sort.idx[r], n,
+        hipLaunchKernelGGL(sp_rank_kernel, dim3(blocks(nv)), dim3(256), 0, st, (const unsigned long long*)L.sort.key[r], (const int*)L.sort.idx[r], n,
                            (const int64_t*)L.scan.offs, (int)sp_nblk(nv), (int*)vcell, (long long*)counters);
     }
-    SP_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -140,39 +97,39 @@ extern "C" int sta_simp_triangles(const int32_t* tris, int64_t nt, int64_t nv, c
     if (sp_check_counts(who, nt, nv)) return -1;
     SpTrisLayout L;
     const int64_t need = sp_tris_layout(work, nt, nv, &L);
-    SP_REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld triangles and %lld vertices", who, (long long)work_bytes, (long long)need,
-               (long long)nt, (long long)nv);
-    SP_REQUIRE(counters && (nt == 0 || (tris && tris_out && tri_src)) && (nv == 0 || (vcell && cell_out && vmap)) && (nt + nv == 0 || work), "%s: null argument", who);
+    REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld triangles and %lld vertices", who, (long long)work_bytes, (long long)need,
+            (long long)nt, (long long)nv);
+    REQUIRE(counters && (nt == 0 || (tris && tris_out && tri_src)) && (nv == 0 || (vcell && cell_out && vmap)) && (nt + nv == 0 || work), "%s: null argument", who);
     hipStream_t st = (hipStream_t)stream;
     const int n = (int)nt, v = (int)nv;
     hipLaunchKernelGGL(sp_zero_kernel, dim3(1), dim3(64), 0, st, (long long*)counters,
                        (1u << STA_SIMP_N_VERTS) | (1u << STA_SIMP_N_TRIS) | (1u << STA_SIMP_N_INVALID) | (1u << STA_SIMP_N_COLLAPSED) | (1u << STA_SIMP_N_DUPLICATE));
-    if (nv > 0) SP_HIPCHK(hipMemsetAsync(L.used, 0, (size_t)nv * 4, st));
+    if (nv > 0) HIPCHK(hipMemsetAsync(L.used, 0, (size_t)nv * 4, st));
     if (nt > 0) {
         const int bits = sp_bits(nv);
-        hipLaunchKernelGGL(sp_tri_key_kernel, dim3(sp_blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, L.sort.key[0], L.sort.idx[0]);
+        hipLaunchKernelGGL(sp_tri_key_kernel, dim3(blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, L.sort.key[0], L.sort.idx[0]);
         int r = sp_sort(st, L.sort, nt, bits);
-        hipLaunchKernelGGL(sp_tri_rekey_kernel, dim3(sp_blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, bits, L.sort.key[r],
+        hipLaunchKernelGGL(sp_tri_rekey_kernel, dim3(blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, bits, L.sort.key[r],
                            (const int*)L.sort.idx[r]);
         r = sp_sort(st, L.sort, nt, 2 * bits, r);
-        hipLaunchKernelGGL(sp_mark_kernel, dim3(sp_blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, (const int*)L.sort.idx[r],
+        hipLaunchKernelGGL(sp_mark_kernel, dim3(blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, (const int*)L.sort.idx[r],
                            L.flag, (long long*)counters);
-        hipLaunchKernelGGL(sp_flag_count_kernel, dim3(sp_blocks(nt)), dim3(256), 0, st, (const int*)L.flag, n, L.tscan.counts);
+        hipLaunchKernelGGL(sp_flag_count_kernel, dim3(blocks(nt)), dim3(256), 0, st, (const int*)L.flag, n, L.tscan.counts);
         sp_scan(st, L.tscan, nt);
-        hipLaunchKernelGGL(sp_tri_emit_kernel, dim3(sp_blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, (const int*)L.flag,
+        hipLaunchKernelGGL(sp_tri_emit_kernel, dim3(blocks(nt)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, n, (long long)nv, (const int*)L.flag,
                            (const int64_t*)L.tscan.offs, (int*)tris_out, (int*)tri_src, L.used);
     }
     if (nv > 0) {
-        hipLaunchKernelGGL(sp_flag_count_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, (const int*)L.used, v, L.cscan.counts);
+        hipLaunchKernelGGL(sp_flag_count_kernel, dim3(blocks(nv)), dim3(256), 0, st, (const int*)L.used, v, L.cscan.counts);
         sp_scan(st, L.cscan, nv);
-        hipLaunchKernelGGL(sp_cell_emit_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, (const int*)L.used, v, (const int64_t*)L.cscan.offs, (int*)cell_out);
+        hipLaunchKernelGGL(sp_cell_emit_kernel, dim3(blocks(nv)), dim3(256), 0, st, (const int*)L.used, v, (const int64_t*)L.cscan.offs, (int*)cell_out);
     }
     const int64_t rows = nt > nv ? nt : nv;
-    hipLaunchKernelGGL(sp_remap_kernel, dim3(rows ? sp_blocks(rows) : 1u), dim3(256), 0, st, n, v, (const int*)vcell, (const int*)cell_out,
+    hipLaunchKernelGGL(sp_remap_kernel, dim3(rows ? blocks(rows) : 1u), dim3(256), 0, st, n, v, (const int*)vcell, (const int*)cell_out,
                        nt > 0 ? (const int64_t*)(L.tscan.offs + sp_nblk(nt)) : (const int64_t*)nullptr,
                        nv > 0 ? (const int64_t*)(L.cscan.offs + sp_nblk(nv)) : (const int64_t*)nullptr, (int*)tris_out, (int*)tri_src, (int*)vmap,
                        (long long*)counters);
-    SP_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -181,25 +138,25 @@ extern "C" int sta_simp_place(const float* verts, const float* colors, int64_t n
                               float* verts_out, float* colors_out, int64_t* counters, void* work, int64_t work_bytes, void* stream) {
     const char* who = "simp_place";
     if (sp_check_counts(who, nt, nv) || sp_check_grid(who, cell, ox, oy, oz)) return -1;
-    SP_REQUIRE(placement == STA_SIMP_PLACE_MEAN || placement == STA_SIMP_PLACE_QUADRIC, "%s: placement must be 0 or 1 (got %d)", who, placement);
-    SP_REQUIRE(sv_ratio >= 0.0 && sv_ratio < 1.0, "%s: sv_ratio must be in [0, 1) (got %g)", who, sv_ratio);
-    SP_REQUIRE((colors != nullptr) == (colors_out != nullptr), "%s: colors (%s) and colors_out (%s) go together", who, colors ? "given" : "NULL",
-               colors_out ? "given" : "NULL");
+    REQUIRE(placement == STA_SIMP_PLACE_MEAN || placement == STA_SIMP_PLACE_QUADRIC, "%s: placement must be 0 or 1 (got %d)", who, placement);
+    REQUIRE(sv_ratio >= 0.0 && sv_ratio < 1.0, "%s: sv_ratio must be in [0, 1) (got %g)", who, sv_ratio);
+    REQUIRE((colors != nullptr) == (colors_out != nullptr), "%s: colors (%s) and colors_out (%s) go together", who, colors ? "given" : "NULL",
+            colors_out ? "given" : "NULL");
     SpPlaceLayout L;
     const int64_t need = sp_place_layout(work, nt, nv, &L);
-    SP_REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld triangles and %lld vertices", who, (long long)work_bytes, (long long)need,
-               (long long)nt, (long long)nv);
+    REQUIRE(work_bytes >= need, "%s: work of %lld bytes, %lld needed for %lld triangles and %lld vertices", who, (long long)work_bytes, (long long)need,
+            (long long)nt, (long long)nv);
     const bool quadric = placement == STA_SIMP_PLACE_QUADRIC && nt > 0;
-    SP_REQUIRE(counters && (nv == 0 || (verts && vcell && cell_out && verts_out && work)) && (!quadric || nv == 0 || tris), "%s: null argument", who);
+    REQUIRE(counters && (nv == 0 || (verts && vcell && cell_out && verts_out && work)) && (!quadric || nv == 0 || tris), "%s: null argument", who);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sp_zero_kernel, dim3(1), dim3(64), 0, st, (long long*)counters, 1u << STA_SIMP_N_FALLBACK);
     if (nv > 0) {
         const int bits = sp_bits(nv), n = (int)nv, m = quadric ? (int)(3 * nt) : 0;
-        hipLaunchKernelGGL(sp_vkey_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, (const int*)vcell, n, L.vsort.key[0], L.vsort.idx[0]);
+        hipLaunchKernelGGL(sp_vkey_kernel, dim3(blocks(nv)), dim3(256), 0, st, (const int*)vcell, n, L.vsort.key[0], L.vsort.idx[0]);
         const int rv = sp_sort(st, L.vsort, nv, bits);
         int rp = 0;
         if (m > 0) {
-            hipLaunchKernelGGL(sp_pkey_kernel, dim3(sp_blocks(m)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, m, (long long)nv, L.psort.key[0], L.psort.idx[0]);
+            hipLaunchKernelGGL(sp_pkey_kernel, dim3(blocks(m)), dim3(256), 0, st, (const int*)tris, (const int*)vcell, m, (long long)nv, L.psort.key[0], L.psort.idx[0]);
             rp = sp_sort(st, L.psort, m, bits);
         }
         SpPlace P;
@@ -209,8 +166,8 @@ extern "C" int sta_simp_place(const float* verts, const float* colors, int64_t n
         P.g.o[0] = ox; P.g.o[1] = oy; P.g.o[2] = oz; P.g.cell = cell;
         P.placement = placement; P.sv_ratio = sv_ratio;
         P.verts_out = verts_out; P.colors_out = colors_out; P.counters = (long long*)counters;
-        hipLaunchKernelGGL(sp_place_kernel, dim3(sp_blocks(nv)), dim3(256), 0, st, P);
+        hipLaunchKernelGGL(sp_place_kernel, dim3(blocks(nv)), dim3(256), 0, st, P);
     }
-    SP_HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }

@@ -326,3 +326,44 @@ __global__ __launch_bounds__(1024) void vox_reduce_long_kernel(const VoxOut p, c
         __syncthreads();
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Host side, shared by every translation unit that sorts or scans (sta_rows.inc and the handle-free libraries): the two layouts, their
+// takers and the launch code.  B is any bump with `void* take(int64_t bytes)`; the take order is part of every workspace's layout.
+struct VoxSort { unsigned long long* key[2]; int* idx[2]; int* hist; int* dtot; };      // m keys and payloads, twice; the pass's histogram
+struct VoxScan { int* counts; int64_t* offs; };                                         // counts[nblk], offs[nblk + 1]: offs[nblk] = the total
+
+// own_idx0 = false: idx[0] lives elsewhere (libsta_cloud.so sorts its payload into the index buffer) and is the caller's to set
+template <class B> static void vox_take_sort(B& b, int64_t m, VoxSort* L, bool own_idx0 = true) {
+    const int64_t nbs = (m + VOX_TILE - 1) / VOX_TILE;
+    L->key[0] = (unsigned long long*)b.take(m * 8);
+    L->key[1] = (unsigned long long*)b.take(m * 8);
+    L->idx[0] = own_idx0 ? (int*)b.take(m * 4) : nullptr;
+    L->idx[1] = (int*)b.take(m * 4);
+    L->hist = (int*)b.take(256 * nbs * 4);
+    L->dtot = (int*)b.take(256 * 4);
+}
+template <class B> static void vox_take_scan(B& b, int64_t nblk, VoxScan* S) {
+    S->counts = (int*)b.take(nblk * 4);
+    S->offs = (int64_t*)b.take((nblk + 1) * 8);
+}
+
+// The stable LSD sort of m keys and payloads on the digits 0 .. passes - 1, from key[cur] / idx[cur]; returns the buffer (0 or 1) that
+// holds the result: cur after an even number of passes.  The caller counts the passes its keys need.
+static inline int vox_sort(hipStream_t st, const VoxSort& L, int m, int passes, int cur = 0) {
+    const int nbs = (m + VOX_TILE - 1) / VOX_TILE;
+    for (int p = 0; p < passes; ++p, cur ^= 1) {
+        const int a = cur, b = cur ^ 1;
+        hipLaunchKernelGGL(vox_hist_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)L.key[a], m, 8 * p, nbs, L.hist);
+        hipLaunchKernelGGL(vox_hist_scan_kernel, dim3(256), dim3(256), 0, st, L.hist, nbs, L.dtot);
+        hipLaunchKernelGGL(vox_scatter_kernel, dim3(nbs), dim3(256), 0, st, (const unsigned long long*)L.key[a], (const int*)L.idx[a], m, 8 * p, nbs,
+                           (const int*)L.hist, (const int*)L.dtot, L.key[b], L.idx[b]);
+    }
+    return cur;
+}
+// The exclusive scan of counts[nblk] into offs[nblk + 1] by cloud_scan_kernel (elementwise.h), which reads these three fields alone.
+static inline void vox_scan(hipStream_t st, int* counts, int64_t* offs, int nblk) {
+    CloudParams sc{};
+    sc.counts = counts; sc.offs = offs; sc.nblk = nblk;
+    hipLaunchKernelGGL(cloud_scan_kernel, dim3(1), dim3(1024), 0, st, sc);
+}
