@@ -1,6 +1,7 @@
 """Per-kernel register / LDS / scratch usage of the built library (reads the code object's metadata notes; no GPU).
 
     python tools/kernel_resources.py [substring ...]      # rows whose demangled name contains every substring
+    python tools/kernel_resources.py --lib ray ry_cast     # another library of the package: libsta_<name>.so, or a path
 """
 import os
 import re
@@ -26,9 +27,13 @@ def code_object(lib):
 
 
 def main():
-    filt = sys.argv[1:]
+    filt, lib = sys.argv[1:], LIB
+    if "--lib" in filt:
+        k = filt.index("--lib")
+        lib = filt[k + 1] if os.path.exists(filt[k + 1]) else os.path.join(ROOT, "vista_slam_amd", "libsta_%s.so" % filt[k + 1])
+        filt = filt[:k] + filt[k + 2:]
     with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
-        f.write(code_object(LIB))
+        f.write(code_object(lib))
         path = f.name
     txt = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", path], capture_output=True, text=True).stdout
     os.unlink(path)

@@ -21,6 +21,7 @@ MESH_LIB_PATH = os.path.join(PKG, "libsta_mesh.so")        # a fifth one (includ
 SURF_LIB_PATH = os.path.join(PKG, "libsta_surf.so")        # a sixth one (include/sta_surf.h): `load_surf()`
 SIMP_LIB_PATH = os.path.join(PKG, "libsta_simp.so")        # a seventh one (include/sta_simp.h): `load_simp()`
 DIST_LIB_PATH = os.path.join(PKG, "libsta_dist.so")        # an eighth one (include/sta_dist.h): `load_dist()`
+RAY_LIB_PATH = os.path.join(PKG, "libsta_ray.so")          # a ninth one (include/sta_ray.h): `load_ray()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -283,6 +284,13 @@ DIST_SIGNATURES = {
     "sta_tri_query": (_i, [_vp, _vp, _i64, _d, _vp, _vp, _vp, _vp]),
     "sta_tri_last_error": (C.c_char_p, []),
 }
+# include/sta_ray.h: libsta_ray.so, handle-free; a table of its own like the seven above (the index of libsta_dist.so goes as four pointers)
+RAY_SIGNATURES = {
+    "sta_ray_plan": (_i, [_i64, _i64, _i64p]),
+    "sta_ray_cast": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp, _vp, _vp]),
+    "sta_ray_occluded": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp]),
+    "sta_ray_last_error": (C.c_char_p, []),
+}
 
 
 class StaTriIndex(C.Structure):
@@ -400,6 +408,7 @@ load_mesh, check_mesh = _satellite(MESH_LIB_PATH, MESH_SIGNATURES, "sta_mesh_las
 load_surf, check_surf = _satellite(SURF_LIB_PATH, SURF_SIGNATURES, "sta_surf_last_error")              # include/sta_surf.h
 load_simp, check_simp = _satellite(SIMP_LIB_PATH, SIMP_SIGNATURES, "sta_simp_last_error")              # include/sta_simp.h
 load_dist, check_dist = _satellite(DIST_LIB_PATH, DIST_SIGNATURES, "sta_tri_last_error")               # include/sta_dist.h: its names are sta_tri_*
+load_ray, check_ray = _satellite(RAY_LIB_PATH, RAY_SIGNATURES, "sta_ray_last_error")                   # include/sta_ray.h
 
 
 def use_test_hooks():

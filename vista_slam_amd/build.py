@@ -5,7 +5,8 @@
                                             #    additionally the kernel-level test / micro-benchmark entry points of
                                             #    include/sta_mi355_debug.h (loaded by tests/ and tools/ only)
                                             #    vista_slam_amd/libsta_<name>.so       one handle-free library per row of SATELLITES:
-                                            #    a translation unit of its own (csrc/sta_<name>.hip) that exports include/sta_<name>.h
+                                            #    and of ADDONS: a translation unit of its own (csrc/sta_<name>.hip) that exports
+                                            #    include/sta_<name>.h
 
 A library's content hash covers its own files and the shared headers it includes, nothing of any other library: the product's hash does
 not move when a satellite's own files change, and the other way round (tests/test_library_table.py).
@@ -42,9 +43,15 @@ SATELLITES = {
     "simp": ("mesh simplification by vertex clustering with quadrics", ["sta_simp.hip", "simp.h", _inc("sta_simp.h")], _SORT),
     "dist": ("exact point-to-triangle distances over an implicit BVH", ["sta_dist.hip", "dist.h", _inc("sta_dist.h")], _SORT),
 }
-# CLOUD_LIB, CLOUD_SOURCES, CLOUD_DEPS, CLOUD_HASH_FILE ... DIST_LIB, DIST_SOURCES, DIST_DEPS, DIST_HASH_FILE: the rows of the table
-# under the names that tools/ and tests/ use.  Every row is built from sta_common.h and the host kit as well.
-for _name, (_what, _own, _shared) in SATELLITES.items():
+# The libraries that came after the table of seven was pinned (tests/test_library_table.py): rows of the same shape, expanded and built
+# by the same loops.  libsta_ray.so reads the index of libsta_dist.so through plain arguments and holds no own file of another library.
+ADDONS = {
+    "ray": ("first hit and occlusion of rays over the triangle index of libsta_dist.so", ["sta_ray.hip", "ray.h", _inc("sta_ray.h")], []),
+}
+# CLOUD_LIB, CLOUD_SOURCES, CLOUD_DEPS, CLOUD_HASH_FILE ... DIST_LIB, DIST_SOURCES, DIST_DEPS, DIST_HASH_FILE, RAY_LIB, RAY_SOURCES,
+# RAY_DEPS, RAY_HASH_FILE: the rows of both tables under the names that tools/ and tests/ use.  Every row is built from sta_common.h and
+# the host kit as well.
+for _name, (_what, _own, _shared) in list(SATELLITES.items()) + list(ADDONS.items()):
     _so = os.path.join(PKG, "libsta_%s.so" % _name)
     globals().update({_name.upper() + "_LIB": _so, _name.upper() + "_SOURCES": _own[:1], _name.upper() + "_HASH_FILE": _so + ".srchash",
                       _name.upper() + "_DEPS": ["sta_exports.map"] + _own + _shared + ["sta_common.h", "sta_hostkit.h"]})
@@ -103,17 +110,18 @@ def _cmd(hipcc, out, hooks, sources=None):
             (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True):
+def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True,
+              ray=True):
     """Build the product library, (test_hooks) the test-hooks library and, each under the keyword of its name, the libraries of
-    SATELLITES; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
-    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist)
-    assert list(wanted) == list(SATELLITES)
+    SATELLITES and ADDONS; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray)
+    assert list(wanted) == list(SATELLITES) + list(ADDONS)
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))
     if test_hooks and (force or is_stale(TEST_LIB, TEST_HASH_FILE)):
         jobs.append((TEST_LIB, TEST_HASH_FILE, True, None, None))
-    for name in SATELLITES:
+    for name in wanted:
         lib, hash_file, sources, deps = (globals()[name.upper() + k] for k in ("_LIB", "_HASH_FILE", "_SOURCES", "_DEPS"))
         if wanted[name] and (force or is_stale(lib, hash_file, deps)):
             jobs.append((lib, hash_file, False, sources, deps))

@@ -9,8 +9,10 @@ chamfer distance, all on the device (formats.world_pointcloud, formats.voxel_dow
 Mesh half (`eval_mesh`, `mesh_depth_l1`): the protocol of the 7-Scenes and Replica evaluations of dense SLAM systems - points drawn
 uniformly by area from the estimated and the ground-truth surface (vista_slam_amd.surface), nearest neighbours both ways
 (vista_slam_amd.cloud), accuracy, completion, completion ratio and F-score; and the L1 difference of the two meshes' depth maps
-(render.mesh_depth).  By default samples are scored against samples; `eval_mesh(mode="surface")` scores them against the other mesh
-itself, with the exact point-to-triangle distances of vista_slam_amd.meshdist.
+(render.mesh_depth, or meshdist.ray_depth with method="rays").  By default samples are scored against samples;
+`eval_mesh(mode="surface")` scores them against the other mesh itself, with the exact point-to-triangle distances of
+vista_slam_amd.meshdist.  `pointmap_range_error` casts a ray from each view's camera centre through each of its predicted world points
+and reads off, with meshdist's exact first hit, where along that ray the surface is.
 
 What this is not: a comparison against evo, Open3D or pykdtree (none is available; ICP's loop and the alignment are restated from
 their published definitions, tests/cloud_cases.py holds the numpy restatement they are tested against); no plots.
@@ -208,17 +210,79 @@ def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: flo
     return MeshScore(acc, comp, ratio, precision, f, (acc + comp) / 2.0, est, gt_pts, n_precise, n_complete)
 
 
-def mesh_depth_l1(frontend, est_mesh, gt_mesh, cameras, H: int, W: int):
+def mesh_depth_l1(frontend, est_mesh, gt_mesh, cameras, H: int, W: int, method: str = "raster"):
     """(mean |depth_est - depth_gt| over the pixels of `cameras` (render.Camera) that both meshes cover, the number of those pixels),
-    through render.mesh_depth; NaN when there is no such pixel.  Plumbing: the triangle pass does the work."""
+    through render.mesh_depth; NaN when there is no such pixel.  Plumbing: the triangle pass does the work.
+    method="rays": the same over meshdist.ray_depth - the exact first hit along each pixel's ray instead of the rasteriser's vertices
+    snapped to 1/256 pixel; one index per mesh, built once."""
     from . import render
+    if method not in ("raster", "rays"):
+        raise ValueError(f"mesh_depth_l1: method must be 'raster' or 'rays' (got {method!r})")
+    if method == "rays":
+        from . import meshdist
+        dev = getattr(frontend, "device", frontend)
+        index = [meshdist.TriIndex.build(SimpleNamespace(vertices=torch.as_tensor(m.vertices).to(dev), triangles=m.triangles)) for m in (est_mesh, gt_mesh)]
+        depth = lambda which, mesh, cam: meshdist.ray_depth(index[which], cam, H, W)
+    else:
+        depth = lambda which, mesh, cam: render.mesh_depth(frontend, mesh, cam, H, W)
     total, count = 0.0, 0
     for cam in cameras:
-        de, dg = render.mesh_depth(frontend, est_mesh, cam, H, W), render.mesh_depth(frontend, gt_mesh, cam, H, W)
+        de, dg = depth(0, est_mesh, cam), depth(1, gt_mesh, cam)
         both = torch.isfinite(de) & torch.isfinite(dg)
         total += float((de.to(torch.float64) - dg.to(torch.float64)).abs()[both].sum().item())
         count += int(both.sum().item())
     return (total / count if count else float("nan")), count
+
+
+class RangeError(NamedTuple):
+    abs_mean: float                # mean of |t - 1| |d| over the rays that hit: the range error along the ray, in world units
+    abs_median: float              # its lower median (torch.median's convention)
+    rel_mean: float                # mean of |t - 1|: the same relative to the predicted range
+    rel_median: float
+    n_hit: int                     # valid rays that hit the mesh
+    n_miss: int                    # valid rays that did not (or whose point is not finite, or lies at the centre)
+
+
+def pointmap_range_error(frontend, mesh_or_index, centres, points, valid=None) -> RangeError:
+    """The range error of predicted pointmaps against a mesh: from each view's camera centre (centres [V,3], world) a ray through each of
+    its predicted world points (points [V,...,3]): o = the centre, d = float32(point - centre), so the prediction sits at t = 1 and the
+    surface is where meshdist's first hit says, at t; the error along the ray is |t - 1| |d|.  valid [V,...] bool: the points that count
+    (None = all).  mesh_or_index: a `tsdf.Mesh` or a `meshdist.TriIndex` of it.  The sums are float64 device reductions and the medians
+    come from a device sort; ONE readback.  NaN statistics when no ray hits."""
+    from . import meshdist
+    dev = getattr(frontend, "device", frontend)
+    index = mesh_or_index if isinstance(mesh_or_index, meshdist.TriIndex) else meshdist.TriIndex.build(
+        SimpleNamespace(vertices=torch.as_tensor(mesh_or_index.vertices).to(dev), triangles=mesh_or_index.triangles))
+    dev = index.device
+    c = torch.as_tensor(_host(centres) if isinstance(centres, (list, tuple)) else centres).to(dev, torch.float32).reshape(-1, 3)
+    p = torch.as_tensor(_host(points) if isinstance(points, (list, tuple)) else points).to(dev, torch.float32)
+    if p.shape[-1] != 3 or p.shape[0] != len(c):
+        raise ValueError(f"pointmap_range_error: points must be [V, ..., 3] for {len(c)} centres (got {tuple(p.shape)})")
+    V = len(c)
+    p = p.reshape(V, -1, 3)
+    o = c[:, None, :].expand_as(p).reshape(-1, 3)
+    d = (p.to(torch.float64) - c[:, None, :].to(torch.float64)).to(torch.float32).reshape(-1, 3)
+    ok = torch.ones(len(d), dtype=torch.bool, device=dev) if valid is None else torch.as_tensor(valid).to(dev).reshape(-1).bool()
+    if len(ok) != len(d):
+        raise ValueError(f"pointmap_range_error: valid must have one entry per point ({len(d)}; got {len(ok)})")
+    t, = index.cast(o, d, 0.0, float("inf"), want=("t",))
+    hit = ok & torch.isfinite(t)
+    rel = (t - 1.0).abs()
+    dd = d.to(torch.float64)
+    ab = rel * torch.sqrt((dd * dd).sum(dim=1))
+    n_hit = hit.sum()
+    mid = torch.clamp((n_hit - 1) // 2, min=0)
+    inf = torch.full_like(rel, float("inf"))
+
+    def stats(x):
+        x = torch.where(hit, x, inf)
+        return torch.where(hit, x, torch.zeros_like(x)).sum() / n_hit, torch.sort(x).values[mid]
+    am, amed = stats(ab)
+    rm, rmed = stats(rel)
+    out = torch.stack([am, amed, rm, rmed, n_hit.to(torch.float64), (ok & ~hit).sum().to(torch.float64)]).cpu().tolist()          # the one readback
+    nan = float("nan")
+    n = int(out[4])
+    return RangeError(*(out[:4] if n else [nan] * 4), n, int(out[5]))
 
 
 def load_data(output_folder, load_view_graph=True, load_gt_depths=True, load_gt_poses=True, load_gt_intrinsic=True, load_unscaled_depths=True,

@@ -10,8 +10,20 @@ the brute-force minimum, lowest triangle index among equals, bit for bit.
     d2, tri, point = idx.query(points, radius=0.5)            # float64 [Q], int32 [Q], float32 [Q,3]; +inf, -1, NaN where nothing is within radius
     d2, tri, point = meshdist.point_to_mesh(points, mesh)     # both in one call, radius = +inf
 
-What it is not: no signed distance, no ray casting, no point-to-plane ICP against the mesh.  Not compared with Open3D's RaycastingScene or
-trimesh's closest_point (neither is available).  DESIGN.md section 9.
+Rays against the same index are libsta_ray.so (include/sta_ray.h holds the contract, tests/ray_cases.py restates it): one lane per ray
+walks the index that TriIndex.build wrote - slab intervals of the boxes widened by one float32 step, Woop-Benthin-Wald's sheared triangle
+test in float64 in a written order, the hit clamped into the slab interval of the triangle's own box - which makes a node's entry
+parameter a lower bound without any margin, so the answer IS the brute-force first hit, lowest triangle index among equals, bit for bit.
+A ray is o + t d with d as given, not normalised: t is in units of |d|.
+
+    t, tri, bary = idx.cast(origins, dirs)                    # float64 [R], int32 [R], float32 [R,3]; +inf, -1, NaN where nothing is hit
+    hidden = idx.occluded(origins, dirs, 0.0, 1.0)            # uint8 [R]: is there a triangle on the segment o .. o + d
+    depth = meshdist.ray_depth(idx, camera, H, W)             # float32 [H,W] along the pixel rays of a render.Camera: t IS the depth
+    seen = meshdist.visible(idx, a, b)                        # bool [R]: nothing between a and b
+
+What it is not: no signed distance and no crossing parity (a hit on a shared edge is accepted by both neighbours by design), no all-hits
+list, no point-to-plane ICP against the mesh.  Not compared with Open3D's RaycastingScene or trimesh's closest_point (neither is
+available).  DESIGN.md section 9.
 """
 from __future__ import annotations
 
@@ -30,6 +42,9 @@ PLAN_SIZES = 2
 COUNTERS = ("valid", "bad_index", "non_finite", "no_area", "status", "reserved_5", "reserved_6", "reserved_7")
 STATUS_BOUND = 1
 WANT = ("d2", "tri", "point")
+RAY_WANT = ("t", "tri", "bary")
+RAY_PLAN_SIZES = 1
+RAY_STATUS_BOUND = 1
 
 
 class Plan(NamedTuple):
@@ -44,6 +59,13 @@ def _check(rc):
         raise (ValueError(str(e)) if str(e).startswith("tri_") else e) from None
 
 
+def _check_ray(rc):
+    try:
+        _lib.check_ray(rc)
+    except _lib.StaError as e:
+        raise (ValueError(str(e)) if str(e).startswith("ray_") else e) from None
+
+
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -53,6 +75,30 @@ def plan(nt: int, Q: int = 1) -> Plan:
     out = (C.c_int64 * PLAN_SIZES)()
     _check(_lib.load_dist().sta_tri_plan(int(nt), int(Q), out))
     return Plan(*[int(v) for v in out])
+
+
+def ray_plan(nt: int, R: int = 1) -> int:
+    """Host only (no GPU): the number of nodes of the index of nt triangles from sta_ray_plan, its refusals as ValueError.  A cast takes
+    no workspace."""
+    out = (C.c_int64 * RAY_PLAN_SIZES)()
+    _check_ray(_lib.load_ray().sta_ray_plan(int(nt), int(R), out))
+    return int(out[0])
+
+
+def ray_check(nt: int, R: int, t_min: float = 0.0, t_max: float = math.inf, occluded: bool = False) -> None:
+    """Host only (no GPU): the refusals of sta_ray_cast (occluded: sta_ray_occluded) for these numbers as ValueError, in the library's
+    own words.  The entry point is called without buffers: it checks the numbers first and launches nothing."""
+    lib = _lib.load_ray()
+    one = (C.c_uint8 * 1)()
+    if occluded:
+        rc = lib.sta_ray_occluded(None, None, None, None, int(nt), None, None, int(R), float(t_min), float(t_max), C.addressof(one), None, None)
+    else:
+        rc = lib.sta_ray_cast(None, None, None, None, int(nt), None, None, int(R), float(t_min), float(t_max), None, None, None, None, None)
+    try:
+        _check_ray(rc)
+    except ValueError as e:
+        if not str(e).endswith(": null argument"):
+            raise
 
 
 def level_counts(nt: int):
@@ -68,6 +114,20 @@ def _points(points, device) -> torch.Tensor:
     if t.dim() != 2 or t.shape[1] != 3:
         raise ValueError(f"points must be [Q, 3] (got {tuple(t.shape)})")
     return t
+
+
+def _rays(origins, dirs, device):
+    """(origins, dirs) as contiguous float32 [R,3] on `device` (None: where they are); origins [3] is broadcast"""
+    d = torch.as_tensor(dirs)
+    o = torch.as_tensor(origins)
+    if d.dim() != 2 or d.shape[1] != 3:
+        raise ValueError(f"dirs must be [R, 3] (got {tuple(d.shape)})")
+    if tuple(o.shape) not in ((3,), (1, 3), (len(d), 3)):
+        raise ValueError(f"origins must be [R, 3] or [3] for {len(d)} rays (got {tuple(o.shape)})")
+    if device is not None:
+        o, d = o.to(device), d.to(device)
+    o, d = o.to(torch.float32), d.to(torch.float32)
+    return o.reshape(-1, 3).expand(len(d), 3).contiguous(), d.contiguous()
 
 
 class TriIndex:
@@ -88,6 +148,7 @@ class TriIndex:
         self.src = view(host.src, self.nt, torch.int32, 4)
         self.boxes = view(host.boxes, self.level_offset[self.levels] * 6, torch.float32, 4).view(-1, 6)
         self.counters = view(host.counters, 8, torch.int32, 4)
+        self._ray_status = None
 
     @staticmethod
     def build(mesh) -> "TriIndex":
@@ -144,6 +205,82 @@ class TriIndex:
         return tuple(out[w] for w in want)
 
 
+    @property
+    def ray_status(self) -> torch.Tensor:
+        """[1] int32 on the device: the status word of this index's ray calls, 0 unless a traversal reached its bound (RAY_STATUS_BOUND)."""
+        if self._ray_status is None:
+            self._ray_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._ray_status
+
+    def _ray_call(self, name, origins, dirs, t_min, t_max, outs):
+        o, d = _rays(origins, dirs, self.device)
+        ptr = lambda t: None if t is None or not t.numel() else t.data_ptr()
+        with torch.cuda.device(self.device):
+            _check_ray(getattr(_lib.load_ray(), name)(ptr(self.tri), ptr(self.src), ptr(self.boxes), ptr(self.counters), self.nt, ptr(o), ptr(d), len(d),
+                                                      float(t_min), float(t_max), *[ptr(t) for t in outs], self.ray_status.data_ptr(), _stream(self.device)))
+
+    def cast(self, origins, dirs, t_min: float = 0.0, t_max: float = math.inf, want: Sequence[str] = RAY_WANT):
+        """The first hit of the rays origins + t dirs (dirs [R,3] as given, NOT normalised: t is in units of |d|; origins [R,3] or [3]) with
+        t in [t_min, t_max], both inclusive: a tuple in the order of `want`, out of t [R] float64, tri [R] int32 (input triangle index) and
+        bary [R,3] float32 (the weights of the triangle's corners); +inf, -1 and NaN where no valid triangle is hit or the ray is not
+        finite or has d = 0.  Device tensors; does not wait for the stream."""
+        want = tuple(want)
+        if not want or any(w not in RAY_WANT for w in want):
+            raise ValueError(f"want must name some of {RAY_WANT} (got {want})")
+        R, dev = len(torch.as_tensor(dirs)), self.device
+        out = {"t": None, "tri": None, "bary": None}
+        if "t" in want:
+            out["t"] = torch.empty(R, dtype=torch.float64, device=dev)
+        if "tri" in want:
+            out["tri"] = torch.empty(R, dtype=torch.int32, device=dev)
+        if "bary" in want:
+            out["bary"] = torch.empty(R, 3, dtype=torch.float32, device=dev)
+        self._ray_call("sta_ray_cast", origins, dirs, t_min, t_max, (out["t"], out["tri"], out["bary"]))
+        return tuple(out[w] for w in want)
+
+    def occluded(self, origins, dirs, t_min: float = 0.0, t_max: float = math.inf) -> torch.Tensor:
+        """uint8 [R]: 1 where some valid triangle is hit with t in [t_min, t_max], i.e. where `cast` with the same arguments returns a
+        triangle; the traversal leaves at the first one it meets.  A device tensor; does not wait for the stream."""
+        occ = torch.empty(len(torch.as_tensor(dirs)), dtype=torch.uint8, device=self.device)
+        self._ray_call("sta_ray_occluded", origins, dirs, t_min, t_max, (occ,))
+        return occ
+
+
 def point_to_mesh(points, mesh, radius: float = math.inf):
     """(d2, tri, point) of `TriIndex.build(mesh).query(points, radius)`."""
     return TriIndex.build(mesh).query(points, radius)
+
+
+def ray_cast(origins, dirs, mesh, t_min: float = 0.0, t_max: float = math.inf):
+    """(t, tri, bary) of `TriIndex.build(mesh).cast(origins, dirs, t_min, t_max)`."""
+    return TriIndex.build(mesh).cast(origins, dirs, t_min, t_max)
+
+
+def camera_rays(camera, H: int, W: int):
+    """float32 (origins [3], dirs [H*W,3]) on the host: the rays through the pixel centres of a `render.Camera`, row-major (pixel (row v,
+    column u) is ray v * W + u).  d has camera-space z = 1 - ((u - cx) / fx, (v - cy) / fy, 1) turned into the world - so the t of a hit
+    IS the depth `render.mesh_depth` speaks of.  Computed in float64 and rounded once."""
+    import numpy as np
+    fx, fy, cx, cy = [float(v) for v in camera.K]
+    Rm, tv = np.asarray(camera.w2c, dtype=np.float64)[:, :3], np.asarray(camera.w2c, dtype=np.float64)[:, 3]
+    u, v = np.meshgrid(np.arange(int(W), dtype=np.float64), np.arange(int(H), dtype=np.float64))
+    dc = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], axis=-1).reshape(-1, 3)
+    return torch.from_numpy((-Rm.T @ tv).astype(np.float32)), torch.from_numpy((dc @ Rm).astype(np.float32))
+
+
+def ray_depth(index: TriIndex, camera, H: int, W: int) -> torch.Tensor:
+    """The depth map of the indexed mesh from a `render.Camera` by rays: float32 [H,W], the depth of the first surface along each pixel's
+    ray between the camera's near and far planes, +inf where there is none.  Unlike the rasteriser it snaps nothing to a sub-pixel grid;
+    any other set of rays (a pointmap, a distorted model, a lidar pattern) goes through `cast` the same way."""
+    o, d = camera_rays(camera, H, W)
+    t, = index.cast(o, d, camera.near, camera.far, want=("t",))
+    return t.to(torch.float32).view(int(H), int(W))
+
+
+def visible(index: TriIndex, a, b, eps: float = 1e-6) -> torch.Tensor:
+    """bool [R]: no valid triangle on the segments a -> b between the parameters eps and 1 - eps (a, b [R,3], or one of them [3]): line of
+    sight against the surface.  A device tensor; does not wait for the stream."""
+    dev = index.device
+    a, b = torch.as_tensor(a).to(dev, torch.float32), torch.as_tensor(b).to(dev, torch.float32)
+    d = (b.reshape(-1, 3).to(torch.float64) - a.reshape(-1, 3).to(torch.float64)).to(torch.float32)
+    return index.occluded(a, d, float(eps), 1.0 - float(eps)) == 0
