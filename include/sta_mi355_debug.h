@@ -341,6 +341,10 @@ STA_API int sta_debug_workspace_fill(sta_handle* h, void* stream, int byte);
 STA_API int sta_debug_workspace_info(sta_handle* h, void* stream, int64_t out[8]);
 STA_API int sta_debug_workspace_tail(sta_handle* h, void* stream, int byte, int64_t* n_bad, int64_t* first_bad);
 
+#ifdef STA_WAVE_SKEW
+#include "sta_mi355_skew.h"      /* two more entries, of libsta_mi355_skew.so alone (the wave-skew schedule tests) */
+#endif
+
 #ifdef __cplusplus
 }
 #endif

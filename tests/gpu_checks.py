@@ -16,6 +16,7 @@ from vista_slam_amd.sta_frontend import STAFrontend, rope2d_inplace
 
 DEV = "cuda:0"
 _models = {}
+_hooks_lib = None        # on_library: the ONE library behind every model() / kernel_handle (None: the product / the test-hooks library)
 last_range = (0, 0)      # (fp16 saturations, fp8 correction-byte saturations) counted during the last run_golden_case (sta_range_report)
 
 
@@ -31,15 +32,32 @@ def model(cfg_name="tiny", qk_gain=1.0, precision="f16x3", seed=43, outlier=0, h
     """Cached frontends (weights are procedural, so (cfg, gain, seed, outlier level) identifies them).  hooks=False: the PRODUCT
     library libsta_mi355.so (what every golden / parity test runs); hooks=True: the test-hooks build libsta_mi355_test.so (same
     translation unit + the kernel-level entry points and experiment switches of include/sta_mi355_debug.h)."""
-    key = (cfg_name, qk_gain, seed, outlier, bool(hooks))
+    lib = _hooks_lib if _hooks_lib is not None else (_lib.load_test() if hooks else None)
+    key = (cfg_name, qk_gain, seed, outlier, bool(hooks)) + ((id(lib),) if _hooks_lib is not None else ())
     if key not in _models:
         cfg = W.TINY if cfg_name == "tiny" else W.FULL
-        m = STAFrontend(cfg, DEV, precision=precision, lib=_lib.load_test() if hooks else None)
+        m = STAFrontend(cfg, DEV, precision=precision, lib=lib)
         m.load_procedural(seed=seed, qk_gain=qk_gain, outlier=outlier)
         _models[key] = m
     m = _models[key]
     m.set_precision(precision)
     return m
+
+
+class on_library:
+    """`with on_library(_lib.load_skew()):` - every frontend that model() / kernel_handle hand out inside the block is one on `lib`, a
+    build that exports the product ABI and the test hooks; what the checks compute and return is unchanged."""
+    def __init__(self, lib):
+        self.lib = lib
+
+    def __enter__(self):
+        global _hooks_lib
+        self.prev, _hooks_lib = _hooks_lib, self.lib
+        return self.lib
+
+    def __exit__(self, *exc):
+        global _hooks_lib
+        _hooks_lib = self.prev
 
 
 def drop_models():

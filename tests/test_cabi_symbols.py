@@ -52,6 +52,24 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert b"gfx950" in lib.sta_version()
 
 
+def test_the_skew_library_exports_the_debug_abi_and_two_names_more():
+    """libsta_mi355_skew.so (the test-hooks build with live skew points, csrc/sta_skew.h) exports include/sta_mi355.h, include/
+    sta_mi355_debug.h and the two names of include/sta_mi355_skew.h - which the debug header includes under -DSTA_WAVE_SKEW alone -
+    and nothing else; neither other build of the translation unit exports those two."""
+    from vista_slam_amd import build, _lib
+    build.build_lib()
+    prod, dbg, skew = declared_symbols("sta_mi355.h"), declared_symbols("sta_mi355_debug.h"), declared_symbols("sta_mi355_skew.h")
+    assert skew == set(_lib.SKEW_SIGNATURES) == {"sta_debug_set_wave_skew", "sta_debug_wave_skew_hits"} and not skew & (prod | dbg)
+    hdr = open(os.path.join(ROOT, "include", "sta_mi355_debug.h")).read()
+    assert '#ifdef STA_WAVE_SKEW\n#include "sta_mi355_skew.h"' in hdr
+    linker = {"_init", "_fini", "_edata", "_end", "__bss_start"}
+    assert all_exported(_lib.SKEW_LIB_PATH) - linker == prod | dbg | skew, sorted((all_exported(_lib.SKEW_LIB_PATH) - linker) ^ (prod | dbg | skew))[:10]
+    assert not skew & (all_exported(_lib.LIB_PATH) | all_exported(_lib.TEST_LIB_PATH))
+    slib = _lib.load_skew()
+    for name in prod | dbg | skew:
+        assert hasattr(slib, name), f"{name} missing from libsta_mi355_skew.so"
+
+
 def test_default_config_matches_reference_constructor():
     from vista_slam_amd import _lib
     from vista_slam_amd import weights as W

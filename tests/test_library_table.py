@@ -67,6 +67,8 @@ def test_the_eight_hashes_differ_and_none_is_stale():
     for name, (lib, hash_file, deps, _own, _sig) in rows.items():
         assert not build.is_stale(lib, hash_file, deps), name
     assert not build.is_stale(build.TEST_LIB, build.TEST_HASH_FILE)
+    assert not build.is_stale(build.SKEW_LIB, build.SKEW_HASH_FILE, None, build.SKEW_FLAGS)
+    assert build.is_stale(build.SKEW_LIB, build.SKEW_HASH_FILE)       # its hash covers its flags: not the product's hash
 
 
 def test_the_exports_are_disjoint_and_the_product_exports_its_header():

@@ -3,7 +3,8 @@
 There is NO fallback: if the HIP library is missing or fails to load, importing the product path
 raises.  (The CPU oracle under oracle/ is test infrastructure and is never imported from here.)
 
-Two builds of the same translation unit (vista_slam_amd/build.py): `load()` = libsta_mi355.so, the product, which exports
+Three builds of the same translation unit (vista_slam_amd/build.py; the third, `load_skew()` = libsta_mi355_skew.so, is the second with live
+skew points behind every barrier, for tests/test_skew_gpu.py alone): `load()` = libsta_mi355.so, the product, which exports
 include/sta_mi355.h and nothing else; `load_test()` = libsta_mi355_test.so (-DSTA_TEST_HOOKS), which additionally exports the
 kernel-level test / micro-benchmark entry points of include/sta_mi355_debug.h.  Only tests/ and tools/ load the second one
 (`STAFrontend(..., lib=_lib.load_test())`, or `_lib.use_test_hooks()` at the top of a tool).
@@ -14,6 +15,7 @@ import os
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libsta_mi355.so")
 TEST_LIB_PATH = os.path.join(PKG, "libsta_mi355_test.so")
+SKEW_LIB_PATH = os.path.join(PKG, "libsta_mi355_skew.so")   # the test-hooks build with live skew points (csrc/sta_skew.h): `load_skew()`
 CLOUD_LIB_PATH = os.path.join(PKG, "libsta_cloud.so")      # a second library with its own ABI (include/sta_cloud.h): `load_cloud()`
 RASTER_LIB_PATH = os.path.join(PKG, "libsta_raster.so")    # a third one (include/sta_raster.h): `load_raster()`
 TSDF_LIB_PATH = os.path.join(PKG, "libsta_tsdf.so")        # a fourth one (include/sta_tsdf.h): `load_tsdf()`
@@ -219,6 +221,12 @@ TEST_SIGNATURES = {
     "sta_debug_workspace_tail": (_i, [_vp, _vp, _i, C.POINTER(_i64), C.POINTER(_i64)]),
 }
 
+# include/sta_mi355_skew.h (what include/sta_mi355_debug.h includes under STA_WAVE_SKEW): exported by libsta_mi355_skew.so alone
+SKEW_SIGNATURES = {
+    "sta_debug_set_wave_skew": (_i, [C.c_uint, C.c_uint, C.c_uint, C.c_uint]),
+    "sta_debug_wave_skew_hits": (_i, [C.POINTER(C.c_ulonglong)]),      # out[34]
+}
+
 # include/sta_cloud.h: libsta_cloud.so, handle-free; NOT part of SIGNATURES (which stays equal to include/sta_mi355.h)
 CLOUD_SIGNATURES = {
     "sta_nn_plan": (_i, [_i64, _i64, C.POINTER(_i64)]),
@@ -301,6 +309,7 @@ class StaTriIndex(C.Structure):
 
 _lib = None
 _test_lib = None
+_skew_lib = None
 _satellites = {}      # path -> the loaded handle-free library
 
 class StaError(RuntimeError):
@@ -369,6 +378,23 @@ def load_test():
     _bind(lib, SIGNATURES, strict=True)
     _bind(lib, TEST_SIGNATURES, strict=True)
     _test_lib = lib
+    return lib
+
+
+def load_skew():
+    """Load libsta_mi355_skew.so: the test-hooks build whose kernels carry live skew points (csrc/sta_skew.h), plus the two
+    sta_debug_*wave_skew* entry points.  tests/test_skew_gpu.py only; `STAFrontend(..., lib=_lib.load_skew())`."""
+    global _skew_lib
+    if _skew_lib is not None:
+        return _skew_lib
+    if not os.path.exists(SKEW_LIB_PATH):
+        raise _missing(SKEW_LIB_PATH)
+    import torch  # noqa: F401
+    lib = C.CDLL(SKEW_LIB_PATH)
+    _bind(lib, SIGNATURES, strict=True)
+    _bind(lib, TEST_SIGNATURES, strict=True)
+    _bind(lib, SKEW_SIGNATURES, strict=True)
+    _skew_lib = lib
     return lib
 
 

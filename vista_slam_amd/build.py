@@ -4,6 +4,9 @@
                                             #    vista_slam_amd/libsta_mi355_test.so   the same translation unit + -DSTA_TEST_HOOKS:
                                             #    additionally the kernel-level test / micro-benchmark entry points of
                                             #    include/sta_mi355_debug.h (loaded by tests/ and tools/ only)
+                                            #    vista_slam_amd/libsta_mi355_skew.so   the same again + -DSTA_WAVE_SKEW: the skew points of
+                                            #    csrc/sta_skew.h are live and the two sta_debug_*wave_skew* entries exist
+                                            #    (tests/test_skew_gpu.py only; in every other library the points expand to nothing)
                                             #    vista_slam_amd/libsta_<name>.so       one handle-free library per row of SATELLITES:
                                             #    and of ADDONS: a translation unit of its own (csrc/sta_<name>.hip) that exports
                                             #    include/sta_<name>.h
@@ -20,9 +23,11 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libsta_mi355.so")
 TEST_LIB = os.path.join(PKG, "libsta_mi355_test.so")
+SKEW_LIB = os.path.join(PKG, "libsta_mi355_skew.so")
 SOURCES = ["sta_api.hip"]
-DEPS = ["sta_exports.map", "sta_api.hip", "sta_launch.inc", "sta_forward.inc", "sta_debug.inc", "sta_rows.inc", "sta_bench.inc", "gemm.h", "gemm2.h", "conv3h.h", "attention.h", "elementwise.h", "geo.h", "select.h", "voxel.h", "flow.h", "loop.h", "pgo.h", "graph.h", "sta_common.h",
-        os.path.join("..", "..", "include", "sta_mi355.h"), os.path.join("..", "..", "include", "sta_mi355_debug.h")]
+DEPS = ["sta_exports.map", "sta_api.hip", "sta_launch.inc", "sta_forward.inc", "sta_debug.inc", "sta_rows.inc", "sta_bench.inc", "gemm.h", "gemm2.h", "conv3h.h", "attention.h", "elementwise.h", "geo.h", "select.h", "voxel.h", "flow.h", "loop.h", "pgo.h", "graph.h", "sta_common.h", "sta_skew.h",
+        os.path.join("..", "..", "include", "sta_mi355.h"), os.path.join("..", "..", "include", "sta_mi355_debug.h"),
+        os.path.join("..", "..", "include", "sta_mi355_skew.h")]
 
 
 def _inc(name):
@@ -32,7 +37,8 @@ def _inc(name):
 # The handle-free libraries.  name: (what it is, its own files, the shared headers it includes).  A library's own files are in no other
 # library's dependency list; a shared header is in several.  raster.h and include/sta_raster.h are shared: the mesh library includes
 # them for the camera and the limits of the canvas.
-_SORT = ["voxel.h", "select.h", "elementwise.h"]      # the sort and scan kernels with their launch code, and what voxel.h includes
+_SORT = ["voxel.h", "select.h", "elementwise.h", "sta_skew.h"]      # the sort and scan kernels with their launch code, and what they include (the
+                                                                     # skew points of sta_skew.h expand to nothing in these libraries)
 _RASTER = ["raster.h", _inc("sta_raster.h")]
 SATELLITES = {
     "cloud": ("nearest neighbours between clouds for the offline metrics", ["sta_cloud.hip", "cloud.h", _inc("sta_cloud.h")], _SORT),
@@ -72,6 +78,8 @@ BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", 
               "-Wl,--version-script=" + os.path.join(CSRC, "sta_exports.map")]
 HASH_FILE = LIB + ".srchash"
 TEST_HASH_FILE = TEST_LIB + ".srchash"
+SKEW_HASH_FILE = SKEW_LIB + ".srchash"
+SKEW_FLAGS = ["-DSTA_TEST_HOOKS", "-DSTA_WAVE_SKEW"]
 
 
 def extra_flags():
@@ -85,34 +93,36 @@ def extra_flags():
     return f
 
 
-def source_hash(deps=None):
+def source_hash(deps=None, flags=()):
     """Content hash of every source the library is built from (mtimes do not survive the gpurun
     snapshot copy, so staleness is decided by content) and of the build flags.  deps: DEPS (the product and test-hooks
-    libraries) unless given (a satellite's <NAME>_DEPS)."""
+    libraries) unless given (a satellite's <NAME>_DEPS).  flags: further build flags that tell two builds of the same sources apart (the skew
+    library's SKEW_FLAGS)."""
     import hashlib
     h = hashlib.sha256()
-    h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags()).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
+    h.update(" ".join([f.replace(CSRC, "csrc") for f in BASE_FLAGS] + extra_flags() + list(flags)).encode())      # (path-independent: the snapshot on the GPU box lives elsewhere)
     for d in (DEPS if deps is None else deps):
         with open(os.path.join(CSRC, d), "rb") as f:
             h.update(f.read())
     return h.hexdigest()
 
 
-def is_stale(lib=LIB, hash_file=HASH_FILE, deps=None):
+def is_stale(lib=LIB, hash_file=HASH_FILE, deps=None, flags=()):
     if not os.path.exists(lib) or not os.path.exists(hash_file):
         return True
     with open(hash_file) as f:
-        return f.read().strip() != source_hash(deps)
+        return f.read().strip() != source_hash(deps, flags)
 
 
 def _cmd(hipcc, out, hooks, sources=None):
+    """hooks: False, True (-DSTA_TEST_HOOKS) or a list of flags (SKEW_FLAGS)."""
     return ([hipcc] + BASE_FLAGS + ["-o", out] + extra_flags() +
-            (["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
+            (list(hooks) if isinstance(hooks, list) else ["-DSTA_TEST_HOOKS"] if hooks else []) + [os.path.join(CSRC, s) for s in (SOURCES if sources is None else sources)])
 
 
-def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True,
+def build_lib(force=False, verbose=True, test_hooks=True, skew=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True,
               ray=True):
-    """Build the product library, (test_hooks) the test-hooks library and, each under the keyword of its name, the libraries of
+    """Build the product library, (test_hooks) the test-hooks library, (skew) the wave-skew library and, each under the keyword of its name, the libraries of
     SATELLITES and ADDONS; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
     wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray)
     assert list(wanted) == list(SATELLITES) + list(ADDONS)
@@ -121,6 +131,8 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
         jobs.append((LIB, HASH_FILE, False, None, None))
     if test_hooks and (force or is_stale(TEST_LIB, TEST_HASH_FILE)):
         jobs.append((TEST_LIB, TEST_HASH_FILE, True, None, None))
+    if skew and (force or is_stale(SKEW_LIB, SKEW_HASH_FILE, None, SKEW_FLAGS)):
+        jobs.append((SKEW_LIB, SKEW_HASH_FILE, SKEW_FLAGS, None, None))
     for name in wanted:
         lib, hash_file, sources, deps = (globals()[name.upper() + k] for k in ("_LIB", "_HASH_FILE", "_SOURCES", "_DEPS"))
         if wanted[name] and (force or is_stale(lib, hash_file, deps)):
@@ -137,7 +149,7 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
             print("[build]", " ".join(cmd), flush=True)
         procs.append((subprocess.Popen(cmd, cwd=CSRC), cmd))
     failed = None
-    for (p, cmd), (out, hf, _hooks, _sources, deps) in zip(procs, jobs):
+    for (p, cmd), (out, hf, hooks, _sources, deps) in zip(procs, jobs):
         if failed is not None:             # a sibling compile already failed: do not leave this one running un-waited
             p.kill()
             p.wait()
@@ -146,7 +158,7 @@ def build_lib(force=False, verbose=True, test_hooks=True, cloud=True, raster=Tru
             failed = subprocess.CalledProcessError(p.returncode, cmd)
             continue
         with open(hf, "w") as f:
-            f.write(source_hash(deps))
+            f.write(source_hash(deps, hooks if isinstance(hooks, list) else ()))
     if failed is not None:
         raise failed
     return LIB

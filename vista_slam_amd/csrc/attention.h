@@ -21,6 +21,7 @@
 // Cross attention = same kernel with kv_shift selecting the other view's K/V.
 #pragma once
 #include "sta_common.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 #include <type_traits>
 
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst_wave_base);   // gemm2.h
@@ -125,7 +126,7 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem,
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if (lane == 0) red[wave] = mx;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(400);
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float sum = 0.f;
     for (int j = tid; j < kpad; j += 256) {
@@ -135,7 +136,7 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem,
     }
     sum = wave_sum(sum);
     if (lane == 0) red[4 + wave] = sum;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(401);
     // wave w: keys [w * kpad / 4, (w + 1) * kpad / 4) (kpad % 64 == 0: whole 16-key groups), two 8-key chunks in flight
     const f16* vh = p.Vt_hi + voff + (size_t)lane * p.npad;
     const f16* vl = SPLIT ? p.Vt_lo + voff + (size_t)lane * p.npad : nullptr;
@@ -155,7 +156,7 @@ __device__ __forceinline__ void attn_pose_query(const AttnParams& p, char* smem,
         }
     }
     red[8 + wave * 64 + lane] = o;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(402);
     if (wave != 0) return;
     o = (red[8 + lane] + red[8 + 64 + lane]) + (red[8 + 128 + lane] + red[8 + 192 + lane]);
     o /= (red[4] + red[5]) + (red[6] + red[7]);
@@ -429,7 +430,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
         if (it + 1 < ntiles_) issue_tile(STG ^ 1, kv0 + ATT_KV);      // stage STG^1 was released by the last barrier
         if (wave_active) tile_body(stage_c, tail_c, kv0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __syncthreads(); STA_SKEW(403);
     };
 
     const int ntiles = (nk + ATT_KV - 1) / ATT_KV, nfull = nk / ATT_KV;
@@ -448,7 +449,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
                 case 1: asm volatile("s_waitcnt vmcnt(%0)" :: "n"(1 * DMAS) : "memory"); break;
                 default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
             }
-            __syncthreads();
+            __syncthreads(); STA_SKEW(404);
             if (wave_active) {
                 if (t >= nfull) tile_body(integral_constant<int, 0>{}, T{}, t * ATT_KV, t);
                 else tile_body(integral_constant<int, 0>{}, F{}, t * ATT_KV, t);
@@ -457,7 +458,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
     } else {
         issue_tile(0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __syncthreads(); STA_SKEW(405);
         int it = 0;
         for (; it + 1 < nfull; it += 2) {
             step(integral_constant<int, 0>{}, F{}, it, ntiles);
@@ -487,7 +488,8 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
         // written with ds_write_b128 - 8 consecutive lanes = 8 consecutive queries = 8 different positions of the same chunk:
         // one 128-B bank row per 8-lane group - and read back with ds_read_b128 whose four 16-lane groups each cover the 16
         // slots of a 256-B bank row exactly once (rows of equal parity differ in their chunk set, the XOR permutes inside it).
-        __syncthreads();                                // every wave is done with the K / V^T stages (all waves reach this point)
+        STA_SKEW_EPI(410);
+        __syncthreads(); STA_SKEW(406);                                // every wave is done with the K / V^T stages (all waves reach this point)
         char* const wl = smem + wave * (64 * 128);
         RangeAcc ra;        // never flushed (dead code): a convex combination of V rows stays inside V's range
 #pragma unroll
@@ -551,6 +553,7 @@ __device__ __forceinline__ void attn_body(const AttnParams& p, const AttnGroupB&
 
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
+    STA_SKEW_ENTRY(407);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body<SPLIT, false>(p, AttnGroupB{}, smem);
 }
@@ -558,6 +561,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const AttnParams p) {
 // Two groups of sequences with their own nq / nk in one launch (AttnGroupB)
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void attn_mixed_kernel(const AttnMixedParams mp) {
+    STA_SKEW_ENTRY(408);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body<SPLIT, true>(mp.a, mp.b, smem);
 }
@@ -565,6 +569,7 @@ __global__ __launch_bounds__(256, 2) void attn_mixed_kernel(const AttnMixedParam
 // One group per sequence (AttnVarlenParams): batch entries with their own token counts in one launch
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void attn_varlen_kernel(const AttnVarlenParams vp) {
+    STA_SKEW_ENTRY(409);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     attn_body<SPLIT, false, true>(vp.a, AttnGroupB{}, smem, &vp);
 }

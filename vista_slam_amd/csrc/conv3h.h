@@ -19,6 +19,7 @@
 //  * Epilogue: the ordinary plane epilogue per 32-pixel row segment (bias, ReLU, residual planes), bounded to the image.
 #pragma once
 #include "gemm2.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 #include <type_traits>
 
 #define C3H_PW 34     // halo width: 32 output columns + 2
@@ -37,6 +38,7 @@ constexpr int conv3h_smem_bytes() { return 2 * conv3h_halo_bytes<SPLIT, BM>() + 
 // were measured and dropped: -0.3 %, equal, -4 %, equal; LABNOTES.md.)
 template <bool SPLIT, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, bool MX>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv3h_kernel(const GemmParams p) {
+    STA_SKEW_ENTRY(304);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MT = WM / 32, NT = WN / 32, TR = BM / 32;
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv3h_kernel(const Gem
 #pragma unroll
     for (int u = 0; u < TPS; ++u) if (u < nkt) issue_b(u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    __syncthreads(); STA_SKEW(300);
     if (p.stamps) st1 = __builtin_amdgcn_s_memrealtime();
 
     // The K loop exists twice, with the input ReLU of resConfUnit*.conv1 resolved at COMPILE time (round 6): tested per fragment
@@ -278,13 +280,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv3h_kernel(const Gem
             do_tap(c, t, cur * TPS + u);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __syncthreads(); STA_SKEW(301);
         tap += TPS;
         if (tap >= 9) { tap -= 9; ++cb; }
     }
     };
     if (EPI != EPI_HEAD && p.relu_in) k_loop(std::integral_constant<bool, true>{});
     else k_loop(std::integral_constant<bool, false>{});
+    STA_SKEW_EPI(306);
 
     if (p.stamps) { asm volatile("" ::"v"(acc[MT - 1][NT - 1][15]), "v"(acc[0][0][0]) : "memory"); st2 = __builtin_amdgcn_s_memrealtime(); }
     // ---- epilogue: MFMA tile (i, j) of this wave = the 32 pixels (y0 + wm*MT + i, x0 .. x0 + 31) x 32 channels
@@ -324,6 +327,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv3h_kernel(const Gem
 // through the aliases this form needs, and those kernels stay what they are, bit for bit.  A change to the K loop belongs in both.
 template <bool SPLIT, int EPI, int BM, int BN, int WAVES_M, int WAVES_N, bool MX>
 __device__ __forceinline__ void conv3h_body(const GemmParams& p, const VlGeo& geo) {
+    STA_SKEW_ENTRY(305);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = WAVES_M * WAVES_N;
     constexpr int WM = BM / WAVES_M, WN = BN / WAVES_N, MT = WM / 32, NT = WN / 32, TR = BM / 32;
@@ -431,7 +435,7 @@ __device__ __forceinline__ void conv3h_body(const GemmParams& p, const VlGeo& ge
 #pragma unroll
     for (int u = 0; u < TPS; ++u) if (u < nkt) issue_b(u);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    __syncthreads(); STA_SKEW(302);
     if (p.stamps) st1 = __builtin_amdgcn_s_memrealtime();
 
     // The K loop exists twice, with the input ReLU of resConfUnit*.conv1 resolved at COMPILE time (round 6): tested per fragment
@@ -564,13 +568,14 @@ __device__ __forceinline__ void conv3h_body(const GemmParams& p, const VlGeo& ge
             do_tap(c, t, cur * TPS + u);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __syncthreads(); STA_SKEW(303);
         tap += TPS;
         if (tap >= 9) { tap -= 9; ++cb; }
     }
     };
     if (EPI != EPI_HEAD && p.relu_in) k_loop(std::integral_constant<bool, true>{});
     else k_loop(std::integral_constant<bool, false>{});
+    STA_SKEW_EPI(307);
 
     if (p.stamps) { asm volatile("" ::"v"(acc[MT - 1][NT - 1][15]), "v"(acc[0][0][0]) : "memory"); st2 = __builtin_amdgcn_s_memrealtime(); }
     // ---- epilogue: MFMA tile (i, j) of this wave = the 32 pixels (y0 + wm*MT + i, x0 .. x0 + 31) x 32 channels

@@ -4,6 +4,7 @@
 // All reductions are wave64 shuffles; all loads/stores are 8-16 B per lane.
 #pragma once
 #include "sta_common.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 #include <type_traits>
 
 // ---------------------------------------------------------------------------------------------
@@ -118,6 +119,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
 // only the add).  One block per row, one float4 per thread (C <= 1024): 1 + nslab independent loads per thread.
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void resid_ln_kernel(const LnParams p) {
+    STA_SKEW_ENTRY(510);
     const int row = blockIdx.x, idx = threadIdx.x * 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool on = idx < p.C;
@@ -136,18 +138,18 @@ __global__ __launch_bounds__(256) void resid_ln_kernel(const LnParams p) {
     __shared__ float red[2][4];
     __shared__ float pivot;
     if (threadIdx.x == 0) pivot = v.x;       // the row's first element (thread 0 always holds column 0): see ln_kernel
-    __syncthreads();
+    __syncthreads(); STA_SKEW(500);
     const float piv = pivot;
     if (on) { v.x -= piv; v.y -= piv; v.z -= piv; v.w -= piv; }
     float sum = wave_sum((v.x + v.y) + (v.z + v.w));
     if (lane == 0) red[0][wave] = sum;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(501);
     const float m = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)p.C;
     float sq = 0.f;
     if (on) { float a = v.x - m, b = v.y - m, c = v.z - m, d = v.w - m; sq = (a * a + b * b) + (c * c + d * d); }
     sq = wave_sum(sq);
     if (lane == 0) red[1][wave] = sq;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(502);
     const float rstd = 1.0f / sqrtf(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)p.C + p.eps);
     if (threadIdx.x == 0 && !(fabsf(piv + m) <= 3.0e38f && rstd <= 3.0e38f && rstd > 0.f)) atomicAdd(p.range, 1ull);   // non-finite row, or a variance that overflowed fp32 (rstd == 0: the row would silently become pure bias)
     if (on) {
@@ -1041,6 +1043,7 @@ __global__ __launch_bounds__(256) void pose_layer_rows_kernel(const float* in, i
 
 // heads fc_t(3) / fc_rot(9) / fc_conf(1) + rotation orthogonalisation + 4x4 packing; one block per sample
 __global__ __launch_bounds__(256) void pose_final_kernel(const PoseParams p, const float* feat) {
+    STA_SKEW_ENTRY(511);
     __shared__ float outv[16];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* in = feat + (size_t)b * p.Hd;
@@ -1059,7 +1062,7 @@ __global__ __launch_bounds__(256) void pose_final_kernel(const PoseParams p, con
         s = wave_sum(s);
         if (lane == 0) outv[n] = s + (n < 3 ? p.bt[n] : (n < 12 ? p.br[n - 3] : p.bc[0]));
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(503);
     if (tid == 0) {
         // m (3x3 row-major from fc_rot) -> normalise rows -> R = nearest rotation of normalised m
         double M[3][3], R[3][3];
@@ -1089,6 +1092,7 @@ __global__ __launch_bounds__(256) void pose_final_kernel(const PoseParams p, con
 // ([W,H] views, utils/misc.py:60-61,81): u = row - H/2 pairs with X, v = col - W/2 with Y, principal point (H/2, W/2).
 __global__ __launch_bounds__(256) void intrinsics_partial_kernel(const float* pts, const float* conf, int B, int H, int W,
                                                                  float* depth, double* partial /*[B][nblk][5]*/, int nblk, int tr) {
+    STA_SKEW_ENTRY(512);
     const int b = blockIdx.y;
     const int64_t hw = (int64_t)H * W;
     const float cx = W / 2.0f, cy = H / 2.0f;
@@ -1117,7 +1121,7 @@ __global__ __launch_bounds__(256) void intrinsics_partial_kernel(const float* pt
         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
         if (lane == 0) red[wave][k] = v;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(504);
     if (threadIdx.x < 5) partial[((int64_t)b * nblk + blockIdx.x) * 5 + threadIdx.x] =
         red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
@@ -1166,6 +1170,7 @@ __global__ void intrinsics_final_kernel(const double* partial, int B, int nblk, 
 // w = clamp(ci*cj, 1e-6).  Single block (n ~ 5e4), fp64 partials.
 __global__ __launch_bounds__(1024) void scale_estimate_kernel(const float* Di, const float* Dj, const float* ci, const float* cj,
                                                                int64_t n, float* s_out) {
+    STA_SKEW_ENTRY(513);
     double num = 0, den = 0;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
         const float w = fmaxf(ci[i] * cj[i], 1e-6f);
@@ -1176,7 +1181,7 @@ __global__ __launch_bounds__(1024) void scale_estimate_kernel(const float* Di, c
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o); den += __shfl_xor(den, o); }
     if (lane == 0) { rn[wave] = num; rd[wave] = den; }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(505);
     if (threadIdx.x == 0) {
         double a = 0, b = 0;
         for (int k = 0; k < (int)(blockDim.x >> 6); ++k) { a += rn[k]; b += rd[k]; }
@@ -1342,23 +1347,25 @@ struct CloudParams {
     float* pts; float* col; uint8_t* rec;
 };
 __global__ __launch_bounds__(256) void cloud_count_kernel(CloudParams p) {
+    STA_SKEW_ENTRY(514);
     const int64_t total = (int64_t)p.N * p.H * p.W, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < total && p.conf[i] > p.thres;
     const unsigned long long b = __ballot(keep);
     __shared__ int wc[4];
     if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(506);
     if (threadIdx.x == 0) p.counts[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 __global__ __launch_bounds__(1024) void cloud_scan_kernel(CloudParams p) {
+    STA_SKEW_ENTRY(515);
     __shared__ int64_t part[1024];
     const int per = (p.nblk + 1023) / 1024, lo = threadIdx.x * per, hi = min(lo + per, p.nblk);
     int64_t s = 0;
     for (int i = lo; i < hi; ++i) s += p.counts[i];
     part[threadIdx.x] = s;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(507);
     if (threadIdx.x == 0) { int64_t run = 0; for (int i = 0; i < 1024; ++i) { const int64_t v = part[i]; part[i] = run; run += v; } p.offs[p.nblk] = run; }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(508);
     int64_t run = part[threadIdx.x];
     for (int i = lo; i < hi; ++i) { p.offs[i] = run; run += p.counts[i]; }
 }
@@ -1373,13 +1380,14 @@ __device__ __forceinline__ void cloud_write_record(uint8_t* r, float wx, float w
     r[26] = (uint8_t)rintf(fminf(fmaxf(cb, 0.f), 1.f) * 255.f);
 }
 __global__ __launch_bounds__(256) void cloud_emit_kernel(CloudParams p) {
+    STA_SKEW_ENTRY(516);
     const int64_t hw = (int64_t)p.H * p.W, total = p.N * hw, i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < total && p.conf[i] > p.thres;
     const unsigned long long b = __ballot(keep);
     __shared__ int wc[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) wc[wave] = __popcll(b);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(509);
     if (!keep) return;
     int rank = __popcll(b & ((1ull << lane) - 1));
     for (int w = 0; w < wave; ++w) rank += wc[w];

@@ -11,6 +11,7 @@
 //   flow_track_kernel       one wave per (point, frame): template in registers, source patch in LDS, float64 scalars in every lane
 //   flow_stats_kernel       per frame: n, the number of tracked points, the sum of their float64 displacements in a fixed order
 #pragma once
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 #define FLOW_MAX_LEVELS 4
 #define FLOW_MAX_WIN 21
@@ -43,6 +44,7 @@ template <bool F32>
 __global__ __launch_bounds__(256) void flow_pyrdown_kernel(const void* __restrict__ src, long long src_stride, int Hs, int Ws,
                                                            uint8_t* __restrict__ src_out, uint8_t* __restrict__ dst, int Hd, int Wd,
                                                            long long pyr_stride) {
+    STA_SKEW_ENTRY(908);
     __shared__ uint8_t tile[35][36];
     const int ox0 = blockIdx.x * 16, oy0 = blockIdx.y * 16, sx0 = 2 * ox0 - 2, sy0 = 2 * oy0 - 2;
     const size_t frame = blockIdx.z;
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void flow_pyrdown_kernel(const void* __restric
         if (src_out && ly >= 2 && ly < 34 && lx >= 2 && lx < 34 && y < Hs && x < Ws)
             src_out[frame * (size_t)pyr_stride + (size_t)y * Ws + x] = (uint8_t)v;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(900);
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15, oy = oy0 + ty, ox = ox0 + tx;
     if (!dst || oy >= Hd || ox >= Wd) return;
     const int k[5] = {1, 4, 6, 4, 1};
@@ -81,6 +83,7 @@ __device__ __forceinline__ long long flow_isqrt(long long v) {
 // inside the tile's own staged region, so the box sums read LDS alone.
 __global__ __launch_bounds__(256) void flow_response_kernel(const uint8_t* __restrict__ img, int H, int W, int r, int* __restrict__ R,
                                                             int* __restrict__ rmax) {
+    STA_SKEW_ENTRY(909);
     __shared__ int im[24][25];
     __shared__ int pxx[22][23], pxy[22][23], pyy[22][23];
     __shared__ int wmax[4];
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(256) void flow_response_kernel(const uint8_t* __res
         const int ly = i / ispan, lx = i - ly * ispan;
         im[ly][lx] = img[(size_t)flow_reflect(y0 - r - 1 + ly, H) * W + flow_reflect(x0 - r - 1 + lx, W)];
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(901);
     for (int i = threadIdx.x; i < pspan * pspan; i += 256) {
         const int ly = i / pspan, lx = i - ly * pspan, y = y0 - r + ly, x = x0 - r + lx;
         if (y < 0 || y >= H || x < 0 || x >= W) continue;
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(256) void flow_response_kernel(const uint8_t* __res
         const int gy = (im[ly + 2][lx] - im[ly][lx]) + 2 * (im[ly + 2][lx + 1] - im[ly][lx + 1]) + (im[ly + 2][lx + 2] - im[ly][lx + 2]);
         pxx[ly][lx] = gx * gx; pxy[ly][lx] = gx * gy; pyy[ly][lx] = gy * gy;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(902);
     const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15, y = y0 + ty, x = x0 + tx;
     int resp = 0;
     if (y < H && x < W) {
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256) void flow_response_kernel(const uint8_t* __res
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
     if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(903);
     if (threadIdx.x == 0) {
         mx = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
         if (mx > 0) atomicMax(rmax, mx);             // integer atomic: the result does not depend on the order
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(256) void flow_rank_kernel(const int* __restrict__ 
 __global__ __launch_bounds__(1024) void flow_suppress_kernel(int* cell, const int* __restrict__ sidx, const int* __restrict__ n_cand, int H, int W,
                                                              int min_distance, int max_corners, float* __restrict__ corners,
                                                              int* __restrict__ n_out) {
+    STA_SKEW_ENTRY(910);
     __shared__ int wfirst[16], wsum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int M = *n_cand, md2 = min_distance * min_distance, reach = min_distance - 1;
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(1024) void flow_suppress_kernel(int* cell, const in
         // u = the first thread whose rank is undecided or past the candidates
         const unsigned long long open = __ballot(r >= M || st == 0);
         if (lane == 0) wfirst[wave] = open ? wave * 64 + __ffsll((long long)open) - 1 : 1024;
-        __syncthreads();                                 // also orders this round's cell writes before the next round's reads
+        __syncthreads(); STA_SKEW(904);                                 // also orders this round's cell writes before the next round's reads
         int u = 1024;
 #pragma unroll
         for (int w = 0; w < 16; ++w) u = min(u, wfirst[w]);
@@ -203,14 +207,14 @@ __global__ __launch_bounds__(1024) void flow_suppress_kernel(int* cell, const in
             if (lane >= o) v += up;
         }
         if (lane == 63) wsum[wave] = v;
-        __syncthreads();
+        __syncthreads(); STA_SKEW(905);
         int before = 0, total = 0;
 #pragma unroll
         for (int w = 0; w < 16; ++w) { if (w < wave) before += wsum[w]; total += wsum[w]; }
         const int pos = n_acc + before + v - mine;
         if (mine && pos < max_corners) { corners[2 * (size_t)pos] = (float)x; corners[2 * (size_t)pos + 1] = (float)y; }
         n_acc += total; lo += u;
-        __syncthreads();                                 // wfirst / wsum are rewritten by the next round
+        __syncthreads(); STA_SKEW(906);                                 // wfirst / wsum are rewritten by the next round
     }
     if (t == 0) *n_out = min(n_acc, max_corners);
 }
@@ -365,6 +369,7 @@ __global__ __launch_bounds__(256) void flow_stats_kernel(const float* __restrict
                                                          const float* __restrict__ out, const uint8_t* __restrict__ status,
                                                          double* __restrict__ stats) {
 #pragma clang fp contract(off)
+    STA_SKEW_ENTRY(911);
     __shared__ double wsum[4];
     __shared__ int wgood[4];
     const int n = n_dev ? min(*n_dev, n_cap) : n_cap, frame = blockIdx.x;
@@ -380,7 +385,7 @@ __global__ __launch_bounds__(256) void flow_stats_kernel(const float* __restrict
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); good += __shfl_xor(good, o); }
     if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = s; wgood[threadIdx.x >> 6] = good; }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(907);
     if (threadIdx.x == 0) {
         stats[3 * (size_t)frame] = (double)n;
         stats[3 * (size_t)frame + 1] = (double)(wgood[0] + wgood[1] + wgood[2] + wgood[3]);

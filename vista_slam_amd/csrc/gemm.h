@@ -20,6 +20,7 @@
 // and the curope rotary kernel (pos_embed/curope/kernels.cu:17-82) fused into the QK epilogue.
 #pragma once
 #include "sta_common.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 #include <type_traits>
 
 enum { A_DENSE = 0, A_CONV3 = 1 };
@@ -591,6 +592,7 @@ struct QkvVarlenParams {
 };
 template <bool SPLIT, typename P = GemmParams>
 __global__ __launch_bounds__(256) void qkv_finish_kernel(const P p) {
+    STA_SKEW_ENTRY(103);
     if constexpr (std::is_same<P, QkvVarlenParams>::value) {
         __shared__ __attribute__((aligned(16))) f16 vt_lds[2][64][72];
         const int tid = threadIdx.x, head = blockIdx.x % p.heads, tile = blockIdx.x / p.heads, seg = blockIdx.y;
@@ -652,7 +654,7 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(const P p) {
                     }
                 }
             }
-            __syncthreads();
+            __syncthreads(); STA_SKEW(100);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int idx = tid + 256 * k, d = idx >> 3, c8 = (idx & 7) * 8;          // eight tokens c8 .. c8 + 7 of row d
@@ -736,6 +738,7 @@ __global__ __launch_bounds__(256) void qkv_finish_kernel(const P p) {
 
 template <bool SPLIT, int AMODE, int EPI>
 __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
+    STA_SKEW_ENTRY(104);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NPL = SPLIT ? 2 : 1;
     constexpr int STAGE = 2 * NPL * GEMM_TILE_BYTES;     // A planes then B planes
@@ -840,7 +843,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
 
     load_tile(0);
     store_tile(0);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(101);
 
     for (int kt = 0; kt < nkt; ++kt) {
         const int cur = kt & 1;
@@ -874,10 +877,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
                 }
         }
         if (kt + 1 < nkt) store_tile(cur ^ 1);
-        __syncthreads();
+        __syncthreads(); STA_SKEW(102);
     }
 
     // ------------------------------------------------------------------ epilogue
+    STA_SKEW_EPI(105);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll

@@ -20,6 +20,7 @@
 //    resident on one XCD share A / W panels in that XCD's L2.
 #pragma once
 #include "gemm.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 #include <type_traits>
 
 typedef short short8 __attribute__((ext_vector_type(8)));
@@ -64,7 +65,7 @@ __device__ __forceinline__ void head_epilogue(const GemmParams& p, const floatx1
 #pragma unroll
         for (int o = 0; o < 4; ++o) w4[j][o] = p.hw4[o * 128 + col];
     }
-    __syncthreads();                                             // every wave has left the operand stages
+    __syncthreads(); STA_SKEW(200);                                             // every wave has left the operand stages
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         float part[64];                                          // [r][o]
@@ -93,7 +94,7 @@ __device__ __forceinline__ void head_epilogue(const GemmParams& p, const floatx1
         const int r = l31 >> 1, row = wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
         *reinterpret_cast<float2*>(red + ((size_t)wn * BM + row) * 4 + (l31 & 1) * 2) = make_float2(part[0], part[1]);
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(201);
     if (tid < BM) {
         const int64_t pix = pix_base + (int64_t)(tid >> 5) * rstride + (tid & 31);
         if (pix < p.M && (tid >> 5) < rows_valid && (tid & 31) < cols_valid) {
@@ -145,7 +146,7 @@ __device__ __forceinline__ void head_epilogue_t(const GemmParams& p, const float
                 wh[w][e] = h_; wl[w][e] = l_;
             }
     }
-    __syncthreads();                                             // every wave has left the operand stages
+    __syncthreads(); STA_SKEW(202);                                             // every wave has left the operand stages
     RangeAcc ra;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
@@ -179,7 +180,7 @@ __device__ __forceinline__ void head_epilogue_t(const GemmParams& p, const float
             make_float4(o[0] / p.hw4_scale[0], o[1] / p.hw4_scale[1], o[2] / p.hw4_scale[2], o[3] / p.hw4_scale[3]);
     }
     ra.flush(p.range);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(203);
     if (tid < BM) {
         const int64_t pix = pix_base + (int64_t)(tid >> 5) * rstride + (tid & 31);
         if (pix < p.M && (tid >> 5) < rows_valid && (tid & 31) < cols_valid) {
@@ -279,10 +280,11 @@ __device__ __forceinline__ void gemm2_tail(const GemmParams& p, const int tb, ch
         load(kt, f);
         mma(f);
     }
+    STA_SKEW_EPI(215);
     float* red = reinterpret_cast<float*>(smem);    // [NW][16][64]
 #pragma unroll
     for (int r = 0; r < 16; ++r) red[(wave * 16 + r) * 64 + lane] = acc[r];
-    __syncthreads();
+    __syncthreads(); STA_SKEW(204);
     if (wave != 0) return;
 #pragma unroll 1
     for (int w = 1; w < NW; ++w) {
@@ -302,6 +304,7 @@ template <bool SPLIT, int AMODE, int EPI, int BM, int BN, int WAVES_M, int WAVES
 __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_id_in, const GEO& geo = GEO{}) {
     constexpr bool VL = !std::is_same<GEO, NoGeo>::value;
     static_assert(!VL || AMODE == A_CONV3 || EPI == EPI_CONVT, "the varlen form exists where geometry is decoded");
+    STA_SKEW_ENTRY(208);
     constexpr int ABL = ABL_ | (NSTG > 2 ? STA_RING_ABL : 0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = WAVES_M * WAVES_N;
@@ -499,7 +502,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
     } else {
         issue_tile(kt0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __syncthreads(); STA_SKEW(205);
         if (p.stamps) st1 = __builtin_amdgcn_s_memrealtime();
     }
 
@@ -701,7 +704,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         // last NSTG - 1 tiles (nothing left to issue, fewer tiles outstanding) are peeled.
         int cur = 0, nxt = NSTG - 1, kt = 0;
         for (; kt + NSTG - 1 < nkt; ++kt) {
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NSTG - 2) * GPW) : "memory");      // tile kt landed; every wave finished tile kt-1
+            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((NSTG - 2) * GPW) : "memory"); STA_SKEW(209);      // tile kt landed; every wave finished tile kt-1
             if (p.stamps && kt == 0) st1 = __builtin_amdgcn_s_memrealtime();
             if (!(ABL & 1)) issue_tile(kt0 + kt + NSTG - 1, nxt);                                    // into the stage tile kt-1 left
             compute_tile(cur, kt, relu_c);
@@ -710,10 +713,10 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         }
         for (; kt < nkt; ++kt) {
             const int rem = nkt - 1 - kt;                                  // younger tiles of this wave still outstanding: 0 .. NSTG-2
-            if (rem == 0) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-            else if (rem == 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(GPW) : "memory");
-            else if (rem == 2) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * GPW) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(3 * GPW) : "memory");
+            if (rem == 0) { asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory"); STA_SKEW(210); }
+            else if (rem == 1) { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(GPW) : "memory"); STA_SKEW(211); }
+            else if (rem == 2) { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(2 * GPW) : "memory"); STA_SKEW(212); }
+            else { asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(3 * GPW) : "memory"); STA_SKEW(213); }
             if (p.stamps && kt == 0) st1 = __builtin_amdgcn_s_memrealtime();
             compute_tile(cur, kt, relu_c);
             cur = cur + 1 == NSTG ? 0 : cur + 1;
@@ -724,7 +727,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
             if (kt + 1 < nkt && !(ABL & 1) && !late_dma) issue_tile(kt0 + kt + 1, cur ^ 1);
             compute_tile(cur, kt, relu_c);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
+            __syncthreads(); STA_SKEW(206);
         }
     }
     };
@@ -756,6 +759,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         asm volatile("" ::"v"(acc[MT - 1][NT - 1][15]), "v"(acc[0][0][0]) : "memory");
         st2 = __builtin_amdgcn_s_memrealtime();
     }
+    STA_SKEW_EPI(214);
     if constexpr (EPI == EPI_HEAD) {
         if constexpr (BN == 128) {
             if constexpr (TRN) head_epilogue_t<BM, MT, WM, WAVES_N>(p, acc, m0, 32, BM / 32, 32, wm, wn, tid, smem);
@@ -766,7 +770,7 @@ __device__ __forceinline__ void gemm2_body(const GemmParams& p, const int block_
         // (two stages: every wave is past the last barrier of the main loop.  The ring form has no barrier behind its last K tile:
         //  one here, so that no wave still reads fragments from the memory another wave's epilogue is about to reuse)
         char* const wave_lds = ((EPI == EPI_QKV || EPI == EPI_GELU || EPI == EPI_F16) && NW * EPI_LDS_BYTES <= NSTG * STAGE) ? smem + wave * EPI_LDS_BYTES : nullptr;
-        if (RING && wave_lds != nullptr) __syncthreads();
+        if (RING && wave_lds != nullptr) { __syncthreads(); STA_SKEW(207); }
 #pragma unroll
         for (int j = 0; j < NT; ++j)
 #pragma unroll

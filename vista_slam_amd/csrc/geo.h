@@ -9,6 +9,7 @@
 //   compute_geo_valid_mask_batched(depth1, depth2, K1, K2, T1, T2, q) -> masks, err < torch.quantile(err of the whole batch, q)
 //   compute_local_pointclouds / depth_from_pointcloud_dot_batched     -> element-wise behind one K^-1 per view
 #pragma once
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 struct GeoPair { float A[9]; float t[3]; float K[9]; float pad[3]; };      // 96 bytes per warp
 static_assert(sizeof(GeoPair) == 96, "GeoPair layout");
@@ -158,9 +159,9 @@ __global__ void sym_pairs_kernel(const float* K, const float* rel, int P, GeoPai
 // one 8-bit digit of the block's keys into the slot's global histogram: LDS atomics, then one global add per non-empty bin
 __device__ inline void geo_hist_block(unsigned* lds, bool active, unsigned digit, unsigned* ghist) {
     lds[threadIdx.x] = 0;                                  // (256 threads = 256 bins)
-    __syncthreads();
+    __syncthreads(); STA_SKEW(800);
     if (active) atomicAdd(&lds[digit], 1u);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(801);
     const unsigned c = lds[threadIdx.x];
     if (c) atomicAdd(&ghist[threadIdx.x], c);
 }
@@ -169,6 +170,7 @@ __device__ inline void geo_hist_block(unsigned* lds, bool active, unsigned digit
 // valid NaN errors per slot and takes the first radix pass (top byte) on the way
 __global__ __launch_bounds__(256) void geo_warp_kernel(const float* depths, const GeoPair* pairs, int H, int W, unsigned* err,
                                                        int* state, unsigned* hist0) {
+    STA_SKEW_ENTRY(807);
     __shared__ unsigned lds[256];
     __shared__ int wc[8];
     const int dir = blockIdx.y, slot = blockIdx.z * 2 + dir, hw = H * W, pix = blockIdx.x * 256 + threadIdx.x;
@@ -205,6 +207,7 @@ __global__ __launch_bounds__(256) void geo_warp_kernel(const float* depths, cons
 
 // radix pass `pass` (1..3): keys whose top 8 * pass bits equal the prefix chosen so far
 __global__ __launch_bounds__(256) void geo_hist_kernel(const unsigned* err, int hw, const int* state, int pass, unsigned* hist) {
+    STA_SKEW_ENTRY(808);
     __shared__ unsigned lds[256];
     const int slot = blockIdx.y, pix = blockIdx.x * 256 + threadIdx.x;
     const unsigned prefix = (unsigned)state[slot * GEO_STATE + GEO_PREFIX];
@@ -282,6 +285,7 @@ __global__ void geo_q_pairs_kernel(const float* K1, const float* K2, const float
 // zero, so (-1, 0) lands on column 0.  The float comparisons fail for NaN / inf / beyond-int32 values: never an index.
 __global__ __launch_bounds__(256) void geo_q_warp_kernel(const float* depth1, const float* depth2, const GeoPair* pairs, int H, int W,
                                                          int gx, unsigned* err, int* state, unsigned* hist0) {
+    STA_SKEW_ENTRY(809);
     __shared__ unsigned lds[256];
     __shared__ int wc[8];
     const int b = blockIdx.x / gx, hw = H * W, pix = (blockIdx.x - b * gx) * 256 + threadIdx.x;
@@ -316,11 +320,12 @@ __global__ __launch_bounds__(256) void geo_q_warp_kernel(const float* depth1, co
 // radix pass `pass` (1..3) for both ranks at once: hist [2, 256], rank r counts the keys under its own prefix.  A workgroup takes
 // 256 * GQ_PER consecutive keys, so the number of global adds per pass stays small next to the number of keys.
 __global__ __launch_bounds__(256) void geo_q_hist_kernel(const unsigned* err, int total, const int* state, int pass, unsigned* hist) {
+    STA_SKEW_ENTRY(805);
     __shared__ unsigned lds[512];
     const unsigned p0 = (unsigned)state[GQ_PREFIX], p1 = (unsigned)state[GQ_PREFIX + 1];
     const int hb = 32 - 8 * pass;
     lds[threadIdx.x] = 0; lds[256 + threadIdx.x] = 0;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(802);
     const int base = blockIdx.x * (256 * GQ_PER) + threadIdx.x;
 #pragma unroll
     for (int q = 0; q < GQ_PER; ++q) {
@@ -331,7 +336,7 @@ __global__ __launch_bounds__(256) void geo_q_hist_kernel(const unsigned* err, in
         if (((bits ^ p0) >> hb) == 0) atomicAdd(&lds[digit], 1u);
         if (((bits ^ p1) >> hb) == 0) atomicAdd(&lds[256 + digit], 1u);
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(803);
     const unsigned c0 = lds[threadIdx.x], c1 = lds[256 + threadIdx.x];
     if (c0) atomicAdd(&hist[threadIdx.x], c0);
     if (c1) atomicAdd(&hist[256 + threadIdx.x], c1);
@@ -343,6 +348,7 @@ __global__ __launch_bounds__(256) void geo_q_hist_kernel(const unsigned* err, in
 // multiply-add per branch, w < 0.5 ? fma(w, b - a, a) : fma(-(b - a), 1 - w, b).  NaN when a valid error is NaN (quantile
 // propagates it) or when no pixel is valid (torch raises; the caller reads count_out).
 __global__ __launch_bounds__(128) void geo_q_pick_kernel(const unsigned* hist, int pass, float q, int* st, float* thres_out, int* count_out) {
+    STA_SKEW_ENTRY(806);
     __shared__ unsigned ab[2];
     const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int count = st[GQ_COUNT];
@@ -375,7 +381,7 @@ __global__ __launch_bounds__(128) void geo_q_pick_kernel(const unsigned* hist, i
         ab[r] = np;
     }
     if (pass != 3) return;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(804);
     if (threadIdx.x == 0) {
         const float a = __uint_as_float(ab[0]), b = __uint_as_float(ab[1]);
         const float w = rank - floorf(rank), diff = b - a;

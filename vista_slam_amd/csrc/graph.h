@@ -5,6 +5,7 @@
 // product is pgo.h's pgo_mul, the one sta_sim3_op runs.
 #include "sta_common.h"
 #include "pgo.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 #define GRAPH_CHUNK 2048          // map elements per workgroup of graph_reduce_kernel / graph_export_kernel (whatever H * W is)
 #define GRAPH_THREADS 256         // 4 waves; a lane takes 4 consecutive floats per pass, a chunk is at most 2 passes
@@ -28,6 +29,7 @@ struct GraphReduceArgs {
 // Every term is float64 from the fp32 inputs; a lane sums its elements in ascending order, a wave by a shuffle tree, the four waves in
 // order through LDS; the chunk's partial is STORED (graph_link_kernel sums the chunks in ascending order).
 __global__ __launch_bounds__(GRAPH_THREADS) void graph_reduce_kernel(const GraphReduceArgs a) {
+    STA_SKEW_ENTRY(1201);
     const GraphNodeJob j = a.job[blockIdx.y];
     const int chunk = blockIdx.x, t = threadIdx.x;
     const int base = chunk * GRAPH_CHUNK;
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(GRAPH_THREADS) void graph_reduce_kernel(const Graph
         for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
         if ((t & 63) == 0) part[t >> 6][q] = v;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1200);
     if (t < 4) {
         double v = part[0][t];
         for (int w = 1; w < GRAPH_THREADS / 64; ++w) v += part[w][t];

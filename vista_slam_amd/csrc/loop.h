@@ -16,6 +16,7 @@
 //   bow_reduce_kernel     one workgroup: word ids -> sorted distinct words, counts, weighted and L1-normalised values
 //   bow_score_kernel      one wave per database row: the L1 score against the query, binary search over the row's words
 #pragma once
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 #define ORB_MAX_LEVELS 8
 #define ORB_MAX_FEATURES 4096
@@ -75,6 +76,7 @@ __global__ __launch_bounds__(256) void orb_resize_kernel(const uint8_t* __restri
 // grid (ceil(W_0 / 16), ceil(H_0 / 16), built): the workgroups past a smaller level's extent leave at once.  score = 0 for a pixel
 // nearer than 3 to the border and for a non-corner.
 __global__ __launch_bounds__(256) void orb_fast_kernel(const uint8_t* __restrict__ img, const OrbLevels lv, uint8_t* __restrict__ score) {
+    STA_SKEW_ENTRY(1010);
     __shared__ uint8_t t[22][23];
     const int l = blockIdx.z, H = lv.h[l], W = lv.w[l], x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
     if (x0 >= W || y0 >= H) return;
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(256) void orb_fast_kernel(const uint8_t* __restrict
         const int ly = i / 22, lx = i - ly * 22, y = y0 - 3 + ly, x = x0 - 3 + lx;
         t[ly][lx] = (y >= 0 && y < H && x >= 0 && x < W) ? im[(size_t)y * W + x] : (uint8_t)0;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1000);
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, x = x0 + tx, y = y0 + ty;
     if (x >= W || y >= H) return;
     int s = 0;
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(256) void orb_harris_kernel(const uint8_t* __restri
 // lower pixel index); the candidates of rank < n_l go to slot sel_off[l] + rank
 __global__ __launch_bounds__(256) void orb_rank_kernel(const OrbLevels lv, const int* __restrict__ ncand, const long long* __restrict__ candR,
                                                        const int* __restrict__ candP, long long* __restrict__ selR, int* __restrict__ selP) {
+    STA_SKEW_ENTRY(1011);
     __shared__ long long sR[256];
     __shared__ int sP[256];
     const int l = blockIdx.y, M = min(ncand[l], lv.cand_cap[l]), i = blockIdx.x * 256 + threadIdx.x;
@@ -190,10 +193,10 @@ __global__ __launch_bounds__(256) void orb_rank_kernel(const OrbLevels lv, const
     const int myP = i < M ? cP[i] : 0;
     int rank = 0;
     for (int base = 0; base < M; base += 256) {
-        __syncthreads();
+        __syncthreads(); STA_SKEW(1001);
         const int j = base + threadIdx.x;
         if (j < M) { sR[threadIdx.x] = cR[j]; sP[threadIdx.x] = cP[j]; }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(1002);
         const int cnt = min(256, M - base);
         for (int k = 0; k < cnt; ++k) rank += (sR[k] > myR || (sR[k] == myR && sP[k] < myP)) ? 1 : 0;
     }
@@ -202,6 +205,7 @@ __global__ __launch_bounds__(256) void orb_rank_kernel(const OrbLevels lv, const
 
 // same grid as orb_fast_kernel: B = (sum_ab k[a] k[b] ext(y + a - 3, x + b - 3) + 2^15) >> 16, reflect-101
 __global__ __launch_bounds__(256) void orb_blur_kernel(const uint8_t* __restrict__ img, const OrbLevels lv, uint8_t* __restrict__ blur) {
+    STA_SKEW_ENTRY(1012);
     __shared__ uint8_t t[22][23];
     __shared__ int hs[22][17];
     const int l = blockIdx.z, H = lv.h[l], W = lv.w[l], x0 = blockIdx.x * 16, y0 = blockIdx.y * 16;
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(256) void orb_blur_kernel(const uint8_t* __restrict
         const int ly = i / 22, lx = i - ly * 22;
         t[ly][lx] = im[(size_t)flow_reflect(y0 - 3 + ly, H) * W + flow_reflect(x0 - 3 + lx, W)];
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1003);
     const int k[7] = {18, 33, 49, 56, 49, 33, 18};
     for (int i = threadIdx.x; i < 22 * 16; i += 256) {             // rows first: exact integers, so the order of the two passes is free
         const int ly = i >> 4, lx = i & 15;
@@ -220,7 +224,7 @@ __global__ __launch_bounds__(256) void orb_blur_kernel(const uint8_t* __restrict
         for (int b = 0; b < 7; ++b) s += k[b] * (int)t[ly][lx + b];
         hs[ly][lx] = s;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1004);
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, x = x0 + tx, y = y0 + ty;
     if (x >= W || y >= H) return;
     int s = 0;
@@ -345,19 +349,20 @@ __global__ __launch_bounds__(1024) void bow_reduce_kernel(const int* __restrict_
                                                           int* __restrict__ words, int* __restrict__ counts, double* __restrict__ vals,
                                                           int* __restrict__ n_words) {
 #pragma clang fp contract(off)
+    STA_SKEW_ENTRY(1013);
     __shared__ int key[ORB_MAX_ROWS], sorted[ORB_MAX_ROWS], endv[ORB_MAX_ROWS];
     __shared__ int wcount[16];
     __shared__ double wsum[16];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     for (int i = t; i < n_cap; i += 1024) key[i] = wid[i];
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1005);
     for (int i = t; i < n_cap; i += 1024) {
         const int my = key[i];
         int r = 0;
         for (int j = 0; j < n_cap; ++j) { const int kj = key[j]; r += (kj < my || (kj == my && j < i)) ? 1 : 0; }
         sorted[r] = my;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1006);
     // thread t owns the consecutive elements [lo, hi)
     const int chunk = (n_cap + 1023) / 1024, lo = min(t * chunk, n_cap), hi = min(lo + chunk, n_cap);
     int heads = 0;
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(1024) void bow_reduce_kernel(const int* __restrict_
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int up = __shfl_up(incl, o); if (lane >= o) incl += up; }
     if (lane == 63) wcount[wave] = incl;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1007);
     int before = 0, nw = 0;
 #pragma unroll
     for (int w = 0; w < 16; ++w) { if (w < wave) before += wcount[w]; nw += wcount[w]; }
@@ -377,7 +382,7 @@ __global__ __launch_bounds__(1024) void bow_reduce_kernel(const int* __restrict_
         if (i == 0 || sorted[i - 1] != s) { key[seen] = i; ++seen; }                      // key is free since the sort: start of run `seen`
         if (i == n_cap - 1 || sorted[i + 1] != s) endv[seen - 1] = i + 1;                 // a tail's run is the last head's at or before it
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1008);
     double part = 0.0;
     for (int s = t; s < nw; s += 1024) {
         const int c = endv[s] - key[s], w = sorted[key[s]];
@@ -387,7 +392,7 @@ __global__ __launch_bounds__(1024) void bow_reduce_kernel(const int* __restrict_
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
     if (lane == 0) wsum[wave] = part;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1009);
     double norm = 0.0;
 #pragma unroll
     for (int w = 0; w < 16; ++w) norm += wsum[w];

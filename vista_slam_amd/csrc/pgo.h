@@ -4,6 +4,7 @@
 // throughout.  The Gauss-Newton matrix is a graph Laplacian with 7x7 weights: H x = per edge S_e (x_b - x_a), per node a signed sum over
 // its incident half-edges in ascending edge order.  Nothing is assembled, and there is no floating-point atomic in this file.
 #include "sta_common.h"
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 // ---- the constants of the contract (the same names in tests/pgo_cases.py) ----
 #define PGO_PHI_SERIES 0.25      // |phi| below: W's A and B from the moment series (above: the closed forms)
@@ -156,6 +157,7 @@ __device__ __forceinline__ bool pgo_edge(const int* __restrict__ edges, const un
 // ONE workgroup.  off [n+1], inc [off[n]] = edge * 2 + side (side 0: the node is a), ascending within a node; tmp: 2 x 2E ints.
 __global__ __launch_bounds__(PGO_THREADS) void pgo_index_kernel(const int* __restrict__ edges, const unsigned char* __restrict__ opt, int n, int E, int* tmp,
                                                                  int* off, int* inc, int* status) {
+    STA_SKEW_ENTRY(1113);
     __shared__ int cur[PGO_MAX_NODES];
     __shared__ int part[PGO_THREADS];
     __shared__ int s_status;
@@ -163,38 +165,38 @@ __global__ __launch_bounds__(PGO_THREADS) void pgo_index_kernel(const int* __res
     int* tmp_half = tmp; int* tmp_node = tmp + 2 * (size_t)E;
     for (int k = tid; k < n; k += PGO_THREADS) cur[k] = 0;
     if (tid == 0) s_status = 0;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1100);
     for (int e = tid; e < E; e += PGO_THREADS) {
         int a, b; bool inr;
         const bool act = pgo_edge(edges, opt, n, e, a, b, inr);
         if (!inr) atomicOr(&s_status, PGO_ST_INDEX);
         if (act) { if (opt[a]) atomicAdd(&cur[a], 1); if (opt[b]) atomicAdd(&cur[b], 1); }
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1101);
     // exclusive scan: 8 consecutive nodes per thread, then the 1024 partial sums
     const int per = PGO_MAX_NODES / PGO_THREADS, k0 = tid * per;
     int sum = 0;
     for (int j = 0; j < per; ++j) if (k0 + j < n) sum += cur[k0 + j];
     part[tid] = sum;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1102);
     for (int s = 1; s < PGO_THREADS; s <<= 1) {
         const int add = tid >= s ? part[tid - s] : 0;
-        __syncthreads();
+        __syncthreads(); STA_SKEW(1103);
         part[tid] += add;
-        __syncthreads();
+        __syncthreads(); STA_SKEW(1104);
     }
     int base = part[tid] - sum;
     const int total = part[PGO_THREADS - 1];
     for (int j = 0; j < per; ++j) if (k0 + j < n) { const int d = cur[k0 + j]; cur[k0 + j] = base; off[k0 + j] = base; base += d; }
     if (tid == 0) { off[n] = total; *status = s_status; }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1105);
     for (int e = tid; e < E; e += PGO_THREADS) {
         int a, b; bool inr;
         if (!pgo_edge(edges, opt, n, e, a, b, inr)) continue;
         if (opt[a]) { const int p = atomicAdd(&cur[a], 1); tmp_half[p] = 2 * e; tmp_node[p] = a; }
         if (opt[b]) { const int p = atomicAdd(&cur[b], 1); tmp_half[p] = 2 * e + 1; tmp_node[p] = b; }
     }
-    __syncthreads();          // workgroup-scope release / acquire: tmp and off were written by other threads of this workgroup
+    __syncthreads(); STA_SKEW(1106);          // workgroup-scope release / acquire: tmp and off were written by other threads of this workgroup
     // a list's entries are distinct (a != b): the rank of an entry is the number of smaller ones
     for (int i = tid; i < total; i += PGO_THREADS) {
         const int k = tmp_node[i], v = tmp_half[i], lo = off[k], hi = cur[k];
@@ -302,16 +304,17 @@ __device__ __forceinline__ double pgo_block_sum(double v, double* red) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     const int tid = threadIdx.x;
     if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1107);
     double s = 0.0;
     for (int i = 0; i < PGO_THREADS / 64; ++i) s += red[i];
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1108);
     return s;
 }
 
 // ONE workgroup: f = the sum of c over the edges (thread t takes t, t + 1024, ... in ascending order, then the fixed tree);
 // rec = {f, status}: PGO_ST_NONFINITE for a non-finite f, ored with *idx_status (may be null)
 __global__ __launch_bounds__(PGO_THREADS) void pgo_cost_kernel(const double* __restrict__ c, int E, const int* __restrict__ idx_status, double* rec) {
+    STA_SKEW_ENTRY(1115);
     __shared__ double red[PGO_THREADS / 64];
     double s = 0.0;
     for (int e = threadIdx.x; e < E; e += PGO_THREADS) s += c[e];
@@ -354,6 +357,7 @@ __global__ __launch_bounds__(PGO_THREADS) void pgo_solve_kernel(const int* __res
                                                                  const int* __restrict__ inc, const double* __restrict__ S, const double* __restrict__ g,
                                                                  const double* __restrict__ blocks, int n, int E, double radius, double dmin, double dmax,
                                                                  double rtol, int max_iter, double* ws, double* x, double* stats) {
+    STA_SKEW_ENTRY(1114);
     __shared__ double red[PGO_THREADS / 64];
     const int tid = threadIdx.x;
     double* L = ws; double* Dk = L + (size_t)n * 49; double* r = Dk + (size_t)n * 7; double* z = r + (size_t)n * 7;
@@ -387,7 +391,7 @@ __global__ __launch_bounds__(PGO_THREADS) void pgo_solve_kernel(const int* __res
                 }
             for (int i = 0; i < 7; ++i) de[(size_t)e * 7 + i] = o[i];
         }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(1109);
         double part = 0.0;
         for (int k = tid; k < n; k += PGO_THREADS) {
             if (!opt[k]) continue;
@@ -463,7 +467,7 @@ __global__ __launch_bounds__(PGO_THREADS) void pgo_solve_kernel(const int* __res
             s_rz += rk[i] * zk[i]; s_rr += rk[i] * rk[i];
         }
     }
-    bad = __syncthreads_or(bad);
+    bad = __syncthreads_or(bad); STA_SKEW(1116);
     double rz = pgo_block_sum(s_rz, red);
     const double gn = sqrt(pgo_block_sum(s_rr, red));
     double rn = gn;
@@ -500,18 +504,18 @@ __global__ __launch_bounds__(PGO_THREADS) void pgo_solve_kernel(const int* __res
                 for (int i = 0; i < 7; ++i) p[(size_t)k * 7 + i] = z[(size_t)k * 7 + i] + beta * p[(size_t)k * 7 + i];
             }
             rz = rz_new;
-            __syncthreads();
+            __syncthreads(); STA_SKEW(1110);
         }
         if (!conv) status |= PGO_ST_MAXITER;
     }
     // the model decrease -2 d.g - d.H d: one more product, without the damping, on p = x
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1111);
     double s_xg = 0.0;
     for (int k = tid; k < n; k += PGO_THREADS) {
         if (!opt[k]) continue;
         for (int i = 0; i < 7; ++i) { const double xk = x[(size_t)k * 7 + i]; p[(size_t)k * 7 + i] = xk; s_xg += xk * g[(size_t)k * 7 + i]; }
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(1112);
     const double xHx = pgo_block_sum(product(false), red);
     const double xg = pgo_block_sum(s_xg, red);
     if (tid == 0) {

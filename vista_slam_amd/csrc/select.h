@@ -5,6 +5,7 @@
 //   patch_select_kernel        grid (B): one workgroup per entry thresholds (+ dilates) or radix-selects the top k, then compacts in order
 // Everything is integer arithmetic on the scores, so the result is defined bit for bit (tests/select_cases.py restates it in numpy).
 #pragma once
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 #define SEL_MAX_PATCHES 8192      // one entry's scores (32 KiB) + two flag grids (16 KiB) stay in static LDS below 64 KiB
 #define SEL_MAX_MARGIN 8
@@ -89,7 +90,7 @@ __device__ __forceinline__ int sel_block_scan(int v, int* wsum) {
         if (lane >= o) v += u;
     }
     if (lane == 63) wsum[wave] = v;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(600);
     for (int w = 0; w < wave; ++w) v += wsum[w];
     return v;
 }
@@ -104,6 +105,7 @@ __device__ __forceinline__ int sel_block_scan(int v, int* wsum) {
 __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int rule, int min_score, int margin, const int32_t* __restrict__ score,
                                                            int64_t* __restrict__ index, int64_t* __restrict__ pos, int32_t* __restrict__ n_sel,
                                                            int32_t* __restrict__ window) {
+    STA_SKEW_ENTRY(609);
     __shared__ int sc[SEL_MAX_PATCHES];
     __shared__ unsigned char flag[SEL_MAX_PATCHES], tmp[SEL_MAX_PATCHES];
     __shared__ int hist[256];
@@ -117,23 +119,23 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int r
         unsigned prefix = 0u, mask = 0u; int krem = g.k[b];
         for (int shift = 24; shift >= 0; shift -= 8) {
             hist[t] = 0;
-            __syncthreads();
+            __syncthreads(); STA_SKEW(601);
             for (int i = t; i < N; i += 256) {
                 const int s = sc[i];
                 if (((unsigned)s & mask) == prefix) atomicAdd(&hist[(s >> shift) & 255], 1);
             }
-            __syncthreads();
+            __syncthreads(); STA_SKEW(602);
             const int d = 255 - t, v = hist[d];               // thread t owns digit 255 - t: the scan runs from the largest digit down
             const int incl = sel_block_scan(v, wsum);
             if (incl - v < krem && krem <= incl) { pick[0] = d; pick[1] = krem - (incl - v); }
-            __syncthreads();
+            __syncthreads(); STA_SKEW(603);
             prefix |= (unsigned)pick[0] << shift; mask |= 255u << shift; krem = pick[1];
         }
         T = (int)prefix; q = krem;
     } else {
         for (int i = t; i < N; i += 256) flag[i] = s_in[i] >= min_score;
         if (margin > 0) {
-            __syncthreads();
+            __syncthreads(); STA_SKEW(604);
             for (int i = t; i < N; i += 256) {
                 const int y = i / wp, x = i - y * wp;
                 const int x0 = x - margin > 0 ? x - margin : 0, x1 = x + margin < wp - 1 ? x + margin : wp - 1;
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int r
                 for (int xx = x0; xx <= x1; ++xx) f |= flag[y * wp + xx];
                 tmp[i] = f;
             }
-            __syncthreads();
+            __syncthreads(); STA_SKEW(605);
             for (int i = t; i < N; i += 256) {
                 const int y = i / wp, x = i - y * wp;
                 const int y0 = y - margin > 0 ? y - margin : 0, y1 = y + margin < hp - 1 ? y + margin : hp - 1;
@@ -150,7 +152,7 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int r
                 flag[i] = f;
             }
         }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(606);
     }
     int64_t* idx = index + off;
     int64_t* ps = pos + 2 * (size_t)off;
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int r
         }
         const unsigned long long bg = __ballot(gt), be = __ballot(eq);
         if (lane == 0) wtot[par][wave] = __popcll(bg) | (__popcll(be) << 16);
-        __syncthreads();
+        __syncthreads(); STA_SKEW(607);
         int pre = 0, tot = 0;
         for (int w = 0; w < 4; ++w) { const int v = wtot[par][w]; tot += v; if (w < wave) pre += v; }
         const int eq_before = base_eq + (pre >> 16) + __popcll(be & below);
@@ -188,7 +190,7 @@ __global__ __launch_bounds__(256) void patch_select_kernel(const SelGeo g, int r
         ymin = a < ymin ? a : ymin; ymax = c > ymax ? c : ymax; xmin = d < xmin ? d : xmin; xmax = e > xmax ? e : xmax;
     }
     if (lane == 0) { box[wave][0] = ymin; box[wave][1] = ymax; box[wave][2] = xmin; box[wave][3] = xmax; }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(608);
     if (t == 0) {
         for (int w = 1; w < 4; ++w) {
             ymin = box[w][0] < ymin ? box[w][0] : ymin; ymax = box[w][1] > ymax ? box[w][1] : ymax;

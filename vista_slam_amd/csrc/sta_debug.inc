@@ -1052,3 +1052,34 @@ extern "C" int sta_debug_workspace_tail(sta_handle* h, void* stream, int byte, i
     *n_bad = (int64_t)host[0]; *first_bad = host[0] ? (int64_t)host[1] : -1;
     return 0;
 }
+
+#ifdef STA_WAVE_SKEW      // libsta_mi355_skew.so only (sta_skew.h; tests/test_skew_gpu.py)
+// The wave-skew configuration of THIS library's kernels.  wave_mask: bit w = wave w of every workgroup is delayed (bit 16: measure the
+// barrier intervals instead, nothing is delayed); point_lo / point_hi: bit (id & 63) selects skew point id; repeat: s_sleep 127 per
+// hit.  Resets the hit counter, the largest interval and the measuring mode's slots.  Synchronous on the null stream.
+extern "C" int sta_debug_set_wave_skew(unsigned wave_mask, unsigned point_lo, unsigned point_hi, unsigned repeat) {
+    REQUIRE(wave_mask <= 0x1ffffu && repeat <= 4096u, "sta_debug_set_wave_skew: bad argument");
+    StaSkewCfg c;
+    c.wave_mask = wave_mask; c.point_lo = point_lo; c.point_hi = point_hi; c.repeat = repeat; c.hits = 0; c.max_gap = 0;
+    memset(c.seen, 0, sizeof(c.seen));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_sta_skew), &c, sizeof(c)));
+    void* last = nullptr;
+    HIPCHK(hipGetSymbolAddress(&last, HIP_SYMBOL(g_sta_skew_last)));
+    HIPCHK(hipMemset(last, 0, sizeof(unsigned long long) * STA_SKEW_SLOTS));
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+// out[34]: out[0] skew points hit by selected waves since the last sta_debug_set_wave_skew; out[1] the largest interval between two
+// consecutive points of one wave in the measuring mode, in ticks of the 100 MHz clock; out[2 .. 33] bit id = point id was hit (ids
+// below 2048).  Synchronous on the null stream.
+extern "C" int sta_debug_wave_skew_hits(unsigned long long* out) {
+    REQUIRE(out, "sta_debug_wave_skew_hits: null output");
+    StaSkewCfg c;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpyFromSymbol(&c, HIP_SYMBOL(g_sta_skew), sizeof(c)));
+    out[0] = c.hits; out[1] = c.max_gap;
+    for (int w = 0; w < STA_SKEW_IDS / 64; ++w) out[2 + w] = (unsigned long long)c.seen[2 * w] | ((unsigned long long)c.seen[2 * w + 1] << 32);
+    return 0;
+}
+#endif

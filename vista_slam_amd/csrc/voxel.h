@@ -8,6 +8,7 @@
 //   vox_row_count_kernel / vox_row_emit_kernel    min_points: ordered compaction of the voxels to output rows (cloud_scan_kernel again)
 //   vox_reduce_kernel / vox_reduce_long_kernel    per-row fp64 sums in a fixed order, means, counts, indices, inverse, PLY records
 #pragma once
+#include "sta_skew.h"       // STA_SKEW points: nothing unless -DSTA_WAVE_SKEW (libsta_mi355_skew.so)
 
 #define VOX_TILE 1024          // keys per workgroup and sort pass: four chunks of 256
 #define VOX_LONG 1024          // a voxel of more points than this is reduced by a whole workgroup of 1024 threads, not by one wave
@@ -32,6 +33,7 @@ __device__ __forceinline__ bool vox_finite3(float x, float y, float z) {
 // Bounds.  min / max are exact and order-free, the dropped count is an integer: the result does not depend on the grid.
 // part [gridDim.x][8] = {min xyz, max xyz, dropped (int bits), 0}
 __global__ __launch_bounds__(256) void vox_bounds_kernel(const float* __restrict__ pts, int M, float* __restrict__ part) {
+    STA_SKEW_ENTRY(714);
     const float inf = __builtin_huge_valf();
     float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
     int dropped = 0;
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void vox_bounds_kernel(const float* __restrict
         for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
         red[wave][6] = __int_as_float(dropped);
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(700);
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) {
             for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], red[w][a]); mx[a] = fmaxf(mx[a], red[w][3 + a]); }
@@ -67,6 +69,7 @@ __global__ __launch_bounds__(256) void vox_bounds_kernel(const float* __restrict
 }
 // one workgroup of 256 threads folds the n <= 1024 partial rows to out[8]
 __global__ __launch_bounds__(256) void vox_bounds_final_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
+    STA_SKEW_ENTRY(715);
     const float inf = __builtin_huge_valf();
     float mn[3] = {inf, inf, inf}, mx[3] = {-inf, -inf, -inf};
     int dropped = 0;
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(256) void vox_bounds_final_kernel(const float* __re
         for (int a = 0; a < 3; ++a) { red[wave][a] = mn[a]; red[wave][3 + a] = mx[a]; }
         red[wave][6] = __int_as_float(dropped);
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(701);
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w) {
             for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], red[w][a]); mx[a] = fmaxf(mx[a], red[w][3 + a]); }
@@ -120,20 +123,22 @@ __global__ __launch_bounds__(256) void vox_key_kernel(const float* __restrict__ 
 // hist [256][nblk]: digit-major, so that one exclusive scan along a row and one over the 256 row totals give every workgroup the
 // first output position of each of its digits.
 __global__ __launch_bounds__(256) void vox_hist_kernel(const unsigned long long* __restrict__ key, int M, int shift, int nblk, int* __restrict__ hist) {
+    STA_SKEW_ENTRY(716);
     __shared__ int h[256];
     h[threadIdx.x] = 0;
-    __syncthreads();
+    __syncthreads(); STA_SKEW(702);
     const int base = blockIdx.x * VOX_TILE;
 #pragma unroll
     for (int c = 0; c < VOX_TILE / 256; ++c) {
         const int i = base + c * 256 + threadIdx.x;
         if (i < M) atomicAdd(&h[(int)(key[i] >> shift) & 255], 1);         // integer LDS atomic: the counts do not depend on the order
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(703);
     hist[(size_t)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
 }
 // grid (256): workgroup d scans row d of hist in place (exclusive) in chunks of 256 with a carried base, total -> dtot[d]
 __global__ __launch_bounds__(256) void vox_hist_scan_kernel(int* __restrict__ hist, int nblk, int* __restrict__ dtot) {
+    STA_SKEW_ENTRY(717);
     __shared__ int wsum[4], tot;
     int* row = hist + (size_t)blockIdx.x * nblk;
     int run = 0;
@@ -143,9 +148,9 @@ __global__ __launch_bounds__(256) void vox_hist_scan_kernel(int* __restrict__ hi
         const int incl = sel_block_scan(v, wsum);
         if (i < nblk) row[i] = run + incl - v;
         if (threadIdx.x == 255) tot = incl;
-        __syncthreads();
+        __syncthreads(); STA_SKEW(704);
         run += tot;
-        __syncthreads();              // wsum and tot are rewritten by the next chunk
+        __syncthreads(); STA_SKEW(705);              // wsum and tot are rewritten by the next chunk
     }
     if (threadIdx.x == 0) dtot[blockIdx.x] = run;
 }
@@ -155,6 +160,7 @@ __global__ __launch_bounds__(256) void vox_hist_scan_kernel(int* __restrict__ hi
 __global__ __launch_bounds__(256) void vox_scatter_kernel(const unsigned long long* __restrict__ kin, const int* __restrict__ iin, int M, int shift,
                                                           int nblk, const int* __restrict__ hist, const int* __restrict__ dtot,
                                                           unsigned long long* __restrict__ kout, int* __restrict__ iout) {
+    STA_SKEW_ENTRY(718);
     __shared__ int base[256], wcnt[4][256], wsum[4];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     {
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(256) void vox_scatter_kernel(const unsigned long lo
         base[t] = incl - v + hist[(size_t)t * nblk + blockIdx.x];
         wcnt[0][t] = 0; wcnt[1][t] = 0; wcnt[2][t] = 0; wcnt[3][t] = 0;
     }
-    __syncthreads();
+    __syncthreads(); STA_SKEW(706);
     const unsigned long long below = (1ull << lane) - 1ull;
     const int first = blockIdx.x * VOX_TILE;
     for (int c = 0; c < VOX_TILE / 256; ++c) {
@@ -180,16 +186,16 @@ __global__ __launch_bounds__(256) void vox_scatter_kernel(const unsigned long lo
         }
         const int rank = __popcll(peer & below);
         if (valid && rank == 0) wcnt[wave][d] = __popcll(peer);
-        __syncthreads();
+        __syncthreads(); STA_SKEW(707);
         if (valid) {
             int pos = base[d] + rank;
             for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
             kout[pos] = k; iout[pos] = iin[i];          // pos < M: the positions of a pass are a permutation of [0, M)
         }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(708);
         base[t] += wcnt[0][t] + wcnt[1][t] + wcnt[2][t] + wcnt[3][t];
         wcnt[0][t] = 0; wcnt[1][t] = 0; wcnt[2][t] = 0; wcnt[3][t] = 0;
-        __syncthreads();
+        __syncthreads(); STA_SKEW(709);
     }
 }
 
@@ -201,7 +207,7 @@ __device__ __forceinline__ int vox_block_rank(bool keep, int* wc) {
     const unsigned long long b = __ballot(keep);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) wc[wave] = __popcll(b);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(710);
     int rank = __popcll(b & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) rank += wc[w];
     return rank;
@@ -210,17 +216,19 @@ __device__ __forceinline__ void vox_block_count(bool keep, int* __restrict__ cou
     const unsigned long long b = __ballot(keep);
     __shared__ int wc[4];
     if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
+    __syncthreads(); STA_SKEW(711);
     if (threadIdx.x == 0) counts[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 // sorted position i < n (the kept points) starts a voxel iff its key differs from the one before
 __global__ __launch_bounds__(256) void vox_head_count_kernel(const unsigned long long* __restrict__ key, int n, int* __restrict__ counts) {
+    STA_SKEW_ENTRY(720);
     const int i = blockIdx.x * 256 + threadIdx.x;
     vox_block_count(i < n && (i == 0 || key[i] != key[i - 1]), counts);
 }
 // seg[u] = first sorted position of voxel u, seg[U] = n
 __global__ __launch_bounds__(256) void vox_head_emit_kernel(const unsigned long long* __restrict__ key, int n, const int64_t* __restrict__ offs, int nblk,
                                                             int* __restrict__ seg) {
+    STA_SKEW_ENTRY(721);
     __shared__ int wc[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool head = i < n && (i == 0 || key[i] != key[i - 1]);
@@ -231,6 +239,7 @@ __global__ __launch_bounds__(256) void vox_head_emit_kernel(const unsigned long 
 // voxel u < U (U = *n_vox, device memory) becomes an output row iff it holds at least min_points points
 __global__ __launch_bounds__(256) void vox_row_count_kernel(const int* __restrict__ seg, const int64_t* __restrict__ n_vox, int min_points,
                                                             int* __restrict__ counts) {
+    STA_SKEW_ENTRY(722);
     const int u = blockIdx.x * 256 + threadIdx.x;
     vox_block_count(u < (int)*n_vox && seg[u + 1] - seg[u] >= min_points, counts);
 }
@@ -239,6 +248,7 @@ __global__ __launch_bounds__(256) void vox_row_count_kernel(const int* __restric
 __global__ __launch_bounds__(256) void vox_row_emit_kernel(const int* __restrict__ seg, const int64_t* __restrict__ n_vox, int min_points,
                                                            const int64_t* __restrict__ offs, int2* __restrict__ rows, int* __restrict__ n_long,
                                                            int* __restrict__ long_rows) {
+    STA_SKEW_ENTRY(723);
     __shared__ int wc[4];
     const int u = blockIdx.x * 256 + threadIdx.x;
     int s = 0, e = 0;
@@ -308,6 +318,7 @@ __global__ __launch_bounds__(256) void vox_reduce_kernel(const VoxOut p) {
 }
 // one workgroup of 1024 threads per long row, walking the list
 __global__ __launch_bounds__(1024) void vox_reduce_long_kernel(const VoxOut p, const int* __restrict__ n_long, const int* __restrict__ long_rows) {
+    STA_SKEW_ENTRY(719);
     __shared__ double part[16][6];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = *n_long;
     for (int slot = blockIdx.x; slot < n; slot += gridDim.x) {
@@ -317,13 +328,13 @@ __global__ __launch_bounds__(1024) void vox_reduce_long_kernel(const VoxOut p, c
         vox_gather(p, se.x + (int)threadIdx.x, se.y, 1024, row, acc);
         vox_wave_sum(acc);
         if (lane == 0) { for (int q = 0; q < 6; ++q) part[wave][q] = acc[q]; }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(712);
         if (threadIdx.x == 0) {
 #pragma unroll 1
             for (int w = 1; w < 16; ++w) { for (int q = 0; q < 6; ++q) acc[q] += part[w][q]; }
             vox_write_row(p, row, se.x, se.y, acc);
         }
-        __syncthreads();
+        __syncthreads(); STA_SKEW(713);
     }
 }
 
