@@ -24,6 +24,7 @@ SURF_LIB_PATH = os.path.join(PKG, "libsta_surf.so")        # a sixth one (includ
 SIMP_LIB_PATH = os.path.join(PKG, "libsta_simp.so")        # a seventh one (include/sta_simp.h): `load_simp()`
 DIST_LIB_PATH = os.path.join(PKG, "libsta_dist.so")        # an eighth one (include/sta_dist.h): `load_dist()`
 RAY_LIB_PATH = os.path.join(PKG, "libsta_ray.so")          # a ninth one (include/sta_ray.h): `load_ray()`
+REG_LIB_PATH = os.path.join(PKG, "libsta_reg.so")          # a tenth one (include/sta_reg.h): `load_reg()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -299,6 +300,13 @@ RAY_SIGNATURES = {
     "sta_ray_occluded": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _d, _d, _vp, _vp, _vp]),
     "sta_ray_last_error": (C.c_char_p, []),
 }
+# include/sta_reg.h: libsta_reg.so, handle-free; a table of its own like the eight above (the index goes as four pointers, T_host and
+# pivot_host as host doubles)
+REG_SIGNATURES = {
+    "sta_reg_plan": (_i, [_i64, _i64, _i64p]),
+    "sta_reg_pass": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _dp, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "sta_reg_last_error": (C.c_char_p, []),
+}
 
 
 class StaTriIndex(C.Structure):
@@ -435,6 +443,7 @@ load_surf, check_surf = _satellite(SURF_LIB_PATH, SURF_SIGNATURES, "sta_surf_las
 load_simp, check_simp = _satellite(SIMP_LIB_PATH, SIMP_SIGNATURES, "sta_simp_last_error")              # include/sta_simp.h
 load_dist, check_dist = _satellite(DIST_LIB_PATH, DIST_SIGNATURES, "sta_tri_last_error")               # include/sta_dist.h: its names are sta_tri_*
 load_ray, check_ray = _satellite(RAY_LIB_PATH, RAY_SIGNATURES, "sta_ray_last_error")                   # include/sta_ray.h
+load_reg, check_reg = _satellite(REG_LIB_PATH, REG_SIGNATURES, "sta_reg_last_error")                   # include/sta_reg.h
 
 
 def use_test_hooks():

@@ -8,7 +8,7 @@
                                             #    csrc/sta_skew.h are live and the two sta_debug_*wave_skew* entries exist
                                             #    (tests/test_skew_gpu.py only; in every other library the points expand to nothing)
                                             #    vista_slam_amd/libsta_<name>.so       one handle-free library per row of SATELLITES:
-                                            #    and of ADDONS: a translation unit of its own (csrc/sta_<name>.hip) that exports
+                                            #    of ADDONS and of EXTENSIONS: a translation unit of its own (csrc/sta_<name>.hip) that exports
                                             #    include/sta_<name>.h
 
 A library's content hash covers its own files and the shared headers it includes, nothing of any other library: the product's hash does
@@ -54,10 +54,15 @@ SATELLITES = {
 ADDONS = {
     "ray": ("first hit and occlusion of rays over the triangle index of libsta_dist.so", ["sta_ray.hip", "ray.h", _inc("sta_ray.h")], []),
 }
+# ... and the libraries that came after that table of one was pinned in its turn (tests/test_ray_abi.py): the same rows, the same loops.
+# libsta_reg.so reads the index of libsta_dist.so through plain arguments, as libsta_ray.so does.
+EXTENSIONS = {
+    "reg": ("point-to-plane and point-to-point registration against the triangle index of libsta_dist.so", ["sta_reg.hip", "reg.h", _inc("sta_reg.h")], []),
+}
 # CLOUD_LIB, CLOUD_SOURCES, CLOUD_DEPS, CLOUD_HASH_FILE ... DIST_LIB, DIST_SOURCES, DIST_DEPS, DIST_HASH_FILE, RAY_LIB, RAY_SOURCES,
-# RAY_DEPS, RAY_HASH_FILE: the rows of both tables under the names that tools/ and tests/ use.  Every row is built from sta_common.h and
-# the host kit as well.
-for _name, (_what, _own, _shared) in list(SATELLITES.items()) + list(ADDONS.items()):
+# RAY_DEPS, RAY_HASH_FILE, REG_LIB, REG_SOURCES, REG_DEPS, REG_HASH_FILE: the rows of the three tables under the names that tools/ and
+# tests/ use.  Every row is built from sta_common.h and the host kit as well.
+for _name, (_what, _own, _shared) in list(SATELLITES.items()) + list(ADDONS.items()) + list(EXTENSIONS.items()):
     _so = os.path.join(PKG, "libsta_%s.so" % _name)
     globals().update({_name.upper() + "_LIB": _so, _name.upper() + "_SOURCES": _own[:1], _name.upper() + "_HASH_FILE": _so + ".srchash",
                       _name.upper() + "_DEPS": ["sta_exports.map"] + _own + _shared + ["sta_common.h", "sta_hostkit.h"]})
@@ -121,11 +126,11 @@ def _cmd(hipcc, out, hooks, sources=None):
 
 
 def build_lib(force=False, verbose=True, test_hooks=True, skew=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True,
-              ray=True):
+              ray=True, reg=True):
     """Build the product library, (test_hooks) the test-hooks library, (skew) the wave-skew library and, each under the keyword of its name, the libraries of
-    SATELLITES and ADDONS; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
-    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray)
-    assert list(wanted) == list(SATELLITES) + list(ADDONS)
+    SATELLITES, ADDONS and EXTENSIONS; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray, reg=reg)
+    assert list(wanted) == list(SATELLITES) + list(ADDONS) + list(EXTENSIONS)
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))

@@ -21,7 +21,7 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -142,10 +142,12 @@ class MeshScore(NamedTuple):
     gt_points: torch.Tensor        # [n,3] f32 (the cloud itself when gt is a cloud)
     n_precise: int                 # the integer counts behind the two ratios
     n_complete: int
+    T: Optional[np.ndarray] = None # [4,4] f64: the transform the estimate was scored under when refine= was given (None otherwise)
 
 
 def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: float = 0.05, max_error: float = 0.5, T=None, seed: int = 0,
-              mode: str = "samples") -> MeshScore:
+              mode: str = "samples", refine: Optional[str] = None, refine_max_corr: Optional[float] = None,
+              refine_min_cos: Optional[float] = None) -> MeshScore:
     """Score a mesh against a ground truth, samples against samples (mode="samples", the default).  gt: a `tsdf.Mesh`, the path of a PLY of `tsdf.write_mesh_ply`, or an
     [M,3] cloud (taken as it is, not sampled).
       1. n_samples points by area from the estimate with `seed`, from the ground-truth mesh with seed + 1 (surface.sample_surface)
@@ -160,22 +162,41 @@ def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: flo
     moved by T through cloud.transform, once), both as sqrt(min(d2, max_error^2)) of meshdist's exact point-to-triangle query with
     radius = max_error.  Scoring samples against samples has a floor of about one sample spacing even for identical surfaces; this has
     none.  When gt is a cloud there is no ground-truth surface: completion is the cloud against the estimate's mesh, accuracy stays the
-    nearest-neighbour distance from the estimate's samples to the cloud, as in the default mode."""
+    nearest-neighbour distance from the estimate's samples to the cloud, as in the default mode.
+    refine="plane" | "point" (gt a mesh; refused for a cloud): before scoring, meshdist.icp registers the estimate's samples (as sampled,
+    not yet moved) against the ground truth's SURFACE, starting at T, with max_corr = refine_max_corr (default max_error); with
+    refine_min_cos the samples' face normals must agree with the matched triangle's to that cosine.  The refined transform replaces T in
+    both modes and is returned in the last field; a score without it carries the residual misalignment of whatever fixed T in every
+    number.  Without refine= nothing changes: the last field is None."""
     from . import surface, tsdf
     if not float(threshold) <= float(max_error):
         raise ValueError(f"eval_mesh: threshold must be <= max_error (got {threshold}, {max_error})")
     if mode not in ("samples", "surface"):
         raise ValueError(f"eval_mesh: mode must be 'samples' or 'surface' (got {mode!r})")
+    if refine not in (None, "point", "plane"):
+        raise ValueError(f"eval_mesh: refine must be None, 'point' or 'plane' (got {refine!r})")
     dev = getattr(frontend, "device", frontend)
     est_m = tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in est_mesh])
-    est = surface.sample_surface(est_m, n_samples, seed=seed).points
-    if T is not None:
-        est = cloud.transform(est, np.asarray(_host(T), dtype=np.float64)[:3])
     if isinstance(gt, (str, os.PathLike)):
         gt = tsdf.mesh_from_ply(gt, dev)
+    if refine is not None and not isinstance(gt, tsdf.Mesh):
+        raise ValueError("eval_mesh: refine= registers against the ground truth's surface: gt must be a mesh, not a cloud")
+    sampled = surface.sample_surface(est_m, n_samples, seed=seed, normals=refine is not None and refine_min_cos is not None)
+    est = sampled.points
     gt_m = None
     if isinstance(gt, tsdf.Mesh):
         gt_m = tsdf.Mesh(*[None if a is None else torch.as_tensor(a).to(dev) for a in gt])
+    T_used = None
+    if refine is not None:
+        from . import meshdist
+        gt_index = meshdist.TriIndex.build(SimpleNamespace(vertices=gt_m.vertices, triangles=gt_m.triangles))
+        reg = meshdist.icp(est, gt_index, float(max_error if refine_max_corr is None else refine_max_corr),
+                           init=None if T is None else np.asarray(_host(T), dtype=np.float64), mode=refine,
+                           normals=sampled.normals if refine_min_cos is not None else None, min_cos=refine_min_cos)
+        T = T_used = reg.T
+    if T is not None:
+        est = cloud.transform(est, np.asarray(_host(T), dtype=np.float64)[:3])
+    if gt_m is not None:
         gt_pts = surface.sample_surface(gt_m, n_samples, seed=int(seed) + 1).points
     else:
         gt_pts = torch.as_tensor(gt).to(dev, torch.float32).reshape(-1, 3).contiguous()
@@ -207,7 +228,7 @@ def eval_mesh(frontend, est_mesh, gt, *, n_samples: int = 200000, threshold: flo
     precision = n_precise / n_est if n_est else float("nan")
     ratio = n_complete / n_gt if n_gt else float("nan")
     f = 2.0 * precision * ratio / (precision + ratio) if precision + ratio > 0 else (0.0 if precision + ratio == 0 else float("nan"))
-    return MeshScore(acc, comp, ratio, precision, f, (acc + comp) / 2.0, est, gt_pts, n_precise, n_complete)
+    return MeshScore(acc, comp, ratio, precision, f, (acc + comp) / 2.0, est, gt_pts, n_precise, n_complete, T_used)
 
 
 def mesh_depth_l1(frontend, est_mesh, gt_mesh, cameras, H: int, W: int, method: str = "raster"):
