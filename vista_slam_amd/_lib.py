@@ -25,6 +25,7 @@ SIMP_LIB_PATH = os.path.join(PKG, "libsta_simp.so")        # a seventh one (incl
 DIST_LIB_PATH = os.path.join(PKG, "libsta_dist.so")        # an eighth one (include/sta_dist.h): `load_dist()`
 RAY_LIB_PATH = os.path.join(PKG, "libsta_ray.so")          # a ninth one (include/sta_ray.h): `load_ray()`
 REG_LIB_PATH = os.path.join(PKG, "libsta_reg.so")          # a tenth one (include/sta_reg.h): `load_reg()`
+KNN_LIB_PATH = os.path.join(PKG, "libsta_knn.so")          # an eleventh one (include/sta_knn.h): `load_knn()`
 
 STA_PREC_F16 = 1
 STA_PREC_F16X3 = 3
@@ -307,6 +308,14 @@ REG_SIGNATURES = {
     "sta_reg_pass": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _dp, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "sta_reg_last_error": (C.c_char_p, []),
 }
+# include/sta_knn.h: libsta_knn.so, handle-free; a table of its own like the nine above (the index of libsta_cloud.so goes as the host
+# struct StaNNIndex, which the header restates as sta_knn_grid; view_host as host doubles)
+KNN_SIGNATURES = {
+    "sta_knn_plan": (_i, [_i64, _i64, _i64, _i64p]),
+    "sta_knn_query": (_i, [C.POINTER(StaNNIndex), _vp, _i64, _vp, _i64, _i64, _d, _vp, _vp, _vp, _vp, _vp]),
+    "sta_knn_moments": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _dp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "sta_knn_last_error": (C.c_char_p, []),
+}
 
 
 class StaTriIndex(C.Structure):
@@ -444,6 +453,7 @@ load_simp, check_simp = _satellite(SIMP_LIB_PATH, SIMP_SIGNATURES, "sta_simp_las
 load_dist, check_dist = _satellite(DIST_LIB_PATH, DIST_SIGNATURES, "sta_tri_last_error")               # include/sta_dist.h: its names are sta_tri_*
 load_ray, check_ray = _satellite(RAY_LIB_PATH, RAY_SIGNATURES, "sta_ray_last_error")                   # include/sta_ray.h
 load_reg, check_reg = _satellite(REG_LIB_PATH, REG_SIGNATURES, "sta_reg_last_error")                   # include/sta_reg.h
+load_knn, check_knn = _satellite(KNN_LIB_PATH, KNN_SIGNATURES, "sta_knn_last_error")                   # include/sta_knn.h
 
 
 def use_test_hooks():

@@ -8,7 +8,7 @@
                                             #    csrc/sta_skew.h are live and the two sta_debug_*wave_skew* entries exist
                                             #    (tests/test_skew_gpu.py only; in every other library the points expand to nothing)
                                             #    vista_slam_amd/libsta_<name>.so       one handle-free library per row of SATELLITES:
-                                            #    of ADDONS and of EXTENSIONS: a translation unit of its own (csrc/sta_<name>.hip) that exports
+                                            #    of ADDONS, of EXTENSIONS and of LATER: a translation unit of its own (csrc/sta_<name>.hip) that exports
                                             #    include/sta_<name>.h
 
 A library's content hash covers its own files and the shared headers it includes, nothing of any other library: the product's hash does
@@ -59,10 +59,18 @@ ADDONS = {
 EXTENSIONS = {
     "reg": ("point-to-plane and point-to-point registration against the triangle index of libsta_dist.so", ["sta_reg.hip", "reg.h", _inc("sta_reg.h")], []),
 }
+# ... and the libraries that came after that table of one was pinned as well (tests/test_reg_abi.py): the same rows, the same loops.
+# Deliberately, the ABI test of a library in THIS table (tests/test_knn_abi.py) pins its own row and not the table's length, so the next
+# library is one more row here and needs no fifth table.  libsta_knn.so reads the index of libsta_cloud.so through a host struct that
+# its header restates and holds no own file of another library.
+LATER = {
+    "knn": ("k nearest neighbours on the grid of libsta_cloud.so and the moments of the neighbourhoods: cloud filters and normals",
+            ["sta_knn.hip", "knn.h", _inc("sta_knn.h")], []),
+}
 # CLOUD_LIB, CLOUD_SOURCES, CLOUD_DEPS, CLOUD_HASH_FILE ... DIST_LIB, DIST_SOURCES, DIST_DEPS, DIST_HASH_FILE, RAY_LIB, RAY_SOURCES,
-# RAY_DEPS, RAY_HASH_FILE, REG_LIB, REG_SOURCES, REG_DEPS, REG_HASH_FILE: the rows of the three tables under the names that tools/ and
-# tests/ use.  Every row is built from sta_common.h and the host kit as well.
-for _name, (_what, _own, _shared) in list(SATELLITES.items()) + list(ADDONS.items()) + list(EXTENSIONS.items()):
+# RAY_DEPS, RAY_HASH_FILE, REG_LIB, REG_SOURCES, REG_DEPS, REG_HASH_FILE, KNN_LIB, KNN_SOURCES, KNN_DEPS, KNN_HASH_FILE: the rows of the four
+# tables under the names that tools/ and tests/ use.  Every row is built from sta_common.h and the host kit as well.
+for _name, (_what, _own, _shared) in list(SATELLITES.items()) + list(ADDONS.items()) + list(EXTENSIONS.items()) + list(LATER.items()):
     _so = os.path.join(PKG, "libsta_%s.so" % _name)
     globals().update({_name.upper() + "_LIB": _so, _name.upper() + "_SOURCES": _own[:1], _name.upper() + "_HASH_FILE": _so + ".srchash",
                       _name.upper() + "_DEPS": ["sta_exports.map"] + _own + _shared + ["sta_common.h", "sta_hostkit.h"]})
@@ -126,11 +134,11 @@ def _cmd(hipcc, out, hooks, sources=None):
 
 
 def build_lib(force=False, verbose=True, test_hooks=True, skew=True, cloud=True, raster=True, tsdf=True, mesh=True, surf=True, simp=True, dist=True,
-              ray=True, reg=True):
+              ray=True, reg=True, knn=True):
     """Build the product library, (test_hooks) the test-hooks library, (skew) the wave-skew library and, each under the keyword of its name, the libraries of
-    SATELLITES, ADDONS and EXTENSIONS; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
-    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray, reg=reg)
-    assert list(wanted) == list(SATELLITES) + list(ADDONS) + list(EXTENSIONS)
+    SATELLITES, ADDONS, EXTENSIONS and LATER; all compile concurrently (one hipcc process each, ~100 s).  Returns the product library's path."""
+    wanted = dict(cloud=cloud, raster=raster, tsdf=tsdf, mesh=mesh, surf=surf, simp=simp, dist=dist, ray=ray, reg=reg, knn=knn)
+    assert list(wanted) == list(SATELLITES) + list(ADDONS) + list(EXTENSIONS) + list(LATER)
     jobs = []           # (output, hash file, test hooks, sources, deps)
     if force or is_stale(LIB, HASH_FILE):
         jobs.append((LIB, HASH_FILE, False, None, None))

@@ -146,8 +146,11 @@ def voxel_downsample(frontend: STAFrontend, points, colors=None, *, voxel_size, 
 
 def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres: float,
                      want_records: bool = False, counts=None, min_views: int = 0, voxel_size=None, voxel_origin=None,
-                     min_points: int = 1):
+                     min_points: int = 1, outlier=None):
     """slam.py:396-408 -> (points [M,3] fp32, colors [M,3] fp32 [, records [M] PLY_RECORD numpy array]).
+
+    outlier: ("statistical", nb, ratio, radius) or ("radius", nb, radius) - the cloud, after the voxel step if there is one, without
+    the points that vista_slam_amd.cloud.remove_statistical_outlier / remove_radius_outlier removes (the floaters); rows stay in order.
 
     counts [N,H,W] (geo.view_consistency_check) with min_views > 0: a pixel is kept iff conf > conf_thres AND counts >= min_views
     (the confidence of the other pixels is lowered to -inf on a copy before the same library call).  voxel_size: the cloud goes
@@ -176,12 +179,17 @@ def world_pointcloud(frontend: STAFrontend, depths, scales, intrinsics, poses, c
                                                  C.byref(cnt), frontend._stream()))
     M = cnt.value
     if voxel_size is not None:
-        return voxel_downsample(frontend, pts[:M], col[:M], voxel_size=voxel_size, origin=voxel_origin, min_points=min_points,
-                                want_records=want_records)
-    if want_records:
-        records = np.frombuffer(rec[:M * 27].cpu().numpy().tobytes(), dtype=PLY_RECORD)
-        return pts[:M], col[:M], records
-    return pts[:M], col[:M]
+        res = voxel_downsample(frontend, pts[:M], col[:M], voxel_size=voxel_size, origin=voxel_origin, min_points=min_points,
+                               want_records=want_records)
+    elif want_records:
+        res = (pts[:M], col[:M], np.frombuffer(rec[:M * 27].cpu().numpy().tobytes(), dtype=PLY_RECORD))
+    else:
+        res = (pts[:M], col[:M])
+    if outlier is not None and res[0].shape[0] > 0:
+        from . import cloud
+        kept, _mask = cloud.filter_outliers(res[0], outlier)
+        res = (res[0][kept], res[1][kept]) + ((res[2][kept.cpu().numpy()],) if want_records else ())
+    return res
 
 
 def write_ply(path: str, records: np.ndarray):
@@ -213,7 +221,8 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
                   view_names: Optional[Sequence[str]] = None, save_view_graph=True, traj_name_postfix=None,
                   save_poses=True, save_images=True, save_scales=True, save_depths=True, save_intrinsics=True,
                   save_confs=True, save_ply=True, gt_poses=None, gt_depths=None, gt_intrinsics=None,
-                  counts=None, min_views: int = 0, ply_voxel_size=None, mesh_min_triangles=None, mesh_simplify_cell=None, mesh_voxel_size=None):
+                  counts=None, min_views: int = 0, ply_voxel_size=None, ply_outlier=None, mesh_min_triangles=None, mesh_simplify_cell=None,
+                  mesh_voxel_size=None):
     """Same switches and files as OnlineSLAM.save_data_all (slam.py:338-421).  poses [N,4,4] (rotation + translation
     of the best node's Sim3), scales [N,1], depths / confs [N,H,W], intrinsics [N,3,3], imgs [N,3,H,W] in [-1,1].
     counts / min_views: pointcloud.ply keeps only pixels that at least min_views neighbouring views agree with
@@ -222,7 +231,9 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
     that voxel size (vista_slam_amd.tsdf.fuse, read back with tsdf.read_mesh_ply); without it every file is byte for byte what it was.
     mesh_min_triangles: that mesh without its connected components of fewer triangles (vista_slam_amd.surface.clean_mesh) - the floaters;
     without it mesh.ply is byte for byte what it was.  mesh_simplify_cell: that mesh, after the cleaning, simplified by vertex clustering on
-    cells of that size (vista_slam_amd.simplify.simplify_mesh, quadric placement); without it mesh.ply is byte for byte what it was."""
+    cells of that size (vista_slam_amd.simplify.simplify_mesh, quadric placement); without it mesh.ply is byte for byte what it was.
+    ply_outlier: ("statistical", nb, ratio, radius) or ("radius", nb, radius) - pointcloud.ply, after the voxel step, without the points
+    that filter of vista_slam_amd.cloud removes (world_pointcloud's `outlier`); without it every file is byte for byte what it was."""
     os.makedirs(output_folder, exist_ok=True)
 
     def host(t):
@@ -246,7 +257,7 @@ def save_data_all(frontend: STAFrontend, output_folder: str, *, poses, scales, d
         np.save(f"{output_folder}/intrinsics.npy", host(intrinsics))
     if save_ply:
         _, _, records = world_pointcloud(frontend, depths, scales, intrinsics, poses, confs, imgs, conf_thres, want_records=True,
-                                         counts=counts, min_views=min_views, voxel_size=ply_voxel_size)
+                                         counts=counts, min_views=min_views, voxel_size=ply_voxel_size, outlier=ply_outlier)
         write_ply(f"{output_folder}/pointcloud.ply", records)
     if mesh_voxel_size is not None:
         from . import tsdf
